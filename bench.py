@@ -64,7 +64,43 @@ def parse_args():
     ap.add_argument("--allow-torch-gather", action="store_true",
                     help="N > 1: if the library's RCCL gather (ctag_gather, the C ABI) cannot come up, fall back to torch.distributed's all_gather "
                          "of the fixed records instead of failing.  Without this flag such a run exits non-zero: the line must not hide a gather failure")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result records of the last timed step (gathered when N > 1) as DIR/<field>.npy "
+                         "(float32 / float64, at most 64 MB in all; a fixed, seeded sample of frames when the whole list is larger)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes of all the .npy payloads of --dump-outputs together
+
+
+def dump_outputs(res, path):
+    """--dump-outputs: the ctag_frame_result records a caller of the timed path receives, one .npy per field (frame-major), so that
+    two builds can be compared output for output.  Integer fields become float64 (exact), float fields stay float32.  When the full
+    list would exceed DUMP_BUDGET, a fixed sample of frames (seeded, in frame order) is written instead; frame_index.npy says which."""
+    fields = []  # (file name, field of the records, dtype written)
+    for name in ("status", "n_markers", "n_features", "flags"):
+        fields.append((name, lambda r, k=name: r[k], np.float64))
+    for name in res.dtype["markers"].base.names:
+        fields.append(("markers_" + name, lambda r, k=name: r["markers"][k], np.float64))
+    for name in res.dtype["features"].base.names:
+        ft = res.dtype["features"].base[name].base
+        fields.append(("features_" + name, lambda r, k=name: r["features"][k], np.float32 if ft.kind == "f" else np.float64))
+    one = res[:1]
+    per_frame = 8 + sum(np.asarray(get(one)).size * np.dtype(dt).itemsize for _, get, dt in fields)  # + frame_index
+    n = len(res)
+    idx = np.arange(n)
+    room = DUMP_BUDGET - 128 * (len(fields) + 1)  # less the .npy headers
+    if n * per_frame > room:
+        idx = np.sort(np.random.RandomState(0).choice(n, room // per_frame, replace=False))
+    sel = res[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frame_index.npy"), idx.astype(np.float64))
+    for name, get, dt in fields:
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(get(sel), dtype=dt))
+    return {"dir": path, "frames": int(len(idx)), "of_frames": int(n), "bytes": int(len(idx) * per_frame)}
 
 
 def device_copy_rate(dev):
@@ -829,6 +865,7 @@ def main():
     ok_frames = int((res["status"] == 0).sum())
     markers_found = int(res["n_markers"].sum())
     sha = hashlib.sha256(res.tobytes()).hexdigest()
+    dumped = dump_outputs(res, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     rc = 0
     one_stream_sha = None
     if world == 1:  # the one-stream steps (`stage_ms_per_step`, `roofline`) must have produced the very same records
@@ -907,6 +944,8 @@ def main():
                "results_of": "the last TIMED step" + ("" if world > 1 else " (snapshot before the one-stream steps; their records hash %s)"
                                                       % ("the same" if one_stream_sha == sha else "DIFFERENTLY: " + str(one_stream_sha))),
                "sources_sha256": src_sha}
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if world > 1:
             out["gather_ms"] = gather_ms
             out["rank_stage_ms"] = rank_stage_ms

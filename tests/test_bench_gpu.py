@@ -27,13 +27,22 @@ def _line(out):
     return json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
 
 
-def test_one_gpu_line_and_two_rank_hash():
+def test_one_gpu_line_and_two_rank_hash(tmp_path):
+    import numpy as np
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "192", "--host-frames", "0",
             "--pose-frames", "0", "--latency-calls", "0"]
-    p = subprocess.run(base + ["--cpu-frames", "24", "--cpu-frames-per-thread", "2"], capture_output=True, text=True, timeout=900)
+    dump = str(tmp_path / "out")
+    p = subprocess.run(base + ["--cpu-frames", "24", "--cpu-frames-per-thread", "2", "--dump-outputs", dump], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     one = _line(p.stdout)
     assert one["n_gpus"] == 1 and one["unit"] == "frames/s" and one["frames_ok"] == 192
+    assert one["steps"] == 2 and one["ms_per_step"] > 0
+    # --dump-outputs: the records of the last timed step, every frame of them (192 frames fit the 64 MB budget)
+    assert one["dumped_outputs"]["frames"] == 192
+    assert (np.load(os.path.join(dump, "frame_index.npy")) == np.arange(192)).all()
+    assert int((np.load(os.path.join(dump, "status.npy")) == 0).sum()) == one["frames_ok"]
+    assert int(np.load(os.path.join(dump, "n_markers.npy")).sum()) == one["markers_decoded_last_step"]
+    assert np.load(os.path.join(dump, "features_corners.npy")).shape == (192, 100, 16)
     assert one["parity"]["mismatches"] == 0 and one["parity"]["frames_checked"] >= 24
     assert one["roofline"]["bound"] == "hbm" and 0.0 < one["roofline"]["frac"] < 1.0 and one["roofline"]["traffic_source"]
     assert one["cpu_baseline"]["kind"] == "port" and one["cpu_baseline"]["cores"] == 1 and one["cpu_baseline"]["value"] > 0
@@ -67,13 +76,7 @@ def test_a_rank_that_dies_ends_the_job_non_zero():
     assert not [l for l in p.stdout.splitlines() if l.startswith("{")]  # no line from a job that lost a rank
 
 
-@pytest.mark.parametrize("frames", [256, 250])
-def test_eight_ranks_give_the_one_gpu_list(frames):
-    """BASELINE config 4's shape before it meets eight GPUs: `python bench.py --gpus 8` (self-launched, eight ranks sharing this box's one
-    GPU through the developer backend) on 256 frames and on 250 (uneven shards: two ranks own 32 frames, six 31).  Rank 0's gathered
-    list must hash like the one-GPU list of the same frames, and the line must carry what a SCALE record is read for: `roofline`,
-    `gather_ms`, every rank's per-kernel times and the gather in use.  What the developer backend replaces is the two ncclAllGather
-    calls only: shards are packed by ctag_pack_results and unpacked by ctag_gather_end's kernels."""
+def _ranks_give_the_one_gpu_list(frames, world):
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", str(frames), "--host-frames", "0",
             "--pose-frames", "0", "--latency-calls", "0", "--cpu-frames", "0", "--pipelined-steps", "0"]
     p = subprocess.run(base, capture_output=True, text=True, timeout=900)
@@ -81,15 +84,36 @@ def test_eight_ranks_give_the_one_gpu_list(frames):
     one = _line(p.stdout)
     assert one["frames_ok"] == frames and one["results_of"].startswith("the last TIMED step") and "the same" in one["results_of"]
     env = dict(os.environ, CTAG_BENCH_BACKEND="gloo", OMP_NUM_THREADS="1")
-    p = subprocess.run(base + ["--gpus", "8"], capture_output=True, text=True, timeout=1500, env=env)
+    p = subprocess.run(base + ["--gpus", str(world)], capture_output=True, text=True, timeout=1500, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
-    eight = _line(p.stdout)
-    assert eight["n_gpus"] == 8 and eight["scaling"] == "strong" and eight["frames_ok"] == frames
-    assert eight["config"]["frames_per_step"] == frames and eight["config"]["frames_per_gpu"] == (frames + 7) // 8
-    assert eight["results_sha256"] == one["results_sha256"]
-    assert eight["roofline"]["bound"] == "hbm" and eight["roofline"]["frac"] > 0 and eight["roofline"]["frames_per_launch"] == (frames + 7) // 8
-    assert eight["gather_ms"] is not None and eight["gather_ms"] > 0
-    assert len(eight["rank_stage_ms"]) == 8 and all(r["edge_refine"] > 0 and r["decimate"] > 0 for r in eight["rank_stage_ms"])
-    assert "ctag_pack_results" in eight["config"]["gather"]  # on RCCL: "ctag_gather (C ABI -> ncclAllGather of packed shards)"
-    gb = eight["config"]["gather_bytes"]
+    many = _line(p.stdout)
+    per_gpu = (frames + world - 1) // world
+    assert many["n_gpus"] == world and many["scaling"] == "strong" and many["frames_ok"] == frames
+    assert many["config"]["frames_per_step"] == frames and many["config"]["frames_per_gpu"] == per_gpu
+    assert many["results_sha256"] == one["results_sha256"]
+    assert many["roofline"]["bound"] == "hbm" and many["roofline"]["frac"] > 0 and many["roofline"]["frames_per_launch"] == per_gpu
+    assert many["gather_ms"] is not None and many["gather_ms"] > 0
+    assert len(many["rank_stage_ms"]) == world and all(r["edge_refine"] > 0 and r["decimate"] > 0 for r in many["rank_stage_ms"])
+    assert "ctag_pack_results" in many["config"]["gather"]  # on RCCL: "ctag_gather (C ABI -> ncclAllGather of packed shards)"
+    gb = many["config"]["gather_bytes"]
     assert 0 < gb["packed_local"] <= gb["padded_per_rank"] < gb["fixed_records_per_rank"]
+
+
+@pytest.mark.parametrize("frames", [256, 250])
+def test_eight_ranks_give_the_one_gpu_list(frames):
+    """BASELINE config 4's shape before it meets eight GPUs: `python bench.py --gpus 8` (self-launched, eight ranks through the developer
+    backend) on 256 frames and on 250 (uneven shards: two ranks own 32 frames, six 31).  Rank 0's gathered list must hash like the
+    one-GPU list of the same frames, and the line must carry what a SCALE record is read for: `roofline`, `gather_ms`, every rank's
+    per-kernel times and the gather in use.  What the developer backend replaces is the two ncclAllGather calls only: shards are packed
+    by ctag_pack_results and unpacked by ctag_gather_end's kernels.
+    Needs one GPU per rank: eight ranks on one GPU would keep it open from nine processes at once (the ranks and this one), more
+    than a shared GPU box allows.  One-GPU boxes skip it and run test_four_ranks_on_one_gpu_give_the_one_gpu_list instead."""
+    import torch
+    if torch.cuda.device_count() < 8:
+        pytest.skip("needs 8 GPUs (one per rank), found %d" % torch.cuda.device_count())
+    _ranks_give_the_one_gpu_list(frames, 8)
+
+
+def test_four_ranks_on_one_gpu_give_the_one_gpu_list():
+    """The same checks with `--gpus 4`, the four ranks sharing this box's one GPU, on 250 frames (uneven shards: 63, 63, 62, 62)."""
+    _ranks_give_the_one_gpu_list(250, 4)
