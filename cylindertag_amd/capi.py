@@ -27,7 +27,7 @@ EXPORTS = ["ctag_create", "ctag_create_ex", "ctag_params_default", "ctag_destroy
            "ctag_stage_name", "ctag_strerror", "ctag_version"]
 # ... and include/ctag_pose.h
 POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag_model_get_view", "ctag_camera_load",
-                "ctag_pose_batch_device", "ctag_estimate_pose", "ctag_pose_last_ms"]
+                "ctag_pose_batch_device", "ctag_estimate_pose", "ctag_pose_last_ms", "ctag_draw_axis", "ctag_draw_axis_batch_device"]
 # ... and include/ctag_gather.h
 GATHER_EXPORTS = ["ctag_shard_range", "ctag_packed_capacity", "ctag_pack_results", "ctag_unpack_results", "ctag_comm_unique_id",
                   "ctag_comm_init", "ctag_comm_attach", "ctag_comm_destroy", "ctag_comm_native", "ctag_comm_last_error", "ctag_gather_begin",
@@ -170,6 +170,11 @@ def load_library():
     L.ctag_estimate_pose.argtypes = [vp, vp, vp, C.POINTER(CameraC), vp]
     L.ctag_pose_last_ms.restype = C.c_float
     L.ctag_pose_last_ms.argtypes = [vp]
+    L.ctag_draw_axis.restype = C.c_int
+    L.ctag_draw_axis.argtypes = [vp, vp, C.c_int, C.c_int, C.c_ssize_t, vp, vp, C.c_int, vp, C.POINTER(CameraC), C.c_int, vp, C.c_ssize_t]
+    L.ctag_draw_axis_batch_device.restype = C.c_int
+    L.ctag_draw_axis_batch_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_ssize_t, vp, vp, vp, C.c_int, vp,
+                                              C.POINTER(CameraC), C.c_int, vp, C.c_ssize_t, C.c_ssize_t]
     u64p = C.POINTER(C.c_uint64)
     L.ctag_shard_range.restype = C.c_int
     L.ctag_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -541,3 +546,33 @@ class Detector:
 
     def pose_last_ms(self):
         return float(self.L.ctag_pose_last_ms(self.h))
+
+    # ---- overlay (CylinderTag::drawAxis)
+    def draw_axis(self, gray, result, poses, model, camera, axis_length=5, out=None):
+        """One frame: gray (rows x cols uint8) + its ctag_frame_result + POSE_DT records -> rows x cols x 3 uint8 overlay.
+        Record k draws marker poses[k]["marker"] with model poses[k]["model_index"] (frame field 0).  `out` may be a
+        (rows, cols, 3) uint8 view with any row stride (e.g. a slice of a wider buffer); only its pixels are written."""
+        gray = np.asarray(gray)
+        assert gray.dtype == np.uint8 and gray.ndim == 2 and gray.strides[1] == 1
+        res = np.ascontiguousarray(result).reshape(1)
+        assert res.dtype == RESULT_DT
+        poses = np.ascontiguousarray(poses, POSE_DT).reshape(-1)
+        rows, cols = gray.shape
+        if out is None:
+            out = np.empty((rows, cols, 3), np.uint8)
+        assert out.dtype == np.uint8 and out.shape == (rows, cols, 3) and out.strides[1:] == (3, 1)
+        st = self.L.ctag_draw_axis(self.h, gray.ctypes.data, rows, cols, gray.strides[0], res.ctypes.data,
+                                   poses.ctypes.data if poses.size else None, poses.size, model.m, C.byref(camera),
+                                   int(axis_length), out.ctypes.data, out.strides[0])
+        if st != 0:
+            raise CtagError(st, "ctag_draw_axis")
+        return out
+
+    def draw_axis_batch_device(self, frames_ptr, n, rows, cols, row_stride, frame_stride, results_ptr, offsets_ptr, poses_ptr,
+                               capacity, model, camera, axis_length, out_ptr, out_row_stride, out_frame_stride):
+        """Device pointers throughout (ctag_pose_batch_device's offsets / poses as they are); enqueued, does not wait."""
+        st = self.L.ctag_draw_axis_batch_device(self.h, frames_ptr, n, rows, cols, row_stride, frame_stride, results_ptr, offsets_ptr,
+                                                poses_ptr, capacity, model.m, C.byref(camera), int(axis_length), out_ptr,
+                                                out_row_stride, out_frame_stride)
+        if st != 0:
+            raise CtagError(st, "ctag_draw_axis_batch_device")

@@ -210,23 +210,15 @@ static size_t flatten(const std::vector<MarkerInfo>& markers, size_t first, ctag
     return m;
 }
 
-// reference: CylinderTag::estimatePose, CylinderTag.cpp:198-209 (+ PoseEstimator::PnPSolver / PoseBA)
-void CylinderTag::estimatePose(const Mat& img, std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, CamInfo camera,
-                               std::vector<PoseInfo>& pose, bool useDensePoseRefine) {
-    (void)img;
-    (void)useDensePoseRefine;
-    pose.clear();
-    if (markers.empty()) return;
-    for (const MarkerInfo& mi : markers)  // checked before anything is allocated: flatten() cannot fail afterwards
-        if (mi.cornerLists.size() > (size_t)CTAG_MAX_FEATURES) throw std::string("estimatePose, a marker with more than 100 features\n");
-    // vector<ModelInfo> -> ctag_model (every model must hold the same number of corners, as loadModel produces)
+// vector<ModelInfo> -> ctag_model (every model must hold the same number of corners, as loadModel produces); the caller frees it
+static ctag_model* make_model(const std::vector<ModelInfo>& reconstruct_model, const char* who) {
     const size_t nm = reconstruct_model.size();
     const size_t per = nm ? reconstruct_model[0].corners.size() : 8;
     std::vector<int32_t> ids(nm);
     std::vector<float> base(nm * 3), axis(nm * 3), corners(nm * per * 3);
     for (size_t i = 0; i < nm; i++) {
         const ModelInfo& mi = reconstruct_model[i];
-        if (mi.corners.size() != per || per % 8 != 0) throw __FUNCTION__ + std::string(", ") + "illegal model\n";
+        if (mi.corners.size() != per || per % 8 != 0) throw who + std::string(", ") + "illegal model\n";
         ids[i] = mi.MarkerID;
         base[3 * i] = mi.base.x, base[3 * i + 1] = mi.base.y, base[3 * i + 2] = mi.base.z;
         axis[3 * i] = mi.axis.x, axis[3 * i + 1] = mi.axis.y, axis[3 * i + 2] = mi.axis.z;
@@ -238,7 +230,12 @@ void CylinderTag::estimatePose(const Mat& img, std::vector<MarkerInfo> markers, 
     }
     ctag_model_view v{(int32_t)nm, (int32_t)(per / 8 ? per / 8 : 1), ids.data(), base.data(), axis.data(), corners.data()};
     ctag_model* model = nullptr;
-    if (ctag_model_create(&v, &model) != CTAG_OK) throw __FUNCTION__ + std::string(", ") + "illegal model\n";
+    if (ctag_model_create(&v, &model) != CTAG_OK) throw who + std::string(", ") + "illegal model\n";
+    return model;
+}
+
+// CamInfo -> ctag_camera (the matrices as float, as cameraParams.yml stores them)
+static ctag_camera make_camera(const CamInfo& camera) {
     ctag_camera cam;
     std::memset(&cam, 0, sizeof(cam));
 #ifdef CTAG_WITH_OPENCV
@@ -253,6 +250,20 @@ void CylinderTag::estimatePose(const Mat& img, std::vector<MarkerInfo> markers, 
     cam.n_dist = camera.distCoeffs.size() > 14 ? 14 : (int)camera.distCoeffs.size();
     for (int i = 0; i < cam.n_dist; i++) cam.dist[i] = camera.distCoeffs[(size_t)i];
 #endif
+    return cam;
+}
+
+// reference: CylinderTag::estimatePose, CylinderTag.cpp:198-209 (+ PoseEstimator::PnPSolver / PoseBA)
+void CylinderTag::estimatePose(const Mat& img, std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, CamInfo camera,
+                               std::vector<PoseInfo>& pose, bool useDensePoseRefine) {
+    (void)img;
+    (void)useDensePoseRefine;
+    pose.clear();
+    if (markers.empty()) return;
+    for (const MarkerInfo& mi : markers)  // checked before anything is allocated: flatten() cannot fail afterwards
+        if (mi.cornerLists.size() > (size_t)CTAG_MAX_FEATURES) throw std::string("estimatePose, a marker with more than 100 features\n");
+    ctag_model* model = make_model(reconstruct_model, __FUNCTION__);
+    const ctag_camera cam = make_camera(camera);
     std::vector<ctag_pose_rec> rec;
     for (size_t first = 0; first < markers.size();) {  // any number of markers: one record (<= 100 markers / features) at a time
         ctag_frame_result res;
@@ -284,4 +295,54 @@ void CylinderTag::estimatePose(const Mat& img, std::vector<MarkerInfo> markers, 
 #endif
         pose.push_back(pi);
     }
+}
+
+static void pose_vectors(const PoseInfo& p, double* r, double* t) {
+#ifdef CTAG_WITH_OPENCV
+    const double *pr = p.rvec.ptr<double>(0), *pt = p.tvec.ptr<double>(0);
+#else
+    const double *pr = p.rvec, *pt = p.tvec;
+#endif
+    for (int i = 0; i < 3; i++) {
+        r[i] = pr[i];
+        t[i] = pt[i];
+    }
+}
+
+// reference: CylinderTag::drawAxis, CylinderTag.cpp:211-246 (the overlay of include/ctag_pose.h: ctag_draw_axis)
+void CylinderTag::drawAxis(const Mat& img, const std::vector<MarkerInfo>& markers, const std::vector<ModelInfo>& reconstruct_model,
+                           const std::vector<PoseInfo>& pose, const CamInfo& camera, int axisLength, unsigned char* out, size_t out_step) {
+    if (img.empty() || img.channels() != 1) throw std::string("drawAxis, the image must be 8-bit gray (cvtColor GRAY2RGB)\n");
+    if (!out || out_step < (size_t)img.cols * 3) throw std::string("drawAxis, bad output buffer\n");
+    if (markers.size() > (size_t)CTAG_MAX_MARKERS) throw std::string("drawAxis, more than 100 markers\n");
+    ctag_frame_result res;
+    if (flatten(markers, 0, res) != markers.size()) throw std::string("drawAxis, more than 100 features\n");
+    // pose[i] with markers[i]: the reference's pairing by list position (poses past the end of the marker list draw nothing)
+    std::vector<ctag_pose_rec> rec;
+    for (size_t i = 0; i < pose.size() && i < markers.size(); i++) {
+        ctag_pose_rec p;
+        std::memset(&p, 0, sizeof(p));
+        p.status = CTAG_POSE_OK;
+        p.model_index = pose[i].markerID;
+        p.frame = 0;
+        p.marker = (int32_t)i;
+        pose_vectors(pose[i], p.rvec, p.tvec);
+        rec.push_back(p);
+    }
+    ctag_model* model = make_model(reconstruct_model, __FUNCTION__);
+    const ctag_camera cam = make_camera(camera);
+    const int st = ctag_draw_axis(h_, img.data, img.rows, img.cols, (ptrdiff_t)(size_t)img.step, &res, rec.data(), (int)rec.size(), model, &cam,
+                                  axisLength, out, (ptrdiff_t)out_step);
+    ctag_model_free(model);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+}
+
+void CylinderTag::drawAxis(const Mat& img, std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, std::vector<PoseInfo>& pose,
+                           CamInfo camera, int axisLength) {
+    AxisImage im;
+    im.rows = img.rows;
+    im.cols = img.cols;
+    im.px.assign((size_t)img.rows * img.cols * 3, 0);
+    drawAxis(img, markers, reconstruct_model, pose, camera, axisLength, im.px.data(), (size_t)img.cols * 3);
+    axis_image_ = std::move(im);  // what the reference passes to imshow("Plot", imgMark)
 }

@@ -5,7 +5,8 @@
 // `throw std::string` error behaviour of the loaders (CylinderTag.cpp:21,39,51,61) and the same two stdout
 // messages with untouched output on the early returns (CylinderTag.cpp:87-96).  loadModel / loadCamera / estimatePose
 // (header/CylinderTag.h:24-30, CylinderTag.cpp:161-209) are here too, on the GPU pose back end of include/ctag_pose.h
-// (EPnP + LM per marker, k_pose.hip); drawAxis is the reference's GUI and stays there.
+// (EPnP + LM per marker, k_pose.hip), and so is drawAxis (header/CylinderTag.h:33, CylinderTag.cpp:211-246) on the overlay
+// of k_draw.hip: the image the reference would imshow is kept in the object (axisImage()).
 //
 // Build with -DCTAG_WITH_OPENCV to use cv::Mat / cv::Point2f / cv::Mat1i (drop-in next to the reference's
 // pose_estimation.cpp); without it a minimal stand-alone Mat / Point2f is used (this image has no OpenCV).
@@ -94,6 +95,11 @@ struct PoseInfo {
     double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
 };
 #endif
+// the annotated frame of drawAxis: rows x cols pixels of 3 bytes, channel c = Scalar component c (imgMark in the reference)
+struct AxisImage {
+    int rows = 0, cols = 0;
+    std::vector<unsigned char> px;  // rows * cols * 3, top-down
+};
 struct ModelInfo {
     int MarkerID = -1;
     ctag_host::Point3f axis, base;
@@ -135,6 +141,17 @@ class CylinderTag {
     void estimatePose(const ctag_host::Mat& img, std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, CamInfo camera,
                       std::vector<PoseInfo>& pose, bool useDensePoseRefine = false);
 
+    // Draw the axes of the posed markers (reference: header/CylinderTag.h:33, CylinderTag.cpp:211-246): pose[i] is drawn on
+    // markers[i] -- the reference pairs them by list position, after estimatePose has erased the poses without a model -- with
+    // model pose[i].markerID.  The image the reference shows with imshow is kept: axisImage().  Throws std::string on error.
+    void drawAxis(const ctag_host::Mat& img, std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model,
+                  std::vector<PoseInfo>& pose, CamInfo camera, int axisLength = 5);
+    // Same into the caller's buffer (new): img.rows rows of 3*img.cols bytes, out_step bytes apart; nothing else is written
+    // and axisImage() is left as it was.
+    void drawAxis(const ctag_host::Mat& img, const std::vector<MarkerInfo>& markers, const std::vector<ModelInfo>& reconstruct_model,
+                  const std::vector<PoseInfo>& pose, const CamInfo& camera, int axisLength, unsigned char* out, size_t out_step);
+    const AxisImage& axisImage() const { return axis_image_; }
+
     int featureSize() const { return featureSize_; }
     ctag_handle* handle() const { return h_; }
 
@@ -148,6 +165,7 @@ class CylinderTag {
     int state_rows_ = 0, state_cols_ = 0;
     int featureSize_ = 0;
     ctag_handle* h_ = nullptr;
+    AxisImage axis_image_;
 };
 
 #endif

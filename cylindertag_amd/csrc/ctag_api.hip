@@ -142,6 +142,9 @@ struct ctag_handle {
     // state of the pose back end (k_pose.hip), created on first use
     void* pose_state = nullptr;
     void (*pose_state_free)(void*) = nullptr;
+    // state of the overlay (k_draw.hip), created on first use
+    void* draw_state = nullptr;
+    void (*draw_state_free)(void*) = nullptr;
     // state of the multi-GPU gather layer (ctag_gather.hip), created on first use
     void* gather_state = nullptr;
     void (*gather_state_free)(void*) = nullptr;
@@ -151,6 +154,10 @@ namespace ctag {
 void** handle_pose_slot(ctag_handle* h, void (*free_fn)(void*)) {
     h->pose_state_free = free_fn;
     return &h->pose_state;
+}
+void** handle_draw_slot(ctag_handle* h, void (*free_fn)(void*)) {
+    h->draw_state_free = free_fn;
+    return &h->draw_state;
 }
 void** handle_gather_slot(ctag_handle* h, void (*free_fn)(void*)) {
     h->gather_state_free = free_fn;
@@ -895,7 +902,7 @@ static int detect_bgr_device_impl(ctag_handle* h, const uint8_t* bgr_dev, int n,
 // ---------------------------------------------------------------------------------------------------
 extern "C" {
 
-int ctag_version(void) { return 110; }  // 110: ctag_params carries struct_size; CTAG_PENDING; test scaffolding left the product ABI (was 100)
+int ctag_version(void) { return 120; }  // 120: the drawAxis overlay (include/ctag_pose.h); 110: ctag_params carries struct_size; CTAG_PENDING; test scaffolding left the product ABI (was 100)
 
 const char* ctag_strerror(int status) {
     switch (status) {
@@ -1082,6 +1089,7 @@ void ctag_destroy(ctag_handle* h) {
     if (h->h_res1) (void)hipHostFree(h->h_res1);
     if (h->d_gray) (void)hipFree(h->d_gray);
     if (h->pose_state && h->pose_state_free) h->pose_state_free(h->pose_state);
+    if (h->draw_state && h->draw_state_free) h->draw_state_free(h->draw_state);
     if (h->gather_state && h->gather_state_free) h->gather_state_free(h->gather_state);
     for (auto& e : h->ev)
         if (e) (void)hipEventDestroy(e);

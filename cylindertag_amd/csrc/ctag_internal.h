@@ -15,9 +15,26 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/ctag_types.h"
 
 struct ctag_handle;
+struct ctag_camera;
+
+// the model list of include/ctag_pose.h (k_pose.hip creates it; k_draw.hip reads it too)
+struct ctag_model {
+    int n_models = 0, model_size = 0;
+    std::vector<int32_t> ids;
+    std::vector<float> base, axis, corners;
+    // device copies, created on first use on a device
+    int device = -1;
+    int32_t* d_ids = nullptr;
+    float* d_corners = nullptr;
+    float* d_base_axis = nullptr;  // one allocation: base [n_models*3], then axis [n_models*3]
+    float* d_base = nullptr;
+    float* d_axis = nullptr;
+};
 
 namespace ctag {
 
@@ -254,6 +271,11 @@ void build_pick_table(uint8_t* table, uint16_t* table16);  // kPickN*20*10 bytes
 
 // accessors of the opaque handle for the pose back end (k_pose.hip)
 void** handle_pose_slot(struct ::ctag_handle* h, void (*free_fn)(void*));
+// ... and for the overlay (k_draw.hip)
+void** handle_draw_slot(struct ::ctag_handle* h, void (*free_fn)(void*));
+// the model's device copies on `device` (k_pose.hip); the camera's distortion model is one the pose back end handles
+int model_to_device(struct ::ctag_model* m, int device);
+bool camera_ok(const struct ::ctag_camera* c);
 // ... and for the multi-GPU gather layer (ctag_gather.hip)
 void** handle_gather_slot(struct ::ctag_handle* h, void (*free_fn)(void*));
 bool handle_timing(const struct ::ctag_handle* h);

@@ -46,6 +46,35 @@ GrayImage read_bmp_gray(const std::string& path) {
     return img;
 }
 
+static void wr32(unsigned char* p, uint32_t v) {
+    for (int i = 0; i < 4; i++) p[i] = (unsigned char)(v >> (8 * i));
+}
+
+void write_bmp24(const std::string& path, const unsigned char* px, int rows, int cols, size_t step) {
+    if (!px || rows <= 0 || cols <= 0 || step < (size_t)cols * 3) throw __FUNCTION__ + std::string(", ") + "bad image\n";
+    const size_t row_bytes = ((size_t)cols * 3 + 3) & ~(size_t)3;
+    std::vector<unsigned char> hdr(54, 0);
+    hdr[0] = 'B';
+    hdr[1] = 'M';
+    wr32(&hdr[2], (uint32_t)(54 + row_bytes * rows));
+    wr32(&hdr[10], 54);
+    wr32(&hdr[14], 40);
+    wr32(&hdr[18], (uint32_t)cols);
+    wr32(&hdr[22], (uint32_t)rows);  // positive height: bottom-up rows
+    hdr[26] = 1;
+    hdr[28] = 24;
+    wr32(&hdr[34], (uint32_t)(row_bytes * rows));
+    std::ofstream f(path, std::ios::binary);
+    if (!f.is_open()) throw __FUNCTION__ + std::string(", ") + "could not open the file\n";
+    f.write(reinterpret_cast<const char*>(hdr.data()), (std::streamsize)hdr.size());
+    std::vector<unsigned char> row(row_bytes, 0);
+    for (int r = rows - 1; r >= 0; r--) {
+        std::memcpy(row.data(), px + (size_t)r * step, (size_t)cols * 3);
+        f.write(reinterpret_cast<const char*>(row.data()), (std::streamsize)row_bytes);
+    }
+    if (!f) throw __FUNCTION__ + std::string(", ") + "could not write the file\n";
+}
+
 }  // namespace ctag_host
 
 // C entry point (used by the tests and by non-C++ callers): returns 0 on success, -1 on error; copies min(cap, rows*cols)

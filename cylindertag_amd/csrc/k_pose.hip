@@ -838,15 +838,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
 // =====================================================================================================
 // host side: model / camera objects, loaders, launch
 // =====================================================================================================
-struct ctag_model {
-    int n_models = 0, model_size = 0;
-    std::vector<int32_t> ids;
-    std::vector<float> base, axis, corners;
-    // device copies, created on first use on a device
-    int device = -1;
-    int32_t* d_ids = nullptr;
-    float* d_corners = nullptr;
-};
+// struct ctag_model: ctag_internal.h (the overlay of k_draw.hip reads it too)
 
 namespace {
 
@@ -883,16 +875,30 @@ PoseState* pose_state(ctag_handle* h) {
     return static_cast<PoseState*>(*slot);
 }
 
+
+}  // namespace
+
+namespace ctag {
+
 int model_to_device(ctag_model* m, int device) {
     if (m->device == device && m->d_ids) return CTAG_OK;
     if (m->d_ids) (void)hipFree(m->d_ids);
     if (m->d_corners) (void)hipFree(m->d_corners);
+    if (m->d_base_axis) (void)hipFree(m->d_base_axis);
     m->d_ids = nullptr;
     m->d_corners = nullptr;
+    m->d_base_axis = m->d_base = m->d_axis = nullptr;
     if (hipMalloc(&m->d_ids, sizeof(int32_t) * std::max<size_t>(1, m->ids.size())) != hipSuccess) return CTAG_ERR_HIP;
     if (hipMalloc(&m->d_corners, sizeof(float) * std::max<size_t>(1, m->corners.size())) != hipSuccess) return CTAG_ERR_HIP;
     if (hipMemcpy(m->d_ids, m->ids.data(), sizeof(int32_t) * m->ids.size(), hipMemcpyHostToDevice) != hipSuccess) return CTAG_ERR_HIP;
     if (hipMemcpy(m->d_corners, m->corners.data(), sizeof(float) * m->corners.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return CTAG_ERR_HIP;
+    const size_t nb = m->base.size();
+    if (hipMalloc(&m->d_base_axis, sizeof(float) * std::max<size_t>(1, 2 * nb)) != hipSuccess) return CTAG_ERR_HIP;
+    m->d_base = m->d_base_axis;
+    m->d_axis = m->d_base_axis + nb;
+    if (nb && (hipMemcpy(m->d_base, m->base.data(), sizeof(float) * nb, hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(m->d_axis, m->axis.data(), sizeof(float) * nb, hipMemcpyHostToDevice) != hipSuccess))
         return CTAG_ERR_HIP;
     m->device = device;
     return CTAG_OK;
@@ -905,7 +911,10 @@ bool camera_ok(const ctag_camera* c) {
     return c->K[0] != 0.f && c->K[4] != 0.f;
 }
 
-}  // namespace
+}  // namespace ctag
+
+using ctag::camera_ok;
+using ctag::model_to_device;
 
 extern "C" {
 
@@ -970,6 +979,7 @@ void ctag_model_free(ctag_model* m) {
     if (!m) return;
     if (m->d_ids) (void)hipFree(m->d_ids);
     if (m->d_corners) (void)hipFree(m->d_corners);
+    if (m->d_base_axis) (void)hipFree(m->d_base_axis);
     delete m;
 }
 

@@ -2,7 +2,9 @@
 //   CylinderTag marker("CTag_2f12c.marker");  frame = imread(bmp) -> gray;  marker.detect(img_gray, markers, 5, true, 5);
 // Prints one line per marker: id, then "pos:id_left:id_right" per feature, then the first corner of every feature.
 // With a model and a camera file the pose half follows (main.cpp:33-34,40: loadModel, loadCamera, estimatePose) on the
-// GPU pose back end: one line per pose "pose <model index> rvec tvec".  drawAxis is the reference's GUI.
+// GPU pose back end: one line per pose "pose <model index> rvec tvec".  With an output path drawAxis follows too (main.cpp:41,
+// axisLength 30) on the device overlay, and the annotated frame the reference would show in its window is written there as a
+// 24-bit BMP.
 #include <cstdio>
 #include <iostream>
 #include <string>
@@ -13,7 +15,7 @@
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s <dictionary.marker> <image.bmp> [adaptiveThresh=5] [cornerSubPix=1] [cornerSubPixDist=5] [model.model cameraParams.yml]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <dictionary.marker> <image.bmp> [adaptiveThresh=5] [cornerSubPix=1] [cornerSubPixDist=5] [model.model cameraParams.yml [annotated.bmp]]\n", argv[0]);
         return 2;
     }
     try {
@@ -51,6 +53,12 @@ int main(int argc, char** argv) {
                 const double *r = p.rvec, *t = p.tvec;
 #endif
                 std::printf("pose %d rvec %.17g %.17g %.17g tvec %.17g %.17g %.17g\n", p.markerID, r[0], r[1], r[2], t[0], t[1], t[2]);
+            }
+            if (argc > 8) {
+                marker.drawAxis(img, markers, model, pose, camera, 30);
+                const AxisImage& a = marker.axisImage();
+                ctag_host::write_bmp24(argv[8], a.px.data(), a.rows, a.cols, (size_t)a.cols * 3);
+                std::printf("annotated %s\n", argv[8]);
             }
         }
     } catch (const std::string& s) {

@@ -13,6 +13,8 @@
  * Levenberg-Marquardt (Release.props:6,11).  Floating point: the parity bar against the CPU oracle is stated in
  * tests/test_pose_gpu.py.
  *
+ * The overlay of CylinderTag::drawAxis (CylinderTag.cpp:211-246) renders from those records where they lie (k_draw.hip).
+ *
  * Plain pointers and sizes only.  Every function returns a CTAG_* status and never throws.
  */
 #ifndef CTAG_POSE_H
@@ -97,6 +99,45 @@ int ctag_estimate_pose(ctag_handle* h, const ctag_frame_result* result, const ct
 
 /* device time of the last ctag_pose_batch_device call (needs CTAG_OPT_TIMING), milliseconds */
 float ctag_pose_last_ms(ctag_handle* h);
+
+/* ---- overlay: CylinderTag::drawAxis (reference CylinderTag.cpp:211-246) ------------------------------------------------
+ * Output: 8-bit, 3 channels, every channel = the gray value (cvtColor GRAY2RGB), then per drawn record, in record order,
+ * what the reference paints with OpenCV 4.5.3 (k_draw.hip restates it):
+ *   model points: corners[pos_j*8 + k] of the record's model for feature j < n_features and k < 8, then base,
+ *                 base + axis*L, base + (0.0372, 0.0372, 0.9986)*L, base + (0.9980, -0.0520, -0.0353)*L (float, L = axis_length);
+ *   projectPoints with rvec, tvec, K and all 14 distortion terms, rounded to float, then to int (nearest, ties to even, saturated);
+ *   filled circles of radius 5 in (255,234,32) at points 0 .. size-6 (the last corner is not drawn: the reference's size()-5 bound);
+ *   arrowedLine(base, end_k, thickness 10, LINE_AA, tip 0.2) in (255,0,0), (0,255,0), (0,0,255); a filled circle of radius 8
+ *   in (247,235,235) at the base.  Scalar component c lands in channel c.
+ * Rules the reference leaves undefined:
+ *   - a record draws only when status == CTAG_POSE_OK, its frame is the frame being drawn, its marker indexes a marker of that
+ *     frame's CTAG_OK result, its model_index a model, and every feature j < n_features has j < n_pos and 0 <= pos < model_size
+ *     (the reference reads out of bounds otherwise; CTAG_POSE_BAD_POS), with n_features <= CTAG_MAX_CODE_POS.  Any other
+ *     record draws nothing, and nothing outside the records' own data is read.
+ *   - a projected point that is not finite removes the primitives that use it (its circle; an arrow whose base or end it is;
+ *     all three arrows and the base circle if it is the base).
+ *   - a marker without features draws its axes only (the reference's size()-5 bound wraps around there).
+ *   - integer arithmetic that would overflow in OpenCV's 32-bit Point is carried out in 64 bits (points beyond +-2^30 px only).
+ * axis_length must lie in [0, 65536], rows and cols in [1, 32768]. */
+#define CTAG_DRAW_MAX_SIDE 32768
+#define CTAG_DRAW_MAX_AXIS_LENGTH 65536
+
+/* One frame, host memory in and out.  gray: rows x cols, row_stride bytes apart.  Record k draws marker poses[k].marker of
+ * *result with model poses[k].model_index; poses[k].frame must be 0.  out: rows rows of 3*cols bytes, out_row_stride
+ * (>= 3*cols) bytes apart; the bytes between 3*cols and out_row_stride are not written.  Waits for completion. */
+int ctag_draw_axis(ctag_handle* h, const uint8_t* gray, int rows, int cols, ptrdiff_t row_stride, const ctag_frame_result* result,
+                   const ctag_pose_rec* poses, int n_poses, const ctag_model* model, const ctag_camera* camera, int axis_length,
+                   uint8_t* out, ptrdiff_t out_row_stride);
+
+/* n_frames frames in DEVICE memory (frame f at frames_dev + f*frame_stride) with their detection results and the offsets /
+ * pose records of ctag_pose_batch_device as it leaves them: frame f draws records offsets_dev[f] .. offsets_dev[f+1]-1 whose
+ * frame field is f.  Records at index >= capacity are not read (ctag_pose_batch_device computes none there).  Output frame f
+ * at out_dev + f*out_frame_stride, rows of 3*cols bytes out_row_stride apart; no byte outside them is written.  Enqueued
+ * on the handle's stream; returns without waiting. */
+int ctag_draw_axis_batch_device(ctag_handle* h, const uint8_t* frames_dev, int n_frames, int rows, int cols, ptrdiff_t row_stride,
+                                ptrdiff_t frame_stride, const ctag_frame_result* results_dev, const int32_t* offsets_dev,
+                                const ctag_pose_rec* poses_dev, int capacity, const ctag_model* model, const ctag_camera* camera,
+                                int axis_length, uint8_t* out_dev, ptrdiff_t out_row_stride, ptrdiff_t out_frame_stride);
 
 #ifdef __cplusplus
 }
