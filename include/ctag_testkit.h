@@ -90,6 +90,23 @@ int ctag_synth3d_frame_host(const int32_t* state, int dict_rows, int dict_cols, 
                             ctag_synth3d_truth* truth);
 int ctag_synth3d_model(const int32_t* state, int dict_rows, int dict_cols, float* corners);
 
+/* ---- edge search of the dense pose-refinement study (tests/dense_testlib.py search_edges, docs/history.md) -------
+ * For one pose (rvec, tvec; Rodrigues, double) and n_seg straight 3-D segments a -> b, each given with the opposite long side
+ * oa -> ob of its black quad (segments: host doubles [n_seg][12] = a, b, oa, ob), samples_per_edge samples per segment at
+ * parameters (i + 0.5) / S.  Each sample is projected with K and the 14 distortion terms (cv::projectPoints, no tilt); the unit
+ * normal of the projected segment there (central difference at +-1/64 of the segment) is turned away from the opposite side's
+ * projection, i.e. from the dark quad to the bright paper; the u8 frame (host, pixel centres at integers) is read bilinearly
+ * at offsets -r, -r + 0.5, ..., r along it; the first maximum of the central difference (I[k+1] - I[k-1]) / 2 is refined by a
+ * three-point parabola.  A sample is dropped when a tap leaves [0, cols-1] x [0, rows-1] or is not finite, the maximum lies at
+ * either end of the difference profile, or it is below min_contrast.
+ * out: host doubles [n_seg * S][5] in segment-major order: projected point x, y, normal x, y, found offset (NaN if dropped);
+ * keep: host int32 [n_seg * S].  Limits: rows, cols in [2, 32768], row_stride >= cols, n_seg in [1, 4096], S in [1, 64],
+ * search_px a multiple of 0.25 in [0.5, 8], min_contrast >= 0 -- otherwise CTAG_ERR_ARG.  Runs on the handle's device and
+ * waits. */
+int ctag_testkit_dense_edge_probe(ctag_handle* h, const uint8_t* gray, int rows, int cols, ptrdiff_t row_stride, const double* segments,
+                                  int n_seg, const double* K, const double* dist, const double* rvec, const double* tvec,
+                                  int samples_per_edge, double search_px, double min_contrast, double* out, int32_t* keep);
+
 #ifdef __cplusplus
 }
 #endif

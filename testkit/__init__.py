@@ -23,7 +23,8 @@ SYNTH_SEED = 0x4354616753594E00  # "CTagSYN\0", SURVEY.md 8(d)
 
 # every symbol include/ctag_testkit.h declares (tests check the library exports all of them)
 EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
-           "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model"]
+           "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model",
+           "ctag_testkit_dense_edge_probe"]
 
 
 def lib_path():
@@ -72,6 +73,9 @@ def load_library():
                                           C.c_double, C.c_double, C.c_double, vp]
     L.ctag_synth3d_model.restype = C.c_int
     L.ctag_synth3d_model.argtypes = [i32p, C.c_int, C.c_int, vp]
+    L.ctag_testkit_dense_edge_probe.restype = C.c_int
+    L.ctag_testkit_dense_edge_probe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_ssize_t, vp, C.c_int, vp, vp, vp, vp, C.c_int,
+                                                C.c_double, C.c_double, vp, vp]
     _lib = L
     return L
 
@@ -179,6 +183,28 @@ class Detector(ca.Detector):
         if what == DBG_PREMARKERS:
             return a[0]
         return a
+
+    def dense_edge_probe(self, gray, segments, K, dist, rvec, tvec, samples_per_edge=8, search_px=3.0, min_contrast=8.0):
+        """Edge search of the dense pose-refinement study on the device (ctag_testkit_dense_edge_probe): segments [n, 12]
+        (a, b, opposite a, opposite b) -> dict of point [m, 2], normal [m, 2], offset [m] (NaN when dropped), keep [m] bool."""
+        gray = np.asarray(gray, np.uint8)
+        assert gray.ndim == 2 and gray.strides[1] == 1
+        seg = np.ascontiguousarray(segments, np.float64).reshape(-1, 12)
+        Kd = np.ascontiguousarray(np.asarray(K, np.float64).ravel())
+        d = np.zeros(14)
+        dd = np.asarray(dist, np.float64).ravel()
+        d[:dd.size] = dd
+        rv, tv = np.ascontiguousarray(rvec, np.float64), np.ascontiguousarray(tvec, np.float64)
+        m = seg.shape[0] * int(samples_per_edge)
+        out = np.zeros((m, 5), np.float64)
+        keep = np.zeros(m, np.int32)
+        st = self.T.ctag_testkit_dense_edge_probe(self.h, gray.ctypes.data, gray.shape[0], gray.shape[1], gray.strides[0], seg.ctypes.data,
+                                                  seg.shape[0], Kd.ctypes.data, d.ctypes.data, rv.ctypes.data, tv.ctypes.data,
+                                                  int(samples_per_edge), float(search_px), float(min_contrast), out.ctypes.data,
+                                                  keep.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_testkit_dense_edge_probe")
+        return {"point": out[:, :2], "normal": out[:, 2:4], "offset": out[:, 4], "keep": keep.astype(bool)}
 
     def math(self, op, a, b=None):
         a = np.ascontiguousarray(a, dtype=np.float64)

@@ -119,6 +119,123 @@ void fill_truth(const ctag_synth::Truth& T, ctag_synth_truth* truth) {
     }
 }
 
+
+// ---- edge search of the dense pose-refinement study (include/ctag_testkit.h) --------------------------------------
+constexpr int kDenseMaxTaps = 33;  // search_px <= 8 in 0.5-px steps
+
+struct DenseProbeCam {
+    double fx, fy, cx, cy;
+    double k[14];
+};
+
+// cv::projectPoints without tilt, double
+__device__ void dense_project(const double* R, const double* t, const DenseProbeCam& c, const double* X, double* u) {
+    const double P0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
+    const double P1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
+    const double P2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+    if (!(P2 > 0.0)) {
+        u[0] = u[1] = __builtin_nan("");
+        return;
+    }
+    const double x = P0 / P2, y = P1 / P2;
+    const double* k = c.k;
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r2 * r2 * r2;
+    const double cd = (1 + k[0] * r2 + k[1] * r4 + k[4] * r6) / (1 + k[5] * r2 + k[6] * r4 + k[7] * r6);
+    const double xd = x * cd + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x) + k[8] * r2 + k[9] * r4;
+    const double yd = y * cd + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y + k[10] * r2 + k[11] * r4;
+    u[0] = c.fx * xd + c.cx;
+    u[1] = c.fy * yd + c.cy;
+}
+
+// one wave; lane = sample (segment-major)
+__global__ __launch_bounds__(64) void k_dense_edge_probe(const uint8_t* __restrict__ img, int rows, int cols, ptrdiff_t row_stride,
+                                                         const double* __restrict__ seg, int n_seg, DenseProbeCam cam, double R0, double R1,
+                                                         double R2, double T0, double T1, double T2, int S, int nt, double r,
+                                                         double min_contrast, double* __restrict__ out, int32_t* __restrict__ keep) {
+    // Rodrigues as tests/pose_testlib.py states it: cos(th) I + sin(th) [w]x + (1 - cos(th)) w w^T
+    double R[9];
+    const double th = __builtin_sqrt(R0 * R0 + R1 * R1 + R2 * R2);
+    if (th < 1e-12) {
+        for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    } else {
+        const double w[3] = {R0 / th, R1 / th, R2 / th}, c = ctm::cos64(th), s = ctm::sin64(th);
+        const double Wx[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+        for (int i = 0; i < 9; i++) R[i] = (c * ((i % 4 == 0) ? 1.0 : 0.0) + s * Wx[i]) + (1 - c) * (w[i / 3] * w[i % 3]);
+    }
+    const double t[3] = {T0, T1, T2};
+    const int n = n_seg * S;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int sg = i / S;
+        const double ss = ((i % S) + 0.5) / S;
+        const double* G = seg + (size_t)sg * 12;
+        double d[3], X[3], Xp[3], Xm[3], Q[3];
+        for (int j = 0; j < 3; j++) {
+            d[j] = G[3 + j] - G[j];
+            X[j] = G[j] + ss * d[j];
+            Xp[j] = X[j] + d[j] / 64;
+            Xm[j] = X[j] - d[j] / 64;
+            Q[j] = G[6 + j] + ss * (G[9 + j] - G[6 + j]);
+        }
+        double P[2], up[2], um[2], q[2];
+        dense_project(R, t, cam, X, P);
+        dense_project(R, t, cam, Xp, up);
+        dense_project(R, t, cam, Xm, um);
+        dense_project(R, t, cam, Q, q);
+        const double Tx = up[0] - um[0], Ty = up[1] - um[1];
+        const double tl = __builtin_sqrt(Tx * Tx + Ty * Ty);
+        double nx = -Ty / tl, ny = Tx / tl;
+        if ((P[0] - q[0]) * nx + (P[1] - q[1]) * ny < 0) {
+            nx = -nx;
+            ny = -ny;
+        }
+        // profile; any tap outside the frame (or not finite) drops the sample
+        double prof[kDenseMaxTaps];
+        bool inside = true;
+        for (int k = 0; k < nt; k++) {
+            const double o = -r + 0.5 * k;
+            const double x = P[0] + o * nx, y = P[1] + o * ny;
+            if (!(x >= 0.0 && y >= 0.0 && x <= cols - 1 && y <= rows - 1)) {
+                inside = false;
+                prof[k] = 0.0;
+                continue;
+            }
+            const int x0 = min((int)floor(x), cols - 2), y0 = min((int)floor(y), rows - 2);
+            const double fx = x - x0, fy = y - y0;
+            const uint8_t* p0 = img + (ptrdiff_t)y0 * row_stride + x0;
+            const uint8_t* p1 = p0 + row_stride;
+            const double top = (1 - fx) * (double)p0[0] + fx * (double)p0[1];
+            const double bot = (1 - fx) * (double)p1[0] + fx * (double)p1[1];
+            prof[k] = (1 - fy) * top + fy * bot;
+        }
+        // difference at tap j + 1 is D[j] = (prof[j + 2] - prof[j]) / 2, j = 0 .. nt - 3; first maximum
+        const int nd = nt - 2;
+        int kb = 0;
+        double db = 0.5 * (prof[2] - prof[0]);
+        for (int j = 1; j < nd; j++) {
+            const double dj = 0.5 * (prof[j + 2] - prof[j]);
+            if (dj > db) {
+                db = dj;
+                kb = j;
+            }
+        }
+        const bool kp = inside && kb > 0 && kb < nd - 1 && db >= min_contrast;
+        double off = __builtin_nan("");
+        if (kp) {
+            const double dm = 0.5 * (prof[kb + 1] - prof[kb - 1]), dp = 0.5 * (prof[kb + 3] - prof[kb + 1]);
+            const double den = dm - 2 * db + dp;
+            const double delta = den < 0 ? 0.5 * (dm - dp) / den : 0.0;
+            off = -r + 0.5 * (kb + 1) + 0.5 * delta;
+        }
+        double* o = out + (size_t)i * 5;
+        o[0] = P[0];
+        o[1] = P[1];
+        o[2] = nx;
+        o[3] = ny;
+        o[4] = off;
+        keep[i] = kp ? 1 : 0;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -363,6 +480,50 @@ int ctag_synth_frame_host(const int32_t* state, int dict_rows, int dict_cols, ui
         for (int x = 0; x < cols; x++) frame[(ptrdiff_t)y * row_stride + x] = ctag_synth::pixel(F, x, y, rows, cols);
     if (truth) fill_truth(T, truth);
     return CTAG_OK;
+}
+
+int ctag_testkit_dense_edge_probe(ctag_handle* h, const uint8_t* gray, int rows, int cols, ptrdiff_t row_stride, const double* segments,
+                                  int n_seg, const double* K, const double* dist, const double* rvec, const double* tvec,
+                                  int samples_per_edge, double search_px, double min_contrast, double* out, int32_t* keep) {
+    if (!h || !gray || !segments || !K || !dist || !rvec || !tvec || !out || !keep) return CTAG_ERR_ARG;
+    if (rows < 2 || cols < 2 || rows > 32768 || cols > 32768 || row_stride < cols || n_seg < 1 || n_seg > 4096) return CTAG_ERR_ARG;
+    if (samples_per_edge < 1 || samples_per_edge > 64 || !(search_px >= 0.5 && search_px <= 8.0) || !(min_contrast >= 0.0)) return CTAG_ERR_ARG;
+    const double q = search_px * 4.0;
+    if (q != (double)(int)q) return CTAG_ERR_ARG;
+    const int nt = (int)q + 1;  // <= kDenseMaxTaps
+    DenseProbeCam cam{};
+    cam.fx = K[0];
+    cam.fy = K[4];
+    cam.cx = K[2];
+    cam.cy = K[5];
+    for (int i = 0; i < 14; i++) cam.k[i] = dist[i];
+    HandleView v{};
+    handle_view(h, &v);
+    TK_TRY(hipSetDevice(v.device));
+    hipStream_t s = static_cast<hipStream_t>(ctag_stream(h));
+    const size_t img_bytes = (size_t)(rows - 1) * row_stride + cols, n = (size_t)n_seg * samples_per_edge;
+    uint8_t* dimg = nullptr;
+    double *dseg = nullptr, *dout = nullptr;
+    int32_t* dkeep = nullptr;
+    int rc = CTAG_OK;
+    if (hipMalloc(reinterpret_cast<void**>(&dimg), img_bytes) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&dseg), (size_t)n_seg * 12 * 8) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&dout), n * 5 * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&dkeep), n * 4) != hipSuccess)
+        rc = CTAG_ERR_HIP;
+    if (rc == CTAG_OK && (hipMemcpy(dimg, gray, img_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(dseg, segments, (size_t)n_seg * 12 * 8, hipMemcpyHostToDevice) != hipSuccess))
+        rc = CTAG_ERR_HIP;
+    if (rc == CTAG_OK) {
+        hipLaunchKernelGGL(k_dense_edge_probe, dim3(1), dim3(64), 0, s, dimg, rows, cols, row_stride, dseg, n_seg, cam, rvec[0], rvec[1], rvec[2],
+                           tvec[0], tvec[1], tvec[2], samples_per_edge, nt, search_px, min_contrast, dout, dkeep);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess || hipMemcpy(out, dout, n * 5 * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(keep, dkeep, n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = CTAG_ERR_HIP;
+    }
+    (void)hipFree(dimg);
+    (void)hipFree(dseg);
+    (void)hipFree(dout);
+    (void)hipFree(dkeep);
+    return rc;
 }
 
 }  // extern "C"
