@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -61,7 +62,7 @@ struct ctag_handle {
     hipEvent_t ev_fork2 = nullptr;
     int streams = 2;
     const Workspace* last_ws = nullptr;  // whichever ran last (handle_view)
-    bool last_fused = false;  // the last chunk took the fused sweep: its workspace holds the threshold mask, not the half-size image
+    ChunkPlan last_plan{};  // ... and its plan (fused: its workspace holds the threshold mask, not the half-size image)
     const uint8_t* last_frames = nullptr;  // ... and the frames it read (the test kit decimates them again for CTAG_DBG_HALF)
     ptrdiff_t last_row_stride = 0, last_frame_stride = 0;
     const ctag_frame_result* last_out = nullptr;  // ... and where its records went (ctag_get_counters)
@@ -124,13 +125,22 @@ struct ctag_handle {
     // hipGraph cache of the per-chunk kernel chain (CTAG_OPT_GRAPH): a chunk with the same pointers, sizes and parameters is
     // replayed with one hipGraphLaunch instead of ~25 launches / memsets -- what a stream of single frames (main.cpp:52-59)
     // and the small per-GPU shards of a multi-GPU job repeat thousands of times
-    struct GraphEntry {
+    struct GraphKey {
         const void* frames = nullptr;
         void* out = nullptr;
         const void* ws_base = nullptr;
         int n = 0, rows = 0, cols = 0, tw = 0, subpix = 0, dist = 0, keep_pre = 0, channels = 1;
         ptrdiff_t row_stride = 0, frame_stride = 0;
         const void* pend_src = nullptr;  // PendingCtx::src baked into k_markers' arguments (null: no list)
+        bool operator==(const GraphKey& o) const {
+            return frames == o.frames && out == o.out && ws_base == o.ws_base && n == o.n && rows == o.rows && cols == o.cols && tw == o.tw && subpix == o.subpix &&
+                   dist == o.dist && keep_pre == o.keep_pre && channels == o.channels && row_stride == o.row_stride && frame_stride == o.frame_stride &&
+                   pend_src == o.pend_src;
+        }
+    };
+    struct GraphEntry {
+        GraphKey key;
+        ChunkPlan plan;  // what the captured chain runs
         hipGraphExec_t exec = nullptr;
         uint64_t last_use = 0;
     };
@@ -138,7 +148,7 @@ struct ctag_handle {
     uint64_t graph_clock = 0;
     int use_graph = 2;   // CTAG_OPT_GRAPH: 0 off, 1 every chunk, 2 (default) few-frame calls whose pointers / sizes / parameters repeat;
                          // back to 0 after a capture failed once (the direct path takes over for good)
-    GraphEntry last_key;  // automatic mode: the previous few-frame chunk (a graph is only worth capturing for a repeat)
+    GraphKey last_key;   // automatic mode: the previous few-frame chunk (a graph is only worth capturing for a repeat)
     // state of the pose back end (k_pose.hip), created on first use
     void* pose_state = nullptr;
     void (*pose_state_free)(void*) = nullptr;
@@ -173,7 +183,7 @@ void handle_view(const ctag_handle* h, HandleView* out) {
     out->dict = h->dict.data();
     out->dict_rows = h->dict_rows;
     out->dict_cols = h->dict_cols;
-    out->fused = h->last_fused;
+    out->fused = h->last_plan.fused;
     out->frames = h->last_frames;
     out->row_stride = h->last_row_stride;
     out->frame_stride = h->last_frame_stride;
@@ -275,8 +285,6 @@ static int ensure_workspace(ctag_handle* h, ctag_handle::WsSlot& S, int rows, in
         W.pick_table = h->d_pick_table;
         W.pick_table16 = reinterpret_cast<const uint16_t*>(h->d_pick_table + (size_t)kPickN * 200);
         W.aux_stream = h->aux_stream;
-        W.wave_points = h->wave_points;
-        W.fuse_mode = h->fuse_mode;
         W.ev_fork = h->ev_fork;
         W.ev_join = h->ev_join;
         W.big = big;
@@ -439,6 +447,120 @@ static int ensure_workspace(ctag_handle* h, ctag_handle::WsSlot& S, int rows, in
     return ensure_n0();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// which kernel forms a chunk runs
+// ---------------------------------------------------------------------------------------------------
+namespace ctag {
+// The one reader of the chain's developer aids.  Most are read once, at the first call; CTAG_GENERAL_RESIZE and the phase clocks of
+// K2 / K6 on every call (a test sets CTAG_GENERAL_RESIZE between calls of one process).
+DevKnobs dev_knobs() {
+    static const DevKnobs once = [] {
+        DevKnobs k;
+        const struct { const char* name; int* v; int lo; } num[] = {  // lo: the least value taken
+            {"CTAG_FUSED_SWEEP", &k.fused_sweep, INT_MIN}, {"CTAG_FUSE_GENERAL", &k.fuse_general, INT_MIN}, {"CTAG_DEC_MIN_BAND", &k.dec_min_band, INT_MIN},
+            {"CTAG_PACK_MAX", &k.pack_max, INT_MIN}, {"CTAG_BIG_POINTS", &k.big_points, INT_MIN}, {"CTAG_PRESCAN", &k.prescan, INT_MIN},
+            {"CTAG_MASK_SCAN", &k.mask_scan, INT_MIN}, {"CTAG_PACK_GX", &k.pack_gx, INT_MIN}, {"CTAG_SCAN_GX", &k.scan_gx, 1}, {"CTAG_MSCAN_GX", &k.mscan_gx, 1},
+            {"CTAG_BIG_COLS", &k.big_cols, INT_MIN}, {"CTAG_WELSCH_GS", &k.welsch_gs, 1}, {"CTAG_WELSCH_GX", &k.welsch_gx, 1},  // (k_welsch's two row ranges each own a class of edges)
+            {"CTAG_REFINE_GX", &k.refine_gx, INT_MIN}, {"CTAG_REFINE_SUMS_GX", &k.refine_sums_gx, INT_MIN}, {"CTAG_REFINE_XCD", &k.refine_xcd, INT_MIN},
+            {"CTAG_REFINE_LARGE", &k.refine_large, INT_MIN}, {"CTAG_STREAMS_MIN", &k.streams_min, 2 * kLatencyFrames + 2}};
+        for (const auto& e : num)
+            if (getenv(e.name)) *e.v = std::max(e.lo, atoi(getenv(e.name)));
+        k.feat_stamps = getenv("CTAG_FEAT_STAMPS") != nullptr;
+        k.stamps = getenv("CTAG_CCL_STAMPS") != nullptr || getenv("CTAG_QUAD_STAMPS") != nullptr || k.feat_stamps;  // they synchronise inside the chain
+        return k;
+    }();
+    DevKnobs k = once;
+    k.general_resize = getenv("CTAG_GENERAL_RESIZE") != nullptr;
+    k.ccl_stamps = getenv("CTAG_CCL_STAMPS") != nullptr;
+    k.quad_stamps = getenv("CTAG_QUAD_STAMPS") != nullptr;
+    return k;
+}
+
+ChunkPlan plan_chunk(const PlanIn& in) {
+    const DevKnobs& K = in.knobs;
+    const int n = in.nframes, hrows = in.rows / 2, hcols = in.cols / 2;
+    ChunkPlan pl{};
+    pl.nframes = n, pl.channels = in.channels, pl.latency = n <= kLatencyFrames;
+    pl.ccl_stamps = K.ccl_stamps, pl.quad_stamps = K.quad_stamps, pl.feat_stamps = K.feat_stamps;
+    const bool aligned = (((uintptr_t)in.frames | (uintptr_t)in.frame_stride | (uintptr_t)in.row_stride) & 15) == 0;
+    // The fused sweep (k_decimate_mask + the mask front end of K2) takes batches of frames whose half size is a multiple of 320 x 5 (round 6; 1080p, 4K, 8K,
+    // 1920x1200, 1280x720, 2560x1440, 640x480 ...) with the reference's 5x5 window and 16-byte aligned rows; everything else keeps the two-kernel form with `half`.
+    // CTAG_OPT_FUSED_SWEEP: 0 never, 1 batches (default), 2 whenever the frame size allows.
+    const int fuse = in.fuse_mode >= 0 ? in.fuse_mode : K.fused_sweep >= 0 ? K.fused_sweep : 1;
+    // half width a multiple of the labelling tile (320 columns: whole mask words, whole threshold tiles, whole 16-pixel lanes), half height of whole
+    // threshold-tile rows; 1080p / 4K / 8K take the compile-time-band build, the others the run-time-band one
+    const bool fuse_size = fuse && !(in.rows & 1) && !(in.cols & 1) && in.tw == 5 && hcols >= kTileW && hcols % kTileW == 0 && hrows >= 10 && hrows % 5 == 0;
+    // bands of the run-time-band build: a multiple of four (the four waves of a block), about 90-150 rows each; reproduces the 135-row bands of 1080p / 4K / 8K
+    const int fuse_bands = 4 * ((hrows + 599) / 600), fuse_xb = (hcols + kFuseCols - 1) / kFuseCols;
+    // few frames: short bands and the latency-tuned kernels of the two-kernel form instead of one 4-wave block per frame walking 135-row bands
+    const bool fuse_batch = fuse >= 2 || (long)n * fuse_xb * fuse_bands >= 2048;
+    // BGR frames take the fused sweep or none: a call of a few of them converts first (k_bgr2gray) and takes the gray chain, as gray calls of that size do;
+    // so do frames whose 32-bit pixel offsets k_edge_refine could not address (check_args has seen the gray pitch only)
+    pl.bgr_direct = in.bgr_direct && fuse_size && fuse_batch && aligned && in.row_stride < (1 << 24) && (long long)in.rows * in.row_stride <= 0xffffffffLL;
+    pl.fused = fuse_size && aligned && (in.channels == 3 || fuse_batch);
+    // K1.  Batches zero the chain's counters with a kernel of their own at its head; a few frames pass them to the run-time-band decimation,
+    // and get the kernel right before the decimation where it takes another form
+    const bool general = (in.rows & 1) || (in.cols & 1) || K.general_resize;  // odd sizes (env: developer aid, runs even sizes through the general kernel)
+    pl.zero_first = !pl.latency;
+    pl.dec_zero_kernel = pl.latency && (pl.fused || general);
+    pl.dec_zero_list = pl.latency && !pl.dec_zero_kernel;
+    if (pl.fused) {
+        const bool exact = hcols % kFuseCols == 0 && hrows % 135 == 0 && (hrows / 135) % 4 == 0;  // (CTAG_FUSE_GENERAL: developer aid, 1 runs 1080p / 4K / 8K through the run-time-band build)
+        pl.dec = exact && !K.fuse_general ? DecForm::Mask : DecForm::MaskBands;
+        pl.dec_xblocks = fuse_xb, pl.dec_bands = exact && !K.fuse_general ? 0 : fuse_bands, pl.dec_yblocks = pl.dec_bands ? pl.dec_bands / 4 : hrows / 540;
+    } else if (general) {
+        pl.dec = DecForm::General;
+    } else {
+        const int xblocks = ((hcols + 7) / 8 + 63) / 64;
+        int bands = 4 * ((hrows + 4 * CTAG_DEC_BAND_MAX - 1) / (4 * CTAG_DEC_BAND_MAX));
+        // small batches (a single frame through ctag_detect_u8): a band is a sequential walk of a wave, so shorter bands -- more
+        // waves -- cut the latency (one 1080p frame: 135-row bands 0.19 ms, 15-row bands 0.034 ms, 8 rows 21 us, 4-row bands < 0.02 ms); a full batch keeps the tall ones
+        while ((long)n * xblocks * bands < 2048 && (hrows + 2 * bands - 1) / (2 * bands) >= K.dec_min_band) bands *= 2;
+        pl.dec_band_rows = (hrows + bands - 1) / bands, pl.dec_yblocks = bands / 4, pl.dec_xblocks = xblocks;
+        const bool has_tail = (hcols & (CTAG_RESIZE_SIMD_LANES - 1)) != 0;
+        if (pl.dec_band_rows == 135 && pl.dec_zero_list) pl.dec_zero_kernel = true;  // (a few frames get here only with CTAG_DEC_MIN_BAND) the forms below do not zero
+        if (aligned && !has_tail && (hcols & 15) == 0 && pl.dec_band_rows == 135) {
+            pl.dec = DecForm::Wide;  // a lane owns 16 output pixels.  Same-box A/B on 4096 1080p frames: 2.276 -> 2.209 ms (5 waves per SIMD: 2.28)
+            pl.dec_xblocks = (hcols / 16 + 63) / 64;
+        } else {
+            pl.dec = !aligned ? DecForm::Unaligned : pl.dec_band_rows == 135 && !has_tail ? DecForm::Banded135 : DecForm::Banded;
+        }
+    }
+    pl.ccl = pl.fused ? CclForm::Mask : in.tw == 5 ? CclForm::Tw5 : CclForm::Any;
+    // K6
+    pl.refprm = in.kp.thr_line == 1.8f && in.kp.thr_expand == 1.2f && in.kp.c2_far == 2 && in.kp.c2_near == 1 && in.kp.expand_eps == 3.0e-6f;
+    pl.pack_max = K.pack_max > 0 ? std::min(K.pack_max, kSG) : kSG;
+    pl.big_points = in.wave_points > 0 ? in.wave_points : K.big_points > 0 ? K.big_points : (pl.latency ? kLatencyBigPoints : 0x7fffffff);
+    pl.small_cfg = (long long)hrows * hcols <= 960LL * 600;  // up to 1920x1200 frames
+    // chunks that took the fused sweep: the silhouettes come from its threshold mask (k_silhouette_mask), whatever the frame size; CTAG_MASK_SCAN=0 (developer aid, A/B) turns it off
+    pl.mask_scan = pl.fused && !pl.latency && K.mask_scan != 0 && (hcols & 63) == 0;
+    // other batches of frames above 1920x1200: the silhouettes of the packed components come from a kernel of their own (PHASE 3 of k_quad_edges_packed)
+    // (measured: 4K frames, quad_edges 4.07 -> 2.78 ms per 1024 frames; 1080p frames 3.88 -> 4.01 per 4096 -- there a component's box is ~75 x 20, the
+    // packed build's eight components per wave amortise the chain of dependent loads a component costs better than a wave per component does; a
+    // scan-only kernel with the packs' own 8 x 8 lanes at 4 / 5 / 6 waves per SIMD: 4.09 / 4.11 / 4.14 -- the scan is not what the small build waits for)
+    pl.prescan = pl.mask_scan || (!pl.latency && (K.prescan == 2 || (K.prescan == 1 && !pl.small_cfg)));
+    // A few frames per call fork the whole-wave components off the packs ... unless every component is a whole-wave one (the default of such calls: a frame
+    // has a few hundred components and the GPU a thousand SIMDs, so the stage is as long as the longest boundary either way, and without packs there is
+    // nothing to fork or join: 0.476 -> 0.46 ms on test.bmp)
+    pl.all_wave = pl.latency && pl.big_points <= 1;
+    pl.fork = pl.latency && !pl.all_wave;
+    pl.pack_gx = K.pack_gx > 0 ? K.pack_gx : 32;
+    pl.scan_gx = K.scan_gx, pl.mscan_gx = K.mscan_gx;  // (k_silhouette_mask: blocks of one wave, two components each per trip)
+    pl.big_cols = K.big_cols > 0 ? K.big_cols : (pl.latency ? 512 : 4);  // (few frames: every component a block of its own up to 512 per frame; a 2666-blob frame 3.0 -> 2.5 ms against 128)
+    pl.big_max_gx = pl.latency ? 8 : 2;
+    // k_welsch: welsch_gs blocks for the edges of <= 10 points, 320 per block; welsch_gx groups of kWE edges with a block of their own, a block loops when a frame
+    // has more (the synthetic frames have ~210 edges of more than 10 points: 17.8 groups)
+    pl.welsch_gs = K.welsch_gs, pl.welsch_gx = K.welsch_gx;
+    // K7 - K9: a few frames take the kernels tuned for latency; edgeRefine (corner_subpix) of a batch is split into searches and sums
+    if (!in.corner_subpix) pl.refine = RefineForm::None;
+    else if (pl.latency || !CTAG_REFINE_SPLIT) pl.refine = RefineForm::One;
+    else if (K.refine_large && (long long)in.rows * in.cols > 1920LL * 1200) pl.refine = RefineForm::SplitLarge;  // (CTAG_REFINE_LARGE=0: the small staging region for every frame size, A/B)
+    else pl.refine = K.refine_xcd & 1 ? RefineForm::SplitLooping : RefineForm::Split;
+    pl.refine_gx = K.refine_gx, pl.refine_sums_gx = K.refine_sums_gx;  // looping blocks per frame of the searches / of k_edge_refine<2>
+    return pl;
+}
+}  // namespace ctag
+
 static int check_args(ctag_handle* h, const void* frames, int n, int rows, int cols, ptrdiff_t row_stride, int adaptive_thresh, int subpix_dist) {
     if (!h || !frames || n < 0 || rows < 4 || cols < 4 || row_stride < cols || adaptive_thresh < 1 || subpix_dist < 0) return CTAG_ERR_ARG;
     if (adaptive_thresh > kMaxThreshWin) return CTAG_ERR_UNSUPPORTED;
@@ -447,43 +569,46 @@ static int check_args(ctag_handle* h, const void* frames, int n, int rows, int c
     return CTAG_OK;
 }
 
+// "the last chunk" of the probes and counters (handle_view, ctag_get_counters)
+static void note_last(ctag_handle* h, const Workspace& ws, const ChunkPlan& pl, const uint8_t* frames_dev, ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                      const ctag_frame_result* out_dev) {
+    h->last_ws = &ws, h->last_plan = pl, h->last_out = out_dev;
+    h->last_frames = pl.channels == 3 ? nullptr : frames_dev;  // (BGR frames handed to the chain as they are: no gray rows for the half-size probe to decimate)
+    h->last_row_stride = row_stride, h->last_frame_stride = frame_stride;
+}
+
 // enqueue the whole pipeline for `n` device-resident frames (n <= workspace capacity); evs: CTAG_NUM_STAGES + 1 timing events or null
 static int enqueue_chunk(ctag_handle* h, const Workspace& ws, const uint8_t* frames_dev, int n, ptrdiff_t row_stride, ptrdiff_t frame_stride,
                          const DetectParams& p, ctag_frame_result* out_dev, hipEvent_t* evs, const PendingCtx& pend, hipStream_t s = nullptr) {
     if (!s) s = h->stream;
-    h->last_ws = &ws;
-    h->last_out = out_dev;
-    h->last_frames = p.channels == 3 ? nullptr : frames_dev;  // (BGR frames handed to the chain as they are: no gray rows for the half-size probe to decimate)
-    h->last_row_stride = row_stride;
-    h->last_frame_stride = frame_stride;
-    const bool zero_in_k1 = n <= kLatencyFrames;  // a few frames: one launch less at the head of the chain
-    if (!zero_in_k1) HIP_TRY(launch_zero_counters(n, ws, s));
+    const ChunkPlan pl = plan_chunk(PlanIn{ws.g.rows, ws.g.cols, ws.g.tw, n, p.channels, p.corner_subpix, frames_dev, frame_stride, row_stride, ws.kp,
+                                           h->fuse_mode, h->wave_points, h->bgr_direct != 0, dev_knobs()});
+    note_last(h, ws, pl, frames_dev, row_stride, frame_stride, out_dev);
+    if (pl.zero_first) HIP_TRY(launch_zero_counters(pl, ws, s));
     int st = 0;
     auto mark = [&](int i) -> hipError_t { return evs ? hipEventRecord(evs[i], s) : hipSuccess; };
     HIP_TRY(mark(0));
-    const bool fused = sweep_fused(frames_dev, frame_stride, row_stride, n, ws, p.channels == 3);  // threshold where the pixels are computed: 1 bit per pixel to K2, no `half`
-    h->last_fused = fused;
-    if (p.channels == 3 && !fused) return CTAG_ERR_UNSUPPORTED;  // (bgr_direct_ok has checked: BGR frames go through k_bgr2gray otherwise)
-    HIP_TRY(launch_decimate(frames_dev, frame_stride, row_stride, n, ws, s, fused, zero_in_k1, p.channels));
+    if (p.channels == 3 && !pl.fused) return CTAG_ERR_UNSUPPORTED;  // (detect_bgr_device_impl has checked: BGR frames go through k_bgr2gray otherwise)
+    HIP_TRY(launch_decimate(pl, frames_dev, frame_stride, row_stride, ws, s));
     HIP_TRY(mark(++st));
-    HIP_TRY(launch_threshold_ccl(n, ws, s, fused));
+    HIP_TRY(launch_threshold_ccl(pl, ws, s));
     HIP_TRY(mark(++st));
-    HIP_TRY(launch_seam_merge(n, ws, s));
+    HIP_TRY(launch_seam_merge(pl, ws, s));
     HIP_TRY(mark(++st));
-    HIP_TRY(launch_resolve(n, ws, s));
+    HIP_TRY(launch_resolve(pl, ws, s));
     HIP_TRY(mark(++st));
-    HIP_TRY(launch_candidates(n, ws, s));
+    HIP_TRY(launch_candidates(pl, ws, s));
     HIP_TRY(mark(++st));
-    HIP_TRY(launch_quads(n, ws, s, evs ? evs + st + 1 : nullptr, fused ? ws.half : nullptr));  // records one event after each of its first five kernels
+    HIP_TRY(launch_quads(pl, ws, s, evs ? evs + st + 1 : nullptr));  // records one event after each of its first five kernels
     st += 5;
     HIP_TRY(mark(++st));
-    HIP_TRY(launch_features(n, ws, p, s));
+    HIP_TRY(launch_features(pl, ws, p, s));
     HIP_TRY(mark(++st));
-    HIP_TRY(launch_edge_refine(frames_dev, frame_stride, row_stride, n, ws, p, s));
+    HIP_TRY(launch_edge_refine(pl, frames_dev, frame_stride, row_stride, ws, p, s));
     HIP_TRY(mark(++st));
     Workspace wtmp = ws;
     if (!h->keep_pre) wtmp.premarkers = nullptr;
-    HIP_TRY(launch_markers(n, wtmp, p, out_dev, pend, s));
+    HIP_TRY(launch_markers(pl, wtmp, p, out_dev, pend, s));
     HIP_TRY(mark(++st));
     return CTAG_OK;
 }
@@ -503,16 +628,13 @@ static void drop_graphs(ctag_handle* h) {
 
 // replay (or first capture) the chunk as a hipGraph; any failure disables the graph path for this handle and the caller
 // falls back to direct launches -- results are the same either way
-static bool run_chunk_graph(ctag_handle* h, const uint8_t* frames_dev, int n, ptrdiff_t row_stride, ptrdiff_t frame_stride, const DetectParams& p,
-                            ctag_frame_result* out_dev, const PendingCtx& pend) {
+static bool run_chunk_graph(ctag_handle* h, const ctag_handle::GraphKey& key, const uint8_t* frames_dev, int n, ptrdiff_t row_stride, ptrdiff_t frame_stride,
+                            const DetectParams& p, ctag_frame_result* out_dev, const PendingCtx& pend) {
     const Workspace& W = h->batch.ws;
     constexpr size_t kMaxGraphs = 8;
     ctag_handle::GraphEntry* hit = nullptr;
     for (auto& g : h->graphs)
-        if (g.frames == frames_dev && g.out == out_dev && g.ws_base == W.base && g.n == n && g.rows == W.g.rows && g.cols == W.g.cols &&
-            g.tw == p.adaptive_thresh && g.subpix == p.corner_subpix && g.dist == p.subpix_dist && g.keep_pre == (h->keep_pre ? 1 : 0) &&
-            g.row_stride == row_stride && g.frame_stride == frame_stride && g.pend_src == (pend.list ? (const void*)pend.src : nullptr) && g.channels == p.channels)
-            hit = &g;
+        if (g.key == key) hit = &g;
     if (!hit) {
         if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed) != hipSuccess) return false;
         const int r = enqueue_chunk(h, W, frames_dev, n, row_stride, frame_stride, p, out_dev, nullptr, pend);
@@ -538,32 +660,11 @@ static bool run_chunk_graph(ctag_handle* h, const uint8_t* frames_dev, int n, pt
             (void)hipGraphExecDestroy(h->graphs[lru].exec);
             h->graphs.erase(h->graphs.begin() + (ptrdiff_t)lru);
         }
-        ctag_handle::GraphEntry g;
-        g.frames = frames_dev;
-        g.out = out_dev;
-        g.ws_base = W.base;
-        g.n = n;
-        g.rows = W.g.rows;
-        g.cols = W.g.cols;
-        g.pend_src = pend.list ? (const void*)pend.src : nullptr;
-        g.tw = p.adaptive_thresh;
-        g.subpix = p.corner_subpix;
-        g.dist = p.subpix_dist;
-        g.keep_pre = h->keep_pre ? 1 : 0;
-        g.row_stride = row_stride;
-        g.frame_stride = frame_stride;
-        g.channels = p.channels;
-        g.exec = exec;
-        h->graphs.push_back(g);
+        h->graphs.push_back(ctag_handle::GraphEntry{key, h->last_plan, exec, 0});
         hit = &h->graphs.back();
     }
     hit->last_use = ++h->graph_clock;
-    h->last_ws = &W;
-    h->last_out = out_dev;
-    h->last_frames = p.channels == 3 ? nullptr : frames_dev;  // (BGR frames handed to the chain as they are: no gray rows for the half-size probe to decimate)
-    h->last_row_stride = row_stride;
-    h->last_frame_stride = frame_stride;
-    h->last_fused = sweep_fused(frames_dev, frame_stride, row_stride, n, W, p.channels == 3);
+    note_last(h, W, hit->plan, frames_dev, row_stride, frame_stride, out_dev);
     return hipGraphLaunch(hit->exec, h->stream) == hipSuccess;
 }
 
@@ -586,20 +687,17 @@ static int run_chunk(ctag_handle* h, const uint8_t* frames_dev, int n, ptrdiff_t
         evs = h->ev.data() + (size_t)h->ev_sets_used * (CTAG_NUM_STAGES + 1);
         h->ev_sets_used++;
     }
-    static const bool stamps = getenv("CTAG_CCL_STAMPS") != nullptr || getenv("CTAG_QUAD_STAMPS") != nullptr || getenv("CTAG_FEAT_STAMPS") != nullptr;  // developer aids that synchronise inside the chain (no graph capture around them)
+    static const bool stamps = dev_knobs().stamps;  // developer aids that synchronise inside the chain (no graph capture around them)
+    // what a captured chain depends on besides the handle's options (a change of those drops the graphs)
+    const ctag_handle::GraphKey key{frames_dev, out_dev, W.base, n, W.g.rows, W.g.cols, p.adaptive_thresh, p.corner_subpix, p.subpix_dist, h->keep_pre ? 1 : 0,
+                                    p.channels, row_stride, frame_stride, pend.list ? (const void*)pend.src : nullptr};
     bool graph = h->use_graph == 1;
     if (h->use_graph == 2 && n <= kLatencyFrames) {  // one frame per call in a loop (main.cpp:52-59): same staging buffers, same sizes every time
-        ctag_handle::GraphEntry& k = h->last_key;
-        const void* psrc = pend.list ? (const void*)pend.src : nullptr;
-        graph = k.frames == frames_dev && k.out == out_dev && k.ws_base == W.base && k.n == n && k.rows == W.g.rows && k.cols == W.g.cols &&
-                k.tw == p.adaptive_thresh && k.subpix == p.corner_subpix && k.dist == p.subpix_dist && k.keep_pre == (h->keep_pre ? 1 : 0) &&
-                k.row_stride == row_stride && k.frame_stride == frame_stride && k.pend_src == psrc;
-        k.frames = frames_dev, k.out = out_dev, k.ws_base = W.base, k.n = n, k.rows = W.g.rows, k.cols = W.g.cols, k.tw = p.adaptive_thresh,
-        k.subpix = p.corner_subpix, k.dist = p.subpix_dist, k.keep_pre = h->keep_pre ? 1 : 0, k.row_stride = row_stride, k.frame_stride = frame_stride,
-        k.pend_src = psrc;
+        graph = key == h->last_key;
+        h->last_key = key;
     }
     if (!evs && graph && !stamps) {
-        if (run_chunk_graph(h, frames_dev, n, row_stride, frame_stride, p, out_dev, pend)) return CTAG_OK;
+        if (run_chunk_graph(h, key, frames_dev, n, row_stride, frame_stride, p, out_dev, pend)) return CTAG_OK;
         h->use_graph = 0;  // capture / instantiate / launch failed: direct launches from now on
         drop_graphs(h);
     }
@@ -639,8 +737,9 @@ static int detect_device_impl(ctag_handle* h, const uint8_t* frames_dev, int n, 
     const int chunk = std::min(n, h->max_chunk);
     DetectParams p{adaptive_thresh, corner_subpix, subpix_dist, h->feature_size, h->dict_rows, h->dict_cols, h->d_dict, h->d_dict_pos};
     p.channels = channels;
-    static const bool two_env = getenv("CTAG_STREAMS_MIN") != nullptr;
-    static const int two_min = two_env ? std::max(2 * kLatencyFrames + 2, atoi(getenv("CTAG_STREAMS_MIN"))) : 256;
+    static const int streams_min = dev_knobs().streams_min;
+    const bool two_env = streams_min > 0;
+    const int two_min = two_env ? streams_min : 256;
     // chunks of [448, 1024) frames stay on one stream: their halves (224-511 frames) leave the stage kernels' grids a partial last round of
     // blocks on each stream.  Measured (round 5, 1080p, two handles alternating, K frames/s split / whole): 256: 189 / 178, 384: 213 / 214,
     // 512: 222 / 237, 640: 229 / 234, 768: 232 / 234, 1024: 247 / 241, 2048: 255 / 250 (tools/step_overlap.py).
@@ -872,9 +971,9 @@ static int detect_bgr_device_impl(ctag_handle* h, const uint8_t* bgr_dev, int n,
     // decimation kernel loads the BGR bytes themselves and converts as it consumes them, edgeRefine converts the boxes it stages: no gray image is
     // written or read back (8.3 of the 24 MB a 1080p frame moved through the gray slab).  CTAG_OPT_BGR_DIRECT 0 turns it off.
     // Calls of a few frames (round 6): the fused sweep's K1 is one block per frame band group -- 0.19 ms for a single 1080p frame against < 0.02 ms
-    // of the short-band kernels -- so they convert first and take the gray chain, as gray calls of that size do (sweep_fused).
-    if (h->bgr_direct && sweep_fused_size(rows, cols, adaptive_thresh, h->fuse_mode) && sweep_fused_batch(rows, cols, n, h->fuse_mode) && row_stride < (1 << 24) && (long long)rows * row_stride <= 0xffffffffLL &&
-        (((uintptr_t)bgr_dev | (uintptr_t)frame_stride | (uintptr_t)row_stride) & 15) == 0) {
+    // of the short-band kernels -- so they convert first and take the gray chain, as gray calls of that size do (plan_chunk).
+    if (plan_chunk(PlanIn{rows, cols, adaptive_thresh, n, 3, corner_subpix, bgr_dev, frame_stride, row_stride, h->kp, h->fuse_mode, h->wave_points, h->bgr_direct != 0,
+                          dev_knobs()}).bgr_direct) {
         const PendingCtx pc{h->d_pending, h->d_pending_count, h->pending_cap, bgr_dev, (int64_t)frame_stride, (int64_t)row_stride,
                             rows, cols, 3, adaptive_thresh, corner_subpix, subpix_dist};
         const int r = detect_device_impl(h, bgr_dev, n, rows, cols, row_stride, frame_stride, adaptive_thresh, corner_subpix, subpix_dist, out_dev, &pc, 3);

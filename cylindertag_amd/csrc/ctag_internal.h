@@ -193,8 +193,6 @@ struct Workspace {
     const uint16_t* pick_table16 = nullptr;  // [kPickN2 - kPickN][20][10]
     hipStream_t aux_stream = nullptr;     // owned by the handle: side branch for few-frame calls (launch_quads)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int wave_points = 0;                  // CTAG_OPT_WAVE_POINTS (0 = automatic)
-    int fuse_mode = -1;                   // CTAG_OPT_FUSED_SWEEP (-1 = not set: CTAG_FUSED_SWEEP from the environment, else 1)
     KParams kp{};                         // the handle's tunables
     // features
     void* quad_derived = nullptr;   // [F][kQuadStride] x 48 B (K7 scratch)
@@ -245,24 +243,80 @@ __device__ __forceinline__ uint32_t gray4_of(uint32_t w0, uint32_t w1, uint32_t 
 }
 #endif
 
-// kernel launchers (each enqueues on `s`, returns hipGetLastError())
-hipError_t launch_zero_counters(int nframes, const Workspace& ws, hipStream_t s);  // frame_ncomp, frame_flags, line_count, clp_used, ovf_count
-// fused: k_decimate_mask + the mask front end of K2 (1 bit per pixel between them, no `half`) -- sweep_fused says when that form applies
-bool sweep_fused(const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, int nframes, const Workspace& ws, bool always = false);
-bool sweep_fused_size(int rows, int cols, int tw, int fuse_mode);
-bool sweep_fused_batch(int rows, int cols, int nframes, int fuse_mode);  // a call of that many frames is a batch for the fused sweep (else: short-band kernels)
-hipError_t launch_decimate(const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, int nframes, const Workspace& ws, hipStream_t s, bool fused = false, bool zero_too = false,
-                           int channels = 1);  // channels = 3: BGR frames, fused form only
-hipError_t launch_threshold_ccl(int nframes, const Workspace& ws, hipStream_t s, bool fused = false);
-hipError_t launch_seam_merge(int nframes, const Workspace& ws, hipStream_t s);
-hipError_t launch_resolve(int nframes, const Workspace& ws, hipStream_t s);
-hipError_t launch_candidates(int nframes, const Workspace& ws, hipStream_t s);
-hipError_t launch_quads(int nframes, const Workspace& ws, hipStream_t s, hipEvent_t* ev5 = nullptr, const uint8_t* mask = nullptr);  // mask: the chunk took the fused sweep (ws.half holds its threshold mask)  // ev5: 5 events, one after each kernel but the last
-hipError_t launch_features(int nframes, const Workspace& ws, const DetectParams& p, hipStream_t s);
-hipError_t launch_edge_refine(const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, int nframes, const Workspace& ws, const DetectParams& p, hipStream_t s);
+// ---- which kernel forms a chunk runs ---------------------------------------------------------------------
+// Host-side constants the choice depends on (the kernels use them too)
+#ifndef CTAG_RESIZE_SIMD_LANES  // width of OpenCV's vector body in the vertical pass of the decimation (k_sweep.hip)
+#define CTAG_RESIZE_SIMD_LANES 8
+#endif
+#ifndef CTAG_DEC_BAND_MAX  // tallest band of the two-kernel decimation (k_sweep.hip)
+#define CTAG_DEC_BAND_MAX 150
+#endif
+#ifndef CTAG_REFINE_SPLIT
+#define CTAG_REFINE_SPLIT 1  // batches: searches and ordered sums as two kernels (k_edge_refine<MODE>)
+#endif
+constexpr int kFuseCols = 960;          // half-resolution columns per wave of the fused sweep (k_decimate_mask)
+constexpr int kSG = 8;                  // lanes per component of the packed quad build (k_quad_edges_packed)
+constexpr int kLatencyBigPoints = 1;    // calls of <= kLatencyFrames frames: components with a boundary capacity above this get a wave of their own -- all of them (launch_quads)
+
+// Developer aids from the environment, all read by dev_knobs (ctag_api.hip); the defaults are what runs without them
+struct DevKnobs {
+    int fused_sweep = -1;                        // CTAG_FUSED_SWEEP: as CTAG_OPT_FUSED_SWEEP (-1: not set)
+    int fuse_general = 0, dec_min_band = 4;      // CTAG_FUSE_GENERAL=1: 1080p / 4K / 8K through the run-time-band fused build; CTAG_DEC_MIN_BAND
+    bool general_resize = false;                 // CTAG_GENERAL_RESIZE: even sizes through the general decimation (read on every call)
+    int pack_max = 0, big_points = 0;            // CTAG_PACK_MAX, CTAG_BIG_POINTS (0: automatic)
+    int prescan = 1, mask_scan = 1;              // CTAG_PRESCAN (0 never, 1 frames above 1920x1200, 2 always), CTAG_MASK_SCAN
+    int pack_gx = 0, scan_gx = 48, mscan_gx = 48, big_cols = 0, welsch_gs = 1, welsch_gx = 18;  // CTAG_PACK_GX ... CTAG_WELSCH_GX: blocks per frame (0: automatic)
+    int refine_gx = 32, refine_sums_gx = 12, refine_xcd = 3, refine_large = 1;                // CTAG_REFINE_GX, _SUMS_GX, _XCD, _LARGE
+    int streams_min = 0;                         // CTAG_STREAMS_MIN (0: the built-in rule)
+    bool stamps = false;                         // a *_STAMPS switch was set at the first call: no graph capture
+    bool ccl_stamps = false, quad_stamps = false, feat_stamps = false;  // CTAG_CCL_STAMPS, CTAG_QUAD_STAMPS (read on every call), CTAG_FEAT_STAMPS
+};
+DevKnobs dev_knobs();
+
+// What a chunk's kernel forms are chosen from: values only (`frames` is looked at for its alignment, never read)
+struct PlanIn {
+    int rows, cols, tw, nframes, channels, corner_subpix;  // nframes: of the chunk (BGR calls: of the call, for bgr_direct)
+    const void* frames;
+    ptrdiff_t frame_stride, row_stride;
+    KParams kp;
+    int fuse_mode, wave_points; bool bgr_direct;  // the handle's CTAG_OPT_FUSED_SWEEP (-1: not set), CTAG_OPT_WAVE_POINTS, CTAG_OPT_BGR_DIRECT
+    DevKnobs knobs;
+};
+enum class DecForm : int32_t { Mask, MaskBands, General, Wide, Banded135, Banded, Unaligned };  // k_decimate_mask<135> / <0>, k_decimate_general, k_decimate_wide, k_decimate
+enum class CclForm : int32_t { Mask, Tw5, Any };                                               // k_threshold_ccl<5, true> / <5> / <0>
+enum class RefineForm : int32_t { None, One, SplitLarge, SplitLooping, Split };                // k_edge_refine<0> / <1, large> / <1> looping / <1>
+// The kernel forms and grid sizes of one chunk (plan_chunk, ctag_api.hip); every launcher of the chain takes it and only launches
+struct ChunkPlan {
+    int nframes, channels;
+    bool fused;           // k_decimate_mask + the mask front end of K2: `half` holds the threshold mask (1 bit per pixel)
+    bool bgr_direct;      // BGR frames: the chain reads them as they are (else k_bgr2gray, then the gray chain)
+    bool zero_first, dec_zero_kernel, dec_zero_list;  // the counters are zeroed by k_zero_counters at the head / right before K1, or inside K1 (ZeroList)
+    DecForm dec; int dec_xblocks, dec_yblocks, dec_band_rows, dec_bands;  // K1 blocks per frame (columns x band groups), rows per band (k_decimate), bands (k_decimate_mask<0>)
+    CclForm ccl;
+    bool latency;         // a few frames: the kernels tuned for the latency of the call
+    bool small_cfg;       // frames up to 1920x1200: the small packed configuration
+    bool refprm;          // the reference's line thresholds: K6's builds with them compiled in
+    bool mask_scan, prescan;  // the packed components' silhouettes from the fused sweep's mask (k_silhouette_mask) / from a kernel of their own
+    bool all_wave, fork;  // every component a wave of its own (no packed build) / packed and whole-wave builds side by side on the handle's second stream
+    int pack_max, big_points, pack_gx, scan_gx, mscan_gx, big_cols, big_max_gx, welsch_gs, welsch_gx;  // k_pack's arguments, K6's blocks per frame
+    RefineForm refine; int refine_gx, refine_sums_gx;
+    bool ccl_stamps, quad_stamps, feat_stamps;
+};
+ChunkPlan plan_chunk(const PlanIn& in);
+
+// kernel launchers of the chain (each enqueues on `s`, returns hipGetLastError())
+hipError_t launch_zero_counters(const ChunkPlan& pl, const Workspace& ws, hipStream_t s);  // frame_ncomp, frame_flags, line_count, clp_used, ovf_count
+hipError_t launch_decimate(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, hipStream_t s);
+hipError_t launch_threshold_ccl(const ChunkPlan& pl, const Workspace& ws, hipStream_t s);
+hipError_t launch_seam_merge(const ChunkPlan& pl, const Workspace& ws, hipStream_t s);
+hipError_t launch_resolve(const ChunkPlan& pl, const Workspace& ws, hipStream_t s);
+hipError_t launch_candidates(const ChunkPlan& pl, const Workspace& ws, hipStream_t s);
+hipError_t launch_quads(const ChunkPlan& pl, const Workspace& ws, hipStream_t s, hipEvent_t* ev5 = nullptr);  // ev5: 5 events, one after each kernel but the last
+hipError_t launch_features(const ChunkPlan& pl, const Workspace& ws, const DetectParams& p, hipStream_t s);
+hipError_t launch_edge_refine(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, const DetectParams& p, hipStream_t s);
+hipError_t launch_markers(const ChunkPlan& pl, const Workspace& ws, const DetectParams& p, ctag_frame_result* out, const PendingCtx& pend, hipStream_t s);
 // sums and maxima over the frames of the last chunk: components, candidates, quads, features, markers -> out10 (device, 5 x int64 sums then 5 x int64 maxima)
 hipError_t launch_counters(int nframes, const Workspace& ws, const ctag_frame_result* results, long long* out10, hipStream_t s);
-hipError_t launch_markers(int nframes, const Workspace& ws, const DetectParams& p, ctag_frame_result* out, const PendingCtx& pend, hipStream_t s);
 size_t threshold_ccl_lds_bytes(int tw);
 // adaptive-threshold bound table for a dark cap (host): returns false when the cap is outside what K2's packed compares hold
 bool build_threshold_table(float dark_cap, uint8_t* table /* 256*256 */, int* dim, int* tcap);

@@ -466,9 +466,6 @@ struct RefinePtrs {
 };
 constexpr int kRefineSamples = 128;               // samples of an edge searched per pass (the reference's minimum sample count, :615)
 constexpr int kRefineThreads = 2 * kRefineSamples; // two edges side by side: waves 0-1 edge e, waves 2-3 edge e + 1
-#ifndef CTAG_REFINE_SPLIT
-#define CTAG_REFINE_SPLIT 1  // batches: searches and ordered sums as two kernels (k_edge_refine<MODE>)
-#endif
 #ifndef CTAG_REFINE_STAGE_DEEP
 #define CTAG_REFINE_STAGE_DEEP 12
 #endif
@@ -1749,8 +1746,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_markers(MarkerPtrs P, int nframe
 // launchers
 // =====================================================================================================
 // developer aid (CTAG_FEAT_STAMPS=1): phase clocks of k_features (slots 0-5) and k_markers (16-24); `report` waits and prints
-static unsigned long long* feat_stamps(hipStream_t s, bool report) {
-    static const bool want = getenv("CTAG_FEAT_STAMPS") != nullptr;
+static unsigned long long* feat_stamps(bool want, hipStream_t s, bool report) {
     static unsigned long long* d = nullptr;
     if (!want) return nullptr;
     if (!d) {
@@ -1769,42 +1765,35 @@ static unsigned long long* feat_stamps(hipStream_t s, bool report) {
     return d;
 }
 
-hipError_t launch_features(int nframes, const Workspace& ws, const DetectParams& p, hipStream_t s) {
-    FeatPtrs P{ws.ncand, ws.quads, reinterpret_cast<QuadDerived*>(ws.quad_derived), ws.quad_index, ws.nquads, ws.nfeat, ws.status, ws.frame_flags, ws.feat0, ws.feat1, ws.feat2, feat_stamps(s, false), ws.kp.angle, ws.frame_long, ws.cand_cap};
-    if (nframes <= kLatencyFrames) hipLaunchKernelGGL(k_features<512>, dim3(nframes), dim3(512), 0, s, P, nframes, p.feature_size);
-    else hipLaunchKernelGGL(k_features<128>, dim3(nframes), dim3(128), 0, s, P, nframes, p.feature_size);
+hipError_t launch_features(const ChunkPlan& pl, const Workspace& ws, const DetectParams& p, hipStream_t s) {
+    FeatPtrs P{ws.ncand, ws.quads, reinterpret_cast<QuadDerived*>(ws.quad_derived), ws.quad_index, ws.nquads, ws.nfeat, ws.status, ws.frame_flags, ws.feat0, ws.feat1, ws.feat2, feat_stamps(pl.feat_stamps, s, false), ws.kp.angle, ws.frame_long, ws.cand_cap};
+    if (pl.latency) hipLaunchKernelGGL(k_features<512>, dim3(pl.nframes), dim3(512), 0, s, P, pl.nframes, p.feature_size);
+    else hipLaunchKernelGGL(k_features<128>, dim3(pl.nframes), dim3(128), 0, s, P, pl.nframes, p.feature_size);
     return hipGetLastError();
 }
-hipError_t launch_edge_refine(const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, int nframes, const Workspace& ws, const DetectParams& p, hipStream_t s) {
-    if (!p.corner_subpix) return hipSuccess;
+hipError_t launch_edge_refine(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, const DetectParams& p, hipStream_t s) {
+    const int nframes = pl.nframes, refine_gx = pl.refine_gx, f8 = ((nframes + 7) / 8) * 8;
     RefinePtrs P{frames, frame_stride, row_stride, ws.nfeat, ws.status, ws.feat1, ws.feat2, ws.refine_n0, ws.frame_long, p.channels == 3 ? 3 : 1};
-    static const int refine_gx = getenv("CTAG_REFINE_GX") ? atoi(getenv("CTAG_REFINE_GX")) : 32;  // looping blocks per frame of the other forms
-    const bool few = nframes <= kLatencyFrames || !CTAG_REFINE_SPLIT;
-    const dim3 grid(few ? CTAG_MAX_FEATURES * 2 : refine_gx, nframes);  // a few frames: a block per quad -- the call is as long as its longest block, and looping blocks triple it
-    static const int refine_sums_gx = getenv("CTAG_REFINE_SUMS_GX") ? atoi(getenv("CTAG_REFINE_SUMS_GX")) : 12;  // looping blocks per frame of k_edge_refine<2>
-    if (few) {  // one kernel, one launch
-        hipLaunchKernelGGL(k_edge_refine<0>, grid, dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, 0);
-    } else {
-        static const int xcd = getenv("CTAG_REFINE_XCD") ? atoi(getenv("CTAG_REFINE_XCD")) : 3;
-        const int f8 = ((nframes + 7) / 8) * 8;
-        // (round 5: searches and sums alternating over slices of 256 / 512 / 1024 frames, so that a slice's n0 is read back while the memory-side cache
-        // still holds it, lost -- 5.13 / 4.95 / 4.84 against 4.71-4.76 ms per 4096 frames: the round trip through HBM is not what the sums kernel waits for)
-        static const int large_env = getenv("CTAG_REFINE_LARGE") ? atoi(getenv("CTAG_REFINE_LARGE")) : 1;  // 0: the small staging region for every frame size (A/B)
-        const bool large = large_env && (long long)ws.g.rows * ws.g.cols > 1920LL * 1200;
-        if (large) hipLaunchKernelGGL((k_edge_refine<1, kRefineRegionLarge>), dim3(f8 * refine_gx), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, refine_gx);
-        else if (xcd & 1) hipLaunchKernelGGL(k_edge_refine<1>, dim3(f8 * refine_gx), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, refine_gx);
-        else hipLaunchKernelGGL(k_edge_refine<1>, grid, dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, 0);
-        hipLaunchKernelGGL(k_edge_refine_sums, dim3(f8 * refine_sums_gx), dim3(64), 0, s, P, nframes, refine_sums_gx);
-        hipLaunchKernelGGL(k_edge_refine_tail, dim3(13, nframes), dim3(64), 0, s, P, nframes, 13);  // 13 x 8 quads: the synthetic frames' 96; a block loops when a frame has more
-        hipLaunchKernelGGL(k_edge_refine_long, dim3(4, nframes), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes);
+    if (pl.refine == RefineForm::None) return hipSuccess;
+    if (pl.refine == RefineForm::One) {  // one kernel, one launch: a block per quad -- the call is as long as its longest block, and looping blocks triple it
+        hipLaunchKernelGGL(k_edge_refine<0>, dim3(CTAG_MAX_FEATURES * 2, nframes), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, 0);
+        return hipGetLastError();
     }
+    // (round 5: searches and sums alternating over slices of 256 / 512 / 1024 frames, so that a slice's n0 is read back while the memory-side cache
+    // still holds it, lost -- 5.13 / 4.95 / 4.84 against 4.71-4.76 ms per 4096 frames: the round trip through HBM is not what the sums kernel waits for)
+    if (pl.refine == RefineForm::SplitLarge) hipLaunchKernelGGL((k_edge_refine<1, kRefineRegionLarge>), dim3(f8 * refine_gx), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, refine_gx);
+    else if (pl.refine == RefineForm::SplitLooping) hipLaunchKernelGGL(k_edge_refine<1>, dim3(f8 * refine_gx), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, refine_gx);
+    else hipLaunchKernelGGL(k_edge_refine<1>, dim3(refine_gx, nframes), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, 0);
+    hipLaunchKernelGGL(k_edge_refine_sums, dim3(f8 * pl.refine_sums_gx), dim3(64), 0, s, P, nframes, pl.refine_sums_gx);
+    hipLaunchKernelGGL(k_edge_refine_tail, dim3(13, nframes), dim3(64), 0, s, P, nframes, 13);  // 13 x 8 quads: the synthetic frames' 96; a block loops when a frame has more
+    hipLaunchKernelGGL(k_edge_refine_long, dim3(4, nframes), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes);
     return hipGetLastError();
 }
-hipError_t launch_markers(int nframes, const Workspace& ws, const DetectParams& p, ctag_frame_result* out, const PendingCtx& pend, hipStream_t s) {
-    MarkerPtrs P{ws.nfeat, ws.status, ws.frame_flags, ws.feat2, p.dict, ws.premarkers, out, feat_stamps(s, false), p.dict_pos, ws.kp, pend, ws.big ? 1 : 0};
-    if (nframes <= kLatencyFrames) hipLaunchKernelGGL(k_markers<8>, dim3(nframes), dim3(512), 0, s, P, nframes, p.feature_size, p.dict_rows, p.dict_cols);
-    else hipLaunchKernelGGL(k_markers<1>, dim3(nframes), dim3(64), 0, s, P, nframes, p.feature_size, p.dict_rows, p.dict_cols);
-    (void)feat_stamps(s, true);
+hipError_t launch_markers(const ChunkPlan& pl, const Workspace& ws, const DetectParams& p, ctag_frame_result* out, const PendingCtx& pend, hipStream_t s) {
+    MarkerPtrs P{ws.nfeat, ws.status, ws.frame_flags, ws.feat2, p.dict, ws.premarkers, out, feat_stamps(pl.feat_stamps, s, false), p.dict_pos, ws.kp, pend, ws.big ? 1 : 0};
+    if (pl.latency) hipLaunchKernelGGL(k_markers<8>, dim3(pl.nframes), dim3(512), 0, s, P, pl.nframes, p.feature_size, p.dict_rows, p.dict_cols);
+    else hipLaunchKernelGGL(k_markers<1>, dim3(pl.nframes), dim3(64), 0, s, P, pl.nframes, p.feature_size, p.dict_rows, p.dict_cols);
+    (void)feat_stamps(pl.feat_stamps, s, true);
     return hipGetLastError();
 }
 

@@ -333,15 +333,6 @@ __device__ __forceinline__ void welsch_restart(const Pts pts, int n, const Picks
 #ifndef CTAG_PACK_WAVES
 #define CTAG_PACK_WAVES 2
 #endif
-#ifndef CTAG_SCAN_ROWS4
-#define CTAG_SCAN_ROWS4 0  // 1: the boundary-only build keeps four label rows in flight per lane (measured: 44 spilled registers, 4.03 vs 3.94 ms)
-#endif
-#ifndef CTAG_PACK_SPLIT_LARGE
-#define CTAG_PACK_SPLIT_LARGE 0  // the same for the large configuration (4K frames)
-#endif
-#ifndef CTAG_PACK_SPLIT
-#define CTAG_PACK_SPLIT 1  // the small-configuration packed build as two kernels (boundary, then edge clusters): see k_quad_edges_packed
-#endif
 constexpr int kPackWords = CTAG_PACK_WORDS;  // LDS words shared by the up to 8 components of a wave (large configuration)
 // Two builds of the packed kernel.  The kernel is bound by dependent LDS round trips (24 % of the issue roof at 2 waves per
 // SIMD), so for frames of 1080p class -- boundaries of ~150 points, a pack of 5 components in 10 KB -- the small configuration
@@ -351,11 +342,9 @@ constexpr int kPackWords = CTAG_PACK_WORDS;  // LDS words shared by the up to 8 
 #define CTAG_PACK_WAVES_P2 4
 #endif
 constexpr int kPackWordsSmall = 2560, kPackWavesSmall = 4, kPackWavesSmallP2 = CTAG_PACK_WAVES_P2;  // (the second kernel's own waves per SIMD: see launch_quads)
-constexpr int kSG = 8;
 constexpr int kUnwind = 8;  // stack frames the whole-wave build tests at once when it unwinds (<= 8: 8 lanes each)
 constexpr int kWaveWords = 8192;      // LDS words of the common whole-wave build (32 KB: five components per CU)
 constexpr int kWaveWordsMax = 36864;  // ... of the build for the longest boundaries (144 KB: one per CU)
-constexpr int kLatencyBigPoints = 1;  // calls of <= kLatencyFrames frames: components with a boundary capacity above this get a wave of their own -- all of them (launch_quads)
 __host__ __device__ __forceinline__ int pack_points(int w, int h) { return min(2 * (w + h), w * h) + 1; }
 // LDS words one component needs in the packed kernel: silhouette arrays + boundary list + stack / ping-pong list
 __host__ __device__ __forceinline__ int pack_need(int w, int h) {
@@ -1626,9 +1615,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                     atomicMax(&rig[y], (unsigned)(xl0 + 32 - __clz(bits)));
                 }
             };
-#ifndef CTAG_SCAN_UNCOND
-#define CTAG_SCAN_UNCOND 1
-#endif
             // Unconditional loads from clamped addresses, the lanes / rows outside the box zeroed by a select: a load inside a branch makes the
             // compiler wait for EVERY load in flight where the branch rejoins, and the rows "in flight" arrived one at a time
             // (Round 5, from the ISA: `ld_ok ? v : 0` behind the load was enough for the compiler to put the load back INSIDE a branch on ld_ok -- with s_waitcnt
@@ -1641,37 +1627,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                 asm volatile("" ::"v"(v.x));
 #endif
             };
-            auto load_row = [&](int y) {
-                if (CTAG_SCAN_UNCOND) {
-                    return *reinterpret_cast<const uint4*>(limg + (size_t)(y_min + min(y, h - 1)) * g.lp + gx0);
-                }
-                uint4 r = make_uint4(0, 0, 0, 0);
-                if (ld_ok && y < h) r = *reinterpret_cast<const uint4*>(limg + (size_t)(y_min + y) * g.lp + gxf);
-                return r;
-            };
-            auto load_row1 = [&](int y) {
-                if (CTAG_SCAN_UNCOND) {
-                    return *reinterpret_cast<const uint4*>(limg + (size_t)(y_min + min(y, h - 1)) * g.lp + gx1);
-                }
-                uint4 r = make_uint4(0, 0, 0, 0);
-                if (ld_ok1 && y < h) r = *reinterpret_cast<const uint4*>(limg + (size_t)(y_min + y) * g.lp + gxf + kChunk);
-                return r;
-            };
+            auto load_row = [&](int y) { return *reinterpret_cast<const uint4*>(limg + (size_t)(y_min + min(y, h - 1)) * g.lp + gx0); };
+            auto load_row1 = [&](int y) { return *reinterpret_cast<const uint4*>(limg + (size_t)(y_min + min(y, h - 1)) * g.lp + gx1); };
             auto process_row = [&](const uint4& v, const uint4& v1, int y) {
-                if (CTAG_SCAN_UNCOND) {
-                    touch(v);
-                    touch(v1);
-                }
+                touch(v);
+                touch(v1);
                 const int trow = ((y_min + y) / kTileH) * g.tiles_x;
                 if (trow != cur_trow) {
                     cur_trow = trow;
                     // the tiles' labels in the packed form (label | label << 16) fg_masks takes; 0xffffffff (no label) stays 0xffffffff
                     unsigned la, lb;
                     labels_of_tile(trow + tcol0, la, lb, over0);
-                    if (CTAG_SCAN_UNCOND && !ld_ok) la = lb = 0xffffffffu, over0 = false;  // a lane whose columns lie outside the box loads the box's first columns: it matches nothing
+                    if (!ld_ok) la = lb = 0xffffffffu, over0 = false;  // a lane whose columns lie outside the box loads the box's first columns: it matches nothing
                     LA0 = (la & 0xffffu) * 0x10001u, LB0 = (lb & 0xffffu) * 0x10001u;
                     LA1 = LB1 = 0xffffffffu, over1 = false;
-                    if (SG == 64 || !CTAG_SCAN_UNCOND || ld_ok1) {  // (most boxes are narrower than 64 columns: no second chunk, no second look-up)
+                    if (SG == 64 || ld_ok1) {  // (most boxes are narrower than 64 columns: no second chunk, no second look-up)
                         labels_of_tile(trow + tcol1, la, lb, over1);
                         LA1 = (la & 0xffffu) * 0x10001u, LB1 = (lb & 0xffffu) * 0x10001u;
                     }
@@ -1692,7 +1662,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             };
             // label rows in flight per lane (the scan is bound by latency, not by bytes): 4 in the large configuration, 2 in the
             // small one, whose 128-register budget the eight row registers of the deeper pipeline would spill
-            if constexpr (WAVES >= 4 && !(PHASE == 1 && CTAG_SCAN_ROWS4)) {
+            if constexpr (WAVES >= 4) {
                 uint4 r0 = load_row(0), r1 = load_row(1);
                 uint4 s0 = load_row1(0), s1 = load_row1(1);
                 for (int y = 0; y < h; y += 2) {
@@ -2919,7 +2889,51 @@ __device__ __forceinline__ void quad_final_one(const QuadPtrs& P, const FrameGeo
     }
 }
 
-hipError_t launch_quads(int nframes, const Workspace& ws, hipStream_t s, hipEvent_t* ev5, const uint8_t* mask) {
+#ifndef CTAG_SCAN_WAVES
+#define CTAG_SCAN_WAVES 4
+#endif
+// K6's boundary kernels in the build for the handle's line thresholds: the packed builds on `s` (none when every component is a whole-wave one),
+// `mid` recorded behind them, then the oversize components, a wave each: working sets up to kWaveWords in a 32 KB build (5 per CU) on `sb`, the
+// rest (up to the 144 KB a 4K frame's longest possible boundary needs three times over) in a build that owns a CU's LDS on `s_max`
+template <bool REF>
+static void launch_quad_edges(const ChunkPlan& pl, const QuadPtrs& P, const FrameGeom& g, hipStream_t s, hipStream_t sb, hipStream_t s_max, hipEvent_t mid) {
+    const int nframes = pl.nframes;
+    const dim3 grid(nframes, pl.pack_gx);
+    if (pl.all_wave) {
+    } else if (pl.prescan) {
+        if (pl.mask_scan)
+            if (pl.small_cfg) hipLaunchKernelGGL((k_silhouette_mask<4, 32, kMaskScanWords>), dim3(nframes, pl.mscan_gx), dim3(64), 0, s, P, g, nframes);
+            else hipLaunchKernelGGL((k_silhouette_mask<8, 64, kMaskScanWordsLarge>), dim3(nframes, 2 * pl.mscan_gx), dim3(64), 0, s, P, g, nframes);
+        else
+            hipLaunchKernelGGL((k_quad_edges_packed<64, kScanWords, CTAG_SCAN_WAVES, false, true, 3>), dim3(nframes, pl.scan_gx), dim3(64), 0, s, P, g, nframes, 0);
+        if (pl.small_cfg) {
+            hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmall, false, REF, 1, true>), grid, dim3(64), 0, s, P, g, nframes, 0);
+            hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmallP2, false, REF, 2>), grid, dim3(64), 0, s, P, g, nframes, 0);
+        } else {
+            hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWords, CTAG_PACK_WAVES, false, REF, 0, true>), grid, dim3(64), 0, s, P, g, nframes, 0);
+        }
+    } else if (pl.small_cfg) {
+        hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmall, false, REF, 1>), grid, dim3(64), 0, s, P, g, nframes, 0);
+        hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmallP2, false, REF, 2>), grid, dim3(64), 0, s, P, g, nframes, 0);
+    } else {
+        hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWords, CTAG_PACK_WAVES, false, REF>), grid, dim3(64), 0, s, P, g, nframes, 0);
+    }
+    if (mid) (void)hipEventRecord(mid, s);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    dev = dev < 0 || dev >= 64 ? 0 : dev;
+    static bool have[64] = {false};
+    if (!have[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quad_edges_packed<64, kWaveWordsMax, 1, true, REF>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  kWaveWordsMax * 4);
+        have[dev] = true;
+    }
+    hipLaunchKernelGGL((k_quad_edges_packed<64, kWaveWords, 1, false, REF>), dim3(nframes, pl.big_cols), dim3(64), 0, sb, P, g, nframes, 0);
+    hipLaunchKernelGGL((k_quad_edges_packed<64, kWaveWordsMax, 1, true, REF>), dim3(nframes, pl.big_max_gx), dim3(64), kWaveWordsMax * 4, s_max, P, g, nframes, kWaveWords);
+}
+
+hipError_t launch_quads(const ChunkPlan& pl, const Workspace& ws, hipStream_t s, hipEvent_t* ev5) {
+    const int nframes = pl.nframes;
     int evi = 0;
     auto mark = [&]() {
         if (ev5) (void)hipEventRecord(ev5[evi++], s);
@@ -2928,108 +2942,28 @@ hipError_t launch_quads(int nframes, const Workspace& ws, hipStream_t s, hipEven
                ws.line_count, ws.clp_used, ws.cl_pool, ws.line_desc, ws.line_sorted, ws.line_long, ws.line_fit, ws.cand_aux, ws.pick_table, ws.pick_table16, ws.pool_tile, ws.member_head, ws.member_next, ws.npacks, ws.packs, ws.pack_order, nullptr, ws.kp.thr_line, ws.kp.thr_expand, ws.kp.rac, ws.kp.c2_far, ws.kp.c2_near,
                ws.cand_cap, ws.line_cap, ws.cl_cap, ws.kp.expand_eps};
     static unsigned long long* d_stamps = nullptr;
-    const bool want_stamps = getenv("CTAG_QUAD_STAMPS") != nullptr;
-    if (want_stamps) {
+    if (pl.quad_stamps) {
         if (!d_stamps) (void)hipMalloc(reinterpret_cast<void**>(&d_stamps), 32 * 8);
         (void)hipMemsetAsync(d_stamps, 0, 32 * 8, s);
         P.stamps = d_stamps;
     }
-    static const int pack_max_env = getenv("CTAG_PACK_MAX") ? atoi(getenv("CTAG_PACK_MAX")) : 0;
-    const int pack_max = pack_max_env > 0 ? std::min(pack_max_env, kSG) : kSG;
-    static const int big_env = getenv("CTAG_BIG_POINTS") ? atoi(getenv("CTAG_BIG_POINTS")) : 0;
-    const bool latency = nframes <= kLatencyFrames;
-    const int big_points = ws.wave_points > 0 ? ws.wave_points : big_env > 0 ? big_env : (latency ? kLatencyBigPoints : 0x7fffffff);
-    const bool small_cfg = (long long)ws.g.hrows * ws.g.hcols <= 960LL * 600;  // up to 1920x1200 frames
-    const int pack_words = small_cfg ? kPackWordsSmall : kPackWords;
-    // batches: the silhouettes of the packed components come from a kernel of their own (PHASE 3 of k_quad_edges_packed); CTAG_PRESCAN=0 (developer aid) keeps the scan in the packed builds
-    static const int prescan_env = getenv("CTAG_PRESCAN") ? atoi(getenv("CTAG_PRESCAN")) : 1;
-    // (measured: 4K frames, quad_edges 4.07 -> 2.78 ms per 1024 frames; 1080p frames 3.88 -> 4.01 per 4096 -- there a component's box is ~75 x 20, the
-    // packed build's eight components per wave amortise the chain of dependent loads a component costs better than a wave per component does; a
-    // scan-only kernel with the packs' own 8 x 8 lanes at 4 / 5 / 6 waves per SIMD: 4.09 / 4.11 / 4.14 -- the scan is not what the small build waits for)
-    const bool small_frames = (long long)ws.g.hrows * ws.g.hcols <= 960LL * 600;
-    // chunks that took the fused sweep: the silhouettes come from its threshold mask (k_silhouette_mask), whatever the frame size; CTAG_MASK_SCAN=0 (developer aid, A/B) turns it off
-    static const int mask_scan_env = getenv("CTAG_MASK_SCAN") ? atoi(getenv("CTAG_MASK_SCAN")) : 1;
-    const bool mask_scan = mask != nullptr && !latency && mask_scan_env != 0 && (ws.g.hcols & 63) == 0;
-    const bool prescan = mask_scan || (!latency && (prescan_env == 2 || (prescan_env == 1 && !small_frames)));
-    P.mask = reinterpret_cast<const uint64_t*>(mask);
+    P.mask = pl.fused ? reinterpret_cast<const uint64_t*>(ws.half) : nullptr;  // the fused sweep's threshold mask
     P.mask_words = ws.g.hcols >> 6;
-    hipLaunchKernelGGL(k_pack, dim3(nframes), dim3(nframes <= kLatencyFrames ? 1024 : 64), 0, s, P, nframes, pack_max, big_points, pack_words, mask_scan ? -(small_cfg ? kMaskScanWords : kMaskScanWordsLarge) : prescan ? kScanWords : 0);
+    const int pack_words = pl.small_cfg ? kPackWordsSmall : kPackWords;
+    const int scan_words = pl.mask_scan ? -(pl.small_cfg ? kMaskScanWords : kMaskScanWordsLarge) : pl.prescan ? kScanWords : 0;
+    hipLaunchKernelGGL(k_pack, dim3(nframes), dim3(pl.latency ? 1024 : 64), 0, s, P, nframes, pl.pack_max, pl.big_points, pack_words, scan_words);
     mark();
     // A few frames per call (the reference's one detect() per camera frame): the call is as long as its slowest component,
     // so the packs and the whole-wave components run side by side (second stream, fork/join by events)
-    // ... unless every component is a whole-wave one (the default of such calls: a frame has a few hundred components and the GPU a thousand SIMDs, so
-    // the stage is as long as the longest boundary either way, and without packs there is nothing to fork or join: 0.476 -> 0.46 ms on test.bmp)
-    const bool all_wave = latency && big_points <= 1;
-    const bool fork = latency && !all_wave && ws.aux_stream != nullptr;
+    const bool fork = pl.fork && ws.aux_stream != nullptr;
     hipStream_t sb = s;
     if (fork) {
         (void)hipEventRecord(ws.ev_fork, s);
         (void)hipStreamWaitEvent(ws.aux_stream, ws.ev_fork, 0);
         sb = ws.aux_stream;
     }
-    static const int pack_gx_env = getenv("CTAG_PACK_GX") ? atoi(getenv("CTAG_PACK_GX")) : 0;
-    const int pack_gx = pack_gx_env > 0 ? pack_gx_env : 32;
-    const bool refprm = ws.kp.thr_line == 1.8f && ws.kp.thr_expand == 1.2f && ws.kp.c2_far == 2 && ws.kp.c2_near == 1 && ws.kp.expand_eps == 3.0e-6f;
-#ifndef CTAG_SCAN_WAVES
-#define CTAG_SCAN_WAVES 4
-#endif
-    static const int scan_gx = getenv("CTAG_SCAN_GX") ? std::max(1, atoi(getenv("CTAG_SCAN_GX"))) : 48;
-    static const int mscan_gx = getenv("CTAG_MSCAN_GX") ? std::max(1, atoi(getenv("CTAG_MSCAN_GX"))) : 48;  // blocks (waves) per frame of k_silhouette_mask, two components each per trip
-#define CTAG_LAUNCH_PACKED(REF)                                                                                                                              \
-    do {                                                                                                                                                     \
-        if (prescan) {                                                                                                                                       \
-            if (mask_scan)                                                                                                                                   \
-                if (small_cfg) hipLaunchKernelGGL((k_silhouette_mask<4, 32, kMaskScanWords>), dim3(nframes, mscan_gx), dim3(64), 0, s, P, ws.g, nframes);     \
-                else hipLaunchKernelGGL((k_silhouette_mask<8, 64, kMaskScanWordsLarge>), dim3(nframes, 2 * mscan_gx), dim3(64), 0, s, P, ws.g, nframes);      \
-            else                                                                                                                                             \
-                hipLaunchKernelGGL((k_quad_edges_packed<64, kScanWords, CTAG_SCAN_WAVES, false, true, 3>), dim3(nframes, scan_gx), dim3(64), 0, s, P, ws.g, nframes, 0); \
-            if (small_cfg) {                                                                                                                                 \
-                hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmall, false, REF, 1, true>), dim3(nframes, pack_gx), dim3(64), 0, s, P, ws.g, nframes, 0); \
-                hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmallP2, false, REF, 2>), dim3(nframes, pack_gx), dim3(64), 0, s, P, ws.g, nframes, 0); \
-            } else {                                                                                                                                         \
-                hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWords, CTAG_PACK_WAVES, false, REF, CTAG_PACK_SPLIT_LARGE ? 1 : 0, true>), dim3(nframes, pack_gx), dim3(64), 0, s, P, ws.g, nframes, 0); \
-                if (CTAG_PACK_SPLIT_LARGE)                                                                                                                   \
-                    hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWords, CTAG_PACK_WAVES, false, REF, 2>), dim3(nframes, pack_gx), dim3(64), 0, s, P, ws.g, nframes, 0); \
-            }                                                                                                                                                \
-        } else if (small_cfg)                                                                                                                                \
-        {                                                                                                                                                    \
-            hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmall, false, REF, CTAG_PACK_SPLIT ? 1 : 0>), dim3(nframes, pack_gx), dim3(64), 0, s, P, ws.g, nframes, 0); \
-            if (CTAG_PACK_SPLIT)                                                                                                                             \
-                hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmallP2, false, REF, 2>), dim3(nframes, pack_gx), dim3(64), 0, s, P, ws.g, nframes, 0); \
-        } else {                                                                                                                                             \
-            hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWords, CTAG_PACK_WAVES, false, REF, CTAG_PACK_SPLIT_LARGE ? 1 : 0>), dim3(nframes, pack_gx), dim3(64), 0, s, P, ws.g, nframes, 0); \
-            if (CTAG_PACK_SPLIT_LARGE)                                                                                                                       \
-                hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWords, CTAG_PACK_WAVES, false, REF, 2>), dim3(nframes, pack_gx), dim3(64), 0, s, P, ws.g, nframes, 0); \
-        }                                                                                                                                                    \
-    } while (0)
-    if (all_wave) {
-    } else if (refprm) CTAG_LAUNCH_PACKED(true);
-    else CTAG_LAUNCH_PACKED(false);
-#undef CTAG_LAUNCH_PACKED
-    mark();
-    // oversize components, a wave each: working sets up to kWaveWords in a 32 KB build (5 per CU), the rest (up to the 144 KB a
-    // 4K frame's longest possible boundary needs three times over) in a build that owns a CU's LDS
-    static const int bcols_env = getenv("CTAG_BIG_COLS") ? atoi(getenv("CTAG_BIG_COLS")) : 0;
-    const int bcols = bcols_env > 0 ? bcols_env : (latency ? 512 : 4);  // (few frames: every component a block of its own up to 512 per frame; a 2666-blob frame 3.0 -> 2.5 ms against 128)
-#define CTAG_LAUNCH_WAVE(REF)                                                                                                                               \
-    do {                                                                                                                                                    \
-        int dev = 0;                                                                                                                                        \
-        (void)hipGetDevice(&dev);                                                                                                                           \
-        dev = dev < 0 || dev >= 64 ? 0 : dev;                                                                                                               \
-        static bool have[64] = {false};                                                                                                                     \
-        if (!have[dev]) {                                                                                                                                   \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quad_edges_packed<64, kWaveWordsMax, 1, true, REF>),                                  \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kWaveWordsMax * 4);                                                       \
-            have[dev] = true;                                                                                                                               \
-        }                                                                                                                                                   \
-        hipLaunchKernelGGL((k_quad_edges_packed<64, kWaveWords, 1, false, REF>), dim3(nframes, bcols), dim3(64), 0, sb, P, ws.g, nframes, 0);                \
-        /* few-frame calls: the build for the longest boundaries (rarely any) behind the packs on the main stream, not behind the 32 KB build */          \
-        hipLaunchKernelGGL((k_quad_edges_packed<64, kWaveWordsMax, 1, true, REF>), dim3(nframes, latency ? 8 : 2), dim3(64), kWaveWordsMax * 4,              \
-                           fork ? s : sb, P, ws.g, nframes, kWaveWords);                                                                                    \
-    } while (0)
-    if (refprm) CTAG_LAUNCH_WAVE(true);
-    else CTAG_LAUNCH_WAVE(false);
-#undef CTAG_LAUNCH_WAVE
+    // (few-frame calls: the build for the longest boundaries (rarely any) behind the packs on the main stream, not behind the 32 KB build)
+    (pl.refprm ? launch_quad_edges<true> : launch_quad_edges<false>)(pl, P, ws.g, s, sb, fork ? s : sb, ev5 ? ev5[evi++] : nullptr);
     if (fork) {
         (void)hipEventRecord(ws.ev_join, sb);
         (void)hipStreamWaitEvent(s, ws.ev_join, 0);
@@ -3037,16 +2971,15 @@ hipError_t launch_quads(int nframes, const Workspace& ws, hipStream_t s, hipEven
     mark();
     hipLaunchKernelGGL(k_line_sort, dim3(nframes), dim3(kLineSortThreads), 0, s, P, nframes);
     mark();
-    static const int welsch_gs = getenv("CTAG_WELSCH_GS") ? std::max(1, atoi(getenv("CTAG_WELSCH_GS"))) : 1;   // blocks per frame for the edges of <= 10 points, 320 per block
-    static const int welsch_gx = getenv("CTAG_WELSCH_GX") ? std::max(1, atoi(getenv("CTAG_WELSCH_GX"))) : 18;   // (both at least 1: the grid's two row ranges each own a class of edges)   // groups of kWE edges per frame with a block of their own; a block loops when a frame has more (the synthetic frames have ~210 edges of more than 10 points: 17.8 groups)
-    if (latency && ws.welsch_rs) {  // one wave per (edge, restart); frames it declines (more edges / longer edges than it holds) fall through to k_welsch
+    const bool welsch_lat = pl.latency && ws.welsch_rs;
+    if (welsch_lat) {  // one wave per (edge, restart); frames it declines (more edges / longer edges than it holds) fall through to k_welsch
         hipLaunchKernelGGL(k_welsch_lat, dim3(20, 512, nframes), dim3(64), 0, s, P, nframes, ws.welsch_rs);
     }
-    hipLaunchKernelGGL(k_welsch, dim3(nframes, welsch_gx + welsch_gs), dim3(kWT), 0, s, P, nframes, latency && ws.welsch_rs ? ws.welsch_rs : (const float*)nullptr, welsch_gx);
+    hipLaunchKernelGGL(k_welsch, dim3(nframes, pl.welsch_gx + pl.welsch_gs), dim3(kWT), 0, s, P, nframes, welsch_lat ? ws.welsch_rs : (const float*)nullptr, pl.welsch_gx);
     mark();
-    if (latency) hipLaunchKernelGGL(k_quad_final<8>, dim3(std::min(ws.cand_cap, kLdsCand) / 8, nframes), dim3(64), 0, s, P, ws.g, nframes);
+    if (pl.latency) hipLaunchKernelGGL(k_quad_final<8>, dim3(std::min(ws.cand_cap, kLdsCand) / 8, nframes), dim3(64), 0, s, P, ws.g, nframes);
     else hipLaunchKernelGGL(k_quad_final<1>, dim3(std::min(ws.cand_cap, kLdsCand) / 64, nframes), dim3(64), 0, s, P, ws.g, nframes);
-    if (want_stamps) {
+    if (pl.quad_stamps) {
         unsigned long long h[32];
         (void)hipStreamSynchronize(s);
         (void)hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost);

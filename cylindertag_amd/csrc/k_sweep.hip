@@ -25,10 +25,9 @@ __device__ __forceinline__ bool map_block(int b, int per_frame, int nframes, int
 static inline int grid_for(int nframes, int per_frame) { return ((nframes + 7) / 8) * 8 * per_frame; }
 
 // the fused sweep (k_decimate_mask below)
-constexpr int kFuseCols = 960;     // half-resolution columns per wave
 constexpr int kFuseLanes = 60;     // ... = 60 lanes x 16 pixels
 constexpr int kFuseTiles = kFuseCols / 5;
-static hipError_t launch_decimate_mask(const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, int nframes, const Workspace& ws, hipStream_t s, int channels);
+static hipError_t launch_decimate_mask(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, hipStream_t s);
 
 // =====================================================================================================
 // K1: bicubic 2x decimation, u8 -> u8.  OpenCV resize(INTER_CUBIC) for an exact 2x scale has the fixed
@@ -41,10 +40,6 @@ static hipError_t launch_decimate_mask(const uint8_t* frames, ptrdiff_t frame_st
 // Band height: the host picks it so that a frame has a multiple of four bands (every 4-wave block full) of at most
 // kDecBandMax rows -- 135 rows for 1080p and 4K.  Taller bands re-read fewer prologue rows (6 source rows per band);
 // measured on 4096 1080p frames: 45 rows 2.35 ms, 90 (half-empty blocks) 2.58, 135 2.21, 180 2.49, 270 2.97.
-#ifndef CTAG_DEC_BAND_MAX
-#define CTAG_DEC_BAND_MAX 150
-#endif
-constexpr int kDecBandMax = CTAG_DEC_BAND_MAX;
 
 struct Raw18 {  // source pixels x0-1 .. x0+16 of one row
     uint32_t w0, w1, w2, w3;
@@ -123,9 +118,6 @@ __device__ __forceinline__ void hpass(const Raw18& r, uint32_t q[4]) {
 
 // Width of OpenCV's vector body in the vertical pass (8: a 128-bit universal-intrinsics build, the assumption; 16: a 256-bit body -- EXTRA=-DCTAG_RESIZE_SIMD_LANES=16
 // with the oracle's ctago_set_variants(.., 16)).  Frames whose half width is a multiple of 16 (1080p, 4K, 8K, test.bmp) give the same image either way.
-#ifndef CTAG_RESIZE_SIMD_LANES
-#define CTAG_RESIZE_SIMD_LANES 8
-#endif
 static_assert(CTAG_RESIZE_SIMD_LANES == 8 || CTAG_RESIZE_SIMD_LANES == 16, "vector body of 8 or 16 columns");
 // vertical pass.  OpenCV's float vector body computes t = s0*b0 + (s1*b1 + (s2*b2 + s3*b3)) with s = 64*q and
 // b = {-192,1216,1216,-192} * 2^-22 and rounds half-to-even.  Every product and partial sum is a multiple of 2^-10 of
@@ -395,92 +387,33 @@ __global__ __launch_bounds__(256) void k_decimate_general(const uint8_t* __restr
     half[((size_t)frame * g.hrows + y) * g.hp + x] = (uint8_t)min(max(out, 0), 255);
 }
 
-// The fused sweep (k_decimate_mask + the mask front end of K2) takes batches of frames whose half size is a multiple of 320 x 5 (round 6; 1080p, 4K, 8K,
-// 1920x1200, 1280x720, 2560x1440, 640x480 ...) with the reference's 5x5 window and 16-byte aligned rows; everything else keeps the two-kernel form with `half`.
-// CTAG_FUSED_SWEEP=0 (developer aid, A/B) turns it off.
-static int fuse_env() {
-    static const int env_mode = getenv("CTAG_FUSED_SWEEP") ? atoi(getenv("CTAG_FUSED_SWEEP")) : -1;
-    return env_mode;
-}
-// the frame sizes the fused sweep takes (adaptiveThresh 5; half size a multiple of 320 x 5), whatever the batch
-bool sweep_fused_size(int rows, int cols, int tw, int fuse_mode) {
-    const int env = fuse_mode >= 0 ? fuse_mode : fuse_env() >= 0 ? fuse_env() : 1;
-    if (!env || (rows & 1) || (cols & 1) || tw != 5) return false;
-    const int hcols = cols / 2, hrows = rows / 2;
-    // (round 6) half width a multiple of the labelling tile (320 columns: whole mask words, whole threshold tiles, whole 16-pixel lanes), half height of whole
-    // threshold-tile rows; 1080p / 4K / 8K take the compile-time-band build, the others (1920x1200, 1280x720, 2560x1440, 640x480 ...) the run-time-band one
-    return hcols >= kTileW && hcols % kTileW == 0 && hrows >= 10 && hrows % 5 == 0;
-}
-static int fuse_bands(int hrows);
-// whether a call of nframes frames of this size is a batch for the fused sweep's tall bands (the rule sweep_fused applies to gray frames): BGR calls
-// below it take k_bgr2gray + the latency-tuned short-band kernels instead of one 4-wave block per frame walking 135-row bands
-bool sweep_fused_batch(int rows, int cols, int nframes, int fuse_mode) {
-    const int env = fuse_mode >= 0 ? fuse_mode : fuse_env() >= 0 ? fuse_env() : 1;
-    return env >= 2 || (long)nframes * ((cols / 2 + kFuseCols - 1) / kFuseCols) * fuse_bands(rows / 2) >= 2048;
-}
-// always: BGR frames (they take this form or none: the caller has checked sweep_fused_size and the alignment)
-bool sweep_fused(const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, int nframes, const Workspace& ws, bool always) {
-    const int env = ws.fuse_mode >= 0 ? ws.fuse_mode : fuse_env() >= 0 ? fuse_env() : 1;  // CTAG_OPT_FUSED_SWEEP: 0 never, 1 batches (default), 2 whenever the frame size allows
+hipError_t launch_decimate(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, hipStream_t s) {
     const FrameGeom& g = ws.g;
-    if (!sweep_fused_size(g.rows, g.cols, g.tw, ws.fuse_mode)) return false;
-    if ((((uintptr_t)frames | (uintptr_t)frame_stride | (uintptr_t)row_stride) & 15) != 0) return false;
-    const int bands = fuse_bands(g.hrows);
-    if (!always && env < 2 && (long)nframes * ((g.hcols + kFuseCols - 1) / kFuseCols) * bands < 2048) return false;  // few frames: short bands and the latency-tuned kernels (launch_decimate)
-    return true;
-}
-
-hipError_t launch_zero_counters(int nframes, const Workspace& ws, hipStream_t s);
-// zero_too: the chain's counters have not been zeroed (a call of a few frames): the run-time-band kernel does it, any other form gets k_zero_counters first
-hipError_t launch_decimate(const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, int nframes, const Workspace& ws, hipStream_t s, bool fused, bool zero_too, int channels) {
-    if (channels != 1 && !(channels == 3 && fused)) return hipErrorInvalidValue;  // BGR frames take the fused sweep or none (bgr_fused, ctag_api.hip)
-    const FrameGeom& g = ws.g;
-    const bool general = (g.rows & 1) || (g.cols & 1) || getenv("CTAG_GENERAL_RESIZE");
-    ZeroList Z{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    if (zero_too) {
-        if (fused || general || nframes > 256) {
-            const hipError_t e = launch_zero_counters(nframes, ws, s);
-            if (e != hipSuccess) return e;
-            zero_too = false;
-        } else {
-            Z = ZeroList{ws.frame_ncomp, ws.frame_flags, ws.line_count, ws.clp_used, ws.ovf_count, nframes};
-        }
+    const int nframes = pl.nframes;
+    if (pl.dec_zero_kernel) {
+        const hipError_t e = launch_zero_counters(pl, ws, s);
+        if (e != hipSuccess) return e;
     }
-    if (fused) return launch_decimate_mask(frames, frame_stride, row_stride, nframes, ws, s, channels);
-    if (general) {  // odd sizes (env: developer aid, runs even sizes through the general kernel)
+    if (pl.fused) return launch_decimate_mask(pl, frames, frame_stride, row_stride, ws, s);
+    if (pl.dec == DecForm::General) {
         hipLaunchKernelGGL(k_decimate_general, dim3((g.hcols + 255) / 256, g.hrows, nframes), dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g,
                            nframes, ws.rz_xofs, ws.rz_alpha, ws.rz_yofs, ws.rz_beta);
         return hipGetLastError();
     }
-    const int lanes = (g.hcols + 7) / 8;
-    const int xblocks = (lanes + 63) / 64;
-    int bands = 4 * ((g.hrows + 4 * kDecBandMax - 1) / (4 * kDecBandMax));
-    // small batches (a single frame through ctag_detect_u8): a band is a sequential walk of a wave, so shorter bands -- more
-    // waves -- cut the latency (one 1080p frame: 135-row bands 0.19 ms, 15-row bands 0.034 ms, 4-row bands < 0.02 ms); a full batch keeps the tall ones
-    static const int min_band = getenv("CTAG_DEC_MIN_BAND") ? atoi(getenv("CTAG_DEC_MIN_BAND")) : 4;  // one frame: 15-row bands 34 us, 8 rows 21, 4 rows < 20
-    while ((long)nframes * xblocks * bands < 2048 && (g.hrows + 2 * bands - 1) / (2 * bands) >= min_band) bands *= 2;
-    const int band_rows = (g.hrows + bands - 1) / bands;
-    const int yblocks = bands / 4;
+    const ZeroList Z = pl.dec_zero_list ? ZeroList{ws.frame_ncomp, ws.frame_flags, ws.line_count, ws.clp_used, ws.ovf_count, nframes} : ZeroList{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    const int xblocks = pl.dec_xblocks, yblocks = pl.dec_yblocks, band_rows = pl.dec_band_rows;
     const int grid = grid_for(nframes, xblocks * yblocks);
-    const bool aligned = (((uintptr_t)frames | (uintptr_t)frame_stride | (uintptr_t)row_stride) & 15) == 0;
 #define CTAG_DEC_LAUNCH(AL, B, TL)                                                                                                         \
     hipLaunchKernelGGL((k_decimate<AL, B, TL>), dim3(grid), dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, nframes, xblocks, \
                        yblocks, band_rows, Z)
-    const bool has_tail = (g.hcols & (CTAG_RESIZE_SIMD_LANES - 1)) != 0;
-    static const int wide_env = getenv("CTAG_DEC_WIDE") ? atoi(getenv("CTAG_DEC_WIDE")) : 1;  // same-box A/B on 4096 1080p frames: 2.276 -> 2.209 ms (5 waves per SIMD: 2.28)
-    if (zero_too && band_rows == 135) {  // (a few frames never get here: their bands are short) the forms below do not zero
-        const hipError_t e = launch_zero_counters(nframes, ws, s);
-        if (e != hipSuccess) return e;
+    switch (pl.dec) {
+        case DecForm::Wide:  // a lane owns 16 output pixels: a wave spans 1024 half-res columns
+            hipLaunchKernelGGL((k_decimate_wide<135>), dim3(grid), dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, nframes, xblocks, yblocks, band_rows);
+            break;
+        case DecForm::Banded135: CTAG_DEC_LAUNCH(true, 135, false); break;  // 1080p and 4K frames
+        case DecForm::Banded: CTAG_DEC_LAUNCH(true, 0, true); break;
+        default: CTAG_DEC_LAUNCH(false, 0, true); break;
     }
-    if (wide_env && aligned && !has_tail && (g.hcols & 15) == 0 && band_rows == 135) {  // a lane owns 16 output pixels: a wave spans 1024 half-res columns
-        const int xb = (g.hcols / 16 + 63) / 64;
-        hipLaunchKernelGGL((k_decimate_wide<135>), dim3(grid_for(nframes, xb * yblocks)), dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, nframes, xb, yblocks,
-                           band_rows);
-    } else if (aligned && band_rows == 135 && !has_tail)  // 1080p and 4K frames
-        CTAG_DEC_LAUNCH(true, 135, false);
-    else if (aligned)
-        CTAG_DEC_LAUNCH(true, 0, true);
-    else
-        CTAG_DEC_LAUNCH(false, 0, true);
 #undef CTAG_DEC_LAUNCH
     return hipGetLastError();
 }
@@ -1030,33 +963,19 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(CH =
     if (ye == g.hrows) emit_tile_row(g.trows - 1);  // the frame's last tile row has no lower neighbour: a border row (bound 0)
 }
 
-// bands of the general form: a multiple of four (the four waves of a block), about 90-150 rows each; reproduces the 135-row bands of 1080p / 4K / 8K
-static int fuse_bands(int hrows) { return 4 * ((hrows + 599) / 600); }
-static bool fuse_exact(const FrameGeom& g) { return g.hcols % kFuseCols == 0 && g.hrows % 135 == 0 && (g.hrows / 135) % 4 == 0; }
-static hipError_t launch_decimate_mask(const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, int nframes, const Workspace& ws, hipStream_t s, int channels) {
+static hipError_t launch_decimate_mask(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, hipStream_t s) {
     const FrameGeom& g = ws.g;
-    const int xb = (g.hcols + kFuseCols - 1) / kFuseCols;
-    static const int gen_env = getenv("CTAG_FUSE_GENERAL") ? atoi(getenv("CTAG_FUSE_GENERAL")) : 0;  // developer aid: 1 runs 1080p / 4K / 8K through the run-time-band build too
-    if (!fuse_exact(g) || gen_env) {
-        const int nb = fuse_bands(g.hrows), yblocks = nb / 4;
-        if (channels == 3)
-            hipLaunchKernelGGL((k_decimate_mask<0, 4, 3>), dim3(grid_for(nframes, xb * yblocks)), dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, ws.kp, nframes, xb, yblocks, nb);
+    const int nframes = pl.nframes, xb = pl.dec_xblocks, yblocks = pl.dec_yblocks;
+    const dim3 grid(grid_for(nframes, xb * yblocks));
+    if (pl.dec == DecForm::MaskBands) {
+        if (pl.channels == 3)
+            hipLaunchKernelGGL((k_decimate_mask<0, 4, 3>), grid, dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, ws.kp, nframes, xb, yblocks, pl.dec_bands);
         else
-            hipLaunchKernelGGL((k_decimate_mask<0, 4>), dim3(grid_for(nframes, xb * yblocks)), dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, ws.kp, nframes, xb, yblocks, nb);
-        return hipGetLastError();
-    }
-    if (channels == 3) {  // BGR frames: converted where they are loaded
-        const int yblocks = g.hrows / 135 / 4;
-        hipLaunchKernelGGL((k_decimate_mask<135, 4, 3>), dim3(grid_for(nframes, xb * yblocks)), dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, ws.kp, nframes, xb, yblocks, 0);
-        return hipGetLastError();
-    }
-    static const int band_env = getenv("CTAG_FUSE_BAND") ? atoi(getenv("CTAG_FUSE_BAND")) : 135;  // developer aid (A/B): 270-row bands in two-wave blocks
-    if (band_env == 270 && g.hrows % 540 == 0) {
-        const int yblocks = g.hrows / 270 / 2;
-        hipLaunchKernelGGL((k_decimate_mask<270, 2>), dim3(grid_for(nframes, xb * yblocks)), dim3(128), 0, s, frames, frame_stride, row_stride, ws.half, g, ws.kp, nframes, xb, yblocks, 0);
+            hipLaunchKernelGGL((k_decimate_mask<0, 4>), grid, dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, ws.kp, nframes, xb, yblocks, pl.dec_bands);
+    } else if (pl.channels == 3) {  // BGR frames: converted where they are loaded
+        hipLaunchKernelGGL((k_decimate_mask<135, 4, 3>), grid, dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, ws.kp, nframes, xb, yblocks, 0);
     } else {
-        const int yblocks = g.hrows / 135 / 4;
-        hipLaunchKernelGGL((k_decimate_mask<135, 4>), dim3(grid_for(nframes, xb * yblocks)), dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, ws.kp, nframes, xb, yblocks, 0);
+        hipLaunchKernelGGL((k_decimate_mask<135, 4>), grid, dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, ws.kp, nframes, xb, yblocks, 0);
     }
     return hipGetLastError();
 }
@@ -1687,14 +1606,14 @@ static_assert(kSlotCapBig < 0x7fff, "labels are 1..slots or 0x8000 | culled slot
 static_assert(2 * kSlotCap <= 256, "FrameGeom::pool_cap = 256 entries per tile holds two first passes");
 static_assert(kRunCapBig % kCclThreads == 0 && kRunCapBig >= (kTileW / 2) * kTileH && kSlotCapBig >= (kTileW / 2) * ((kTileH + 1) / 2), "second-pass caps hold any tile");
 
-hipError_t launch_threshold_ccl(int nframes, const Workspace& ws, hipStream_t s, bool fused) {
+hipError_t launch_threshold_ccl(const ChunkPlan& pl, const Workspace& ws, hipStream_t s) {
     const FrameGeom& g = ws.g;
+    const int nframes = pl.nframes;
     const size_t lds = threshold_ccl_lds_bytes(g.tw);
     const int grid = grid_for(nframes, g.tiles_x * g.tiles_y);  // one 320x30 tile per block
     SweepPtrs P = sweep_ptrs(ws);
     static unsigned long long* d_stamps = nullptr;
-    const bool want_stamps = getenv("CTAG_CCL_STAMPS") != nullptr;
-    if (want_stamps) {
+    if (pl.ccl_stamps) {
         if (!d_stamps) (void)hipMalloc(reinterpret_cast<void**>(&d_stamps), 16 * 8);
         (void)hipMemsetAsync(d_stamps, 0, 16 * 8, s);
         P.stamps = d_stamps;
@@ -1712,14 +1631,14 @@ hipError_t launch_threshold_ccl(int nframes, const Workspace& ws, hipStream_t s,
         }
     };
     static size_t have_big5[64] = {0}, have_big0[64] = {0}, have_0[64] = {0}, have_big5m[64] = {0};
-    if (fused) {
+    if (pl.ccl == CclForm::Mask) {
         // (measured and not kept: K2 over work lists of the tiles with foreground, flagged by k_decimate_mask -- as looping blocks 1.33-1.55 ms, as a
         // block per list entry 1.36 ms per 4096 frames against 1.25 ms for a block per tile: the blocks of background tiles load, look and leave in the
         // shadow of their neighbours' label phases, while the lists cost two more dependent loads per tile and 0.1 ms of atomics in K1)
         hipLaunchKernelGGL((k_threshold_ccl<5, true>), dim3(grid), dim3(kCclThreads), lds, s, P, g, ws.kp, nframes);
         want_lds(reinterpret_cast<const void*>(k_threshold_ccl_big<5, true>), lds_big, have_big5m);
         hipLaunchKernelGGL((k_threshold_ccl_big<5, true>), dim3(grid_big), dim3(kCclThreads), lds_big, s, P, g, ws.kp);
-    } else if (g.tw == 5) {
+    } else if (pl.ccl == CclForm::Tw5) {
         hipLaunchKernelGGL(k_threshold_ccl<5>, dim3(grid), dim3(kCclThreads), lds, s, P, g, ws.kp, nframes);
         want_lds(reinterpret_cast<const void*>(k_threshold_ccl_big<5>), lds_big, have_big5);
         hipLaunchKernelGGL(k_threshold_ccl_big<5>, dim3(grid_big), dim3(kCclThreads), lds_big, s, P, g, ws.kp);
@@ -1729,7 +1648,7 @@ hipError_t launch_threshold_ccl(int nframes, const Workspace& ws, hipStream_t s,
         want_lds(reinterpret_cast<const void*>(k_threshold_ccl_big<0>), lds_big, have_big0);
         hipLaunchKernelGGL(k_threshold_ccl_big<0>, dim3(grid_big), dim3(kCclThreads), lds_big, s, P, g, ws.kp);
     }
-    if (want_stamps) {
+    if (pl.ccl_stamps) {
         unsigned long long h[16];
         (void)hipStreamSynchronize(s);
         (void)hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost);
@@ -1881,7 +1800,8 @@ __global__ __launch_bounds__(256) void k_seam_merge(SweepPtrs P, FrameGeom g, in
     }
 }
 
-hipError_t launch_seam_merge(int nframes, const Workspace& ws, hipStream_t s) {
+hipError_t launch_seam_merge(const ChunkPlan& pl, const Workspace& ws, hipStream_t s) {
+    const int nframes = pl.nframes;
     const FrameGeom& g = ws.g;
     const int n = (g.tiles_y - 1) * ((g.hcols + 7) >> 3) + (g.tiles_x - 1) * g.hrows;
     if (n <= 0) return hipSuccess;
@@ -1924,13 +1844,14 @@ __global__ __launch_bounds__(256) void k_zero_counters(int32_t* a, uint32_t* b, 
     }
     if (i == 0) *one = 0;
 }
-hipError_t launch_zero_counters(int nframes, const Workspace& ws, hipStream_t s) {
+hipError_t launch_zero_counters(const ChunkPlan& pl, const Workspace& ws, hipStream_t s) {
+    const int nframes = pl.nframes;
     hipLaunchKernelGGL(k_zero_counters, dim3((nframes + 255) / 256), dim3(256), 0, s, ws.frame_ncomp, ws.frame_flags, ws.line_count, ws.clp_used, ws.ovf_count, nframes);
     return hipGetLastError();
 }
 
-hipError_t launch_resolve(int nframes, const Workspace& ws, hipStream_t s) {
-    const int per_frame = 2;
+hipError_t launch_resolve(const ChunkPlan& pl, const Workspace& ws, hipStream_t s) {
+    const int nframes = pl.nframes, per_frame = 2;
     hipLaunchKernelGGL(k_resolve, dim3(grid_for(nframes, per_frame)), dim3(256), 0, s, sweep_ptrs(ws), nframes, per_frame, ws.g.pool_cap);
     return hipGetLastError();
 }
@@ -2065,8 +1986,8 @@ hipError_t launch_counters(int nframes, const Workspace& ws, const ctag_frame_re
     return hipGetLastError();
 }
 
-hipError_t launch_candidates(int nframes, const Workspace& ws, hipStream_t s) {
-    hipLaunchKernelGGL(k_candidates, dim3(nframes), dim3(256), 0, s, sweep_ptrs(ws), ws.g, nframes, ws.kp.area_min);
+hipError_t launch_candidates(const ChunkPlan& pl, const Workspace& ws, hipStream_t s) {
+    hipLaunchKernelGGL(k_candidates, dim3(pl.nframes), dim3(256), 0, s, sweep_ptrs(ws), ws.g, pl.nframes, ws.kp.area_min);
     return hipGetLastError();
 }
 

@@ -107,6 +107,15 @@ int ctag_testkit_dense_edge_probe(ctag_handle* h, const uint8_t* gray, int rows,
                                   int n_seg, const double* K, const double* dist, const double* rvec, const double* tvec,
                                   int samples_per_edge, double search_px, double min_contrast, double* out, int32_t* keep);
 
+/* ---- the kernel forms the library picks for a chunk (plan_chunk, cylindertag_amd/csrc/ctag_api.hip) ------------------
+ * For `nframes` frames of rows x cols (gray, or BGR for channels == 3) at `frames` (only its alignment is looked at) with the given
+ * strides, the handle options CTAG_OPT_FUSED_SWEEP (-1: not set), CTAG_OPT_WAVE_POINTS, CTAG_OPT_BGR_DIRECT, CTAG_OPT_EXPAND_EXACT,
+ * default ctag_params and no developer aids in the environment.  Host only.  Writes min(capacity, count) int32 fields in the order
+ * of testkit.PLAN_FIELDS; returns their count. */
+int ctag_testkit_plan(int rows, int cols, int adaptive_thresh, int nframes, int channels, int corner_subpix, const void* frames,
+                      ptrdiff_t frame_stride, ptrdiff_t row_stride, int fuse_mode, int wave_points, int bgr_direct, int expand_exact,
+                      int32_t* out, int capacity);
+
 #ifdef __cplusplus
 }
 #endif

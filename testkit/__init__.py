@@ -24,7 +24,14 @@ SYNTH_SEED = 0x4354616753594E00  # "CTagSYN\0", SURVEY.md 8(d)
 # every symbol include/ctag_testkit.h declares (tests check the library exports all of them)
 EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
            "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model",
-           "ctag_testkit_dense_edge_probe"]
+           "ctag_testkit_dense_edge_probe", "ctag_testkit_plan"]
+# the fields ctag_testkit_plan writes, in order (cylindertag_amd/csrc/ctag_internal.h: ChunkPlan)
+PLAN_FIELDS = ("fused", "bgr_direct", "zero_first", "dec_zero_kernel", "dec_zero_list", "dec", "dec_xblocks", "dec_yblocks", "dec_band_rows", "dec_bands",
+               "ccl", "latency", "small_cfg", "refprm", "mask_scan", "prescan", "all_wave", "fork", "pack_max", "big_points", "pack_gx", "scan_gx",
+               "mscan_gx", "big_cols", "big_max_gx", "welsch_gs", "welsch_gx", "refine", "refine_gx", "refine_sums_gx")
+DEC_FORMS = ("mask", "mask_bands", "general", "wide", "banded135", "banded", "unaligned")  # ChunkPlan::dec
+CCL_FORMS = ("mask", "tw5", "any")                                                          # ChunkPlan::ccl
+REFINE_FORMS = ("none", "one", "split_large", "split_looping", "split")                     # ChunkPlan::refine
 
 
 def lib_path():
@@ -73,6 +80,9 @@ def load_library():
                                           C.c_double, C.c_double, C.c_double, vp]
     L.ctag_synth3d_model.restype = C.c_int
     L.ctag_synth3d_model.argtypes = [i32p, C.c_int, C.c_int, vp]
+    L.ctag_testkit_plan.restype = C.c_int
+    L.ctag_testkit_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, i32p, C.c_int]
     L.ctag_testkit_dense_edge_probe.restype = C.c_int
     L.ctag_testkit_dense_edge_probe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_ssize_t, vp, C.c_int, vp, vp, vp, vp, C.c_int,
                                                 C.c_double, C.c_double, vp, vp]
@@ -129,6 +139,23 @@ def synth_truth(state, frame_index, rows=1080, cols=1920, seed=SYNTH_SEED, marke
     if st != 0:
         raise CtagError(st)
     return truth[0]
+
+
+def chunk_plan(rows, cols, nframes, adaptive_thresh=5, channels=1, corner_subpix=1, frames=0x10000, frame_stride=None, row_stride=None,
+               fuse_mode=-1, wave_points=0, bgr_direct=1, expand_exact=0):
+    """The kernel forms the library picks for a chunk (ctag_testkit_plan) as a dict over PLAN_FIELDS; the forms by name.  Host only.
+    `frames` is an address (never read); the strides default to packed rows."""
+    L = load_library()
+    row_stride = cols * channels if row_stride is None else row_stride
+    frame_stride = row_stride * rows if frame_stride is None else frame_stride
+    out = np.zeros(len(PLAN_FIELDS), np.int32)
+    n = L.ctag_testkit_plan(rows, cols, adaptive_thresh, nframes, channels, corner_subpix, frames, frame_stride, row_stride, fuse_mode, wave_points,
+                            bgr_direct, expand_exact, out.ctypes.data_as(C.POINTER(C.c_int32)), len(out))
+    if n != len(PLAN_FIELDS):
+        raise RuntimeError("ctag_testkit_plan writes %d fields, PLAN_FIELDS names %d" % (n, len(PLAN_FIELDS)))
+    plan = dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+    plan["dec"], plan["ccl"], plan["refine"] = DEC_FORMS[plan["dec"]], CCL_FORMS[plan["ccl"]], REFINE_FORMS[plan["refine"]]
+    return plan
 
 
 class Detector(ca.Detector):

@@ -262,8 +262,10 @@ long ctag_debug_fetch(ctag_handle* h, int frame, int what, void* dst, size_t cap
                     uint8_t* tmp = nullptr;
                     if (hipMalloc(reinterpret_cast<void**>(&tmp), (size_t)g.hrows * g.hp + 256) != hipSuccess) return -2;
                     T.half = tmp;
-                    bool ok = launch_decimate(v.frames + (ptrdiff_t)frame * v.frame_stride, v.frame_stride, v.row_stride, 1, T, s, false) == hipSuccess &&
-                              hipStreamSynchronize(s) == hipSuccess;
+                    const uint8_t* src = v.frames + (ptrdiff_t)frame * v.frame_stride;
+                    ChunkPlan pl = plan_chunk(PlanIn{g.rows, g.cols, g.tw, 1, 1, 0, src, v.frame_stride, v.row_stride, W.kp, 0, 0, false, dev_knobs()});
+                    pl.dec_zero_kernel = pl.dec_zero_list = false;  // T shares the chunk's counters: decimate only
+                    bool ok = launch_decimate(pl, src, v.frame_stride, v.row_stride, T, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
                     ok = ok && hipMemcpy2D(dst, g.hcols, tmp, g.hp, g.hcols, g.hrows, hipMemcpyDeviceToHost) == hipSuccess;
                     (void)hipFree(tmp);
                     if (!ok) return -2;
@@ -524,6 +526,25 @@ int ctag_testkit_dense_edge_probe(ctag_handle* h, const uint8_t* gray, int rows,
     (void)hipFree(dout);
     (void)hipFree(dkeep);
     return rc;
+}
+
+int ctag_testkit_plan(int rows, int cols, int adaptive_thresh, int nframes, int channels, int corner_subpix, const void* frames, ptrdiff_t frame_stride,
+                      ptrdiff_t row_stride, int fuse_mode, int wave_points, int bgr_direct, int expand_exact, int32_t* out, int capacity) {
+    // KParams of ctag_params_default as far as the plan reads them (threshold_line 1.8, threshold_expand 1.2, collinear_cost 1.05)
+    KParams kp{};
+    kp.thr_line = 1.8f;
+    kp.thr_expand = 1.2f;
+    kp.c2_far = 2;
+    kp.c2_near = 1;
+    kp.expand_eps = expand_exact ? INFINITY : 3.0e-6f;
+    const ChunkPlan p = plan_chunk(PlanIn{rows, cols, adaptive_thresh, nframes, channels, corner_subpix, frames, frame_stride, row_stride, kp, fuse_mode, wave_points,
+                                          bgr_direct != 0, DevKnobs{}});
+    const int32_t f[] = {p.fused, p.bgr_direct, p.zero_first, p.dec_zero_kernel, p.dec_zero_list, (int32_t)p.dec, p.dec_xblocks, p.dec_yblocks, p.dec_band_rows,
+                         p.dec_bands, (int32_t)p.ccl, p.latency, p.small_cfg, p.refprm, p.mask_scan, p.prescan, p.all_wave, p.fork, p.pack_max, p.big_points,
+                         p.pack_gx, p.scan_gx, p.mscan_gx, p.big_cols, p.big_max_gx, p.welsch_gs, p.welsch_gx, (int32_t)p.refine, p.refine_gx, p.refine_sums_gx};
+    constexpr int n = (int)(sizeof(f) / sizeof(f[0]));
+    if (out) std::memcpy(out, f, sizeof(int32_t) * (size_t)std::min(std::max(capacity, 0), n));
+    return n;
 }
 
 }  // extern "C"
