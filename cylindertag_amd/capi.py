@@ -27,7 +27,8 @@ EXPORTS = ["ctag_create", "ctag_create_ex", "ctag_params_default", "ctag_destroy
            "ctag_stage_name", "ctag_strerror", "ctag_version"]
 # ... and include/ctag_pose.h
 POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag_model_get_view", "ctag_camera_load",
-                "ctag_pose_batch_device", "ctag_estimate_pose", "ctag_pose_last_ms", "ctag_draw_axis", "ctag_draw_axis_batch_device"]
+                "ctag_pose_batch_device", "ctag_estimate_pose", "ctag_pose_last_ms", "ctag_draw_axis", "ctag_draw_axis_batch_device",
+                "ctag_rigs_create", "ctag_rigs_free", "ctag_rig_pose_batch_device", "ctag_estimate_rig_pose"]
 # ... and include/ctag_gather.h
 GATHER_EXPORTS = ["ctag_shard_range", "ctag_packed_capacity", "ctag_pack_results", "ctag_unpack_results", "ctag_comm_unique_id",
                   "ctag_comm_init", "ctag_comm_attach", "ctag_comm_destroy", "ctag_comm_native", "ctag_comm_last_error", "ctag_gather_begin",
@@ -38,7 +39,13 @@ COMM_ID_BYTES = 128
 POSE_DT = np.dtype([("status", "<i4"), ("model_index", "<i4"), ("frame", "<i4"), ("marker", "<i4"),
                     ("n_points", "<i4"), ("iterations", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)),
                     ("rvec0", "<f8", (3,)), ("tvec0", "<f8", (3,)), ("cost0", "<f8"), ("cost", "<f8")])
-POSE_OK, POSE_NO_MODEL, POSE_TOO_FEW, POSE_BAD_POS, POSE_DEGENERATE = range(5)
+POSE_OK, POSE_NO_MODEL, POSE_TOO_FEW, POSE_BAD_POS, POSE_DEGENERATE, POSE_NOT_SEEN = range(6)
+# ctag_rig_pose_rec: one pose per rig of markers (include/ctag_pose.h)
+RIG_POSE_DT = np.dtype([("status", "<i4"), ("rig", "<i4"), ("frame", "<i4"), ("n_members", "<i4"), ("n_excluded", "<i4"),
+                        ("n_points", "<i4"), ("iterations", "<i4"), ("reserved", "<i4"), ("member_mask", "<u4", (4,)),
+                        ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("rvec0", "<f8", (3,)), ("tvec0", "<f8", (3,)),
+                        ("cost0", "<f8"), ("cost", "<f8")])
+RIG_MAX_POINTS = 800
 
 
 class ParamsC(C.Structure):  # ctag_params (include/ctag_types.h): the reference's tunables
@@ -175,6 +182,14 @@ def load_library():
     L.ctag_draw_axis_batch_device.restype = C.c_int
     L.ctag_draw_axis_batch_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_ssize_t, vp, vp, vp, C.c_int, vp,
                                               C.POINTER(CameraC), C.c_int, vp, C.c_ssize_t, C.c_ssize_t]
+    L.ctag_rigs_create.restype = C.c_int
+    L.ctag_rigs_create.argtypes = [vp, i32p, C.c_int, C.POINTER(vp)]
+    L.ctag_rigs_free.restype = None
+    L.ctag_rigs_free.argtypes = [vp]
+    L.ctag_rig_pose_batch_device.restype = C.c_int
+    L.ctag_rig_pose_batch_device.argtypes = [vp, vp, C.c_int, vp, vp, C.POINTER(CameraC), vp]
+    L.ctag_estimate_rig_pose.restype = C.c_int
+    L.ctag_estimate_rig_pose.argtypes = [vp, vp, vp, vp, C.POINTER(CameraC), vp]
     u64p = C.POINTER(C.c_uint64)
     L.ctag_shard_range.restype = C.c_int
     L.ctag_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -288,6 +303,32 @@ class Model:
         if getattr(self, "m", None):
             self.L.ctag_model_free(self.m)
             self.m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Rigs:
+    """ctag_rigs: rig_of_model[model's n_models] maps each model index to a rig (-1: none, 0 .. n_rigs-1).  n_rigs defaults
+    to one more than the largest entry."""
+
+    def __init__(self, model, rig_of_model, n_rigs=None):
+        self.L = load_library()
+        self.rig_of_model = np.ascontiguousarray(rig_of_model, np.int32).ravel()
+        self.n_rigs = int(n_rigs if n_rigs is not None else (self.rig_of_model.max(initial=-1) + 1))
+        r = C.c_void_p()
+        st = self.L.ctag_rigs_create(model.m, self.rig_of_model.ctypes.data_as(C.POINTER(C.c_int32)), self.n_rigs, C.byref(r))
+        if st != 0:
+            raise CtagError(st, "ctag_rigs_create")
+        self.r = r
+
+    def close(self):
+        if getattr(self, "r", None):
+            self.L.ctag_rigs_free(self.r)
+            self.r = None
 
     def __del__(self):
         try:
@@ -543,6 +584,23 @@ class Detector:
                                            capacity)
         if st != 0:
             raise CtagError(st, "ctag_pose_batch_device")
+
+    def estimate_rig_pose(self, result, model, rigs, camera):
+        """One frame: host ctag_frame_result record -> rigs.n_rigs RIG_POSE_DT records (record g = rig g)."""
+        res = np.ascontiguousarray(result).reshape(1)
+        assert res.dtype == RESULT_DT
+        out = np.zeros(rigs.n_rigs, RIG_POSE_DT)
+        st = self.L.ctag_estimate_rig_pose(self.h, res.ctypes.data, model.m, rigs.r, C.byref(camera), out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_estimate_rig_pose")
+        return out
+
+    def rig_pose_batch_device(self, results_ptr, n_frames, model, rigs, camera, out_ptr):
+        """n_frames device result records -> n_frames * rigs.n_rigs device RIG_POSE_DT records at out_ptr (record f*n_rigs + g);
+        enqueued on the handle's stream."""
+        st = self.L.ctag_rig_pose_batch_device(self.h, results_ptr, n_frames, model.m, rigs.r, C.byref(camera), out_ptr)
+        if st != 0:
+            raise CtagError(st, "ctag_rig_pose_batch_device")
 
     def pose_last_ms(self):
         return float(self.L.ctag_pose_last_ms(self.h))

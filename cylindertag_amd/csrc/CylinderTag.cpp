@@ -297,6 +297,45 @@ void CylinderTag::estimatePose(const Mat& img, std::vector<MarkerInfo> markers, 
     }
 }
 
+void CylinderTag::estimateRigPose(std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, const std::vector<int>& rigOfModel,
+                                  CamInfo camera, std::vector<RigPoseInfo>& pose) {
+    pose.clear();
+    if (rigOfModel.size() != reconstruct_model.size()) throw __FUNCTION__ + std::string(", ") + "one rig entry per model\n";
+    int n_rigs = 0;
+    for (int g : rigOfModel) n_rigs = g + 1 > n_rigs ? g + 1 : n_rigs;
+    if (markers.empty() || n_rigs == 0) return;
+    if (markers.size() > (size_t)CTAG_MAX_MARKERS) throw __FUNCTION__ + std::string(", ") + "more than 100 markers\n";
+    ctag_frame_result res;
+    if (flatten(markers, 0, res) != markers.size()) throw __FUNCTION__ + std::string(", ") + "more than 100 features\n";
+    ctag_model* model = make_model(reconstruct_model, __FUNCTION__);
+    ctag_rigs* rigs = nullptr;
+    int st = ctag_rigs_create(model, rigOfModel.data(), n_rigs, &rigs);
+    std::vector<ctag_rig_pose_rec> rec((size_t)n_rigs);
+    const ctag_camera cam = make_camera(camera);
+    if (st == CTAG_OK) st = ctag_estimate_rig_pose(h_, &res, model, rigs, &cam, rec.data());
+    ctag_rigs_free(rigs);
+    ctag_model_free(model);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    for (const ctag_rig_pose_rec& p : rec) {
+        if (p.status == CTAG_POSE_NOT_SEEN) continue;  // erased, as estimatePose erases markers without a model
+        if (p.status != CTAG_POSE_OK) throw __FUNCTION__ + std::string(", ") + "rig without a usable point set\n";
+        RigPoseInfo ri;
+        ri.rigID = p.rig;
+#ifdef CTAG_WITH_OPENCV
+        ri.rvec = (cv::Mat_<double>(3, 1) << p.rvec[0], p.rvec[1], p.rvec[2]);
+        ri.tvec = (cv::Mat_<double>(3, 1) << p.tvec[0], p.tvec[1], p.tvec[2]);
+#else
+        for (int i = 0; i < 3; i++) {
+            ri.rvec[i] = p.rvec[i];
+            ri.tvec[i] = p.tvec[i];
+        }
+#endif
+        for (int k = 0; k < CTAG_MAX_MARKERS; k++)
+            if ((p.member_mask[k >> 5] >> (k & 31)) & 1u) ri.members.push_back(k);
+        pose.push_back(ri);
+    }
+}
+
 static void pose_vectors(const PoseInfo& p, double* r, double* t) {
 #ifdef CTAG_WITH_OPENCV
     const double *pr = p.rvec.ptr<double>(0), *pt = p.tvec.ptr<double>(0);

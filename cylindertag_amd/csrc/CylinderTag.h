@@ -85,6 +85,12 @@ struct PoseInfo {
     int markerID;
     cv::Mat rvec, tvec;
 };
+// one pose per rig of markers (new): the pose of the rig's common model frame, members = indices into the marker list
+struct RigPoseInfo {
+    int rigID;
+    cv::Mat rvec, tvec;
+    std::vector<int> members;
+};
 #else
 struct CamInfo {
     float Intrinsic[9] = {0};       // row-major 3x3
@@ -93,6 +99,11 @@ struct CamInfo {
 struct PoseInfo {
     int markerID = -1;
     double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
+};
+struct RigPoseInfo {
+    int rigID = -1;
+    double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
+    std::vector<int> members;
 };
 #endif
 // the annotated frame of drawAxis: rows x cols pixels of 3 bytes, channel c = Scalar component c (imgMark in the reference)
@@ -140,6 +151,14 @@ class CylinderTag {
     // useDensePoseRefine is accepted and ignored: the reference's DenseSolver is empty (pose_estimation.cpp:145-148).
     void estimatePose(const ctag_host::Mat& img, std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, CamInfo camera,
                       std::vector<PoseInfo>& pose, bool useDensePoseRefine = false);
+
+    // One pose per rig of markers (new; include/ctag_pose.h, ctag_estimate_rig_pose): rigOfModel[i] is the rig of model i (-1: none,
+    // rigs 0 .. max), the models of one rig share one frame.  The pose of a rig is EPnP + PoseBA over the union of its member
+    // markers' correspondences; RigPoseInfo::members lists the members as indices into `markers`.  Rigs with no member in the
+    // list are erased (as estimatePose erases markers without a model).  `markers` must fit one detection record (<= 100 markers,
+    // <= 100 features, as detect() returns them).  Throws std::string on error or on a rig whose points do not give a pose.
+    void estimateRigPose(std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, const std::vector<int>& rigOfModel,
+                         CamInfo camera, std::vector<RigPoseInfo>& pose);
 
     // Draw the axes of the posed markers (reference: header/CylinderTag.h:33, CylinderTag.cpp:211-246): pose[i] is drawn on
     // markers[i] -- the reference pairs them by list position, after estimatePose has erased the poses without a model -- with

@@ -155,6 +155,9 @@ struct ctag_handle {
     // state of the overlay (k_draw.hip), created on first use
     void* draw_state = nullptr;
     void (*draw_state_free)(void*) = nullptr;
+    // state of the rig poses (k_rig_pose.hip), created on first use
+    void* rig_state = nullptr;
+    void (*rig_state_free)(void*) = nullptr;
     // state of the multi-GPU gather layer (ctag_gather.hip), created on first use
     void* gather_state = nullptr;
     void (*gather_state_free)(void*) = nullptr;
@@ -168,6 +171,10 @@ void** handle_pose_slot(ctag_handle* h, void (*free_fn)(void*)) {
 void** handle_draw_slot(ctag_handle* h, void (*free_fn)(void*)) {
     h->draw_state_free = free_fn;
     return &h->draw_state;
+}
+void** handle_rig_slot(ctag_handle* h, void (*free_fn)(void*)) {
+    h->rig_state_free = free_fn;
+    return &h->rig_state;
 }
 void** handle_gather_slot(ctag_handle* h, void (*free_fn)(void*)) {
     h->gather_state_free = free_fn;
@@ -1189,6 +1196,7 @@ void ctag_destroy(ctag_handle* h) {
     if (h->d_gray) (void)hipFree(h->d_gray);
     if (h->pose_state && h->pose_state_free) h->pose_state_free(h->pose_state);
     if (h->draw_state && h->draw_state_free) h->draw_state_free(h->draw_state);
+    if (h->rig_state && h->rig_state_free) h->rig_state_free(h->rig_state);
     if (h->gather_state && h->gather_state_free) h->gather_state_free(h->gather_state);
     for (auto& e : h->ev)
         if (e) (void)hipEventDestroy(e);

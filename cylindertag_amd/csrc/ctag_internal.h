@@ -327,6 +327,8 @@ void build_pick_table(uint8_t* table, uint16_t* table16);  // kPickN*20*10 bytes
 void** handle_pose_slot(struct ::ctag_handle* h, void (*free_fn)(void*));
 // ... and for the overlay (k_draw.hip)
 void** handle_draw_slot(struct ::ctag_handle* h, void (*free_fn)(void*));
+// ... and for the rig poses (k_rig_pose.hip)
+void** handle_rig_slot(struct ::ctag_handle* h, void (*free_fn)(void*));
 // the model's device copies on `device` (k_pose.hip); the camera's distortion model is one the pose back end handles
 int model_to_device(struct ::ctag_model* m, int device);
 bool camera_ok(const struct ::ctag_camera* c);

@@ -100,6 +100,65 @@ int ctag_estimate_pose(ctag_handle* h, const ctag_frame_result* result, const ct
 /* device time of the last ctag_pose_batch_device call (needs CTAG_OPT_TIMING), milliseconds */
 float ctag_pose_last_ms(ctag_handle* h);
 
+/* ---- rig pose: one pose per rigid object that carries several markers (k_rig_pose.hip) -------------------------------------
+ * A rig set maps each model index to a rig: rig_of_model[n_models], -1 = in no rig, 0 .. n_rigs-1 = that rig.  The markers of
+ * one rig have their model corners in one common frame.  The record of frame f and rig g:
+ *   1. res[f].status != CTAG_OK: status CTAG_POSE_NOT_SEEN, every other field 0 except rig and frame.
+ *   2. Markers k = 0 .. min(n_markers, CTAG_MAX_MARKERS)-1 are visited in order.  Model index mi = the first model with the
+ *      marker's marker_id (as ctag_pose_batch_device looks it up).  The marker is skipped when there is no model or
+ *      rig_of_model[mi] != g.  Otherwise it is excluded, and counted in n_excluded, when
+ *        - an earlier marker of the frame has the same model index (a duplicate: the first marker with a model index claims it,
+ *          whether or not that marker became a member), or
+ *        - the per-marker correspondence builder rejects it (what gives CTAG_POSE_BAD_POS in ctag_pose_rec), or
+ *        - its points would take the rig's total past CTAG_RIG_MAX_POINTS.
+ *      Any other marker is a member: bit k of member_mask is set and its correspondences are appended in the builder's own
+ *      order (PnPSolver's rule: the end-feature skip, corners 0 1 4 5 [2 3 6 7]).
+ *   3. No member: CTAG_POSE_NOT_SEEN.  n < 4 points: CTAG_POSE_TOO_FEW.  Otherwise EPnP then PoseBA over the n concatenated
+ *      points, with the arithmetic of ctag_pose_batch_device; a non-finite EPnP result gives CTAG_POSE_DEGENERATE.  Pose fields
+ *      (rvec .. cost, iterations) are 0 unless the status is CTAG_POSE_OK.
+ *   4. Detection records can never exceed CTAG_RIG_MAX_POINTS (features are disjoint across markers); only hand-built or
+ *      corrupted records can.
+ * Identity: a rig holding one model, seen once in a frame, has the n_points, iterations, rvec, tvec, rvec0, tvec0, cost0 and
+ * cost bytes of that marker's ctag_pose_rec. */
+#define CTAG_POSE_NOT_SEEN 5       /* rig pose: the frame is not CTAG_OK, or no marker of the rig is a member */
+#define CTAG_RIG_MAX_POINTS 800    /* CTAG_MAX_FEATURES x 8 corners */
+
+typedef struct ctag_rig_pose_rec {
+    int32_t status;          /* CTAG_POSE_OK, _TOO_FEW, _DEGENERATE or _NOT_SEEN */
+    int32_t rig;             /* rig index g */
+    int32_t frame;           /* frame index f in the batch */
+    int32_t n_members;       /* markers whose points were used */
+    int32_t n_excluded;      /* markers of the rig left out (duplicate, rejected by the builder, over CTAG_RIG_MAX_POINTS) */
+    int32_t n_points;        /* correspondences used */
+    int32_t iterations;      /* LM iterations taken */
+    int32_t reserved;        /* 0 */
+    uint32_t member_mask[4]; /* bit k (word k/32, bit k%32): marker k of the frame is a member */
+    double rvec[3];          /* pose of the rig's common frame after PoseBA */
+    double tvec[3];
+    double rvec0[3];         /* EPnP result the refinement started from */
+    double tvec0[3];
+    double cost0;            /* 0.5 * sum of squared reprojection residuals at the EPnP pose */
+    double cost;             /* ... at the final pose */
+} ctag_rig_pose_rec;         /* 160 bytes */
+
+typedef struct ctag_rigs ctag_rigs; /* host + device copy of a rig set */
+
+/* Host only.  Copies rig_of_model[model's n_models]; CTAG_ERR_ARG for null pointers, n_rigs < 1 or an entry outside
+ * [-1, n_rigs).  The device copy is made on the handle's device at the first pose call.  A pose call with a model whose
+ * n_models differs from the one given here returns CTAG_ERR_ARG. */
+int ctag_rigs_create(const ctag_model* model, const int32_t* rig_of_model, int n_rigs, ctag_rigs** out);
+void ctag_rigs_free(ctag_rigs* rigs);
+
+/* Rig poses of n_frames detection results resident in DEVICE memory: writes exactly n_frames x n_rigs records to out_dev,
+ * record f*n_rigs + g for frame f and rig g, and no byte outside them.  Enqueued on the handle's stream; returns without
+ * waiting. */
+int ctag_rig_pose_batch_device(ctag_handle* h, const ctag_frame_result* results_dev, int n_frames, const ctag_model* model,
+                               const ctag_rigs* rigs, const ctag_camera* camera, ctag_rig_pose_rec* out_dev);
+
+/* One frame, host result in, n_rigs host records out.  Waits for completion. */
+int ctag_estimate_rig_pose(ctag_handle* h, const ctag_frame_result* result, const ctag_model* model, const ctag_rigs* rigs,
+                           const ctag_camera* camera, ctag_rig_pose_rec* out);
+
 /* ---- overlay: CylinderTag::drawAxis (reference CylinderTag.cpp:211-246) ------------------------------------------------
  * Output: 8-bit, 3 channels, every channel = the gray value (cvtColor GRAY2RGB), then per drawn record, in record order,
  * what the reference paints with OpenCV 4.5.3 (k_draw.hip restates it):
