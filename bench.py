@@ -11,13 +11,17 @@ refine -> decode) over the job's batch of frames.  Frames are independent, so wi
 shard of the SAME 4096-frame batch (BASELINE config 4: strong scaling; `--scaling weak` gives every GPU its own 4096)
 and the only collective is the final gather of the marker lists: the library's ctag_gather (packed shards, RCCL called
 from the C ABI, include/ctag_gather.h), pipelined against the next step's detection.
-Prints ONE JSON line on rank 0 (contract in the task statement), with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints the headline with what the timed steps produced:
+  results_sha256  hash of the (gathered) result list in frame order: equal for N = 1, 2, 4, 8 in strong scaling
+`--full` adds everything that is measured or checked beyond the timed steps, among it:
   roofline        the threshold+label sweep (2*W*H algorithmic bytes per frame) against 8 TB/s HBM,
                   timed with HIP events on the library's own stream
   cpu_baseline    the CPU restatement (oracle/, "port") timed on the host cores on a bounded sample of the batch
   parity          the GPU records of the timed configuration compared byte for byte with the oracle's records of the
                   same frames (the ones the cpu_baseline leg computes anyway); a mismatch makes the exit code 1
-  results_sha256  hash of the (gathered) result list in frame order: equal for N = 1, 2, 4, 8 in strong scaling
+and the side measurements (two handles, PCIe, BGR, single-frame latency, poses; N > 1: the gather alone, every rank's
+per-kernel times).
 PyTorch is used only for device memory, synchronisation and the torch.distributed bootstrap.
 """
 import argparse
@@ -48,19 +52,22 @@ def parse_args():
                     help="N > 1: strong = the same --frames batch sharded over the GPUs (BASELINE config 4), weak = --frames per GPU")
     ap.add_argument("--chunk", type=int, default=4096, help="frames per pipeline pass (workspace size)")
     ap.add_argument("--markers", type=int, default=4)
-    ap.add_argument("--cpu-frames", type=int, default=384, help="sample size of the one-thread CPU baseline (0 = skip CPU legs and parity)")
-    ap.add_argument("--cpu-frames-per-thread", type=int, default=128, help="all-cores CPU baseline: frames per hardware thread")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: per-kernel times and rooflines, "
+                         "the CPU baseline and parity, and the side measurements below (a plain run does none of it)")
+    ap.add_argument("--cpu-frames", type=int, default=384, help="--full: sample size of the one-thread CPU baseline (0 = skip CPU legs and parity)")
+    ap.add_argument("--cpu-frames-per-thread", type=int, default=128, help="--full: all-cores CPU baseline, frames per hardware thread")
     ap.add_argument("--host-frames", type=int, default=1024,
-                    help="frames of the host-memory (PCIe-inclusive) side measurement, 0 = skip; never `value`")
+                    help="--full: frames of the host-memory (PCIe-inclusive) side measurement, 0 = skip; never `value`")
     ap.add_argument("--pose-frames", type=int, default=1024,
-                    help="frames of the detect()+estimatePose side measurement on camera content, 0 = skip; never `value`")
+                    help="--full: frames of the detect()+estimatePose side measurement on camera content, 0 = skip; never `value`")
     ap.add_argument("--size", default="1920x1080", help="frame size WxH; the headline metric is 1920x1080 (other sizes are side measurements)")
     ap.add_argument("--no-subpix", action="store_true")
     ap.add_argument("--streams", type=int, default=0, choices=[0, 1, 2, 3, 4],
                     help="CTAG_OPT_STREAMS of the timed steps: 2 (the library's default) runs the halves of a chunk on two internal streams; 1 for profiler runs "
                          "(every launch then covers a whole chunk)")
-    ap.add_argument("--latency-calls", type=int, default=200, help="single-frame ctag_detect_u8 calls of the latency side measurement, 0 = skip")
-    ap.add_argument("--pipelined-steps", type=int, default=6, help="steps of the two-handle side measurement at N = 1, 0 = skip")
+    ap.add_argument("--latency-calls", type=int, default=200, help="--full: single-frame ctag_detect_u8 calls of the latency side measurement, 0 = skip")
+    ap.add_argument("--pipelined-steps", type=int, default=6, help="--full: steps of the two-handle side measurement at N = 1, 0 = skip")
     ap.add_argument("--allow-torch-gather", action="store_true",
                     help="N > 1: if the library's RCCL gather (ctag_gather, the C ABI) cannot come up, fall back to torch.distributed's all_gather "
                          "of the fixed records instead of failing.  Without this flag such a run exits non-zero: the line must not hide a gather failure")
@@ -781,7 +788,7 @@ def main():
     if os.environ.get("CTAG_BENCH_FAULT") == "rank1_exit" and rank == 1:  # test hook (tests/test_bench_gpu.py): a rank that dies mid-job
         os._exit(17)
     # The timed steps run as the library runs any device-memory batch: every chunk as two halves on two internal streams
-    # (CTAG_OPT_STREAMS, default 2), no events.  Per-kernel device time comes from the SAME number of extra steps behind the timed
+    # (CTAG_OPT_STREAMS, default 2), no events.  Per-kernel device time (--full) comes from the SAME number of extra steps behind the timed
     # region with CTAG_OPT_TIMING on -- HIP events recorded by the library on ITS stream around every kernel (torch.cuda.Event would
     # only see torch's current stream), which keeps those steps on ONE stream: between two interleaved streams an event pair around
     # a kernel would time the neighbour's kernels as well.  (At N > 1 one extra step: it would serialise the detect / gather pipeline.)
@@ -795,8 +802,9 @@ def main():
     single_stream_dt = None
     timed_records = None
     if world == 1:
-        # the records the TIMED steps left (the one-stream steps below write the same buffer): what `results_sha256` hashes and `parity` compares
+        # the records the TIMED steps left (the one-stream steps of --full write the same buffer): what `results_sha256` hashes and `parity` compares
         timed_records = local_bufs[0][:n].clone()
+    if world == 1 and args.full:
         det.set_option(capi.OPT_TIMING, 1)
         step()  # warm: the one-stream workspace
         fence()
@@ -814,49 +822,50 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     last = step_no[0] - 1
-    if timed_with_events:
-        stage_ms = {k: v / max(1, args.steps) for k, v in acc.items()}  # per step (n frames)
-    else:
-        det.set_option(capi.OPT_TIMING, 1)
-        det.detect_batch_device(frames.data_ptr(), n, ROWS, COLS, COLS, ROWS * COLS, local_bufs[(last + 1) % 2].data_ptr(), 5, subpix, 5)
-        det.sync()
-        stage_ms = det.timings()
-        det.set_option(capi.OPT_TIMING, 0)
-    launches = (n + chunk - 1) // chunk
-    stage_ms = dict(stage_ms)
-    # what the frames held (ctag_get_counters: the last chunk of this rank's last step) -- SURVEY.md 5's metrics row
-    try:
-        frame_counters = det.counters()
-    except Exception as e:  # noqa: BLE001
-        frame_counters = {"error": "%s: %s" % (type(e).__name__, e)}
-    # N > 1: what the exchange costs by itself -- one more gather of the last step's records, alone on the GPU, wall clock from
-    # ctag_gather_begin to the end of ctag_gather_wait (max over ranks) -- and every rank's per-kernel times, so that a SCALE
-    # record says where a step went
-    gather_ms, rank_stage_ms = None, None
-    if world > 1:
-        cpu_side = dist.get_backend() != "nccl"
-        if comm is not None:
-            fence()
-            g0 = time.perf_counter()
-            comm.begin(local_bufs[last % len(local_bufs)][:n], n_total)
-            comm.end(gathered[(last + 1) % 2])
-            comm.wait()
+    if args.full:
+        if timed_with_events:
+            stage_ms = {k: v / max(1, args.steps) for k, v in acc.items()}  # per step (n frames)
+        else:
+            det.set_option(capi.OPT_TIMING, 1)
+            det.detect_batch_device(frames.data_ptr(), n, ROWS, COLS, COLS, ROWS * COLS, local_bufs[(last + 1) % 2].data_ptr(), 5, subpix, 5)
             det.sync()
-            g = torch.tensor([(time.perf_counter() - g0) * 1e3], dtype=torch.float64, device="cpu" if cpu_side else dev)
-            dist.all_reduce(g, op=dist.ReduceOp.MAX)
-            gather_ms = round(float(g.item()), 3)
-        elif dist.get_backend() != "nccl":
-            fence()
-            g0 = time.perf_counter()
-            host_packed_gather(det, local_bufs[last % len(local_bufs)], gathered[(last + 1) % 2])
-            g = torch.tensor([(time.perf_counter() - g0) * 1e3], dtype=torch.float64)
-            dist.all_reduce(g, op=dist.ReduceOp.MAX)
-            gather_ms = round(float(g.item()), 3)
-        mine = torch.tensor([stage_ms[k] for k in ca.STAGE_NAMES], dtype=torch.float64, device="cpu" if cpu_side else dev)
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        rank_stage_ms = [{k: round(float(v), 3) for k, v in zip(ca.STAGE_NAMES, t.tolist())} for t in allr]
-    stage_ms["quad"] = sum(stage_ms[k] for k in capi.QUAD_STAGES)  # a4 edgeExtraction: the six kernels of the quad stage
+            stage_ms = det.timings()
+            det.set_option(capi.OPT_TIMING, 0)
+        launches = (n + chunk - 1) // chunk
+        stage_ms = dict(stage_ms)
+        # what the frames held (ctag_get_counters: the last chunk of this rank's last step) -- SURVEY.md 5's metrics row
+        try:
+            frame_counters = det.counters()
+        except Exception as e:  # noqa: BLE001
+            frame_counters = {"error": "%s: %s" % (type(e).__name__, e)}
+        # N > 1: what the exchange costs by itself -- one more gather of the last step's records, alone on the GPU, wall clock from
+        # ctag_gather_begin to the end of ctag_gather_wait (max over ranks) -- and every rank's per-kernel times, so that a SCALE
+        # record says where a step went
+        gather_ms, rank_stage_ms = None, None
+        if world > 1:
+            cpu_side = dist.get_backend() != "nccl"
+            if comm is not None:
+                fence()
+                g0 = time.perf_counter()
+                comm.begin(local_bufs[last % len(local_bufs)][:n], n_total)
+                comm.end(gathered[(last + 1) % 2])
+                comm.wait()
+                det.sync()
+                g = torch.tensor([(time.perf_counter() - g0) * 1e3], dtype=torch.float64, device="cpu" if cpu_side else dev)
+                dist.all_reduce(g, op=dist.ReduceOp.MAX)
+                gather_ms = round(float(g.item()), 3)
+            elif dist.get_backend() != "nccl":
+                fence()
+                g0 = time.perf_counter()
+                host_packed_gather(det, local_bufs[last % len(local_bufs)], gathered[(last + 1) % 2])
+                g = torch.tensor([(time.perf_counter() - g0) * 1e3], dtype=torch.float64)
+                dist.all_reduce(g, op=dist.ReduceOp.MAX)
+                gather_ms = round(float(g.item()), 3)
+            mine = torch.tensor([stage_ms[k] for k in ca.STAGE_NAMES], dtype=torch.float64, device="cpu" if cpu_side else dev)
+            allr = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(allr, mine)
+            rank_stage_ms = [{k: round(float(v), 3) for k, v in zip(ca.STAGE_NAMES, t.tolist())} for t in allr]
+        stage_ms["quad"] = sum(stage_ms[k] for k in capi.QUAD_STAGES)  # a4 edgeExtraction: the six kernels of the quad stage
 
     # ---- outcome of the last step: the job's result list in frame order (gathered when N > 1)
     # N = 1: of the last TIMED step (snapshot taken before the one-stream steps reused the buffer); N > 1: the gathered list of the last timed step
@@ -868,54 +877,13 @@ def main():
     dumped = dump_outputs(res, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     rc = 0
     one_stream_sha = None
-    if world == 1:  # the one-stream steps (`stage_ms_per_step`, `roofline`) must have produced the very same records
+    if world == 1 and args.full:  # the one-stream steps (`stage_ms_per_step`, `roofline`) must have produced the very same records
         one_stream_sha = hashlib.sha256(local_bufs[0][:n].cpu().numpy().tobytes()).hexdigest()
         if one_stream_sha != sha:
             print("bench.py: the one-stream steps' records differ from the timed steps' (%s vs %s)" % (one_stream_sha[:16], sha[:16]), file=sys.stderr, flush=True)
             rc = 1
 
     if rank == 0:
-        sweep_ms = sum(stage_ms[k] for k in SWEEP_STAGES)
-        achieved = ALGO_BYTES_PER_FRAME * n / (sweep_ms * 1e-3) / 1e9 if sweep_ms > 0 else 0.0
-        traffic, traffic_source, traffic_profile = None, None, None
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        import srcsha
-        src_sha = srcsha.sources_sha256()
-        import glob
-        # per-round PMC passes, one file per frame size they were collected on (r05_pmc_traffic.json: 1080p; r05_4k_pmc_traffic.json: 3840x2160); latest round wins
-        pat = {(1080, 1920): "r[0-9][0-9]_pmc_traffic.json", (2160, 3840): "r[0-9][0-9]_4k_pmc_traffic.json"}.get((ROWS, COLS))
-        cands = sorted(glob.glob(os.path.join(ROOT, "profiles", pat))) if pat else []
-        tpath = cands[-1] if cands else ""
-        if os.path.exists(tpath):
-            try:
-                tprof = json.load(open(tpath))
-                traffic = tprof.get("sweep_bytes_per_frame") * min(n, chunk)  # measured per frame
-                psha = (tprof.get("sources_sha256") or {}).get("sweep")
-                # the profile says which sweep sources it was collected on; a profile of other kernels than this tree's is flagged, not hidden
-                traffic_profile = {"file": os.path.relpath(tpath, ROOT), "git_head": tprof.get("git_head"), "sweep_sources_sha256": psha,
-                                   "this_tree_sweep_sources_sha256": src_sha["sweep"],
-                                   "matches_this_tree": None if psha is None else psha == src_sha["sweep"]}
-                traffic_source = "replayed from %s (separate rocprofv3 --pmc passes; not collected in this run)" % os.path.relpath(tpath, ROOT)
-            except Exception:
-                traffic = None
-        try:
-            copy_gbs = device_copy_rate(dev) if world == 1 else None
-        except Exception:  # noqa: BLE001
-            copy_gbs = None
-        roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
-                    "traffic_profile": traffic_profile,
-                    "measured_device_copy": None if not copy_gbs else {
-                        "GB/s": round(copy_gbs, 1), "frac_of_copy": round(achieved / copy_gbs, 5),
-                        "note": "plain device-to-device copy of 2 GiB (read + written bytes), best of 5, measured in this run: the rate a "
-                                "streaming kernel reaches on this GPU; `frac` stays priced at the 8 TB/s specification"},
-                    "kernel": "threshold+label sweep = " + "+".join("k_" + k for k in SWEEP_STAGES),
-                    "algorithmic_bytes_per_launch": ALGO_BYTES_PER_FRAME * min(n, chunk),
-                    "avg_launch_ms": round(sweep_ms / launches, 4), "launches_per_step": launches,
-                    "frames_per_launch": min(n, chunk),
-                    "timing": "HIP events on the library's stream, " + ("%d one-stream steps right behind the timed region (the timed steps run the halves of a "
-                                                                             "chunk on two streams, where an event pair would time the neighbour's kernels too)" % args.steps
-                                                                             if timed_with_events else "one extra untimed step on rank 0 (N > 1)")}
         out = {"metric": "frames/sec detect() %dx%d" % (COLS, ROWS), "value": round(n_total * args.steps / dt, 2),
                "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong" if strong else "weak",
@@ -928,79 +896,121 @@ def main():
                           "pipelining": ("steps alternate between %d handles (streams)" % len(dets)) if len(dets) > 1 else
                           ("one handle; the library runs the parts of a chunk on its internal streams (CTAG_OPT_STREAMS: library default)" if args.streams == 0 else
                            "one handle, CTAG_OPT_STREAMS = %d (--streams)" % args.streams)},
-               "one_stream": None if single_stream_dt is None else {
-                   "value": round(n_total * args.steps / single_stream_dt, 2), "unit": "frames/s", "ms_per_step": round(single_stream_dt / args.steps * 1e3, 3),
-                   "note": "the same steps with CTAG_OPT_TIMING on (one stream, per-kernel HIP events read back every step): the steps `stage_ms_per_step` and "
-                           "`roofline` are measured on"},
-               "roofline": roofline,
-               "issue_roofline": issue_rooflines(stage_ms, n),
-               "stage_ms_per_step": {k: round(v, 3) for k, v in stage_ms.items()},
-               "frame_counters": frame_counters if "error" in frame_counters else {
-                   "frames": frame_counters["frames"], "any_frame_reruns": frame_counters["reruns"],
-                   **{k: {"mean": round(frame_counters[k][0], 2), "max": frame_counters[k][1]} for k in capi.COUNTER_NAMES},
-                   "note": "per-frame counts of the last chunk of the last step (ctag_get_counters): components the label sweep published, "
-                           "candidates (area in [30 px, 1 %]), quads, features, decoded markers"},
                "frames_ok": ok_frames, "markers_decoded_last_step": markers_found, "results_sha256": sha,
-               "results_of": "the last TIMED step" + ("" if world > 1 else " (snapshot before the one-stream steps; their records hash %s)"
-                                                      % ("the same" if one_stream_sha == sha else "DIFFERENTLY: " + str(one_stream_sha))),
-               "sources_sha256": src_sha}
+               "results_of": "the last TIMED step" + ("" if one_stream_sha is None else " (snapshot before the one-stream steps; their records hash %s)"
+                                                      % ("the same" if one_stream_sha == sha else "DIFFERENTLY: " + str(one_stream_sha)))}
         if dumped is not None:
             out["dumped_outputs"] = dumped
-        if world > 1:
-            out["gather_ms"] = gather_ms
-            out["rank_stage_ms"] = rank_stage_ms
-        if comm is not None:
-            lb, pb = det.gather_last_bytes()
-            out["config"]["gather_bytes"] = {"packed_local": lb, "padded_per_rank": pb, "fixed_records_per_rank": n * rec_bytes}
-        elif host_stats:
-            out["config"]["gather_bytes"] = dict(host_stats)
-        # side legs: a failure in one of them is reported in its place and never costs the headline line
-        def side(name, fn):
+        if args.full:
+            sweep_ms = sum(stage_ms[k] for k in SWEEP_STAGES)
+            achieved = ALGO_BYTES_PER_FRAME * n / (sweep_ms * 1e-3) / 1e9 if sweep_ms > 0 else 0.0
+            traffic, traffic_source, traffic_profile = None, None, None
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            import srcsha
+            src_sha = srcsha.sources_sha256()
+            import glob
+            # per-round PMC passes, one file per frame size they were collected on (r05_pmc_traffic.json: 1080p; r05_4k_pmc_traffic.json: 3840x2160); latest round wins
+            pat = {(1080, 1920): "r[0-9][0-9]_pmc_traffic.json", (2160, 3840): "r[0-9][0-9]_4k_pmc_traffic.json"}.get((ROWS, COLS))
+            cands = sorted(glob.glob(os.path.join(ROOT, "profiles", pat))) if pat else []
+            tpath = cands[-1] if cands else ""
+            if os.path.exists(tpath):
+                try:
+                    tprof = json.load(open(tpath))
+                    traffic = tprof.get("sweep_bytes_per_frame") * min(n, chunk)  # measured per frame
+                    psha = (tprof.get("sources_sha256") or {}).get("sweep")
+                    # the profile says which sweep sources it was collected on; a profile of other kernels than this tree's is flagged, not hidden
+                    traffic_profile = {"file": os.path.relpath(tpath, ROOT), "git_head": tprof.get("git_head"), "sweep_sources_sha256": psha,
+                                       "this_tree_sweep_sources_sha256": src_sha["sweep"],
+                                       "matches_this_tree": None if psha is None else psha == src_sha["sweep"]}
+                    traffic_source = "replayed from %s (separate rocprofv3 --pmc passes; not collected in this run)" % os.path.relpath(tpath, ROOT)
+                except Exception:
+                    traffic = None
             try:
-                out[name] = fn()
-            except Exception as e:  # noqa: BLE001
-                out[name] = {"error": "%s: %s" % (type(e).__name__, e)}
+                copy_gbs = device_copy_rate(dev) if world == 1 else None
+            except Exception:  # noqa: BLE001
+                copy_gbs = None
+            roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
+                        "traffic_profile": traffic_profile,
+                        "measured_device_copy": None if not copy_gbs else {
+                            "GB/s": round(copy_gbs, 1), "frac_of_copy": round(achieved / copy_gbs, 5),
+                            "note": "plain device-to-device copy of 2 GiB (read + written bytes), best of 5, measured in this run: the rate a "
+                                    "streaming kernel reaches on this GPU; `frac` stays priced at the 8 TB/s specification"},
+                        "kernel": "threshold+label sweep = " + "+".join("k_" + k for k in SWEEP_STAGES),
+                        "algorithmic_bytes_per_launch": ALGO_BYTES_PER_FRAME * min(n, chunk),
+                        "avg_launch_ms": round(sweep_ms / launches, 4), "launches_per_step": launches,
+                        "frames_per_launch": min(n, chunk),
+                        "timing": "HIP events on the library's stream, " + ("%d one-stream steps right behind the timed region (the timed steps run the halves of a "
+                                                                                 "chunk on two streams, where an event pair would time the neighbour's kernels too)" % args.steps
+                                                                                 if timed_with_events else "one extra untimed step on rank 0 (N > 1)")}
+            out.update({"one_stream": None if single_stream_dt is None else {
+                            "value": round(n_total * args.steps / single_stream_dt, 2), "unit": "frames/s", "ms_per_step": round(single_stream_dt / args.steps * 1e3, 3),
+                            "note": "the same steps with CTAG_OPT_TIMING on (one stream, per-kernel HIP events read back every step): the steps `stage_ms_per_step` and "
+                                    "`roofline` are measured on"},
+                        "roofline": roofline,
+                        "issue_roofline": issue_rooflines(stage_ms, n),
+                        "stage_ms_per_step": {k: round(v, 3) for k, v in stage_ms.items()},
+                        "frame_counters": frame_counters if "error" in frame_counters else {
+                            "frames": frame_counters["frames"], "any_frame_reruns": frame_counters["reruns"],
+                            **{k: {"mean": round(frame_counters[k][0], 2), "max": frame_counters[k][1]} for k in capi.COUNTER_NAMES},
+                            "note": "per-frame counts of the last chunk of the last step (ctag_get_counters): components the label sweep published, "
+                                    "candidates (area in [30 px, 1 %]), quads, features, decoded markers"},
+                        "sources_sha256": src_sha})
+            if world > 1:
+                out["gather_ms"] = gather_ms
+                out["rank_stage_ms"] = rank_stage_ms
+            if comm is not None:
+                lb, pb = det.gather_last_bytes()
+                out["config"]["gather_bytes"] = {"packed_local": lb, "padded_per_rank": pb, "fixed_records_per_rank": n * rec_bytes}
+            elif host_stats:
+                out["config"]["gather_bytes"] = dict(host_stats)
+            # side legs: a failure in one of them is reported in its place and never costs the headline line
+            def side(name, fn):
+                try:
+                    out[name] = fn()
+                except Exception as e:  # noqa: BLE001
+                    out[name] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-        oracle_records = [None]
+            oracle_records = [None]
 
-        def cpu_leg():
-            obj, recs = cpu_baseline(frames, min(args.cpu_frames, n), args.cpu_frames_per_thread, state, fs, subpix)
-            oracle_records[0] = recs
-            return obj
+            def cpu_leg():
+                obj, recs = cpu_baseline(frames, min(args.cpu_frames, n), args.cpu_frames_per_thread, state, fs, subpix)
+                oracle_records[0] = recs
+                return obj
 
-        if world == 1 and args.cpu_frames > 0:
-            side("cpu_baseline", cpu_leg)
-            recs = oracle_records[0]
-            if recs is not None:  # parity of the timed configuration itself (chunk %d): GPU records vs oracle records, byte for byte
-                bad = [int(f) for f in range(len(recs)) if recs[f].tobytes() != res[f].tobytes()]
-                out["parity"] = {"frames_checked": len(recs), "mismatches": len(bad), "first_mismatching_frames": bad[:8],
-                                 "bar": "byte-identical ctag_frame_result records (ids, order, float corners)"}
-                if bad:
+            if world == 1 and args.cpu_frames > 0:
+                side("cpu_baseline", cpu_leg)
+                recs = oracle_records[0]
+                if recs is not None:  # parity of the timed configuration itself (chunk %d): GPU records vs oracle records, byte for byte
+                    bad = [int(f) for f in range(len(recs)) if recs[f].tobytes() != res[f].tobytes()]
+                    out["parity"] = {"frames_checked": len(recs), "mismatches": len(bad), "first_mismatching_frames": bad[:8],
+                                     "bar": "byte-identical ctag_frame_result records (ids, order, float corners)"}
+                    if bad:
+                        rc = 1
+                else:
+                    out["parity"] = {"frames_checked": 0, "mismatches": None, "note": "cpu_baseline leg failed"}
                     rc = 1
             else:
-                out["parity"] = {"frames_checked": 0, "mismatches": None, "note": "cpu_baseline leg failed"}
-                rc = 1
-        else:
-            out["cpu_baseline"] = None
-            out["parity"] = None
-        if world == 1 and args.cpu_frames > 0 and frames is not None:
-            side("opencv_stage_probe", lambda: opencv_stage_probe(frames[:16].cpu().numpy()))
-        if world == 1 and args.pipelined_steps > 0 and frames is not None:
-            side("pipelined_two_handles", lambda: pipelined_steps_rate(det, state, fs, dev_index, frames, n, chunk, subpix, local_bufs[0], args.pipelined_steps))
-        if world == 1 and args.host_frames > 0:
-            side("pcie_inclusive", lambda: host_stream_rate(det, frames, min(args.host_frames, n), subpix))
-            side("pcie_inclusive_bgr", lambda: host_stream_rate_bgr(det, frames, min(args.host_frames // 2, n), subpix))
-        if world == 1 and args.host_frames > 0 and frames is not None:
-            side("bgr_device_resident", lambda: bgr_resident_rate(det, frames, min(args.host_frames, n), subpix, out["value"]))
-        if world == 1 and args.latency_calls > 0:
-            side("single_frame_latency", lambda: latency_side(det, state, fs, args.latency_calls))
-        if world == 1 and args.pose_frames > 0:
-            del frames
-            frames = None
-            if (ROWS, COLS) == (1080, 1920):
-                side("pose_side", lambda: pose_side(det, args.pose_frames, dev))
-            else:
-                side("pose_side", lambda: pose_side_3d(det, state, args.pose_frames, dev, 256))
+                out["cpu_baseline"] = None
+                out["parity"] = None
+            if world == 1 and args.cpu_frames > 0 and frames is not None:
+                side("opencv_stage_probe", lambda: opencv_stage_probe(frames[:16].cpu().numpy()))
+            if world == 1 and args.pipelined_steps > 0 and frames is not None:
+                side("pipelined_two_handles", lambda: pipelined_steps_rate(det, state, fs, dev_index, frames, n, chunk, subpix, local_bufs[0], args.pipelined_steps))
+            if world == 1 and args.host_frames > 0:
+                side("pcie_inclusive", lambda: host_stream_rate(det, frames, min(args.host_frames, n), subpix))
+                side("pcie_inclusive_bgr", lambda: host_stream_rate_bgr(det, frames, min(args.host_frames // 2, n), subpix))
+            if world == 1 and args.host_frames > 0 and frames is not None:
+                side("bgr_device_resident", lambda: bgr_resident_rate(det, frames, min(args.host_frames, n), subpix, out["value"]))
+            if world == 1 and args.latency_calls > 0:
+                side("single_frame_latency", lambda: latency_side(det, state, fs, args.latency_calls))
+            if world == 1 and args.pose_frames > 0:
+                del frames
+                frames = None
+                if (ROWS, COLS) == (1080, 1920):
+                    side("pose_side", lambda: pose_side(det, args.pose_frames, dev))
+                else:
+                    side("pose_side", lambda: pose_side_3d(det, state, args.pose_frames, dev, 256))
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,7 +1,8 @@
-"""bench.py itself, on the GPU box: the one-GPU line carries the objects the contract asks for and verifies what it times, and
-the N > 1 logic (shards, double-buffered gathers, the hash of the gathered list) gives the same result list as N = 1 -- run
-with two ranks sharing the one GPU through the developer backend (RCCL refuses two ranks on one device, so the gather goes
-through gloo and host memory there; the RCCL gather itself is covered by test_packed_shards_and_rccl_gather_single_rank)."""
+"""bench.py itself, on a GPU: the one-GPU `--full` line carries the objects the contract asks for and verifies what it times, a
+plain run gives the same records with the headline alone, and the N > 1 logic (shards, double-buffered gathers, the hash of
+the gathered list) gives the same result list as N = 1 -- run with two ranks sharing the one GPU through the developer backend
+(RCCL refuses two ranks on one device, so the gather goes through gloo and host memory there; the RCCL gather itself is
+covered by test_packed_shards_and_rccl_gather_single_rank)."""
 import json
 import os
 import socket
@@ -32,7 +33,7 @@ def test_one_gpu_line_and_two_rank_hash(tmp_path):
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "192", "--host-frames", "0",
             "--pose-frames", "0", "--latency-calls", "0"]
     dump = str(tmp_path / "out")
-    p = subprocess.run(base + ["--cpu-frames", "24", "--cpu-frames-per-thread", "2", "--dump-outputs", dump], capture_output=True, text=True, timeout=900)
+    p = subprocess.run(base + ["--full", "--cpu-frames", "24", "--cpu-frames-per-thread", "2", "--dump-outputs", dump], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     one = _line(p.stdout)
     assert one["n_gpus"] == 1 and one["unit"] == "frames/s" and one["frames_ok"] == 192
@@ -47,6 +48,17 @@ def test_one_gpu_line_and_two_rank_hash(tmp_path):
     assert one["roofline"]["bound"] == "hbm" and 0.0 < one["roofline"]["frac"] < 1.0 and one["roofline"]["traffic_source"]
     assert one["cpu_baseline"]["kind"] == "port" and one["cpu_baseline"]["cores"] == 1 and one["cpu_baseline"]["value"] > 0
     assert set(one["issue_roofline"]["kernels"]) >= {"k_edge_refine", "k_welsch", "k_quad_edges_packed"}
+    # a plain run (no --full) times the same steps and prints the headline and what they produced, nothing measured beyond them
+    plain_dump = str(tmp_path / "plain")
+    p = subprocess.run(base + ["--dump-outputs", plain_dump], capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    plain = _line(p.stdout)
+    assert plain["metric"] == one["metric"] and plain["unit"] == "frames/s" and plain["higher_is_better"] is True and plain["dtype"] == "u8"
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["results_sha256"] == one["results_sha256"] and plain["frames_ok"] == 192 and plain["dumped_outputs"]["frames"] == 192
+    assert not {"roofline", "issue_roofline", "stage_ms_per_step", "cpu_baseline", "parity", "one_stream", "pose_side"} & set(plain)
+    for f in os.listdir(dump):
+        assert np.load(os.path.join(plain_dump, f)).tobytes() == np.load(os.path.join(dump, f)).tobytes(), f
     # N = 2 the way the driver starts it: `python bench.py --gpus 2 ...`, no launcher around it -- bench.py starts torch.distributed.run
     # itself as a child process before anything touches the GPU (launch_ranks) and hands back the launcher's exit code
     env = dict(os.environ, CTAG_BENCH_BACKEND="gloo")
@@ -56,6 +68,7 @@ def test_one_gpu_line_and_two_rank_hash(tmp_path):
     assert two["n_gpus"] == 2 and two["scaling"] == "strong" and two["config"]["frames_per_gpu"] == 96 and two["frames_ok"] == 192
     assert two["results_sha256"] == one["results_sha256"]  # the gathered list equals the one-GPU list
     assert two["config"]["pipelining"].startswith("steps alternate between 2 handles")
+    assert "gather_ms" not in two and "rank_stage_ms" not in two  # measured beyond the timed steps: --full only
     # ... and under an explicit launcher (the other command shape of the contract)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port())] + base[1:] + ["--gpus", "2", "--cpu-frames", "0"]
@@ -77,7 +90,7 @@ def test_a_rank_that_dies_ends_the_job_non_zero():
 
 
 def _ranks_give_the_one_gpu_list(frames, world):
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", str(frames), "--host-frames", "0",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--frames", str(frames), "--host-frames", "0",
             "--pose-frames", "0", "--latency-calls", "0", "--cpu-frames", "0", "--pipelined-steps", "0"]
     p = subprocess.run(base, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
