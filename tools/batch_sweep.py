@@ -11,13 +11,11 @@ import testkit as tk
 from cylindertag_amd import capi
 from ctag_testlib import Oracle, read_marker_file, GOLDEN
 state, fs = read_marker_file(os.path.join(GOLDEN, "CTag_2f12c.marker"))
-src = open(os.path.join(ROOT, "tests", "test_gpu_parity.py")).read()
-ns = {"ca": ca, "np": np, "tk": tk}
-exec(src[src.index("def _random_shapes_frame"):src.index("def test_random_shapes_fuzz")], ns)
+from edge_testlib import random_shapes_frame
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 rows, cols = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (720, 1152)
 seed0 = int(os.environ.get("CTAG_SWEEP_SEED", "5000"))  # another population of shapes
-frames = np.stack([ns["_random_shapes_frame"](state, seed0 + i, rows, cols) for i in range(n)])
+frames = np.stack([random_shapes_frame(state, seed0 + i, rows, cols) for i in range(n)])
 orc, det = Oracle(), tk.Detector(state, fs)
 for chunk in (1024, 37):
     det.set_option(capi.OPT_MAX_CHUNK, chunk)

@@ -5,7 +5,7 @@ import numpy as np
 import cylindertag_amd as ca, testkit as tk
 from cylindertag_amd import capi
 from ctag_testlib import GOLDEN, Oracle, read_marker_file
-from test_gpu_parity import _random_shapes_frame
+from edge_testlib import random_shapes_frame as _random_shapes_frame
 state, fs = read_marker_file(os.path.join(GOLDEN, "CTag_2f12c.marker"))
 orc = Oracle(); det = tk.Detector(state, fs, device=0)
 det.set_option(capi.OPT_FUSED_SWEEP, 2)
