@@ -12,6 +12,7 @@
 #include <fstream>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ctag.h"
@@ -28,6 +29,34 @@ using namespace ctag;
         }                                                                                               \
     } while (0)
 
+// One call -- or the frames [f0, f0 + m) of one (sub) -- as the host layer hands it down: where the frames lie and how they are to be detected
+struct Call {
+    const uint8_t* frames;
+    int n, rows, cols, channels;  // channels 3: 8-bit BGR, 3 bytes per pixel
+    ptrdiff_t row_stride, frame_stride;
+    int adaptive_thresh, corner_subpix, subpix_dist;
+    Call sub(int f0, int m) const {
+        Call c = *this;
+        c.frames += (ptrdiff_t)f0 * frame_stride;
+        c.n = m;
+        return c;
+    }
+};
+
+// One result record in pinned host memory, written by k_markers itself through its device address: no download behind the chain
+struct MappedRec {
+    ctag_frame_result* host = nullptr;
+    ctag_frame_result* dev = nullptr;
+    hipError_t ensure() {
+        if (host) return hipSuccess;
+        const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&host), sizeof(ctag_frame_result), hipHostMallocMapped);
+        return e != hipSuccess ? e : hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), host, 0);
+    }
+    ~MappedRec() {
+        if (host) (void)hipHostFree(host);
+    }
+};
+
 struct ctag_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -36,29 +65,28 @@ struct ctag_handle {
     std::vector<int32_t> dict;
     ctag_params params{};            // the tunables this handle was created with (ctag_params_default unless ctag_create_ex said otherwise)
     KParams kp{};                    // ... as the kernels consume them
-    uint8_t* d_thr_table = nullptr;  // adaptive-threshold bound table for params.dark_cap
-    int32_t* d_dict = nullptr;
-    uint32_t* d_dict_pos = nullptr;  // [dict_rows][64]: columns holding each symbol (k_markers' bit-parallel coverage); null for > 32 columns
-    uint8_t* d_pick_table = nullptr;
+    DevBuf<uint8_t> d_thr_table;     // adaptive-threshold bound table for params.dark_cap
+    DevBuf<int32_t> d_dict;
+    DevBuf<uint32_t> d_dict_pos;     // [dict_rows][64]: columns holding each symbol (k_markers' bit-parallel coverage); null for > 32 columns
+    DevBuf<uint8_t> d_pick_table;
     int dict_rows = 0, dict_cols = 0, feature_size = 0;
-    // Two workspaces: `batch` holds chunks of frames with pools sized for what a frame of its size ordinarily needs (make_caps);
-    // `big` holds ONE frame with pools no frame of that size can exhaust -- a frame that overflowed a batch pool (thousands of
-    // blobs, fine texture: CTAG_FLAG_POOL_OVERFLOW -> CTAG_PENDING) is run again there (rerun_frame).  `big` is allocated on first use.
+    // Two kinds of workspace: a batch one holds chunks of frames with pools sized for what a frame of its size ordinarily needs (make_caps);
+    // the big one holds ONE frame with pools no frame of that size can exhaust -- a frame that overflowed a batch pool (thousands of
+    // blobs, fine texture: CTAG_FLAG_POOL_OVERFLOW -> CTAG_PENDING) is run again there (rerun_frame).  Each is allocated on first use.
     struct WsSlot {
         Workspace ws;
+        DevBuf<char> mem;           // ws.base
         int rows = 0, cols = 0, tw = 0, cap = 0;
-        double* n0_buf = nullptr;   // refine_n0, allocated when a chunk of more than kLatencyFrames frames first runs with corner_subpix
-        size_t n0_frames = 0;
+        DevBuf<double> n0;          // refine_n0, allocated when a chunk of more than kLatencyFrames frames first runs with corner_subpix
     };
-    WsSlot batch, big;
-    // CTAG_OPT_STREAMS = 2 (default): a chunk of a device-memory batch runs as two halves on two streams (`stream` + `stream2`, workspaces
-    // `batch` + `batch2`), so that the tail of one half's kernels -- a few long boundary / Welsch blocks -- overlaps the other half's next
-    // kernel.  stream2 forks from `stream` at the head of a call and joins it at the end: callers still order against `stream` alone.
+    // CTAG_OPT_STREAMS = 2 (default): a chunk of a device-memory batch runs as two halves on two streams (`stream` + `streamx[0]`, workspaces
+    // `slot[0]` + `slot[1]`), so that the tail of one half's kernels -- a few long boundary / Welsch blocks -- overlaps the other half's next
+    // kernel.  The extra streams fork from `stream` at the head of a call and join it at the end: callers still order against `stream` alone.
     static constexpr int kMaxStreams = 4;
-    WsSlot batchx[kMaxStreams - 1];                 // workspaces of the extra streams (stream k > 0 uses batchx[k - 1])
-    hipStream_t streamx[kMaxStreams - 1] = {};      // (stream2 = streamx[0])
+    static constexpr int kBigSlot = kMaxStreams;
+    WsSlot slot[kMaxStreams + 1];                   // stream k (0: `stream`, k > 0: streamx[k - 1]) uses slot[k] (comments that speak of `batch` / `batch2` mean slot[0] / slot[1]); slot[kBigSlot] is the any-frame workspace
+    hipStream_t streamx[kMaxStreams - 1] = {};
     hipEvent_t ev_joinx[kMaxStreams - 1] = {};
-    hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork2 = nullptr;
     int streams = 2;
     const Workspace* last_ws = nullptr;  // whichever ran last (handle_view)
@@ -67,28 +95,22 @@ struct ctag_handle {
     ptrdiff_t last_row_stride = 0, last_frame_stride = 0;
     const ctag_frame_result* last_out = nullptr;  // ... and where its records went (ctag_get_counters)
     // frames of device-memory calls that wait for the any-frame pass (k_markers appends, finish_pending drains)
-    PendingRec* d_pending = nullptr;
-    int32_t* d_pending_count = nullptr;
+    DevBuf<PendingRec> d_pending;
+    DevBuf<int32_t> d_pending_count;  // 256 bytes: the count, and the sums of ctag_get_counters
     int pending_cap = 65536;
     bool pending_dirty = false;      // a device-memory call was enqueued since the list was last read
     uint64_t pending_gen = 0;        // ... and how many such calls there were
-    uint8_t* d_big_frame = nullptr;  // private copy of a pending frame (host-memory calls upload it again; BGR frames are converted into d_big_gray)
-    size_t d_big_frame_bytes = 0;
-    uint8_t* d_big_gray = nullptr;
-    size_t d_big_gray_bytes = 0;
-    ctag_frame_result* d_big_result = nullptr;
+    DevBuf<uint8_t> d_big_frame;     // private copy of a pending frame (host-memory calls upload it again; BGR frames are converted into d_big_gray)
+    DevBuf<uint8_t> d_big_gray;
+    DevBuf<ctag_frame_result> d_big_result;
     int reruns = 0;                  // frames completed through the any-frame workspace so far (ctag_get_counters)
     // ctag_submit_u8 / ctag_collect: frames in flight, one per call (a camera loop, main.cpp:44-61).  Slot k: a device slab for the frame (filled on
     // copy_stream), a device record and its pinned host copy; `up` = upload done, `done` = record downloaded
     struct AsyncSlot {
-        uint8_t* d_frame = nullptr;
-        size_t d_bytes = 0;
-        ctag_frame_result* d_res = nullptr;
-        ctag_frame_result* h_res = nullptr;
+        DevBuf<uint8_t> d_frame;
+        MappedRec res;
         hipEvent_t up = nullptr, done = nullptr;
-        const uint8_t* host = nullptr;  // the caller's frame (valid until its ctag_collect: a pending frame is uploaded again from it)
-        int rows = 0, cols = 0, ch = 1, tw = 0, subpix = 0, dist = 0;
-        ptrdiff_t row_stride = 0;
+        Call host{};  // the caller's frame (valid until its ctag_collect: a pending frame is uploaded again from it)
     };
     static constexpr int kAsyncDepth = 2;
     AsyncSlot aslot[kAsyncDepth];
@@ -106,17 +128,13 @@ struct ctag_handle {
     float stage_ms[CTAG_NUM_STAGES] = {};
     // staging for host-memory entry points: two slabs of `host_sub` frames, filled on copy_stream while the
     // other slab is being processed on `stream`
-    uint8_t* d_frames = nullptr;
-    size_t d_frames_bytes = 0;
-    ctag_frame_result* d_results = nullptr;
-    ctag_frame_result* h_res1 = nullptr;       // pinned: the record of a one-frame host call, written by k_markers itself (no download)
-    ctag_frame_result* h_res1_dev = nullptr;   // ... as the device addresses it
-    size_t d_results_count = 0;
+    DevBuf<uint8_t> d_frames;
+    DevBuf<ctag_frame_result> d_results;
+    MappedRec res1;                            // the record of a one-frame host call
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_copied[2] = {}, ev_done[2] = {};
     // BGR ingest (ctag_detect_*bgr8*): the gray frames of the chunk in flight, written by k_bgr2gray and read by K1 / K8
-    uint8_t* d_gray = nullptr;
-    size_t d_gray_bytes = 0;
+    DevBuf<uint8_t> d_gray;
     ptrdiff_t gray_row_stride = 0, gray_frame_stride = 0;
     bool last_was_bgr = false;
     int host_sub = 128;
@@ -149,36 +167,17 @@ struct ctag_handle {
     int use_graph = 2;   // CTAG_OPT_GRAPH: 0 off, 1 every chunk, 2 (default) few-frame calls whose pointers / sizes / parameters repeat;
                          // back to 0 after a capture failed once (the direct path takes over for good)
     GraphKey last_key;   // automatic mode: the previous few-frame chunk (a graph is only worth capturing for a repeat)
-    // state of the pose back end (k_pose.hip), created on first use
-    void* pose_state = nullptr;
-    void (*pose_state_free)(void*) = nullptr;
-    // state of the overlay (k_draw.hip), created on first use
-    void* draw_state = nullptr;
-    void (*draw_state_free)(void*) = nullptr;
-    // state of the rig poses (k_rig_pose.hip), created on first use
-    void* rig_state = nullptr;
-    void (*rig_state_free)(void*) = nullptr;
-    // state of the multi-GPU gather layer (ctag_gather.hip), created on first use
-    void* gather_state = nullptr;
-    void (*gather_state_free)(void*) = nullptr;
+    // states of the back ends (SiblingState, ctag_internal.h), each created on first use
+    struct {
+        void* p = nullptr;
+        void (*free_fn)(void*) = nullptr;
+    } state[kNumSiblingStates];
 };
 
 namespace ctag {
-void** handle_pose_slot(ctag_handle* h, void (*free_fn)(void*)) {
-    h->pose_state_free = free_fn;
-    return &h->pose_state;
-}
-void** handle_draw_slot(ctag_handle* h, void (*free_fn)(void*)) {
-    h->draw_state_free = free_fn;
-    return &h->draw_state;
-}
-void** handle_rig_slot(ctag_handle* h, void (*free_fn)(void*)) {
-    h->rig_state_free = free_fn;
-    return &h->rig_state;
-}
-void** handle_gather_slot(ctag_handle* h, void (*free_fn)(void*)) {
-    h->gather_state_free = free_fn;
-    return &h->gather_state;
+void** handle_state_slot(ctag_handle* h, SiblingState which, void (*free_fn)(void*)) {
+    h->state[which].free_fn = free_fn;
+    return &h->state[which].p;
 }
 bool handle_timing(const ctag_handle* h) { return h->timing; }
 int handle_device(const ctag_handle* h) { return h->device; }
@@ -195,7 +194,7 @@ void handle_view(const ctag_handle* h, HandleView* out) {
     out->row_stride = h->last_row_stride;
     out->frame_stride = h->last_frame_stride;
     out->stream = h->stream;
-    out->gray = h->last_was_bgr ? h->d_gray : nullptr;
+    out->gray = h->last_was_bgr ? h->d_gray.p : nullptr;
     out->gray_row_stride = h->gray_row_stride;
     out->gray_frame_stride = h->gray_frame_stride;
 }
@@ -283,34 +282,109 @@ static Caps make_caps(const FrameGeom& g, const ctag_params& prm, bool big) {
     return c;
 }
 
+// every stream the handle owns idle: what comes before anything that frees or replaces memory a stream may still read (a workspace, a slab, the
+// kernarg storage of a graph exec), and before a failed host-memory call returns.  Never on the path of a call that finds its buffers in place.
+// Every stream is waited for whatever the others answered; the first error is returned, and last_error is the caller's to write (HIP_TRY) or to leave.
+static hipError_t quiesce(ctag_handle* h) {
+    hipError_t first = hipSuccess;
+    auto wait = [&](hipStream_t s) {
+        const hipError_t e = s ? hipStreamSynchronize(s) : hipSuccess;
+        if (first == hipSuccess) first = e;
+    };
+    wait(h->copy_stream);
+    for (hipStream_t x : h->streamx) wait(x);
+    wait(h->aux_stream);  // side branch of few-frame calls
+    wait(h->stream);
+    return first;
+}
+
+static size_t label_bytes(const FrameGeom& g, size_t frames) { return frames * g.hrows * g.lp * 2 + 256; }
+static size_t tile_bytes(const FrameGeom& g, size_t frames) { return frames * g.tiles_x * g.tiles_y * 4; }
+
+// The arrays of a workspace for `frames` frames (W.g and the caps are set), in the order they lie in its one allocation, each on a 256-byte boundary:
+// every array is named here once, with its byte count.  With base == nullptr this only adds up; with the allocation it sets the pointers.  Returns the total.
+static size_t carve_workspace(Workspace& W, size_t frames, char* base) {
+    const FrameGeom& g = W.g;
+    const size_t F = frames, CC = (size_t)W.cand_cap, LC = (size_t)W.line_cap;
+    size_t off = 0;
+    auto put = [&](auto*& field, size_t bytes) {
+        field = base ? reinterpret_cast<std::remove_reference_t<decltype(field)>>(base + off) : nullptr;
+        off = (off + bytes + 255) & ~(size_t)255;
+    };
+    put(W.half, F * g.hrows * g.hp + 256);
+    put(W.labels, label_bytes(g, F));
+    put(W.tile_base, tile_bytes(g, F));
+    put(W.tile_dirty, tile_bytes(g, F));
+    put(W.frame_ncomp, F * 4);
+    put(W.frame_flags, F * 4);
+    put(W.ovf_count, 256);
+    put(W.ovf_list, tile_bytes(g, F));
+    const size_t pool = F * (size_t)g.pool_cap * 4;
+    put(W.parent, pool);
+    put(W.root_of, pool);
+    put(W.area, pool);
+    put(W.xmin, pool);
+    put(W.ymin, pool);
+    put(W.xmax, pool);
+    put(W.ymax, pool);
+    put(W.key, pool);
+    put(W.pool_tile, pool);
+    put(W.member_head, pool);
+    put(W.member_next, pool);
+    put(W.ncand, F * 4);
+    put(W.nroots, F * 4);
+    put(W.cand, F * CC * sizeof(Candidate));
+    put(W.quads, F * CC * sizeof(QuadOut));
+    put(W.line_count, F * 4);
+    put(W.clp_used, F * 4);
+    put(W.line_long, F * 4);
+    put(W.cl_pool, F * (size_t)W.cl_cap * 4 + 16);  // + one element: welsch_restart requests one point past a cluster's last
+    put(W.line_desc, F * LC * sizeof(LineDesc));
+    put(W.line_sorted, F * LC * 4);
+    put(W.line_fit, F * LC * 16);
+    put(W.cand_aux, F * CC * sizeof(CandAux));
+    put(W.npacks, F * 8);
+    put(W.packs, F * CC * 4);
+    put(W.pack_order, F * CC * 4);
+    put(W.welsch_rs, std::min<size_t>(F, kLatencyFrames) * kLatLines * 20 * 6 * 4);
+    put(W.quad_derived, F * kQuadStride * 48);
+    put(W.quad_index, F * kQuadStride * 4);
+    put(W.nquads, F * 4);
+    put(W.nfeat, F * 4);
+    put(W.status, F * 4);
+    put(W.feat0, F * CTAG_MAX_FEATURES * sizeof(FeatureDev));
+    put(W.feat1, F * CTAG_MAX_FEATURES * sizeof(FeatureDev));
+    put(W.feat2, F * CTAG_MAX_FEATURES * sizeof(FeatureDev));
+    put(W.premarkers, F * sizeof(ctag_frame_result));
+    put(W.frame_long, F * 4);
+    put(W.rz_xofs, (size_t)g.hcols * 4);
+    put(W.rz_alpha, (size_t)g.hcols * 8);
+    put(W.rz_yofs, (size_t)g.hrows * 4);
+    put(W.rz_beta, (size_t)g.hrows * 8);
+    return off;
+}
+
 static int ensure_workspace(ctag_handle* h, ctag_handle::WsSlot& S, int rows, int cols, int tw, int frames, bool big, bool need_n0) {
     auto refresh = [&](Workspace& W) {
         const Caps c = make_caps(make_geom(rows, cols, tw, h->params.area_max_fraction), h->params, big);
         W.g = make_geom(rows, cols, tw, h->params.area_max_fraction);
         W.g.pool_cap = c.pool_cap;
         W.kp = h->kp;
-        W.pick_table = h->d_pick_table;
-        W.pick_table16 = reinterpret_cast<const uint16_t*>(h->d_pick_table + (size_t)kPickN * 200);
+        W.pick_table = h->d_pick_table.p;
+        W.pick_table16 = reinterpret_cast<const uint16_t*>(h->d_pick_table.p + (size_t)kPickN * 200);
         W.aux_stream = h->aux_stream;
         W.ev_fork = h->ev_fork;
         W.ev_join = h->ev_join;
         W.big = big;
     };
     auto ensure_n0 = [&]() -> int {  // the searches -> sums hand-over of k_edge_refine<1> / <2>: 0.8 MB per frame, batches with corner_subpix only
-        if (!need_n0 || S.n0_frames >= (size_t)S.cap) {
-            S.ws.refine_n0 = S.n0_buf;
-            return CTAG_OK;
+        const size_t need = (size_t)S.cap * CTAG_MAX_FEATURES * 2 * 4 * 128;
+        if (need_n0 && S.n0.cap < need) {
+            HIP_TRY(quiesce(h));
+            drop_graphs(h);
+            HIP_TRY(S.n0.grow(need));
         }
-        for (hipStream_t x : h->streamx)
-            if (x) HIP_TRY(hipStreamSynchronize(x));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        drop_graphs(h);
-        if (S.n0_buf) HIP_TRY(hipFree(S.n0_buf));
-        S.n0_buf = nullptr;
-        S.n0_frames = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&S.n0_buf), (size_t)S.cap * CTAG_MAX_FEATURES * 2 * 4 * 128 * 8));
-        S.n0_frames = (size_t)S.cap;
-        S.ws.refine_n0 = S.n0_buf;
+        S.ws.refine_n0 = S.n0.p;
         return CTAG_OK;
     };
     if (S.ws.base && S.rows == rows && S.cols == cols && S.cap >= frames) {
@@ -319,14 +393,10 @@ static int ensure_workspace(ctag_handle* h, ctag_handle::WsSlot& S, int rows, in
         return ensure_n0();
     }
     if (S.ws.base) {
-        for (hipStream_t x : h->streamx)
-            if (x) HIP_TRY(hipStreamSynchronize(x));
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(quiesce(h));
         drop_graphs(h);  // they hold pointers into the old workspace
-        HIP_TRY(hipFree(S.ws.base));
-        if (S.n0_buf) HIP_TRY(hipFree(S.n0_buf));
-        S.n0_buf = nullptr;
-        S.n0_frames = 0;
+        S.mem.release();
+        S.n0.release();
         if (h->last_ws == &S.ws) h->last_ws = nullptr;
         S.ws = Workspace{};
         S.cap = 0;
@@ -339,104 +409,14 @@ static int ensure_workspace(ctag_handle* h, ctag_handle::WsSlot& S, int rows, in
     W.cl_cap = caps.cl_cap;
     const FrameGeom& g = W.g;
     const size_t F = (size_t)frames;
-    const size_t tiles = (size_t)g.tiles_x * g.tiles_y;
-    const size_t CC = (size_t)W.cand_cap, LC = (size_t)W.line_cap;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t o_half = take(F * g.hrows * g.hp + 256);
-    const size_t o_labels = take(F * g.hrows * g.lp * 2 + 256);
-    const size_t o_tbase = take(F * tiles * 4), o_tdirty = take(F * tiles * 4);
-    const size_t o_ncomp = take(F * 4);
-    const size_t o_flags = take(F * 4);
-    const size_t o_ovfc = take(256);
-    const size_t o_ovfl = take(F * tiles * 4);
-    const size_t pool = F * (size_t)g.pool_cap * 4;
-    const size_t o_parent = take(pool), o_root = take(pool), o_area = take(pool), o_xmin = take(pool), o_ymin = take(pool),
-                 o_xmax = take(pool), o_ymax = take(pool), o_key = take(pool), o_ptile = take(pool), o_mhead = take(pool), o_mnext = take(pool);
-    const size_t o_ncand = take(F * 4), o_nroots = take(F * 4);
-    const size_t o_cand = take(F * CC * sizeof(Candidate));
-    const size_t o_quads = take(F * CC * sizeof(QuadOut));
-    const size_t o_lcount = take(F * 4), o_clused = take(F * 4), o_llong = take(F * 4);
-    const size_t o_clpool = take(F * (size_t)W.cl_cap * 4 + 16);  // + one element: welsch_restart requests one point past a cluster's last
-    const size_t o_ldesc = take(F * LC * sizeof(LineDesc));
-    const size_t o_lsort = take(F * LC * 4);
-    const size_t o_lfit = take(F * LC * 16);
-    const size_t o_aux = take(F * CC * sizeof(CandAux));
-    const size_t o_npk = take(F * 8), o_pk = take(F * CC * 4), o_pord = take(F * CC * 4);
-    const size_t o_wrs = take(std::min<size_t>(F, kLatencyFrames) * kLatLines * 20 * 6 * 4);
-    const size_t o_der = take(F * kQuadStride * 48);
-    const size_t o_qidx = take(F * kQuadStride * 4);
-    const size_t o_nq = take(F * 4), o_nf = take(F * 4), o_st = take(F * 4);
-    const size_t o_f0 = take(F * CTAG_MAX_FEATURES * sizeof(FeatureDev));
-    const size_t o_f1 = take(F * CTAG_MAX_FEATURES * sizeof(FeatureDev));
-    const size_t o_f2 = take(F * CTAG_MAX_FEATURES * sizeof(FeatureDev));
-    const size_t o_pre = take(F * sizeof(ctag_frame_result));
-    const size_t o_flong = take(F * 4);
-    const size_t o_rzx = take((size_t)g.hcols * 4), o_rza = take((size_t)g.hcols * 8), o_rzy = take((size_t)g.hrows * 4), o_rzb = take((size_t)g.hrows * 8);
-    void* base = nullptr;
-    HIP_TRY(hipMalloc(&base, off));
-    char* b = static_cast<char*>(base);
-    W.base = base;
-    W.bytes = off;
+    HIP_TRY(S.mem.grow(carve_workspace(W, F, nullptr)));
+    W.base = S.mem.p;
+    W.bytes = carve_workspace(W, F, S.mem.p);
     W.chunk_frames = frames;
-    W.half = reinterpret_cast<uint8_t*>(b + o_half);
-    W.labels = reinterpret_cast<uint16_t*>(b + o_labels);
-    W.tile_base = reinterpret_cast<int32_t*>(b + o_tbase);
-    W.tile_dirty = reinterpret_cast<int32_t*>(b + o_tdirty);
     // the label image's invariant: a tile whose tile_dirty is 0 holds zeros
-    HIP_TRY(hipMemsetAsync(W.labels, 0, F * g.hrows * g.lp * 2 + 256, h->stream));
-    HIP_TRY(hipMemsetAsync(W.tile_dirty, 0, F * tiles * 4, h->stream));
-    HIP_TRY(hipMemsetAsync(W.tile_base, 0, F * tiles * 4, h->stream));  // the fused sweep leaves the entries of tiles without foreground alone: they must stay valid offsets
-    W.frame_ncomp = reinterpret_cast<int32_t*>(b + o_ncomp);
-    W.frame_flags = reinterpret_cast<uint32_t*>(b + o_flags);
-    W.ovf_count = reinterpret_cast<int32_t*>(b + o_ovfc);
-    W.ovf_list = reinterpret_cast<int32_t*>(b + o_ovfl);
-    W.parent = reinterpret_cast<uint32_t*>(b + o_parent);
-    W.root_of = reinterpret_cast<int32_t*>(b + o_root);
-    W.area = reinterpret_cast<int32_t*>(b + o_area);
-    W.xmin = reinterpret_cast<int32_t*>(b + o_xmin);
-    W.ymin = reinterpret_cast<int32_t*>(b + o_ymin);
-    W.xmax = reinterpret_cast<int32_t*>(b + o_xmax);
-    W.ymax = reinterpret_cast<int32_t*>(b + o_ymax);
-    W.key = reinterpret_cast<int32_t*>(b + o_key);
-    W.pool_tile = reinterpret_cast<int32_t*>(b + o_ptile);
-    W.member_head = reinterpret_cast<int32_t*>(b + o_mhead);
-    W.member_next = reinterpret_cast<int32_t*>(b + o_mnext);
-    W.ncand = reinterpret_cast<int32_t*>(b + o_ncand);
-    W.nroots = reinterpret_cast<int32_t*>(b + o_nroots);
-    W.cand = reinterpret_cast<Candidate*>(b + o_cand);
-    W.quads = reinterpret_cast<QuadOut*>(b + o_quads);
-    W.line_count = reinterpret_cast<int32_t*>(b + o_lcount);
-    W.clp_used = reinterpret_cast<int32_t*>(b + o_clused);
-    W.cl_pool = reinterpret_cast<uint32_t*>(b + o_clpool);
-    W.line_desc = reinterpret_cast<LineDesc*>(b + o_ldesc);
-    W.line_sorted = reinterpret_cast<int32_t*>(b + o_lsort);
-    W.line_long = reinterpret_cast<int32_t*>(b + o_llong);
-    W.line_fit = reinterpret_cast<float*>(b + o_lfit);
-    W.cand_aux = reinterpret_cast<CandAux*>(b + o_aux);
-    W.npacks = reinterpret_cast<int32_t*>(b + o_npk);
-    W.packs = reinterpret_cast<uint32_t*>(b + o_pk);
-    W.pack_order = reinterpret_cast<uint32_t*>(b + o_pord);
-    W.welsch_rs = reinterpret_cast<float*>(b + o_wrs);
-    W.quad_derived = b + o_der;
-    W.quad_index = reinterpret_cast<int32_t*>(b + o_qidx);
-    W.nquads = reinterpret_cast<int32_t*>(b + o_nq);
-    W.nfeat = reinterpret_cast<int32_t*>(b + o_nf);
-    W.status = reinterpret_cast<int32_t*>(b + o_st);
-    W.feat0 = reinterpret_cast<FeatureDev*>(b + o_f0);
-    W.feat1 = reinterpret_cast<FeatureDev*>(b + o_f1);
-    W.feat2 = reinterpret_cast<FeatureDev*>(b + o_f2);
-    W.premarkers = reinterpret_cast<ctag_frame_result*>(b + o_pre);
-    W.refine_n0 = nullptr;
-    W.frame_long = reinterpret_cast<int32_t*>(b + o_flong);
-    W.rz_xofs = reinterpret_cast<int32_t*>(b + o_rzx);
-    W.rz_alpha = reinterpret_cast<int16_t*>(b + o_rza);
-    W.rz_yofs = reinterpret_cast<int32_t*>(b + o_rzy);
-    W.rz_beta = reinterpret_cast<int16_t*>(b + o_rzb);
+    HIP_TRY(hipMemsetAsync(W.labels, 0, label_bytes(g, F), h->stream));
+    HIP_TRY(hipMemsetAsync(W.tile_dirty, 0, tile_bytes(g, F), h->stream));
+    HIP_TRY(hipMemsetAsync(W.tile_base, 0, tile_bytes(g, F), h->stream));  // the fused sweep leaves the entries of tiles without foreground alone: they must stay valid offsets
     {   // tap tables of the general decimation (used for odd sizes only; a few KB)
         std::vector<int32_t> xo, yo;
         std::vector<int16_t> al, be;
@@ -568,35 +548,48 @@ ChunkPlan plan_chunk(const PlanIn& in) {
 }
 }  // namespace ctag
 
-static int check_args(ctag_handle* h, const void* frames, int n, int rows, int cols, ptrdiff_t row_stride, int adaptive_thresh, int subpix_dist) {
-    if (!h || !frames || n < 0 || rows < 4 || cols < 4 || row_stride < cols || adaptive_thresh < 1 || subpix_dist < 0) return CTAG_ERR_ARG;
-    if (adaptive_thresh > kMaxThreshWin) return CTAG_ERR_UNSUPPORTED;
-    if (rows / 2 > 16000 || cols / 2 > 16000) return CTAG_ERR_UNSUPPORTED;
-    if (row_stride >= (1 << 24) || (long long)rows * row_stride > 0xffffffffLL) return CTAG_ERR_UNSUPPORTED;  // 32-bit pixel offsets (k_edge_refine)
+// (BGR frames: the 32-bit pixel offsets are those of the gray slab the frames are converted into.  The direct form, which reads the BGR rows themselves,
+// is only chosen for a row_stride and a frame span within the same limits: plan_chunk, pl.bgr_direct)
+static int check_args(ctag_handle* h, const Call& c) {
+    const ptrdiff_t gray_stride = c.channels == 3 ? ((ptrdiff_t)c.cols + 15) & ~(ptrdiff_t)15 : c.row_stride;
+    if (!h || !c.frames || c.n < 0 || c.rows < 4 || c.cols < 4 || c.row_stride < (ptrdiff_t)c.cols * c.channels || c.adaptive_thresh < 1 || c.subpix_dist < 0)
+        return CTAG_ERR_ARG;
+    if (c.adaptive_thresh > kMaxThreshWin) return CTAG_ERR_UNSUPPORTED;
+    if (c.rows / 2 > 16000 || c.cols / 2 > 16000) return CTAG_ERR_UNSUPPORTED;
+    if (gray_stride >= (1 << 24) || (long long)c.rows * gray_stride > 0xffffffffLL) return CTAG_ERR_UNSUPPORTED;  // 32-bit pixel offsets (k_edge_refine)
     return CTAG_OK;
 }
 
-// "the last chunk" of the probes and counters (handle_view, ctag_get_counters)
-static void note_last(ctag_handle* h, const Workspace& ws, const ChunkPlan& pl, const uint8_t* frames_dev, ptrdiff_t row_stride, ptrdiff_t frame_stride,
-                      const ctag_frame_result* out_dev) {
-    h->last_ws = &ws, h->last_plan = pl, h->last_out = out_dev;
-    h->last_frames = pl.channels == 3 ? nullptr : frames_dev;  // (BGR frames handed to the chain as they are: no gray rows for the half-size probe to decimate)
-    h->last_row_stride = row_stride, h->last_frame_stride = frame_stride;
+static DetectParams detect_params(const ctag_handle* h, const Call& c) {
+    DetectParams p{c.adaptive_thresh, c.corner_subpix, c.subpix_dist, h->feature_size, h->dict_rows, h->dict_cols, h->d_dict.p, h->d_dict_pos.p};
+    p.channels = c.channels;
+    return p;
+}
+// c: frames in the CALLER's device memory -- what one of them that needs the any-frame pass is read from again
+static PendingCtx pending_ctx(const ctag_handle* h, const Call& c) {
+    return PendingCtx{h->d_pending.p, h->d_pending_count.p, h->pending_cap, c.frames, (int64_t)c.frame_stride, (int64_t)c.row_stride,
+                      c.rows, c.cols, c.channels, c.adaptive_thresh, c.corner_subpix, c.subpix_dist};
 }
 
-// enqueue the whole pipeline for `n` device-resident frames (n <= workspace capacity); evs: CTAG_NUM_STAGES + 1 timing events or null
-static int enqueue_chunk(ctag_handle* h, const Workspace& ws, const uint8_t* frames_dev, int n, ptrdiff_t row_stride, ptrdiff_t frame_stride,
-                         const DetectParams& p, ctag_frame_result* out_dev, hipEvent_t* evs, const PendingCtx& pend, hipStream_t s = nullptr) {
-    if (!s) s = h->stream;
-    const ChunkPlan pl = plan_chunk(PlanIn{ws.g.rows, ws.g.cols, ws.g.tw, n, p.channels, p.corner_subpix, frames_dev, frame_stride, row_stride, ws.kp,
+// "the last chunk" of the probes and counters (handle_view, ctag_get_counters)
+static void note_last(ctag_handle* h, const Workspace& ws, const ChunkPlan& pl, const Call& c, const ctag_frame_result* out_dev) {
+    h->last_ws = &ws, h->last_plan = pl, h->last_out = out_dev;
+    h->last_frames = pl.channels == 3 ? nullptr : c.frames;  // (BGR frames handed to the chain as they are: no gray rows for the half-size probe to decimate)
+    h->last_row_stride = c.row_stride, h->last_frame_stride = c.frame_stride;
+}
+
+// enqueue the whole pipeline for the c.n device-resident frames of `c` (c.n <= workspace capacity) on stream s; evs: CTAG_NUM_STAGES + 1 timing events or null
+static int enqueue_chunk(ctag_handle* h, const Workspace& ws, const Call& c, ctag_frame_result* out_dev, hipEvent_t* evs, const PendingCtx& pend, hipStream_t s) {
+    const DetectParams p = detect_params(h, c);
+    const ChunkPlan pl = plan_chunk(PlanIn{ws.g.rows, ws.g.cols, ws.g.tw, c.n, p.channels, p.corner_subpix, c.frames, c.frame_stride, c.row_stride, ws.kp,
                                            h->fuse_mode, h->wave_points, h->bgr_direct != 0, dev_knobs()});
-    note_last(h, ws, pl, frames_dev, row_stride, frame_stride, out_dev);
+    note_last(h, ws, pl, c, out_dev);
     if (pl.zero_first) HIP_TRY(launch_zero_counters(pl, ws, s));
     int st = 0;
     auto mark = [&](int i) -> hipError_t { return evs ? hipEventRecord(evs[i], s) : hipSuccess; };
     HIP_TRY(mark(0));
     if (p.channels == 3 && !pl.fused) return CTAG_ERR_UNSUPPORTED;  // (detect_bgr_device_impl has checked: BGR frames go through k_bgr2gray otherwise)
-    HIP_TRY(launch_decimate(pl, frames_dev, frame_stride, row_stride, ws, s));
+    HIP_TRY(launch_decimate(pl, c.frames, c.frame_stride, c.row_stride, ws, s));
     HIP_TRY(mark(++st));
     HIP_TRY(launch_threshold_ccl(pl, ws, s));
     HIP_TRY(mark(++st));
@@ -611,7 +604,7 @@ static int enqueue_chunk(ctag_handle* h, const Workspace& ws, const uint8_t* fra
     HIP_TRY(mark(++st));
     HIP_TRY(launch_features(pl, ws, p, s));
     HIP_TRY(mark(++st));
-    HIP_TRY(launch_edge_refine(pl, frames_dev, frame_stride, row_stride, ws, p, s));
+    HIP_TRY(launch_edge_refine(pl, c.frames, c.frame_stride, c.row_stride, ws, p, s));
     HIP_TRY(mark(++st));
     Workspace wtmp = ws;
     if (!h->keep_pre) wtmp.premarkers = nullptr;
@@ -622,9 +615,7 @@ static int enqueue_chunk(ctag_handle* h, const Workspace& ws, const uint8_t* fra
 
 // an exec owns the kernarg storage of its launches: nothing it enqueued may still be running when it is destroyed
 static void graphs_idle(ctag_handle* h) {
-    if (h->graphs.empty()) return;
-    if (h->aux_stream) (void)hipStreamSynchronize(h->aux_stream);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (!h->graphs.empty()) (void)quiesce(h);
 }
 static void drop_graphs(ctag_handle* h) {
     graphs_idle(h);
@@ -635,16 +626,15 @@ static void drop_graphs(ctag_handle* h) {
 
 // replay (or first capture) the chunk as a hipGraph; any failure disables the graph path for this handle and the caller
 // falls back to direct launches -- results are the same either way
-static bool run_chunk_graph(ctag_handle* h, const ctag_handle::GraphKey& key, const uint8_t* frames_dev, int n, ptrdiff_t row_stride, ptrdiff_t frame_stride,
-                            const DetectParams& p, ctag_frame_result* out_dev, const PendingCtx& pend) {
-    const Workspace& W = h->batch.ws;
+static bool run_chunk_graph(ctag_handle* h, const ctag_handle::GraphKey& key, const Call& c, ctag_frame_result* out_dev, const PendingCtx& pend) {
+    const Workspace& W = h->slot[0].ws;
     constexpr size_t kMaxGraphs = 8;
     ctag_handle::GraphEntry* hit = nullptr;
     for (auto& g : h->graphs)
         if (g.key == key) hit = &g;
     if (!hit) {
         if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed) != hipSuccess) return false;
-        const int r = enqueue_chunk(h, W, frames_dev, n, row_stride, frame_stride, p, out_dev, nullptr, pend);
+        const int r = enqueue_chunk(h, W, c, out_dev, nullptr, pend, h->stream);
         hipGraph_t graph = nullptr;
         const hipError_t e = hipStreamEndCapture(h->stream, &graph);
         if (r != CTAG_OK || e != hipSuccess || !graph) {
@@ -671,20 +661,22 @@ static bool run_chunk_graph(ctag_handle* h, const ctag_handle::GraphKey& key, co
         hit = &h->graphs.back();
     }
     hit->last_use = ++h->graph_clock;
-    note_last(h, W, hit->plan, frames_dev, row_stride, frame_stride, out_dev);
+    note_last(h, W, hit->plan, c, out_dev);
     return hipGraphLaunch(hit->exec, h->stream) == hipSuccess;
 }
 
-static int run_chunk(ctag_handle* h, const uint8_t* frames_dev, int n, ptrdiff_t row_stride, ptrdiff_t frame_stride, const DetectParams& p,
-                     ctag_frame_result* out_dev, const PendingCtx& pend) {
-    const Workspace& W = h->batch.ws;
-    h->last_chunk_frames = n;
+// one piece of a call: the frames of `c` through workspace slot k on stream k.  alone: the call's pieces all run on `stream` (slot 0), one
+// behind the other -- such a piece may be timed and replayed as a graph
+static int run_chunk(ctag_handle* h, int k, bool alone, const Call& c, ctag_frame_result* out_dev, const PendingCtx& pend) {
+    const Workspace& W = h->slot[k].ws;
+    const hipStream_t s = k ? h->streamx[k - 1] : h->stream;
+    h->last_chunk_frames = c.n;
     if (pend.list) {
         h->pending_dirty = true;
         h->pending_gen++;
     }
     hipEvent_t* evs = nullptr;
-    if (h->timing) {
+    if (h->timing) {  // (the call is `alone`: detect_device_impl)
         const size_t need = (size_t)(h->ev_sets_used + 1) * (CTAG_NUM_STAGES + 1);
         while (h->ev.size() < need) {
             hipEvent_t e = nullptr;
@@ -696,19 +688,19 @@ static int run_chunk(ctag_handle* h, const uint8_t* frames_dev, int n, ptrdiff_t
     }
     static const bool stamps = dev_knobs().stamps;  // developer aids that synchronise inside the chain (no graph capture around them)
     // what a captured chain depends on besides the handle's options (a change of those drops the graphs)
-    const ctag_handle::GraphKey key{frames_dev, out_dev, W.base, n, W.g.rows, W.g.cols, p.adaptive_thresh, p.corner_subpix, p.subpix_dist, h->keep_pre ? 1 : 0,
-                                    p.channels, row_stride, frame_stride, pend.list ? (const void*)pend.src : nullptr};
-    bool graph = h->use_graph == 1;
-    if (h->use_graph == 2 && n <= kLatencyFrames) {  // one frame per call in a loop (main.cpp:52-59): same staging buffers, same sizes every time
+    const ctag_handle::GraphKey key{c.frames, out_dev, W.base, c.n, W.g.rows, W.g.cols, c.adaptive_thresh, c.corner_subpix, c.subpix_dist, h->keep_pre ? 1 : 0,
+                                    c.channels, c.row_stride, c.frame_stride, pend.list ? (const void*)pend.src : nullptr};
+    bool graph = alone && h->use_graph == 1;
+    if (alone && h->use_graph == 2 && c.n <= kLatencyFrames) {  // one frame per call in a loop (main.cpp:52-59): same staging buffers, same sizes every time
         graph = key == h->last_key;
         h->last_key = key;
     }
     if (!evs && graph && !stamps) {
-        if (run_chunk_graph(h, key, frames_dev, n, row_stride, frame_stride, p, out_dev, pend)) return CTAG_OK;
+        if (run_chunk_graph(h, key, c, out_dev, pend)) return CTAG_OK;
         h->use_graph = 0;  // capture / instantiate / launch failed: direct launches from now on
         drop_graphs(h);
     }
-    return enqueue_chunk(h, W, frames_dev, n, row_stride, frame_stride, p, out_dev, evs, pend);
+    return enqueue_chunk(h, W, c, out_dev, evs, pend, s);
 }
 
 // public entry points call begin_timings() before their first chunk and collect_timings() after their last
@@ -732,18 +724,15 @@ static int collect_timings(ctag_handle* h) {
     return finish_pending(h);  // the call has waited anyway: frames that need the any-frame pass are completed now (outside the stage times)
 }
 
-// pend: where the frames of this call live in the CALLER's device memory (what a frame that needs the any-frame pass is read from
-// again: `frames_dev` itself for gray calls, the BGR source for colour calls), or null for host-memory calls -- their frames
+// src: where the frames of this call live in the CALLER's device memory (what a frame that needs the any-frame pass is read from
+// again: `c` itself for gray calls, the BGR source for colour calls), or null for host-memory calls -- their frames
 // pass through staging slabs that are reused, and they find CTAG_PENDING records in the results they download
-static int detect_device_impl(ctag_handle* h, const uint8_t* frames_dev, int n, int rows, int cols, ptrdiff_t row_stride, ptrdiff_t frame_stride,
-                              int adaptive_thresh, int corner_subpix, int subpix_dist, ctag_frame_result* out_dev, const PendingCtx* pend, int channels = 1) {
-    const int rc = check_args(h, frames_dev, n, rows, cols, row_stride, adaptive_thresh, subpix_dist);
+static int detect_device_impl(ctag_handle* h, const Call& c, ctag_frame_result* out_dev, const Call* src) {
+    const int rc = check_args(h, c);
     if (rc != CTAG_OK) return rc;
-    if (n == 0) return CTAG_OK;
+    if (c.n == 0) return CTAG_OK;
     HIP_TRY(hipSetDevice(h->device));
-    const int chunk = std::min(n, h->max_chunk);
-    DetectParams p{adaptive_thresh, corner_subpix, subpix_dist, h->feature_size, h->dict_rows, h->dict_cols, h->d_dict, h->d_dict_pos};
-    p.channels = channels;
+    const int chunk = std::min(c.n, h->max_chunk);
     static const int streams_min = dev_knobs().streams_min;
     const bool two_env = streams_min > 0;
     const int two_min = two_env ? streams_min : 256;
@@ -754,54 +743,29 @@ static int detect_device_impl(ctag_handle* h, const uint8_t* frames_dev, int n, 
     // the same (a 4K frame is four 1080p frames of blocks: its chunks of 112-255 frames, the equivalent window, are below two_min and stay whole anyway); the ragged tail of
     // a longer call (n = 1100 at max_chunk 1024: 512 + 512 + 76) is a piece of its own on the next stream; CTAG_STREAMS_MIN (developer aid) replaces the rule altogether.
     const bool whole = !two_env && chunk >= 448 && chunk < 1024;
-    if (h->streams >= 2 && !h->timing && chunk >= two_min && !whole && h->stream2) {
-        const int ns = std::min(h->streams, (int)ctag_handle::kMaxStreams);
-        // two halves of every chunk side by side (see WsSlot batch2).  With CTAG_OPT_TIMING the chunk stays on one stream: the HIP events
-        // around a kernel would otherwise time the other stream's kernels as well.
-        // (measured, round 4: pieces of 1024 / 512 frames instead of half a chunk 226 / 203 K frames/s against 231 K; the second stream half a
-        // piece out of phase -- one stream in its memory-bound sweep while the other computes -- 216-227 K: the kernels' tails want large pieces)
-        const int piece = (chunk + ns - 1) / ns;
-        ctag_handle::WsSlot* slot[ctag_handle::kMaxStreams] = {&h->batch, &h->batchx[0], &h->batchx[1], &h->batchx[2]};
-        for (int k = 0; k < ns; k++) {
-            const int wr = ensure_workspace(h, *slot[k], rows, cols, adaptive_thresh, std::max(piece, slot[k]->rows == rows && slot[k]->cols == cols ? slot[k]->cap : 0),
-                                            false, corner_subpix != 0);
-            if (wr != CTAG_OK) return wr;
-        }
-        HIP_TRY(hipEventRecord(h->ev_fork2, h->stream));
-        for (int k = 1; k < ns; k++) HIP_TRY(hipStreamWaitEvent(h->streamx[k - 1], h->ev_fork2, 0));
-        int k = 0;
-        for (int f0 = 0; f0 < n; f0 += piece, k = (k + 1) % ns) {
-            const int m = std::min(piece, n - f0);
-            PendingCtx pc{};
-            if (pend) {
-                pc = *pend;
-                pc.src = pend->src + (ptrdiff_t)f0 * pend->frame_stride;
-                h->pending_dirty = true;
-                h->pending_gen++;
-            }
-            h->last_chunk_frames = m;
-            const int r = enqueue_chunk(h, slot[k]->ws, frames_dev + (ptrdiff_t)f0 * frame_stride, m, row_stride, frame_stride, p, out_dev + f0, nullptr, pc,
-                                        k ? h->streamx[k - 1] : h->stream);
-            if (r != CTAG_OK) return r;
-        }
-        for (int j = 1; j < ns; j++) {
-            HIP_TRY(hipEventRecord(h->ev_joinx[j - 1], h->streamx[j - 1]));
-            HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_joinx[j - 1], 0));
-        }
-        return CTAG_OK;
+    const bool split = h->streams >= 2 && !h->timing && chunk >= two_min && !whole && h->streamx[0];
+    const int ns = split ? std::min(h->streams, (int)ctag_handle::kMaxStreams) : 1;
+    // two halves of every chunk side by side (see WsSlot batch2).  With CTAG_OPT_TIMING the chunk stays on one stream: the HIP events
+    // around a kernel would otherwise time the other stream's kernels as well.
+    // (measured, round 4: pieces of 1024 / 512 frames instead of half a chunk 226 / 203 K frames/s against 231 K; the second stream half a
+    // piece out of phase -- one stream in its memory-bound sweep while the other computes -- 216-227 K: the kernels' tails want large pieces)
+    const int piece = (chunk + ns - 1) / ns;
+    for (int k = 0; k < ns; k++) {
+        ctag_handle::WsSlot& S = h->slot[k];
+        const int wr = ensure_workspace(h, S, c.rows, c.cols, c.adaptive_thresh, std::max(piece, S.rows == c.rows && S.cols == c.cols ? S.cap : 0), false,
+                                        c.corner_subpix != 0 && chunk > kLatencyFrames);
+        if (wr != CTAG_OK) return wr;
     }
-    const int wr = ensure_workspace(h, h->batch, rows, cols, adaptive_thresh, std::max(chunk, h->batch.rows == rows && h->batch.cols == cols ? h->batch.cap : 0),
-                                    false, corner_subpix != 0 && chunk > kLatencyFrames);
-    if (wr != CTAG_OK) return wr;
-    for (int f0 = 0; f0 < n; f0 += chunk) {
-        const int m = std::min(chunk, n - f0);
-        PendingCtx pc{};
-        if (pend) {
-            pc = *pend;
-            pc.src = pend->src + (ptrdiff_t)f0 * pend->frame_stride;
-        }
-        const int r = run_chunk(h, frames_dev + (ptrdiff_t)f0 * frame_stride, m, row_stride, frame_stride, p, out_dev + f0, pc);
+    if (split) HIP_TRY(hipEventRecord(h->ev_fork2, h->stream));
+    for (int k = 1; k < ns; k++) HIP_TRY(hipStreamWaitEvent(h->streamx[k - 1], h->ev_fork2, 0));
+    for (int f0 = 0, k = 0; f0 < c.n; f0 += piece, k = (k + 1) % ns) {
+        const int m = std::min(piece, c.n - f0);
+        const int r = run_chunk(h, k, !split, c.sub(f0, m), out_dev + f0, src ? pending_ctx(h, src->sub(f0, m)) : PendingCtx{});
         if (r != CTAG_OK) return r;
+    }
+    for (int j = 1; j < ns; j++) {
+        HIP_TRY(hipEventRecord(h->ev_joinx[j - 1], h->streamx[j - 1]));
+        HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_joinx[j - 1], 0));
     }
     return CTAG_OK;
 }
@@ -835,99 +799,90 @@ __global__ __launch_bounds__(256) void k_bgr2gray(const uint8_t* __restrict__ bg
 static int ensure_gray(ctag_handle* h, int frames, int rows, int cols) {
     const ptrdiff_t pitch = ((ptrdiff_t)cols + 15) & ~(ptrdiff_t)15;
     const size_t need = (size_t)pitch * rows * (size_t)frames;
-    if (h->d_gray_bytes < need || h->gray_row_stride != pitch || h->gray_frame_stride != pitch * rows) {
-        if (h->d_gray_bytes < need) {
-            if (h->copy_stream) HIP_TRY(hipStreamSynchronize(h->copy_stream));
-            if (h->aux_stream) HIP_TRY(hipStreamSynchronize(h->aux_stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            drop_graphs(h);  // they hold the old slab's address
-            if (h->d_gray) HIP_TRY(hipFree(h->d_gray));
-            h->d_gray = nullptr;
-            h->d_gray_bytes = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_gray), need));
-            h->d_gray_bytes = need;
-        }
-        h->gray_row_stride = pitch;
-        h->gray_frame_stride = pitch * rows;
+    if (h->d_gray.cap < need) {
+        HIP_TRY(quiesce(h));
+        drop_graphs(h);  // they hold the old slab's address
+        HIP_TRY(h->d_gray.grow(need));
     }
+    h->gray_row_stride = pitch;
+    h->gray_frame_stride = pitch * rows;
     return CTAG_OK;
 }
 
-static int enqueue_bgr2gray(ctag_handle* h, const uint8_t* bgr_dev, int n, int rows, int cols, ptrdiff_t row_stride, ptrdiff_t frame_stride, uint8_t* gray = nullptr) {
-    const int aligned = ((reinterpret_cast<uintptr_t>(bgr_dev) | (uintptr_t)row_stride | (uintptr_t)frame_stride) & 3u) == 0 ? 1 : 0;
-    const ptrdiff_t pitch = ((ptrdiff_t)cols + 15) & ~(ptrdiff_t)15;  // == gray_row_stride of the chunk slab
-    hipLaunchKernelGGL(k_bgr2gray, dim3((cols + 1023) / 1024, rows, n), dim3(256), 0, h->stream, bgr_dev, frame_stride, row_stride, gray ? gray : h->d_gray,
-                       gray ? pitch * rows : h->gray_frame_stride, gray ? pitch : h->gray_row_stride, rows, cols, aligned);
+// the BGR frames of `bgr` -> gray, into `gray` (packed rows of the slab's pitch) or, by default, into the chunk slab
+static int enqueue_bgr2gray(ctag_handle* h, const Call& bgr, uint8_t* gray = nullptr) {
+    const int aligned = ((reinterpret_cast<uintptr_t>(bgr.frames) | (uintptr_t)bgr.row_stride | (uintptr_t)bgr.frame_stride) & 3u) == 0 ? 1 : 0;
+    const ptrdiff_t pitch = ((ptrdiff_t)bgr.cols + 15) & ~(ptrdiff_t)15;  // == gray_row_stride of the chunk slab
+    hipLaunchKernelGGL(k_bgr2gray, dim3((bgr.cols + 1023) / 1024, bgr.rows, bgr.n), dim3(256), 0, h->stream, bgr.frames, bgr.frame_stride, bgr.row_stride,
+                       gray ? gray : h->d_gray.p, gray ? pitch * bgr.rows : h->gray_frame_stride, gray ? pitch : h->gray_row_stride, bgr.rows, bgr.cols, aligned);
     HIP_TRY(hipGetLastError());
     return CTAG_OK;
+}
+// `c` with its frames replaced by gray ones
+static Call as_gray(const Call& c, const uint8_t* gray, ptrdiff_t row_stride, ptrdiff_t frame_stride) {
+    Call g = c;
+    g.frames = gray, g.channels = 1, g.row_stride = row_stride, g.frame_stride = frame_stride;
+    return g;
 }
 
 // ---------------------------------------------------------------------------------------------------
 // the any-frame pass: frames that exceeded a pool of the batch workspace
 // ---------------------------------------------------------------------------------------------------
-static int grow(ctag_handle* h, uint8_t** buf, size_t* have, size_t need) {
-    if (*have >= need) return CTAG_OK;
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(buf), need));
-    *have = need;
+// the chain of the handle's own calls idle: `stream` and its side branch.  Not quiesce: this is the wait of finish_pending, which every ctag_sync behind a
+// device-memory call goes through -- a steady-state path -- and what it reads was written on `stream` (the extra streams have joined it by event)
+static int wait_chain(ctag_handle* h) {
+    if (h->aux_stream) HIP_TRY(hipStreamSynchronize(h->aux_stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return CTAG_OK;
 }
 
-// One frame in device memory (gray, or BGR for ch == 3) through the workspace whose pools hold any frame of its size; the record
+// One frame in device memory (gray, or BGR for channels == 3) through the workspace whose pools hold any frame of its size; the record
 // goes to out_dev.  Enqueued on the handle's stream; the caller waits.  The reference has none of the batch workspace's limits
 // (corner_detector.cpp:81-107 keeps every component of [area_min, 1 %], :171-405 walks them all), so neither does a result.
-static int rerun_frame(ctag_handle* h, const uint8_t* src_dev, int ch, int rows, int cols, ptrdiff_t row_stride, int tw, int subpix, int dist,
-                       ctag_frame_result* out_dev) {
-    const int wr = ensure_workspace(h, h->big, rows, cols, tw, 1, true, false);
+static int rerun_frame(ctag_handle* h, const Call& c, ctag_frame_result* out_dev) {
+    ctag_handle::WsSlot& big = h->slot[ctag_handle::kBigSlot];
+    const int wr = ensure_workspace(h, big, c.rows, c.cols, c.adaptive_thresh, 1, true, false);
     if (wr != CTAG_OK) return wr;
-    const uint8_t* gray = src_dev;
-    ptrdiff_t gstride = row_stride;
-    if (ch == 3) {
-        const ptrdiff_t pitch = ((ptrdiff_t)cols + 15) & ~(ptrdiff_t)15;
-        const int gr = grow(h, &h->d_big_gray, &h->d_big_gray_bytes, (size_t)pitch * rows);
-        if (gr != CTAG_OK) return gr;
-        const int r = enqueue_bgr2gray(h, src_dev, 1, rows, cols, row_stride, 0, h->d_big_gray);
+    Call g = as_gray(c, c.frames, c.row_stride, c.row_stride * c.rows);
+    if (c.channels == 3) {
+        const ptrdiff_t pitch = ((ptrdiff_t)c.cols + 15) & ~(ptrdiff_t)15;
+        HIP_TRY(h->d_big_gray.grow((size_t)pitch * c.rows));
+        const int r = enqueue_bgr2gray(h, c, h->d_big_gray.p);
         if (r != CTAG_OK) return r;
-        gray = h->d_big_gray;
-        gstride = pitch;
+        g = as_gray(c, h->d_big_gray.p, pitch, pitch * c.rows);
     }
-    DetectParams p{tw, subpix, dist, h->feature_size, h->dict_rows, h->dict_cols, h->d_dict, h->d_dict_pos};
     h->last_chunk_frames = 1;
     h->reruns++;
-    return enqueue_chunk(h, h->big.ws, gray, 1, gstride, (ptrdiff_t)gstride * rows, p, out_dev, nullptr, PendingCtx{});
+    return enqueue_chunk(h, big.ws, g, out_dev, nullptr, PendingCtx{}, h->stream);
 }
 
 // drain the list device-memory calls left (see handle_finish_pending, ctag_internal.h)
 static int finish_pending(ctag_handle* h) {
     if (!h->pending_dirty) return CTAG_OK;
     HIP_TRY(hipSetDevice(h->device));
-    if (h->aux_stream) HIP_TRY(hipStreamSynchronize(h->aux_stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (wait_chain(h) != CTAG_OK) return CTAG_ERR_HIP;
     int count = 0;
-    HIP_TRY(hipMemcpy(&count, h->d_pending_count, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&count, h->d_pending_count.p, 4, hipMemcpyDeviceToHost));
     h->pending_dirty = false;
     if (count <= 0) return CTAG_OK;
     const int take = std::min(count, h->pending_cap);
     std::vector<PendingRec> recs((size_t)take);
-    HIP_TRY(hipMemcpy(recs.data(), h->d_pending, sizeof(PendingRec) * (size_t)take, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(h->d_pending_count, 0, 4));
+    HIP_TRY(hipMemcpy(recs.data(), h->d_pending.p, sizeof(PendingRec) * (size_t)take, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(h->d_pending_count.p, 0, 4));
     // "the last chunk" (ctag_get_counters, the parity probes) stays the caller's chunk, not the one-frame passes below (round-4 ADVICE)
     const Workspace* const keep_ws = h->last_ws;
     const ctag_frame_result* const keep_out = h->last_out;
     const int keep_frames = h->last_chunk_frames;
     int rc = CTAG_OK;
     for (const PendingRec& r : recs) {
-        rc = rerun_frame(h, r.src, r.ch, r.rows, r.cols, (ptrdiff_t)r.row_stride, r.tw, r.subpix, r.dist, r.out);
+        rc = rerun_frame(h, Call{r.src, 1, r.rows, r.cols, r.ch, (ptrdiff_t)r.row_stride, 0, r.tw, r.subpix, r.dist}, r.out);
         if (rc != CTAG_OK) break;
     }
     h->last_ws = keep_ws;
     h->last_out = keep_out;
     h->last_chunk_frames = keep_frames;
     if (rc != CTAG_OK) return rc;
-    if (h->aux_stream) HIP_TRY(hipStreamSynchronize(h->aux_stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (wait_chain(h) != CTAG_OK) return CTAG_ERR_HIP;
     if (count > h->pending_cap) {  // more than the list holds between two synchronisation points: k_markers gave the surplus the terminal status CTAG_ERR_LIMIT
         std::snprintf(h->last_error, sizeof(h->last_error), "%d frames waited for the any-frame pass, the list holds %d: the surplus carries CTAG_ERR_LIMIT; synchronise more often",
                       count, h->pending_cap);
@@ -938,9 +893,9 @@ static int finish_pending(ctag_handle* h) {
 namespace ctag {
 int handle_finish_pending(ctag_handle* h) { return h ? finish_pending(h) : CTAG_ERR_ARG; }
 bool handle_pending_state(ctag_handle* h, const int32_t** count_dev, uint64_t* gen) {
-    *count_dev = h->d_pending_count;
+    *count_dev = h->d_pending_count.p;
     *gen = h->pending_gen;
-    return h->pending_dirty && h->d_pending_count != nullptr;
+    return h->pending_dirty && h->d_pending_count.p != nullptr;
 }
 void handle_pending_clean(ctag_handle* h, uint64_t gen) {
     if (h->pending_gen == gen) h->pending_dirty = false;
@@ -948,55 +903,49 @@ void handle_pending_clean(ctag_handle* h, uint64_t gen) {
 }  // namespace ctag
 
 // host-memory calls: the records are on the host already; a CTAG_PENDING one is completed from the caller's own frame
-static int rerun_host_frames(ctag_handle* h, const uint8_t* frames, int n, int rows, int cols, ptrdiff_t row_stride, ptrdiff_t frame_stride, int ch, int tw,
-                             int subpix, int dist, ctag_frame_result* out) {
-    for (int i = 0; i < n; i++) {
+static int rerun_host_frames(ctag_handle* h, const Call& c, ctag_frame_result* out) {
+    for (int i = 0; i < c.n; i++) {
         if (out[i].status != CTAG_PENDING) continue;
-        const ptrdiff_t rowbytes = (ptrdiff_t)cols * ch, dstride = (rowbytes + 15) & ~(ptrdiff_t)15;
-        int r = grow(h, &h->d_big_frame, &h->d_big_frame_bytes, (size_t)dstride * rows);
+        const ptrdiff_t rowbytes = (ptrdiff_t)c.cols * c.channels, dstride = (rowbytes + 15) & ~(ptrdiff_t)15;
+        HIP_TRY(h->d_big_frame.grow((size_t)dstride * c.rows));
+        HIP_TRY(h->d_big_result.grow(1));
+        HIP_TRY(hipMemcpy2DAsync(h->d_big_frame.p, dstride, c.frames + (ptrdiff_t)i * c.frame_stride, c.row_stride, (size_t)rowbytes, c.rows, hipMemcpyHostToDevice,
+                                 h->stream));
+        Call one = c.sub(i, 1);
+        one.frames = h->d_big_frame.p, one.row_stride = dstride, one.frame_stride = 0;
+        const int r = rerun_frame(h, one, h->d_big_result.p);
         if (r != CTAG_OK) return r;
-        if (!h->d_big_result) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_big_result), sizeof(ctag_frame_result)));
-        HIP_TRY(hipMemcpy2DAsync(h->d_big_frame, dstride, frames + (ptrdiff_t)i * frame_stride, row_stride, (size_t)rowbytes, rows, hipMemcpyHostToDevice, h->stream));
-        r = rerun_frame(h, h->d_big_frame, ch, rows, cols, dstride, tw, subpix, dist, h->d_big_result);
-        if (r != CTAG_OK) return r;
-        HIP_TRY(hipMemcpyAsync(out + i, h->d_big_result, sizeof(ctag_frame_result), hipMemcpyDeviceToHost, h->stream));
-        if (h->aux_stream) HIP_TRY(hipStreamSynchronize(h->aux_stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipMemcpyAsync(out + i, h->d_big_result.p, sizeof(ctag_frame_result), hipMemcpyDeviceToHost, h->stream));
+        if (wait_chain(h) != CTAG_OK) return CTAG_ERR_HIP;
     }
     return CTAG_OK;
 }
 
 // n BGR frames in device memory -> gray (chunk by chunk, on the handle's stream) -> the detection chain
-static int detect_bgr_device_impl(ctag_handle* h, const uint8_t* bgr_dev, int n, int rows, int cols, ptrdiff_t row_stride, ptrdiff_t frame_stride,
-                                  int adaptive_thresh, int corner_subpix, int subpix_dist, ctag_frame_result* out_dev) {
-    if (row_stride < (ptrdiff_t)cols * 3) return CTAG_ERR_ARG;
-    const int rc = check_args(h, bgr_dev, n, rows, cols, ((ptrdiff_t)cols + 15) & ~(ptrdiff_t)15, adaptive_thresh, subpix_dist);
+static int detect_bgr_device_impl(ctag_handle* h, const Call& c, ctag_frame_result* out_dev) {
+    const int rc = check_args(h, c);
     if (rc != CTAG_OK) return rc;
-    if (n == 0) return CTAG_OK;
+    if (c.n == 0) return CTAG_OK;
     HIP_TRY(hipSetDevice(h->device));
     // The direct form (round 5): frames of a size the fused sweep takes (half size a multiple of 320 x 5; adaptiveThresh 5), rows and frames 16-byte aligned -- the
     // decimation kernel loads the BGR bytes themselves and converts as it consumes them, edgeRefine converts the boxes it stages: no gray image is
     // written or read back (8.3 of the 24 MB a 1080p frame moved through the gray slab).  CTAG_OPT_BGR_DIRECT 0 turns it off.
     // Calls of a few frames (round 6): the fused sweep's K1 is one block per frame band group -- 0.19 ms for a single 1080p frame against < 0.02 ms
     // of the short-band kernels -- so they convert first and take the gray chain, as gray calls of that size do (plan_chunk).
-    if (plan_chunk(PlanIn{rows, cols, adaptive_thresh, n, 3, corner_subpix, bgr_dev, frame_stride, row_stride, h->kp, h->fuse_mode, h->wave_points, h->bgr_direct != 0,
-                          dev_knobs()}).bgr_direct) {
-        const PendingCtx pc{h->d_pending, h->d_pending_count, h->pending_cap, bgr_dev, (int64_t)frame_stride, (int64_t)row_stride,
-                            rows, cols, 3, adaptive_thresh, corner_subpix, subpix_dist};
-        const int r = detect_device_impl(h, bgr_dev, n, rows, cols, row_stride, frame_stride, adaptive_thresh, corner_subpix, subpix_dist, out_dev, &pc, 3);
+    if (plan_chunk(PlanIn{c.rows, c.cols, c.adaptive_thresh, c.n, 3, c.corner_subpix, c.frames, c.frame_stride, c.row_stride, h->kp, h->fuse_mode, h->wave_points,
+                          h->bgr_direct != 0, dev_knobs()}).bgr_direct) {
+        const int r = detect_device_impl(h, c, out_dev, &c);
         h->last_was_bgr = false;  // no gray image to probe
         return r;
     }
-    const int chunk = std::min(n, h->max_chunk);
-    const int gr = ensure_gray(h, chunk, rows, cols);
+    const int chunk = std::min(c.n, h->max_chunk);
+    const int gr = ensure_gray(h, chunk, c.rows, c.cols);
     if (gr != CTAG_OK) return gr;
-    for (int f0 = 0; f0 < n; f0 += chunk) {
-        const int m = std::min(chunk, n - f0);
-        int r = enqueue_bgr2gray(h, bgr_dev + (ptrdiff_t)f0 * frame_stride, m, rows, cols, row_stride, frame_stride);
+    for (int f0 = 0; f0 < c.n; f0 += chunk) {
+        const Call bgr = c.sub(f0, std::min(chunk, c.n - f0));
+        int r = enqueue_bgr2gray(h, bgr);
         if (r != CTAG_OK) return r;
-        const PendingCtx pc{h->d_pending, h->d_pending_count, h->pending_cap, bgr_dev + (ptrdiff_t)f0 * frame_stride, (int64_t)frame_stride, (int64_t)row_stride,
-                            rows, cols, 3, adaptive_thresh, corner_subpix, subpix_dist};
-        r = detect_device_impl(h, h->d_gray, m, rows, cols, h->gray_row_stride, h->gray_frame_stride, adaptive_thresh, corner_subpix, subpix_dist, out_dev + f0, &pc);
+        r = detect_device_impl(h, as_gray(bgr, h->d_gray.p, h->gray_row_stride, h->gray_frame_stride), out_dev + f0, &bgr);
         if (r != CTAG_OK) return r;
     }
     h->last_was_bgr = true;
@@ -1119,18 +1068,16 @@ int ctag_create_ex(const int32_t* state, int dict_rows, int dict_cols, int featu
         ok = ok && hipStreamCreateWithFlags(&h->streamx[k], hipStreamNonBlocking) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&h->ev_joinx[k], hipEventDisableTiming) == hipSuccess;
     }
-    h->stream2 = h->streamx[0];
     ok = ok && hipEventCreateWithFlags(&h->ev_fork2, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&h->d_dict), h->dict.size() * 4) == hipSuccess;
-    ok = ok && hipMemcpy(h->d_dict, h->dict.data(), h->dict.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && h->d_dict.grow(h->dict.size()) == hipSuccess;
+    ok = ok && hipMemcpy(h->d_dict.p, h->dict.data(), h->dict.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
     if (ok && dict_cols <= 32) {
         std::vector<uint32_t> pos((size_t)dict_rows * 64, 0u);
         for (int i = 0; i < dict_rows; i++)
             for (int c = 0; c < dict_cols; c++) pos[(size_t)i * 64 + (state[(size_t)i * dict_cols + c] & 63)] |= 1u << c;
-        ok = hipMalloc(reinterpret_cast<void**>(&h->d_dict_pos), pos.size() * 4) == hipSuccess &&
-             hipMemcpy(h->d_dict_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+        ok = h->d_dict_pos.grow(pos.size()) == hipSuccess && hipMemcpy(h->d_dict_pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
     }
     if (ok) {
         // fitLine2D's initial samples: cv::RNG is seeded the same way for every fit, so the ten points a restart starts from depend on the edge's
@@ -1139,18 +1086,17 @@ int ctag_create_ex(const int32_t* state, int dict_rows, int dict_cols, int featu
         std::vector<uint8_t> tab(nb);
         std::vector<uint16_t> tab16(nh);
         build_pick_table(tab.data(), tab16.data());
-        ok = hipMalloc(reinterpret_cast<void**>(&h->d_pick_table), nb + nh * 2) == hipSuccess &&
-             hipMemcpy(h->d_pick_table, tab.data(), nb, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(h->d_pick_table + nb, tab16.data(), nh * 2, hipMemcpyHostToDevice) == hipSuccess;
+        ok = h->d_pick_table.grow(nb + nh * 2) == hipSuccess && hipMemcpy(h->d_pick_table.p, tab.data(), nb, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(h->d_pick_table.p + nb, tab16.data(), nh * 2, hipMemcpyHostToDevice) == hipSuccess;
     }
     if (ok) {
         const size_t tb = (size_t)kp.thr_dim * kp.thr_dim;
-        ok = hipMalloc(reinterpret_cast<void**>(&h->d_thr_table), tb) == hipSuccess && hipMemcpy(h->d_thr_table, thr.data(), tb, hipMemcpyHostToDevice) == hipSuccess;
-        kp.thr_table = h->d_thr_table;
+        ok = h->d_thr_table.grow(tb) == hipSuccess && hipMemcpy(h->d_thr_table.p, thr.data(), tb, hipMemcpyHostToDevice) == hipSuccess;
+        kp.thr_table = h->d_thr_table.p;
         h->kp = kp;
     }
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&h->d_pending), sizeof(PendingRec) * (size_t)h->pending_cap) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&h->d_pending_count), 256) == hipSuccess && hipMemset(h->d_pending_count, 0, 256) == hipSuccess;
+    ok = ok && h->d_pending.grow((size_t)h->pending_cap) == hipSuccess;
+    ok = ok && h->d_pending_count.grow(64) == hipSuccess && hipMemset(h->d_pending_count.p, 0, 256) == hipSuccess;
     if (!ok) {
         ctag_destroy(h);
         return CTAG_ERR_HIP;
@@ -1159,57 +1105,26 @@ int ctag_create_ex(const int32_t* state, int dict_rows, int dict_cols, int featu
     return CTAG_OK;
 }
 
+// what is not a buffer: the order of things, streams and events (the buffers go with the handle)
 void ctag_destroy(ctag_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-    if (h->aux_stream) (void)hipStreamSynchronize(h->aux_stream);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    (void)quiesce(h);
     drop_graphs(h);
-    for (int k = 0; k < ctag_handle::kMaxStreams - 1; k++) {
-        if (h->streamx[k]) (void)hipStreamSynchronize(h->streamx[k]);
-        if (h->ev_joinx[k]) (void)hipEventDestroy(h->ev_joinx[k]);
-    }
-    if (h->ev_fork2) (void)hipEventDestroy(h->ev_fork2);
-    for (ctag_handle::WsSlot* S : {&h->batch, &h->batchx[0], &h->batchx[1], &h->batchx[2], &h->big}) {
-        if (S->ws.base) (void)hipFree(S->ws.base);
-        if (S->n0_buf) (void)hipFree(S->n0_buf);
-    }
-    if (h->d_pending) (void)hipFree(h->d_pending);
-    if (h->d_pending_count) (void)hipFree(h->d_pending_count);
-    if (h->d_big_frame) (void)hipFree(h->d_big_frame);
-    if (h->d_big_gray) (void)hipFree(h->d_big_gray);
-    if (h->d_big_result) (void)hipFree(h->d_big_result);
-    for (auto& A : h->aslot) {
-        if (A.d_frame) (void)hipFree(A.d_frame);
-        if (A.h_res) (void)hipHostFree(A.h_res);
-        if (A.up) (void)hipEventDestroy(A.up);
-        if (A.done) (void)hipEventDestroy(A.done);
-    }
-    if (h->d_dict) (void)hipFree(h->d_dict);
-    if (h->d_thr_table) (void)hipFree(h->d_thr_table);
-    if (h->d_dict_pos) (void)hipFree(h->d_dict_pos);
-    if (h->d_pick_table) (void)hipFree(h->d_pick_table);
-    if (h->d_frames) (void)hipFree(h->d_frames);
-    if (h->d_results) (void)hipFree(h->d_results);
-    if (h->h_res1) (void)hipHostFree(h->h_res1);
-    if (h->d_gray) (void)hipFree(h->d_gray);
-    if (h->pose_state && h->pose_state_free) h->pose_state_free(h->pose_state);
-    if (h->draw_state && h->draw_state_free) h->draw_state_free(h->draw_state);
-    if (h->rig_state && h->rig_state_free) h->rig_state_free(h->rig_state);
-    if (h->gather_state && h->gather_state_free) h->gather_state_free(h->gather_state);
-    for (auto& e : h->ev)
+    for (auto& st : h->state)  // pose, draw, rig, gather
+        if (st.p && st.free_fn) st.free_fn(st.p);
+    auto drop = [](hipEvent_t e) {
         if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < 2; i++) {
-        if (h->ev_copied[i]) (void)hipEventDestroy(h->ev_copied[i]);
-        if (h->ev_done[i]) (void)hipEventDestroy(h->ev_done[i]);
-    }
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+    };
+    for (auto& A : h->aslot) drop(A.up), drop(A.done);
+    for (hipEvent_t e : h->ev) drop(e);
+    for (hipEvent_t e : h->ev_joinx) drop(e);
+    for (int i = 0; i < 2; i++) drop(h->ev_copied[i]), drop(h->ev_done[i]);
+    drop(h->ev_fork2), drop(h->ev_fork), drop(h->ev_join);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
-    for (int k = 0; k < ctag_handle::kMaxStreams - 1; k++)
-        if (h->streamx[k]) (void)hipStreamDestroy(h->streamx[k]);
+    for (hipStream_t x : h->streamx)
+        if (x) (void)hipStreamDestroy(x);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1300,7 +1215,7 @@ int ctag_get_counters(ctag_handle* h, ctag_counters* out) {
     const int fr = finish_pending(h);
     if (fr != CTAG_OK) return fr;
     out->reruns = h->reruns;
-    long long* d = reinterpret_cast<long long*>(h->d_pending_count + 16);  // 80 bytes of the 256-byte counter block
+    long long* d = reinterpret_cast<long long*>(h->d_pending_count.p + 16);  // 80 bytes of the 256-byte counter block
     HIP_TRY(launch_counters(h->last_chunk_frames, *h->last_ws, h->last_out, d, h->stream));
     long long v[10];
     HIP_TRY(hipMemcpyAsync(v, d, sizeof(v), hipMemcpyDeviceToHost, h->stream));
@@ -1329,9 +1244,8 @@ int ctag_detect_batch_device(ctag_handle* h, const uint8_t* frames_dev, int n, i
     if (!h || !out_dev) return CTAG_ERR_ARG;
     begin_timings(h);
     h->last_was_bgr = false;
-    const PendingCtx pc{h->d_pending, h->d_pending_count, h->pending_cap, frames_dev, (int64_t)frame_stride, (int64_t)row_stride,
-                        rows, cols, 1, adaptive_thresh, corner_subpix, subpix_dist};
-    const int r = detect_device_impl(h, frames_dev, n, rows, cols, row_stride, frame_stride, adaptive_thresh, corner_subpix, subpix_dist, out_dev, &pc);
+    const Call c{frames_dev, n, rows, cols, 1, row_stride, frame_stride, adaptive_thresh, corner_subpix, subpix_dist};
+    const int r = detect_device_impl(h, c, out_dev, &c);
     if (r != CTAG_OK) {
         h->ev_sets_used = 0;
         return r;
@@ -1339,100 +1253,97 @@ int ctag_detect_batch_device(ctag_handle* h, const uint8_t* frames_dev, int n, i
     return collect_timings(h);  // with CTAG_OPT_TIMING the call waits for its last chunk (and completes CTAG_PENDING frames); otherwise it returns at once
 }
 
-// both streams idle: every exit of the host-batch path that leaves copies or kernels in flight goes through here, and so does
-// every reallocation of the staging slabs (an upload still running on copy_stream must not lose its destination)
-static int quiesce(ctag_handle* h) {
-    if (h->copy_stream) HIP_TRY(hipStreamSynchronize(h->copy_stream));
-    for (hipStream_t x : h->streamx)
-        if (x) HIP_TRY(hipStreamSynchronize(x));
-    if (h->aux_stream) HIP_TRY(hipStreamSynchronize(h->aux_stream));  // side branch of few-frame calls
-    HIP_TRY(hipStreamSynchronize(h->stream));
+// the copy stream of the host-memory entry points and its events, created on first use
+static int ensure_copy_stream(ctag_handle* h) {
+    if (h->copy_stream) return CTAG_OK;
+    HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < 2; i++) {
+        HIP_TRY(hipEventCreateWithFlags(&h->ev_copied[i], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&h->ev_done[i], hipEventDisableTiming));
+    }
     return CTAG_OK;
 }
 
-static int detect_batch_u8_impl(ctag_handle* h, const uint8_t* frames, int n, int rows, int cols, ptrdiff_t row_stride, ptrdiff_t frame_stride,
-                                int adaptive_thresh, int corner_subpix, int subpix_dist, ctag_frame_result* out, int ch = 1) {
+// a host-memory call failed with r: uploads / kernels may still be in flight, and nothing may outlive the call (the caller frees its frames)
+static int fail_idle(ctag_handle* h, int r) {
+    h->ev_sets_used = 0;
+    (void)quiesce(h);  // (last_error stays that of the failure)
+    return r;
+}
+
+static int detect_batch_u8_impl(ctag_handle* h, const Call& c, ctag_frame_result* out) {
     // Frames stream through two device slabs: while slab k is processed on the compute stream, slab k+1 is filled over
     // PCIe on the copy stream (main.cpp:29,36,52-54 feed one frame at a time; this is the batched equivalent).  The
-    // copies only overlap when `frames` is pinned (ctag_host_alloc / hipHostRegister); pageable memory still works.
+    // copies only overlap when the frames are pinned (ctag_host_alloc / hipHostRegister); pageable memory still works.
+    const int n = c.n, rows = c.rows;
     const int sub = std::min(n, std::min(h->max_chunk, h->host_sub));
-    // ch = 3: BGR frames (3 bytes per pixel) are uploaded as they are and converted on the device (k_bgr2gray) into the gray slab
-    const ptrdiff_t rowbytes = (ptrdiff_t)cols * ch;
+    // channels = 3: BGR frames (3 bytes per pixel) are uploaded as they are and converted on the device (k_bgr2gray) into the gray slab
+    const ptrdiff_t rowbytes = (ptrdiff_t)c.cols * c.channels;
     const ptrdiff_t dstride = (rowbytes + 15) & ~(ptrdiff_t)15;  // packed, 16-byte aligned rows on the device
-    if (ch == 3) {
-        const int gr = ensure_gray(h, sub, rows, cols);
+    if (c.channels == 3) {
+        const int gr = ensure_gray(h, sub, rows, c.cols);
         if (gr != CTAG_OK) return gr;
     }
     const size_t dframe = (size_t)dstride * rows;
-    if (h->d_frames_bytes < dframe * sub * 2) {
-        if (quiesce(h) != CTAG_OK) return CTAG_ERR_HIP;
-        if (h->d_frames) HIP_TRY(hipFree(h->d_frames));
-        h->d_frames = nullptr;
-        h->d_frames_bytes = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_frames), dframe * sub * 2));
-        h->d_frames_bytes = dframe * sub * 2;
+    if (h->d_frames.cap < dframe * sub * 2) {
+        HIP_TRY(quiesce(h));  // (an upload still running on copy_stream must not lose its destination)
+        HIP_TRY(h->d_frames.grow(dframe * sub * 2));
     }
-    if (h->d_results_count < (size_t)sub * 2) {
-        if (quiesce(h) != CTAG_OK) return CTAG_ERR_HIP;
-        if (h->d_results) HIP_TRY(hipFree(h->d_results));
-        h->d_results = nullptr;
-        h->d_results_count = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_results), sizeof(ctag_frame_result) * sub * 2));
-        h->d_results_count = (size_t)sub * 2;
+    if (h->d_results.cap < (size_t)sub * 2) {
+        HIP_TRY(quiesce(h));
+        HIP_TRY(h->d_results.grow((size_t)sub * 2));
     }
-    if (!h->copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            HIP_TRY(hipEventCreateWithFlags(&h->ev_copied[i], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&h->ev_done[i], hipEventDisableTiming));
-        }
-    }
-    const bool packed = row_stride == rowbytes && dstride == rowbytes && frame_stride == (ptrdiff_t)rows * rowbytes;
-    const size_t slab_frames = h->d_frames_bytes / dframe / 2;
+    const int cs = ensure_copy_stream(h);
+    if (cs != CTAG_OK) return cs;
+    const bool packed = c.row_stride == rowbytes && dstride == rowbytes && c.frame_stride == (ptrdiff_t)rows * rowbytes;
+    const size_t slab_frames = h->d_frames.cap / dframe / 2;
     const int nsub = (n + sub - 1) / sub;
+    // the frames [f0, f0 + m) as they lie in a slab
+    auto in_slab = [&](uint8_t* slab, int f0, int m) {
+        Call d = c.sub(f0, m);
+        d.frames = slab, d.row_stride = dstride, d.frame_stride = (ptrdiff_t)dframe;
+        return d;
+    };
     auto upload = [&](int k) -> int {  // enqueue the upload of sub-chunk k on the copy stream
         const int f0 = k * sub, m = std::min(sub, n - f0), slot = k & 1;
-        uint8_t* slab = h->d_frames + dframe * slab_frames * slot;
+        uint8_t* slab = h->d_frames.p + dframe * slab_frames * slot;
         if (k >= 2) HIP_TRY(hipStreamWaitEvent(h->copy_stream, h->ev_done[slot], 0));  // the slab's previous sub-chunk is finished
         if (packed) {
-            HIP_TRY(hipMemcpyAsync(slab, frames + (ptrdiff_t)f0 * frame_stride, dframe * m, hipMemcpyHostToDevice, h->copy_stream));
+            HIP_TRY(hipMemcpyAsync(slab, c.frames + (ptrdiff_t)f0 * c.frame_stride, dframe * m, hipMemcpyHostToDevice, h->copy_stream));
         } else {
             for (int i = 0; i < m; i++)
-                HIP_TRY(hipMemcpy2DAsync(slab + dframe * i, dstride, frames + (ptrdiff_t)(f0 + i) * frame_stride, row_stride, (size_t)rowbytes, rows,
+                HIP_TRY(hipMemcpy2DAsync(slab + dframe * i, dstride, c.frames + (ptrdiff_t)(f0 + i) * c.frame_stride, c.row_stride, (size_t)rowbytes, rows,
                                          hipMemcpyHostToDevice, h->copy_stream));
         }
         HIP_TRY(hipEventRecord(h->ev_copied[slot], h->copy_stream));
         return CTAG_OK;
     };
-    if (n == 1 && ch == 1) {
+    if (n == 1 && c.channels == 1) {
         // One frame (main.cpp:52-59: the reference's loop): everything on the compute stream -- a second stream and its event cost the call more than
         // they could hide -- and the record written by the last kernel straight into pinned host memory instead of fetched by a copy behind it
-        if (!h->h_res1) {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_res1), sizeof(ctag_frame_result), hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->h_res1_dev), h->h_res1, 0));
-        }
-        uint8_t* slab = h->d_frames;
-        if (packed) HIP_TRY(hipMemcpyAsync(slab, frames, dframe, hipMemcpyHostToDevice, h->stream));
-        else HIP_TRY(hipMemcpy2DAsync(slab, dstride, frames, row_stride, (size_t)rowbytes, rows, hipMemcpyHostToDevice, h->stream));
-        const int r1 = detect_device_impl(h, slab, 1, rows, cols, dstride, (ptrdiff_t)dframe, adaptive_thresh, corner_subpix, subpix_dist, h->h_res1_dev, nullptr);
+        HIP_TRY(h->res1.ensure());
+        uint8_t* slab = h->d_frames.p;
+        if (packed) HIP_TRY(hipMemcpyAsync(slab, c.frames, dframe, hipMemcpyHostToDevice, h->stream));
+        else HIP_TRY(hipMemcpy2DAsync(slab, dstride, c.frames, c.row_stride, (size_t)rowbytes, rows, hipMemcpyHostToDevice, h->stream));
+        const int r1 = detect_device_impl(h, in_slab(slab, 0, 1), h->res1.dev, nullptr);
         if (r1 != CTAG_OK) return r1;
         HIP_TRY(hipStreamSynchronize(h->stream));
-        std::memcpy(out, h->h_res1, sizeof(ctag_frame_result));
-        return rerun_host_frames(h, frames, n, rows, cols, row_stride, frame_stride, ch, adaptive_thresh, corner_subpix, subpix_dist, out);
+        std::memcpy(out, h->res1.host, sizeof(ctag_frame_result));
+        return rerun_host_frames(h, c, out);
     }
     int r = upload(0);
     if (r != CTAG_OK) return r;
     for (int k = 0; k < nsub; k++) {
         const int f0 = k * sub, m = std::min(sub, n - f0), slot = k & 1;
-        uint8_t* slab = h->d_frames + dframe * slab_frames * slot;
-        ctag_frame_result* res = h->d_results + (h->d_results_count / 2) * slot;
+        const Call slab = in_slab(h->d_frames.p + dframe * slab_frames * slot, f0, m);
+        ctag_frame_result* res = h->d_results.p + (h->d_results.cap / 2) * slot;
         HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_copied[slot], 0));
-        if (ch == 3) {
-            r = enqueue_bgr2gray(h, slab, m, rows, cols, dstride, (ptrdiff_t)dframe);
+        if (c.channels == 3) {
+            r = enqueue_bgr2gray(h, slab);
             if (r != CTAG_OK) return r;
-            r = detect_device_impl(h, h->d_gray, m, rows, cols, h->gray_row_stride, h->gray_frame_stride, adaptive_thresh, corner_subpix, subpix_dist, res, nullptr);
+            r = detect_device_impl(h, as_gray(slab, h->d_gray.p, h->gray_row_stride, h->gray_frame_stride), res, nullptr);
         } else {
-            r = detect_device_impl(h, slab, m, rows, cols, dstride, (ptrdiff_t)dframe, adaptive_thresh, corner_subpix, subpix_dist, res, nullptr);
+            r = detect_device_impl(h, slab, res, nullptr);
         }
         if (r != CTAG_OK) return r;
         HIP_TRY(hipEventRecord(h->ev_done[slot], h->stream));
@@ -1442,77 +1353,63 @@ static int detect_batch_u8_impl(ctag_handle* h, const uint8_t* frames, int n, in
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     // a frame that exceeded a pool of the batch workspace came back CTAG_PENDING: complete it through the any-frame workspace
-    return rerun_host_frames(h, frames, n, rows, cols, row_stride, frame_stride, ch, adaptive_thresh, corner_subpix, subpix_dist, out);
+    return rerun_host_frames(h, c, out);
+}
+
+// the host-memory batch entry points: gray (channels 1) and BGR (3)
+static int detect_batch_host(ctag_handle* h, const Call& c, ctag_frame_result* out) {
+    if (!h || !out) return CTAG_ERR_ARG;
+    const int rc = check_args(h, c);
+    if (rc != CTAG_OK) return rc;
+    if (c.n == 0) return CTAG_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    begin_timings(h);
+    if (c.channels == 1) h->last_was_bgr = false;
+    const int r = detect_batch_u8_impl(h, c, out);
+    if (r != CTAG_OK) return fail_idle(h, r);
+    if (c.channels == 3) h->last_was_bgr = true;
+    return collect_timings(h);
 }
 
 int ctag_detect_batch_u8(ctag_handle* h, const uint8_t* frames, int n, int rows, int cols, ptrdiff_t row_stride, ptrdiff_t frame_stride,
                          int adaptive_thresh, int corner_subpix, int subpix_dist, ctag_frame_result* out) {
-    if (!h || !out) return CTAG_ERR_ARG;
-    const int rc = check_args(h, frames, n, rows, cols, row_stride, adaptive_thresh, subpix_dist);
-    if (rc != CTAG_OK) return rc;
-    if (n == 0) return CTAG_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    begin_timings(h);
-    h->last_was_bgr = false;
-    const int r = detect_batch_u8_impl(h, frames, n, rows, cols, row_stride, frame_stride, adaptive_thresh, corner_subpix, subpix_dist, out);
-    if (r != CTAG_OK) {  // uploads / kernels may still be in flight: nothing may outlive this call (the caller frees `frames`)
-        h->ev_sets_used = 0;
-        char keep[sizeof(h->last_error)];
-        std::memcpy(keep, h->last_error, sizeof(keep));
-        (void)quiesce(h);
-        std::memcpy(h->last_error, keep, sizeof(keep));
-        return r;
-    }
-    return collect_timings(h);
+    return detect_batch_host(h, Call{frames, n, rows, cols, 1, row_stride, frame_stride, adaptive_thresh, corner_subpix, subpix_dist}, out);
 }
 
 // ---- one frame per call, not waited for (include/ctag.h) ----------------------------------------------------------------------------
 int ctag_submit_u8(ctag_handle* h, const uint8_t* gray, int rows, int cols, ptrdiff_t row_stride, int adaptive_thresh, int corner_subpix, int subpix_dist) {
     if (!h) return CTAG_ERR_ARG;
     h->last_error[0] = 0;
-    const int rc = check_args(h, gray, 1, rows, cols, row_stride, adaptive_thresh, subpix_dist);
+    const Call c{gray, 1, rows, cols, 1, row_stride, 0, adaptive_thresh, corner_subpix, subpix_dist};
+    const int rc = check_args(h, c);
     if (rc != CTAG_OK) return rc;
     if (h->a_count >= ctag_handle::kAsyncDepth) return CTAG_ERR_ARG;  // collect first
     HIP_TRY(hipSetDevice(h->device));
     ctag_handle::AsyncSlot& A = h->aslot[(h->a_head + h->a_count) % ctag_handle::kAsyncDepth];
     const ptrdiff_t dstride = ((ptrdiff_t)cols + 15) & ~(ptrdiff_t)15;
     const size_t need = (size_t)dstride * rows;
-    if (!h->copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            HIP_TRY(hipEventCreateWithFlags(&h->ev_copied[i], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&h->ev_done[i], hipEventDisableTiming));
-        }
-    }
+    const int cs = ensure_copy_stream(h);
+    if (cs != CTAG_OK) return cs;
     if (!A.up) {
         HIP_TRY(hipEventCreateWithFlags(&A.up, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&A.done, hipEventDisableTiming));
-        // the record is written by k_markers itself into pinned host memory (d_res = that memory as the device addresses it): no download behind the chain
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&A.h_res), sizeof(ctag_frame_result), hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&A.d_res), A.h_res, 0));
+        HIP_TRY(A.res.ensure());
     }
-    if (A.d_bytes < need) {  // the slot is free: nothing reads its slab
-        drop_graphs(h);      // ... but a captured chain may hold its address
-        if (A.d_frame) HIP_TRY(hipFree(A.d_frame));
-        A.d_frame = nullptr;
-        A.d_bytes = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&A.d_frame), need));
-        A.d_bytes = need;
+    if (A.d_frame.cap < need) {  // the slot is free: nothing reads its slab
+        drop_graphs(h);          // ... but a captured chain may hold its address
+        HIP_TRY(A.d_frame.grow(need));
     }
-    A.host = gray, A.rows = rows, A.cols = cols, A.ch = 1, A.row_stride = row_stride, A.tw = adaptive_thresh, A.subpix = corner_subpix, A.dist = subpix_dist;
+    A.host = c;
     // the upload runs on the copy stream while the previous frame's kernels run on the compute stream (the slab's previous reader finished before its
     // ctag_collect returned); the detection waits for it; the record comes back into pinned memory behind the detection
-    HIP_TRY(hipMemcpy2DAsync(A.d_frame, dstride, gray, row_stride, (size_t)cols, rows, hipMemcpyHostToDevice, h->copy_stream));
+    HIP_TRY(hipMemcpy2DAsync(A.d_frame.p, dstride, gray, row_stride, (size_t)cols, rows, hipMemcpyHostToDevice, h->copy_stream));
     HIP_TRY(hipEventRecord(A.up, h->copy_stream));
     HIP_TRY(hipStreamWaitEvent(h->stream, A.up, 0));
     h->last_was_bgr = false;
     begin_timings(h);
-    const int r = detect_device_impl(h, A.d_frame, 1, rows, cols, dstride, (ptrdiff_t)need, adaptive_thresh, corner_subpix, subpix_dist, A.d_res, nullptr);
+    const int r = detect_device_impl(h, as_gray(c, A.d_frame.p, dstride, (ptrdiff_t)need), A.res.dev, nullptr);
     h->ev_sets_used = 0;
-    if (r != CTAG_OK) {
-        (void)quiesce(h);
-        return r;
-    }
+    if (r != CTAG_OK) return fail_idle(h, r);
     HIP_TRY(hipEventRecord(A.done, h->stream));
     h->a_count++;
     return CTAG_OK;
@@ -1527,9 +1424,9 @@ int ctag_collect(ctag_handle* h, ctag_frame_result* out) {
     HIP_TRY(hipEventSynchronize(A.done));
     h->a_head = (h->a_head + 1) % ctag_handle::kAsyncDepth;
     h->a_count--;
-    *out = *A.h_res;
+    *out = *A.res.host;
     if (out->status == CTAG_PENDING) {  // needs the any-frame workspace: from the caller's frame, like every host-memory call
-        const int r = rerun_host_frames(h, A.host, 1, A.rows, A.cols, A.row_stride, 0, A.ch, A.tw, A.subpix, A.dist, out);
+        const int r = rerun_host_frames(h, A.host, out);
         if (r != CTAG_OK) return r;
     }
     return out->status;
@@ -1556,7 +1453,7 @@ int ctag_detect_batch_bgr8_device(ctag_handle* h, const uint8_t* bgr_dev, int n,
                                   int adaptive_thresh, int corner_subpix, int subpix_dist, ctag_frame_result* out_dev) {
     if (!h || !out_dev) return CTAG_ERR_ARG;
     begin_timings(h);
-    const int r = detect_bgr_device_impl(h, bgr_dev, n, rows, cols, row_stride, frame_stride, adaptive_thresh, corner_subpix, subpix_dist, out_dev);
+    const int r = detect_bgr_device_impl(h, Call{bgr_dev, n, rows, cols, 3, row_stride, frame_stride, adaptive_thresh, corner_subpix, subpix_dist}, out_dev);
     if (r != CTAG_OK) {
         h->ev_sets_used = 0;
         return r;
@@ -1566,23 +1463,7 @@ int ctag_detect_batch_bgr8_device(ctag_handle* h, const uint8_t* bgr_dev, int n,
 
 int ctag_detect_batch_bgr8(ctag_handle* h, const uint8_t* bgr, int n, int rows, int cols, ptrdiff_t row_stride, ptrdiff_t frame_stride, int adaptive_thresh,
                            int corner_subpix, int subpix_dist, ctag_frame_result* out) {
-    if (!h || !out || row_stride < (ptrdiff_t)cols * 3) return CTAG_ERR_ARG;
-    const int rc = check_args(h, bgr, n, rows, cols, ((ptrdiff_t)cols + 15) & ~(ptrdiff_t)15, adaptive_thresh, subpix_dist);
-    if (rc != CTAG_OK) return rc;
-    if (n == 0) return CTAG_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    begin_timings(h);
-    const int r = detect_batch_u8_impl(h, bgr, n, rows, cols, row_stride, frame_stride, adaptive_thresh, corner_subpix, subpix_dist, out, 3);
-    if (r != CTAG_OK) {
-        h->ev_sets_used = 0;
-        char keep[sizeof(h->last_error)];
-        std::memcpy(keep, h->last_error, sizeof(keep));
-        (void)quiesce(h);
-        std::memcpy(h->last_error, keep, sizeof(keep));
-        return r;
-    }
-    h->last_was_bgr = true;
-    return collect_timings(h);
+    return detect_batch_host(h, Call{bgr, n, rows, cols, 3, row_stride, frame_stride, adaptive_thresh, corner_subpix, subpix_dist}, out);
 }
 
 int ctag_detect_bgr8(ctag_handle* h, const uint8_t* bgr, int rows, int cols, ptrdiff_t row_stride, int adaptive_thresh, int corner_subpix, int subpix_dist,

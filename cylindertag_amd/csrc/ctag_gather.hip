@@ -84,15 +84,10 @@ struct GatherState {
     ncclComm_t comm = nullptr;
     bool own_comm = false;
     int rank = 0, world = 1;
-    unsigned char* d_packed = nullptr;
-    size_t packed_cap = 0;
-    unsigned char* d_gathered = nullptr;
-    size_t gathered_cap = 0;
-    uint64_t* d_off = nullptr;       // per-frame payload offsets of the work on the gather stream (pack: n+1, unpack: n_total + world)
-    size_t off_cap = 0;
-    uint64_t* d_off_main = nullptr;  // the same for the stand-alone ctag_pack_results / ctag_unpack_results (handle's main stream)
-    size_t off_main_cap = 0;
-    uint64_t* d_sizes = nullptr;     // [world] packed size of every rank
+    ctag::DevBuf<unsigned char> d_packed, d_gathered;
+    ctag::DevBuf<uint64_t> d_off;       // per-frame payload offsets of the work on the gather stream (pack: n+1, unpack: n_total + world)
+    ctag::DevBuf<uint64_t> d_off_main;  // the same for the stand-alone ctag_pack_results / ctag_unpack_results (handle's main stream)
+    ctag::DevBuf<uint64_t> d_sizes;     // [world] packed size of every rank
     uint64_t* h_sizes = nullptr;     // pinned copy
     int n_local = 0, n_total = 0;
     const ctag_frame_result* local_dev = nullptr;  // of the gather in flight (a rank with pending frames packs again in ctag_gather_end)
@@ -121,15 +116,10 @@ void gather_state_free(void* p) {
     release_comm(g);
     if (was_dead || (g->err[0] && drain_ms > 1000)) drain_ms = 1000;
     if (g->gstream && !stream_idle_within(g->gstream, drain_ms)) {
-        // the gather stream does not drain (an aborted collective that never left?): what it may still touch is leaked rather than freed under it
-        delete g;
+        // the gather stream does not drain (an aborted collective that never left?): what it may still touch is leaked rather than freed under it --
+        // the state as a whole, so that no buffer it owns, now or later, is freed by a destructor here
         return;
     }
-    if (g->d_packed) (void)hipFree(g->d_packed);
-    if (g->d_gathered) (void)hipFree(g->d_gathered);
-    if (g->d_off) (void)hipFree(g->d_off);
-    if (g->d_off_main) (void)hipFree(g->d_off_main);
-    if (g->d_sizes) (void)hipFree(g->d_sizes);
     if (g->h_sizes) (void)hipHostFree(g->h_sizes);
     for (hipEvent_t e : {g->ev_main, g->ev_packed, g->ev_sizes, g->ev_done})
         if (e) (void)hipEventDestroy(e);
@@ -138,7 +128,7 @@ void gather_state_free(void* p) {
 }
 
 GatherState* gather_state(ctag_handle* h) {
-    void** slot = ctag::handle_gather_slot(h, gather_state_free);
+    void** slot = ctag::handle_state_slot(h, ctag::kGatherState, gather_state_free);
     if (!*slot) {
         GatherState* g = new (std::nothrow) GatherState();
         if (!g) return nullptr;
@@ -147,7 +137,7 @@ GatherState* gather_state(ctag_handle* h) {
         ok = ok && hipStreamCreateWithFlags(&g->gstream, hipStreamNonBlocking) == hipSuccess;
         for (hipEvent_t* e : {&g->ev_main, &g->ev_packed, &g->ev_sizes, &g->ev_done})
             ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipMalloc(reinterpret_cast<void**>(&g->d_sizes), (kMaxWorld + 1) * sizeof(uint64_t)) == hipSuccess;
+        ok = ok && g->d_sizes.grow(kMaxWorld + 1) == hipSuccess;
         ok = ok && hipHostMalloc(reinterpret_cast<void**>(&g->h_sizes), (kMaxWorld + 1) * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
         if (!ok) {
             gather_state_free(g);
@@ -413,24 +403,13 @@ void release_comm(GatherState* g) {
     g->own_comm = false;
 }
 
-int grow(GatherState* g, unsigned char** p, size_t* cap, size_t need) {
-    if (*cap >= need) return CTAG_OK;
-    G_HIP(hipDeviceSynchronize());  // rare: a buffer grows; nothing on either stream may still use the old one
-    if (*p) G_HIP(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 2 + 4096;
-    G_HIP(hipMalloc(reinterpret_cast<void**>(p), want));
-    *cap = want;
+// rare: a buffer grows (to half as much again as asked for, so that it does not at every call); nothing on either stream may still use the old one
+template <class T>
+int grow_idle(GatherState* g, ctag::DevBuf<T>& b, size_t need) {
+    if (b.cap >= need) return CTAG_OK;
+    G_HIP(hipDeviceSynchronize());
+    G_HIP(b.grow(need + need / 2 + 4096 / sizeof(T)));
     return CTAG_OK;
-}
-int grow_off(GatherState* g, uint64_t** off, size_t* off_cap, size_t entries) {
-    size_t cap = *off_cap * sizeof(uint64_t);
-    unsigned char* p = reinterpret_cast<unsigned char*>(*off);
-    const int r = grow(g, &p, &cap, entries * sizeof(uint64_t));
-    *off = reinterpret_cast<uint64_t*>(p);
-    *off_cap = cap / sizeof(uint64_t);
-    return r;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -553,20 +532,20 @@ Segments build_segments(int n_total, int world, uint64_t width) {
 }
 
 int enqueue_pack(GatherState* g, bool main_stream, const ctag_frame_result* results_dev, int n, unsigned char* packed, uint64_t* size_dev, hipStream_t s) {
-    uint64_t** off = main_stream ? &g->d_off_main : &g->d_off;
-    const int r = grow_off(g, off, main_stream ? &g->off_main_cap : &g->off_cap, (size_t)n + 1 + kMaxWorld);
+    ctag::DevBuf<uint64_t>& off = main_stream ? g->d_off_main : g->d_off;
+    const int r = grow_idle(g, off, (size_t)n + 1 + kMaxWorld);
     if (r != CTAG_OK) return r;
-    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, s, results_dev, n, *off, packed, size_dev);
-    if (n > 0) hipLaunchKernelGGL(k_pack, dim3(std::min(n, 65535)), dim3(128), 0, s, results_dev, n, *off, packed);
+    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, s, results_dev, n, off.p, packed, size_dev);
+    if (n > 0) hipLaunchKernelGGL(k_pack, dim3(std::min(n, 65535)), dim3(128), 0, s, results_dev, n, off.p, packed);
     G_HIP(hipGetLastError());
     return CTAG_OK;
 }
 
 int enqueue_unpack(GatherState* g, bool main_stream, const unsigned char* gathered, const Segments& S, int n_total, ctag_frame_result* out, hipStream_t s) {
-    uint64_t** offp = main_stream ? &g->d_off_main : &g->d_off;
-    const int r = grow_off(g, offp, main_stream ? &g->off_main_cap : &g->off_cap, (size_t)n_total + 1 + kMaxWorld);
+    ctag::DevBuf<uint64_t>& off = main_stream ? g->d_off_main : g->d_off;
+    const int r = grow_idle(g, off, (size_t)n_total + 1 + kMaxWorld);
     if (r != CTAG_OK) return r;
-    uint64_t* d_off = *offp;
+    uint64_t* d_off = off.p;
     int nmax = 0;
     for (int k = 0; k < S.world; k++) nmax = std::max(nmax, S.n[k]);
     hipLaunchKernelGGL(k_unpack_scan, dim3(S.world), dim3(1024), 0, s, gathered, S, d_off);
@@ -630,10 +609,10 @@ int ctag_pack_results(ctag_handle* h, const ctag_frame_result* results_dev, int 
         if (fr != CTAG_OK) return fr;
     }
     hipStream_t s = static_cast<hipStream_t>(ctag_stream(h));
-    const int r = enqueue_pack(g, true, results_dev, n, static_cast<unsigned char*>(packed_dev), packed_bytes_host ? g->d_sizes + kSoloSlot : nullptr, s);
+    const int r = enqueue_pack(g, true, results_dev, n, static_cast<unsigned char*>(packed_dev), packed_bytes_host ? g->d_sizes.p + kSoloSlot : nullptr, s);
     if (r != CTAG_OK) return r;
     if (packed_bytes_host) {  // a slot of its own: a gather in flight on the gather stream owns slots 0..world-1
-        G_HIP(hipMemcpyAsync(g->h_sizes + kSoloSlot, g->d_sizes + kSoloSlot, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        G_HIP(hipMemcpyAsync(g->h_sizes + kSoloSlot, g->d_sizes.p + kSoloSlot, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         G_HIP(hipStreamSynchronize(s));
         *packed_bytes_host = g->h_sizes[kSoloSlot];
     }
@@ -784,25 +763,25 @@ int ctag_gather_begin(ctag_handle* h, const ctag_frame_result* local_dev, int n_
     const int n_max = (n_total + g->world - 1) / g->world;
     // the payload all-gather sends the largest packed size ROUNDED UP to 256 bytes from this buffer
     const size_t packed_need = (ctag_packed_capacity(n_max) + 255) & ~(size_t)255;
-    const bool fresh = g->packed_cap < packed_need;
-    int r = grow(g, &g->d_packed, &g->packed_cap, packed_need);
+    const bool fresh = g->d_packed.cap < packed_need;
+    int r = grow_idle(g, g->d_packed, packed_need);
     if (r != CTAG_OK) return r;
-    if (fresh) G_HIP(hipMemsetAsync(g->d_packed, 0, g->packed_cap, g->gstream));  // padding bytes that travel are defined
+    if (fresh) G_HIP(hipMemsetAsync(g->d_packed.p, 0, g->d_packed.cap, g->gstream));  // padding bytes that travel are defined
     // the gather stream picks up behind the detection already enqueued on the main stream
     G_HIP(hipEventRecord(g->ev_main, main_s));
     G_HIP(hipStreamWaitEvent(g->gstream, g->ev_main, 0));
-    r = enqueue_pack(g, false, local_dev, n_local, g->d_packed, g->d_sizes + g->rank, g->gstream);
+    r = enqueue_pack(g, false, local_dev, n_local, g->d_packed.p, g->d_sizes.p + g->rank, g->gstream);
     if (r != CTAG_OK) return r;
-    if (g->tagged) hipLaunchKernelGGL(k_tag_pending, dim3(1), dim3(1), 0, g->gstream, g->d_sizes + g->rank, pend_count);
+    if (g->tagged) hipLaunchKernelGGL(k_tag_pending, dim3(1), dim3(1), 0, g->gstream, g->d_sizes.p + g->rank, pend_count);
     // local_dev may be overwritten by whatever the caller enqueues next on the main stream: order it behind the pack
     G_HIP(hipEventRecord(g->ev_packed, g->gstream));
     G_HIP(hipStreamWaitEvent(main_s, g->ev_packed, 0));
     if (g->comm) {
         ncclResult_t nr = ncclSuccess;
-        G_HIP(ordered_collective(g->comm, g->gstream, [&] { return R->AllGather(g->d_sizes + g->rank, g->d_sizes, 1, ncclUint64, g->comm, g->gstream); }, &nr));
+        G_HIP(ordered_collective(g->comm, g->gstream, [&] { return R->AllGather(g->d_sizes.p + g->rank, g->d_sizes.p, 1, ncclUint64, g->comm, g->gstream); }, &nr));
         G_NCCL(nr);
     }
-    G_HIP(hipMemcpyAsync(g->h_sizes, g->d_sizes, sizeof(uint64_t) * g->world, hipMemcpyDeviceToHost, g->gstream));
+    G_HIP(hipMemcpyAsync(g->h_sizes, g->d_sizes.p, sizeof(uint64_t) * g->world, hipMemcpyDeviceToHost, g->gstream));
     G_HIP(hipEventRecord(g->ev_sizes, g->gstream));
     g->n_local = n_local;
     g->n_total = n_total;
@@ -839,16 +818,16 @@ int ctag_gather_end(ctag_handle* h, ctag_frame_result* out_dev) {
             hipStream_t main_s = static_cast<hipStream_t>(ctag_stream(h));
             G_HIP(hipEventRecord(g->ev_main, main_s));
             G_HIP(hipStreamWaitEvent(g->gstream, g->ev_main, 0));
-            const int pr = enqueue_pack(g, false, g->local_dev, g->n_local, g->d_packed, g->d_sizes + g->rank, g->gstream);
+            const int pr = enqueue_pack(g, false, g->local_dev, g->n_local, g->d_packed.p, g->d_sizes.p + g->rank, g->gstream);
             if (pr != CTAG_OK) return pr;
             G_HIP(hipEventRecord(g->ev_packed, g->gstream));
             G_HIP(hipStreamWaitEvent(main_s, g->ev_packed, 0));
             if (g->comm) {
                 ncclResult_t nr = ncclSuccess;
-                G_HIP(ordered_collective(g->comm, g->gstream, [&] { return R->AllGather(g->d_sizes + g->rank, g->d_sizes, 1, ncclUint64, g->comm, g->gstream); }, &nr));
+                G_HIP(ordered_collective(g->comm, g->gstream, [&] { return R->AllGather(g->d_sizes.p + g->rank, g->d_sizes.p, 1, ncclUint64, g->comm, g->gstream); }, &nr));
                 G_NCCL(nr);
             }
-            G_HIP(hipMemcpyAsync(g->h_sizes, g->d_sizes, sizeof(uint64_t) * g->world, hipMemcpyDeviceToHost, g->gstream));
+            G_HIP(hipMemcpyAsync(g->h_sizes, g->d_sizes.p, sizeof(uint64_t) * g->world, hipMemcpyDeviceToHost, g->gstream));
             const int wr = bounded_stream(g, g->gstream, "second all-gather of the packed sizes");
             if (wr != CTAG_OK) return wr;
             for (int r = 0; r < g->world; r++) g->h_sizes[r] &= kSizeMask;
@@ -866,14 +845,14 @@ int ctag_gather_end(ctag_handle* h, ctag_frame_result* out_dev) {
     g->last_local = g->h_sizes[g->rank];
     g->last_padded = width;
     const Segments S = build_segments(g->n_total, g->world, width);
-    const unsigned char* gathered = g->d_packed;
+    const unsigned char* gathered = g->d_packed.p;
     if (g->comm) {
-        const int rc = grow(g, &g->d_gathered, &g->gathered_cap, (size_t)width * g->world);
+        const int rc = grow_idle(g, g->d_gathered, (size_t)width * g->world);
         if (rc != CTAG_OK) return rc;
         ncclResult_t nr = ncclSuccess;
-        G_HIP(ordered_collective(g->comm, g->gstream, [&] { return R->AllGather(g->d_packed, g->d_gathered, (size_t)width, ncclUint8, g->comm, g->gstream); }, &nr));
+        G_HIP(ordered_collective(g->comm, g->gstream, [&] { return R->AllGather(g->d_packed.p, g->d_gathered.p, (size_t)width, ncclUint8, g->comm, g->gstream); }, &nr));
         G_NCCL(nr);
-        gathered = g->d_gathered;
+        gathered = g->d_gathered.p;
     }
     const int rc = enqueue_unpack(g, false, gathered, S, g->n_total, out_dev, g->gstream);
     if (rc != CTAG_OK) return rc;

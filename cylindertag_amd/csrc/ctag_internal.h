@@ -22,6 +22,33 @@
 struct ctag_handle;
 struct ctag_camera;
 
+namespace ctag {
+// A device buffer the library's host code owns: pointer and capacity in elements.  grow() frees, then allocates (the old contents are gone); the
+// destructor frees.  Neither waits for anything: whoever grows or drops a buffer first makes sure that nothing still reads it.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    hipError_t grow(size_t need) {
+        if (p && cap >= need) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), need * sizeof(T));
+        if (e != hipSuccess) p = nullptr;
+        else cap = need;
+        return e;
+    }
+};
+}  // namespace ctag
+
 // the model list of include/ctag_pose.h (k_pose.hip creates it; k_draw.hip reads it too)
 struct ctag_model {
     int n_models = 0, model_size = 0;
@@ -29,9 +56,9 @@ struct ctag_model {
     std::vector<float> base, axis, corners;
     // device copies, created on first use on a device
     int device = -1;
-    int32_t* d_ids = nullptr;
-    float* d_corners = nullptr;
-    float* d_base_axis = nullptr;  // one allocation: base [n_models*3], then axis [n_models*3]
+    ctag::DevBuf<int32_t> d_ids;
+    ctag::DevBuf<float> d_corners;
+    ctag::DevBuf<float> d_base_axis;  // one allocation: base [n_models*3], then axis [n_models*3]
     float* d_base = nullptr;
     float* d_axis = nullptr;
 };
@@ -144,7 +171,7 @@ struct FrameGeom {
     int pool_cap;              // component pool entries per frame
 };
 
-// Per-chunk device workspace (structure of arrays; one allocation, carved by Workspace::layout()).
+// Per-chunk device workspace (structure of arrays; one allocation, carved by carve_workspace, ctag_api.hip).
 struct Workspace {
     int chunk_frames = 0;
     FrameGeom g{};
@@ -323,17 +350,13 @@ bool build_threshold_table(float dark_cap, uint8_t* table /* 256*256 */, int* di
 void build_pick_table(uint8_t* table, uint16_t* table16);  // kPickN*20*10 bytes, (kPickN2 - kPickN)*20*10 halfwords
 
 
-// accessors of the opaque handle for the pose back end (k_pose.hip)
-void** handle_pose_slot(struct ::ctag_handle* h, void (*free_fn)(void*));
-// ... and for the overlay (k_draw.hip)
-void** handle_draw_slot(struct ::ctag_handle* h, void (*free_fn)(void*));
-// ... and for the rig poses (k_rig_pose.hip)
-void** handle_rig_slot(struct ::ctag_handle* h, void (*free_fn)(void*));
+// accessor of the opaque handle for the state of its back ends, each created on first use: the pose back end (k_pose.hip), the overlay (k_draw.hip),
+// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip).  ctag_destroy frees them in this order.
+enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kNumSiblingStates };
+void** handle_state_slot(struct ::ctag_handle* h, SiblingState which, void (*free_fn)(void*));
 // the model's device copies on `device` (k_pose.hip); the camera's distortion model is one the pose back end handles
 int model_to_device(struct ::ctag_model* m, int device);
 bool camera_ok(const struct ::ctag_camera* c);
-// ... and for the multi-GPU gather layer (ctag_gather.hip)
-void** handle_gather_slot(struct ::ctag_handle* h, void (*free_fn)(void*));
 bool handle_timing(const struct ::ctag_handle* h);
 // completes the frames of earlier device-memory calls that wait for the any-frame workspace (CTAG_PENDING records); waits for the
 // handle's stream when there may be any.  Every entry point that reads result records on the device calls it first.

@@ -587,43 +587,18 @@ __global__ __launch_bounds__(kWave) void k_draw_raster(RasterArgs A) {
 }
 
 struct DrawState {
-    uint8_t* d_gray = nullptr;
-    size_t gray_bytes = 0;
-    uint8_t* d_out = nullptr;
-    size_t out_bytes = 0;
-    ctag_frame_result* d_res = nullptr;
-    int32_t* d_offsets = nullptr;
-    ctag_pose_rec* d_poses = nullptr;
-    int poses_cap = 0;
+    DevBuf<uint8_t> d_gray, d_out;
+    DevBuf<ctag_frame_result> d_res;
+    DevBuf<int32_t> d_offsets;
+    DevBuf<ctag_pose_rec> d_poses;
 };
 
-void draw_state_free(void* p) {
-    DrawState* s = static_cast<DrawState*>(p);
-    if (s->d_gray) (void)hipFree(s->d_gray);
-    if (s->d_out) (void)hipFree(s->d_out);
-    if (s->d_res) (void)hipFree(s->d_res);
-    if (s->d_offsets) (void)hipFree(s->d_offsets);
-    if (s->d_poses) (void)hipFree(s->d_poses);
-    delete s;
-}
+void draw_state_free(void* p) { delete static_cast<DrawState*>(p); }
 
 DrawState* draw_state(ctag_handle* h) {
-    void** slot = handle_draw_slot(h, draw_state_free);
+    void** slot = handle_state_slot(h, kDrawState, draw_state_free);
     if (!*slot) *slot = new (std::nothrow) DrawState();
     return static_cast<DrawState*>(*slot);
-}
-
-bool grow(void** p, size_t* have, size_t need) {
-    if (*have >= need && *p) return true;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc(p, need) != hipSuccess) {
-        *p = nullptr;
-        return false;
-    }
-    *have = need;
-    return true;
 }
 
 constexpr int kMaxSide = 1 << 15;
@@ -655,7 +630,7 @@ int enqueue(ctag_handle* h, const uint8_t* frames, int n, int rows, int cols, pt
     A.out = out;
     A.out_row_stride = out_row_stride;
     A.out_frame_stride = out_frame_stride;
-    A.model = DrawModel{model->n_models, model->model_size, model->d_corners, model->d_base, model->d_axis};
+    A.model = DrawModel{model->n_models, model->model_size, model->d_corners.p, model->d_base, model->d_axis};
     A.cam.fx = (double)camera->K[0];
     A.cam.fy = (double)camera->K[4];
     A.cam.cx = (double)camera->K[2];
@@ -702,30 +677,20 @@ int ctag_draw_axis(ctag_handle* h, const uint8_t* gray, int rows, int cols, ptrd
     ctag::DrawState* st = ctag::draw_state(h);
     if (!st) return CTAG_ERR_HIP;
     const size_t gb = (size_t)rows * cols, ob = gb * 3;
-    if (!ctag::grow(reinterpret_cast<void**>(&st->d_gray), &st->gray_bytes, gb)) return CTAG_ERR_HIP;
-    if (!ctag::grow(reinterpret_cast<void**>(&st->d_out), &st->out_bytes, ob)) return CTAG_ERR_HIP;
-    if (!st->d_res) {
-        if (hipMalloc(&st->d_res, sizeof(ctag_frame_result)) != hipSuccess) return CTAG_ERR_HIP;
-        if (hipMalloc(&st->d_offsets, 2 * sizeof(int32_t)) != hipSuccess) return CTAG_ERR_HIP;
-    }
-    if (n_poses > st->poses_cap) {
-        if (st->d_poses) (void)hipFree(st->d_poses);
-        st->d_poses = nullptr;
-        st->poses_cap = 0;
-        if (hipMalloc(&st->d_poses, sizeof(ctag_pose_rec) * (size_t)n_poses) != hipSuccess) return CTAG_ERR_HIP;
-        st->poses_cap = n_poses;
-    }
+    if (st->d_gray.grow(gb) != hipSuccess || st->d_out.grow(ob) != hipSuccess) return CTAG_ERR_HIP;
+    if (st->d_res.grow(1) != hipSuccess || st->d_offsets.grow(2) != hipSuccess) return CTAG_ERR_HIP;
+    if (n_poses > 0 && st->d_poses.grow((size_t)n_poses) != hipSuccess) return CTAG_ERR_HIP;
     hipStream_t s = static_cast<hipStream_t>(ctag_stream(h));
     const int32_t off[2] = {0, n_poses};
-    if (hipMemcpy2DAsync(st->d_gray, cols, gray, row_stride, cols, rows, hipMemcpyHostToDevice, s) != hipSuccess) return CTAG_ERR_HIP;
-    if (hipMemcpyAsync(st->d_res, result, sizeof(ctag_frame_result), hipMemcpyHostToDevice, s) != hipSuccess) return CTAG_ERR_HIP;
-    if (hipMemcpyAsync(st->d_offsets, off, sizeof(off), hipMemcpyHostToDevice, s) != hipSuccess) return CTAG_ERR_HIP;
-    if (n_poses > 0 && hipMemcpyAsync(st->d_poses, poses, sizeof(ctag_pose_rec) * (size_t)n_poses, hipMemcpyHostToDevice, s) != hipSuccess)
+    if (hipMemcpy2DAsync(st->d_gray.p, cols, gray, row_stride, cols, rows, hipMemcpyHostToDevice, s) != hipSuccess) return CTAG_ERR_HIP;
+    if (hipMemcpyAsync(st->d_res.p, result, sizeof(ctag_frame_result), hipMemcpyHostToDevice, s) != hipSuccess) return CTAG_ERR_HIP;
+    if (hipMemcpyAsync(st->d_offsets.p, off, sizeof(off), hipMemcpyHostToDevice, s) != hipSuccess) return CTAG_ERR_HIP;
+    if (n_poses > 0 && hipMemcpyAsync(st->d_poses.p, poses, sizeof(ctag_pose_rec) * (size_t)n_poses, hipMemcpyHostToDevice, s) != hipSuccess)
         return CTAG_ERR_HIP;
-    int rc = ctag::enqueue(h, st->d_gray, 1, rows, cols, cols, (ptrdiff_t)gb, st->d_res, st->d_offsets, st->d_poses, n_poses,
-                           const_cast<ctag_model*>(model), camera, axis_length, st->d_out, 3 * (ptrdiff_t)cols, (ptrdiff_t)ob);
+    int rc = ctag::enqueue(h, st->d_gray.p, 1, rows, cols, cols, (ptrdiff_t)gb, st->d_res.p, st->d_offsets.p, st->d_poses.p, n_poses,
+                           const_cast<ctag_model*>(model), camera, axis_length, st->d_out.p, 3 * (ptrdiff_t)cols, (ptrdiff_t)ob);
     if (rc != CTAG_OK) return rc;
-    if (hipMemcpy2DAsync(out, out_row_stride, st->d_out, 3 * (size_t)cols, 3 * (size_t)cols, rows, hipMemcpyDeviceToHost, s) != hipSuccess)
+    if (hipMemcpy2DAsync(out, out_row_stride, st->d_out.p, 3 * (size_t)cols, 3 * (size_t)cols, rows, hipMemcpyDeviceToHost, s) != hipSuccess)
         return CTAG_ERR_HIP;
     if (hipStreamSynchronize(s) != hipSuccess) return CTAG_ERR_HIP;
     return CTAG_OK;

@@ -124,23 +124,20 @@ struct PoseState {
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool pending = false;
     float last_ms = 0.f;
-    int32_t* d_offsets = nullptr;  // scratch of ctag_estimate_pose
-    ctag_pose_rec* d_poses = nullptr;
-    ctag_frame_result* d_result = nullptr;
+    ctag::DevBuf<int32_t> d_offsets;  // scratch of ctag_estimate_pose
+    ctag::DevBuf<ctag_pose_rec> d_poses;
+    ctag::DevBuf<ctag_frame_result> d_result;
 };
 
 void pose_state_free(void* p) {
     PoseState* s = static_cast<PoseState*>(p);
     for (auto& e : s->ev)
         if (e) (void)hipEventDestroy(e);
-    if (s->d_offsets) (void)hipFree(s->d_offsets);
-    if (s->d_poses) (void)hipFree(s->d_poses);
-    if (s->d_result) (void)hipFree(s->d_result);
     delete s;
 }
 
 PoseState* pose_state(ctag_handle* h) {
-    void** slot = ctag::handle_pose_slot(h, pose_state_free);
+    void** slot = ctag::handle_state_slot(h, ctag::kPoseState, pose_state_free);
     if (!*slot) {
         PoseState* s = new (std::nothrow) PoseState();
         if (!s) return nullptr;
@@ -159,22 +156,20 @@ PoseState* pose_state(ctag_handle* h) {
 namespace ctag {
 
 int model_to_device(ctag_model* m, int device) {
-    if (m->device == device && m->d_ids) return CTAG_OK;
-    if (m->d_ids) (void)hipFree(m->d_ids);
-    if (m->d_corners) (void)hipFree(m->d_corners);
-    if (m->d_base_axis) (void)hipFree(m->d_base_axis);
-    m->d_ids = nullptr;
-    m->d_corners = nullptr;
-    m->d_base_axis = m->d_base = m->d_axis = nullptr;
-    if (hipMalloc(&m->d_ids, sizeof(int32_t) * std::max<size_t>(1, m->ids.size())) != hipSuccess) return CTAG_ERR_HIP;
-    if (hipMalloc(&m->d_corners, sizeof(float) * std::max<size_t>(1, m->corners.size())) != hipSuccess) return CTAG_ERR_HIP;
-    if (hipMemcpy(m->d_ids, m->ids.data(), sizeof(int32_t) * m->ids.size(), hipMemcpyHostToDevice) != hipSuccess) return CTAG_ERR_HIP;
-    if (hipMemcpy(m->d_corners, m->corners.data(), sizeof(float) * m->corners.size(), hipMemcpyHostToDevice) != hipSuccess)
+    if (m->device == device && m->d_ids.p) return CTAG_OK;
+    m->d_ids.release();  // (they may lie on another device)
+    m->d_corners.release();
+    m->d_base_axis.release();
+    m->d_base = m->d_axis = nullptr;
+    if (m->d_ids.grow(std::max<size_t>(1, m->ids.size())) != hipSuccess) return CTAG_ERR_HIP;
+    if (m->d_corners.grow(std::max<size_t>(1, m->corners.size())) != hipSuccess) return CTAG_ERR_HIP;
+    if (hipMemcpy(m->d_ids.p, m->ids.data(), sizeof(int32_t) * m->ids.size(), hipMemcpyHostToDevice) != hipSuccess) return CTAG_ERR_HIP;
+    if (hipMemcpy(m->d_corners.p, m->corners.data(), sizeof(float) * m->corners.size(), hipMemcpyHostToDevice) != hipSuccess)
         return CTAG_ERR_HIP;
     const size_t nb = m->base.size();
-    if (hipMalloc(&m->d_base_axis, sizeof(float) * std::max<size_t>(1, 2 * nb)) != hipSuccess) return CTAG_ERR_HIP;
-    m->d_base = m->d_base_axis;
-    m->d_axis = m->d_base_axis + nb;
+    if (m->d_base_axis.grow(std::max<size_t>(1, 2 * nb)) != hipSuccess) return CTAG_ERR_HIP;
+    m->d_base = m->d_base_axis.p;
+    m->d_axis = m->d_base_axis.p + nb;
     if (nb && (hipMemcpy(m->d_base, m->base.data(), sizeof(float) * nb, hipMemcpyHostToDevice) != hipSuccess ||
                hipMemcpy(m->d_axis, m->axis.data(), sizeof(float) * nb, hipMemcpyHostToDevice) != hipSuccess))
         return CTAG_ERR_HIP;
@@ -254,10 +249,6 @@ int ctag_model_load(const char* path, ctag_model** out) {
 }
 
 void ctag_model_free(ctag_model* m) {
-    if (!m) return;
-    if (m->d_ids) (void)hipFree(m->d_ids);
-    if (m->d_corners) (void)hipFree(m->d_corners);
-    if (m->d_base_axis) (void)hipFree(m->d_base_axis);
     delete m;
 }
 
@@ -345,7 +336,7 @@ int ctag_pose_batch_device(ctag_handle* h, const ctag_frame_result* results_dev,
     }
     hipStream_t s = static_cast<hipStream_t>(ctag_stream(h));
     const ctag::PoseCam cam = ctag::make_pose_cam(camera);
-    ctag::PoseModelDev md{model->n_models, model->model_size, model->d_ids, model->d_corners};
+    ctag::PoseModelDev md{model->n_models, model->model_size, model->d_ids.p, model->d_corners.p};
     const bool timing = ctag::handle_timing(h);
     if (timing && hipEventRecord(st->ev[0], s) != hipSuccess) return CTAG_ERR_HIP;
     hipLaunchKernelGGL(ctag::k_pose_offsets, dim3(1), dim3(256), 0, s, results_dev, n_frames, offsets_dev);
@@ -397,16 +388,12 @@ int ctag_estimate_pose(ctag_handle* h, const ctag_frame_result* result, const ct
     if (hipSetDevice(dev) != hipSuccess) return CTAG_ERR_HIP;
     PoseState* st = pose_state(h);
     if (!st) return CTAG_ERR_HIP;
-    if (!st->d_result) {
-        if (hipMalloc(&st->d_result, sizeof(ctag_frame_result)) != hipSuccess) return CTAG_ERR_HIP;
-        if (hipMalloc(&st->d_offsets, 2 * sizeof(int32_t)) != hipSuccess) return CTAG_ERR_HIP;
-        if (hipMalloc(&st->d_poses, CTAG_MAX_MARKERS * sizeof(ctag_pose_rec)) != hipSuccess) return CTAG_ERR_HIP;
-    }
+    if (st->d_result.grow(1) != hipSuccess || st->d_offsets.grow(2) != hipSuccess || st->d_poses.grow(CTAG_MAX_MARKERS) != hipSuccess) return CTAG_ERR_HIP;
     hipStream_t s = static_cast<hipStream_t>(ctag_stream(h));
-    if (hipMemcpyAsync(st->d_result, result, sizeof(ctag_frame_result), hipMemcpyHostToDevice, s) != hipSuccess) return CTAG_ERR_HIP;
-    const int rc = ctag_pose_batch_device(h, st->d_result, 1, model, camera, st->d_offsets, st->d_poses, CTAG_MAX_MARKERS);
+    if (hipMemcpyAsync(st->d_result.p, result, sizeof(ctag_frame_result), hipMemcpyHostToDevice, s) != hipSuccess) return CTAG_ERR_HIP;
+    const int rc = ctag_pose_batch_device(h, st->d_result.p, 1, model, camera, st->d_offsets.p, st->d_poses.p, CTAG_MAX_MARKERS);
     if (rc != CTAG_OK) return rc;
-    if (hipMemcpyAsync(out, st->d_poses, sizeof(ctag_pose_rec) * result->n_markers, hipMemcpyDeviceToHost, s) != hipSuccess)
+    if (hipMemcpyAsync(out, st->d_poses.p, sizeof(ctag_pose_rec) * result->n_markers, hipMemcpyDeviceToHost, s) != hipSuccess)
         return CTAG_ERR_HIP;
     if (hipStreamSynchronize(s) != hipSuccess) return CTAG_ERR_HIP;
     return CTAG_OK;

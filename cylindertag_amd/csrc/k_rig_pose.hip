@@ -30,7 +30,7 @@ static_assert(CTAG_RIG_MAX_POINTS == CTAG_MAX_FEATURES * 8, "every valid detecti
 struct ctag_rigs {
     int n_models = 0, n_rigs = 0;
     std::vector<int32_t> rig_of_model;
-    int32_t* d_rig = nullptr;  // device copy, made on `device` at the first pose call
+    ctag::DevBuf<int32_t> d_rig;  // device copy, made on `device` at the first pose call
     int device = -1;
 };
 
@@ -128,29 +128,20 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 namespace {
 
 struct RigState {
-    int32_t* d_lists = nullptr;  // 2 x list_items work items
-    int32_t* d_counts = nullptr; // the two lists' lengths
-    long long list_items = 0;
-    ctag_frame_result* d_result = nullptr;  // scratch of ctag_estimate_rig_pose
-    ctag_rig_pose_rec* d_out = nullptr;
-    int out_cap = 0;
+    ctag::DevBuf<int32_t> d_lists;   // 2 x n_items work items
+    ctag::DevBuf<int32_t> d_counts;  // the two lists' lengths
+    ctag::DevBuf<ctag_frame_result> d_result;  // scratch of ctag_estimate_rig_pose
+    ctag::DevBuf<ctag_rig_pose_rec> d_out;
 };
 
-void rig_state_free(void* p) {
-    RigState* s = static_cast<RigState*>(p);
-    if (s->d_lists) (void)hipFree(s->d_lists);
-    if (s->d_counts) (void)hipFree(s->d_counts);
-    if (s->d_result) (void)hipFree(s->d_result);
-    if (s->d_out) (void)hipFree(s->d_out);
-    delete s;
-}
+void rig_state_free(void* p) { delete static_cast<RigState*>(p); }
 
 RigState* rig_state(ctag_handle* h) {
-    void** slot = ctag::handle_rig_slot(h, rig_state_free);
+    void** slot = ctag::handle_state_slot(h, ctag::kRigState, rig_state_free);
     if (!*slot) {
         RigState* s = new (std::nothrow) RigState();
         if (!s) return nullptr;
-        if (hipMalloc(&s->d_counts, 2 * sizeof(int32_t)) != hipSuccess) {
+        if (s->d_counts.grow(2) != hipSuccess) {
             rig_state_free(s);
             return nullptr;
         }
@@ -160,12 +151,11 @@ RigState* rig_state(ctag_handle* h) {
 }
 
 int rigs_to_device(ctag_rigs* r, int device) {
-    if (r->device == device && r->d_rig) return CTAG_OK;
-    if (r->d_rig) (void)hipFree(r->d_rig);
-    r->d_rig = nullptr;
-    if (hipMalloc(&r->d_rig, sizeof(int32_t) * std::max<size_t>(1, r->rig_of_model.size())) != hipSuccess) return CTAG_ERR_HIP;
+    if (r->device == device && r->d_rig.p) return CTAG_OK;
+    r->d_rig.release();  // (it may lie on another device)
+    if (r->d_rig.grow(std::max<size_t>(1, r->rig_of_model.size())) != hipSuccess) return CTAG_ERR_HIP;
     if (!r->rig_of_model.empty() &&
-        hipMemcpy(r->d_rig, r->rig_of_model.data(), sizeof(int32_t) * r->rig_of_model.size(), hipMemcpyHostToDevice) != hipSuccess)
+        hipMemcpy(r->d_rig.p, r->rig_of_model.data(), sizeof(int32_t) * r->rig_of_model.size(), hipMemcpyHostToDevice) != hipSuccess)
         return CTAG_ERR_HIP;
     r->device = device;
     return CTAG_OK;
@@ -189,8 +179,6 @@ int ctag_rigs_create(const ctag_model* model, const int32_t* rig_of_model, int n
 }
 
 void ctag_rigs_free(ctag_rigs* r) {
-    if (!r) return;
-    if (r->d_rig) (void)hipFree(r->d_rig);
     delete r;
 }
 
@@ -214,27 +202,21 @@ int ctag_rig_pose_batch_device(ctag_handle* h, const ctag_frame_result* results_
         if (fr != CTAG_OK) return fr;
     }
     hipStream_t s = static_cast<hipStream_t>(ctag_stream(h));
-    if (st->list_items < n_items) {
-        if (st->d_lists) {  // an earlier call's kernels may still read the old lists
-            if (hipStreamSynchronize(s) != hipSuccess) return CTAG_ERR_HIP;
-            (void)hipFree(st->d_lists);
-            st->d_lists = nullptr;
-            st->list_items = 0;
-        }
-        if (hipMalloc(&st->d_lists, sizeof(int32_t) * 2 * (size_t)n_items) != hipSuccess) return CTAG_ERR_HIP;
-        st->list_items = n_items;
+    if (st->d_lists.cap < 2 * (size_t)n_items) {
+        if (st->d_lists.p && hipStreamSynchronize(s) != hipSuccess) return CTAG_ERR_HIP;  // an earlier call's kernels may still read the old lists
+        if (st->d_lists.grow(2 * (size_t)n_items) != hipSuccess) return CTAG_ERR_HIP;
     }
     const int ni = (int)n_items;
     const ctag::PoseCam cam = ctag::make_pose_cam(camera);
-    const ctag::PoseModelDev md{model->n_models, model->model_size, model->d_ids, model->d_corners};
-    if (hipMemsetAsync(st->d_counts, 0, 2 * sizeof(int32_t), s) != hipSuccess) return CTAG_ERR_HIP;
-    hipLaunchKernelGGL(ctag::k_rig_count, dim3(std::min((ni + 255) / 256, 1024)), dim3(256), 0, s, results_dev, n_frames, md, rigs->d_rig,
-                       rigs->n_rigs, out_dev, st->d_lists, st->d_counts);
+    const ctag::PoseModelDev md{model->n_models, model->model_size, model->d_ids.p, model->d_corners.p};
+    if (hipMemsetAsync(st->d_counts.p, 0, 2 * sizeof(int32_t), s) != hipSuccess) return CTAG_ERR_HIP;
+    hipLaunchKernelGGL(ctag::k_rig_count, dim3(std::min((ni + 255) / 256, 1024)), dim3(256), 0, s, results_dev, n_frames, md, rigs->d_rig.p,
+                       rigs->n_rigs, out_dev, st->d_lists.p, st->d_counts.p);
     // grids for the worst case (every item in one list); a workgroup past its list's length exits at once
     hipLaunchKernelGGL((ctag::k_rig_solve<ctag::kRigSmallPts, 64>), dim3(std::min(ni, 256 * 16)), dim3(64), 0, s, results_dev, rigs->n_rigs,
-                       st->d_lists, st->d_counts, md, cam, out_dev);
+                       st->d_lists.p, st->d_counts.p, md, cam, out_dev);
     hipLaunchKernelGGL((ctag::k_rig_solve<ctag::kRigMaxPts, ctag::kRigLargeThreads>), dim3(std::min(ni, 256)), dim3(ctag::kRigLargeThreads), 0, s,
-                       results_dev, rigs->n_rigs, st->d_lists + ni, st->d_counts + 1, md, cam, out_dev);
+                       results_dev, rigs->n_rigs, st->d_lists.p + ni, st->d_counts.p + 1, md, cam, out_dev);
     if (hipGetLastError() != hipSuccess) return CTAG_ERR_HIP;
     return CTAG_OK;
 }
@@ -247,21 +229,15 @@ int ctag_estimate_rig_pose(ctag_handle* h, const ctag_frame_result* result, cons
     RigState* st = rig_state(h);
     if (!st) return CTAG_ERR_HIP;
     hipStream_t s = static_cast<hipStream_t>(ctag_stream(h));
-    if (!st->d_result && hipMalloc(&st->d_result, sizeof(ctag_frame_result)) != hipSuccess) return CTAG_ERR_HIP;
-    if (st->out_cap < rigs->n_rigs) {
-        if (st->d_out) {
-            if (hipStreamSynchronize(s) != hipSuccess) return CTAG_ERR_HIP;
-            (void)hipFree(st->d_out);
-            st->d_out = nullptr;
-            st->out_cap = 0;
-        }
-        if (hipMalloc(&st->d_out, sizeof(ctag_rig_pose_rec) * (size_t)rigs->n_rigs) != hipSuccess) return CTAG_ERR_HIP;
-        st->out_cap = rigs->n_rigs;
+    if (st->d_result.grow(1) != hipSuccess) return CTAG_ERR_HIP;
+    if (st->d_out.cap < (size_t)rigs->n_rigs) {
+        if (st->d_out.p && hipStreamSynchronize(s) != hipSuccess) return CTAG_ERR_HIP;
+        if (st->d_out.grow((size_t)rigs->n_rigs) != hipSuccess) return CTAG_ERR_HIP;
     }
-    if (hipMemcpyAsync(st->d_result, result, sizeof(ctag_frame_result), hipMemcpyHostToDevice, s) != hipSuccess) return CTAG_ERR_HIP;
-    const int rc = ctag_rig_pose_batch_device(h, st->d_result, 1, model, rigs, camera, st->d_out);
+    if (hipMemcpyAsync(st->d_result.p, result, sizeof(ctag_frame_result), hipMemcpyHostToDevice, s) != hipSuccess) return CTAG_ERR_HIP;
+    const int rc = ctag_rig_pose_batch_device(h, st->d_result.p, 1, model, rigs, camera, st->d_out.p);
     if (rc != CTAG_OK) return rc;
-    if (hipMemcpyAsync(out, st->d_out, sizeof(ctag_rig_pose_rec) * (size_t)rigs->n_rigs, hipMemcpyDeviceToHost, s) != hipSuccess)
+    if (hipMemcpyAsync(out, st->d_out.p, sizeof(ctag_rig_pose_rec) * (size_t)rigs->n_rigs, hipMemcpyDeviceToHost, s) != hipSuccess)
         return CTAG_ERR_HIP;
     if (hipStreamSynchronize(s) != hipSuccess) return CTAG_ERR_HIP;
     return CTAG_OK;
