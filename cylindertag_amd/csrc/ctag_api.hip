@@ -10,6 +10,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <map>
+#include <mutex>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -461,6 +463,31 @@ DevKnobs dev_knobs() {
     k.ccl_stamps = getenv("CTAG_CCL_STAMPS") != nullptr;
     k.quad_stamps = getenv("CTAG_QUAD_STAMPS") != nullptr;
     return k;
+}
+
+unsigned long long* Stamps::zeroed(hipStream_t s) {
+    if (!d && hipMalloc(reinterpret_cast<void**>(&d), kSlots * sizeof(*d)) != hipSuccess) return d = nullptr;
+    (void)hipMemsetAsync(d, 0, kSlots * sizeof(*d), s);
+    return d;
+}
+void Stamps::read(hipStream_t s, unsigned long long* h, int n) const {
+    (void)hipStreamSynchronize(s);
+    memset(h, 0, n * sizeof(*h));
+    if (d) (void)hipMemcpy(h, d, n * sizeof(*d), hipMemcpyDeviceToHost);
+}
+
+void ensure_dynamic_lds(const void* fn, size_t bytes) {
+    if (bytes <= 64 * 1024) return;  // what every kernel may ask for as it is
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> have;  // (kernel, device) -> bytes it may ask for
+    const std::lock_guard<std::mutex> lock(mu);
+    size_t& h = have[{fn, dev}];
+    if (bytes > h) {
+        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        h = bytes;
+    }
 }
 
 ChunkPlan plan_chunk(const PlanIn& in) {

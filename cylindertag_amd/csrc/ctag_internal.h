@@ -299,6 +299,18 @@ struct DevKnobs {
     bool ccl_stamps = false, quad_stamps = false, feat_stamps = false;  // CTAG_CCL_STAMPS, CTAG_QUAD_STAMPS (read on every call), CTAG_FEAT_STAMPS
 };
 DevKnobs dev_knobs();
+// The developer phase clocks ("stamps", the CTAG_*_STAMPS switches): kSlots 64-bit counters in device memory that the kernels of one launcher add clock ticks
+// to (a null pointer: no clocks).  A launcher keeps one as a static: the buffer is allocated at the first use and stays for the life of the process.  read()
+// waits for the stream, which is why these switches turn graph capture off (DevKnobs::stamps).
+struct Stamps {
+    static constexpr int kSlots = 32;
+    unsigned long long* d = nullptr;
+    unsigned long long* zeroed(hipStream_t s);                           // the buffer, zeroed on `s` behind what is enqueued there (null: no memory)
+    void read(hipStream_t s, unsigned long long* h, int n) const;        // waits for `s`, then slots [0, n) -> h
+};
+// A kernel that asks for more than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize raised first: per kernel and device, and it only ever
+// grows.  Call it before every such launch; it is a table lookup once the attribute holds `bytes`.
+void ensure_dynamic_lds(const void* fn, size_t bytes);
 
 // What a chunk's kernel forms are chosen from: values only (`frames` is looked at for its alignment, never read)
 struct PlanIn {

@@ -332,4 +332,15 @@ CTM_HD float fast_atan2_deg(float y, float x) {
     return a;
 }
 
+// determinant + solve for 2x2 CV_32F (cv::solve, DECOMP_LU on a 2x2 system) -- SURVEY.md App. A.7
+CTM_HD bool solve2x2(float a00, float a01, float a10, float a11, float b0, float b1, float& x0, float& x1) {
+    double d = (double)a00 * a11 - (double)a01 * a10;
+    if (d == 0.) return false;
+    d = 1. / d;
+    const float t = (float)(((double)b0 * a11 - (double)b1 * a01) * d);
+    x1 = (float)(((double)b1 * a00 - (double)b0 * a10) * d);
+    x0 = t;
+    return true;
+}
+
 }  // namespace ctm

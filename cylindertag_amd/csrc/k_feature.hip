@@ -14,6 +14,7 @@
 #include "ctag_internal.h"
 #include "ctag_math.h"
 #include "ctag_refine.h"
+#include "ctag_wave.h"
 
 namespace ctag {
 
@@ -25,15 +26,6 @@ struct P2 {
 __device__ __forceinline__ float dist2p(P2 a, P2 b) { return ctm::sqrt32((a.x - b.x) * (a.x - b.x) + (a.y - b.y) * (a.y - b.y)); }
 // atan2(float,float)*180/CV_PI as the reference writes it: float atan2, float*int, then a double division
 __device__ __forceinline__ double angdeg(float dy, float dx) { return ctm::atan2_32(dy, dx) * 180 / kPi; }
-__device__ __forceinline__ bool solve2x2f(float a00, float a01, float a10, float a11, float b0, float b1, float& x0, float& x1) {
-    double d = (double)a00 * a11 - (double)a01 * a10;
-    if (d == 0.) return false;
-    d = 1. / d;
-    const float t = (float)(((double)b0 * a11 - (double)b1 * a01) * d);
-    x1 = (float)(((double)b1 * a00 - (double)b0 * a10) * d);
-    x0 = t;
-    return true;
-}
 
 // =====================================================================================================
 // K7
@@ -60,6 +52,13 @@ struct FeatPtrs {
     int32_t* frame_long;         // [F] reset here for K8 (k_edge_refine<1> sets it)
     int cand_cap;                // candidates per frame the workspace holds (stride of `quads`)
 };
+static FeatPtrs feat_ptrs(const Workspace& ws, unsigned long long* stamps) {
+    FeatPtrs P{};
+    P.ncand = ws.ncand, P.quads = ws.quads, P.derived = reinterpret_cast<QuadDerived*>(ws.quad_derived), P.quad_index = ws.quad_index, P.nquads = ws.nquads;
+    P.nfeat = ws.nfeat, P.status = ws.status, P.frame_flags = ws.frame_flags, P.feat0 = ws.feat0, P.feat1 = ws.feat1, P.feat2 = ws.feat2;
+    P.stamps = stamps, P.threshold_angle = ws.kp.angle, P.frame_long = ws.frame_long, P.cand_cap = ws.cand_cap;
+    return P;
+}
 static_assert(kQuadStride > CTAG_MAX_QUADS, "K7 keeps every quad of a frame it goes on with");
 
 // developer aid: phase clock of a block (thread 0), summed over blocks into `stamps[base + phase]`
@@ -464,6 +463,12 @@ struct RefinePtrs {
     int32_t* frame_long; // [F] 1: the frame has a quad with an edge of more than kRefineSamples samples (those quads take the one-kernel form)
     int ch;              // 1: gray frames; 3: BGR frames (3 bytes per pixel), converted -- cvtColor(BGR2GRAY), gray_of -- where a pixel is loaded
 };
+static RefinePtrs refine_ptrs(const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, const DetectParams& p) {
+    RefinePtrs P{};
+    P.frames = frames, P.frame_stride = frame_stride, P.row_stride = row_stride, P.ch = p.channels == 3 ? 3 : 1;
+    P.nfeat = ws.nfeat, P.status = ws.status, P.feat1 = ws.feat1, P.feat2 = ws.feat2, P.n0 = ws.refine_n0, P.frame_long = ws.frame_long;
+    return P;
+}
 constexpr int kRefineSamples = 128;               // samples of an edge searched per pass (the reference's minimum sample count, :615)
 constexpr int kRefineThreads = 2 * kRefineSamples; // two edges side by side: waves 0-1 edge e, waves 2-3 edge e + 1
 #ifndef CTAG_REFINE_STAGE_DEEP
@@ -528,15 +533,18 @@ __device__ __forceinline__ void refine_corner(const double* A, int it, int off, 
     }
 }
 
-// Barrier of the edgeRefine blocks: their phases exchange data through LDS only, so it waits for LDS traffic and NOT for vector memory -- __syncthreads() would also
-// wait for the block's n0 stores (the vector-memory counter counts stores on gfx9) before the next quad's box may be requested.  A value a thread loaded itself is
-// waited for where it is used, as always.
-// Holds only while no phase of these blocks hands data to another thread through GLOBAL memory (none does: n0 is re-read by other kernels only).  A build with
-// EXTRA=-DCTAG_REFINE_PLAIN_SYNC=1 replaces both macros by __syncthreads(): the parity tests pass with either (tests/test_refine_sync_gpu.py runs them on that build).
+// edgeRefine's two ordering points.  refine_sync, the barrier of its blocks: their phases exchange data through LDS only, and __syncthreads() would also wait for
+// the block's n0 stores before the next quad's box may be requested; no phase hands data to another thread through global memory (n0 is re-read by other kernels
+// only).  sums_sync, between the phases of k_edge_refine_sums, whose block is ONE wave (it checks its launch size and traps otherwise): __syncthreads() would wait
+// for the NEXT quad's n0, requested a quad ahead precisely so that nobody waits for it (the kernel then ran at 0.38 of its vector-issue rate:
+// profiles/r05_pmc_instmix.json).  What the two rely on is stated at lds_barrier / lds_wait (ctag_wave.h); a build with EXTRA=-DCTAG_REFINE_PLAIN_SYNC=1 makes both
+// __syncthreads(), and tests/test_variant_builds_gpu.py holds its records against the oracle as it does the default build's.
 #if defined(CTAG_REFINE_PLAIN_SYNC) && CTAG_REFINE_PLAIN_SYNC
-#define REFINE_SYNC() __syncthreads()
+__device__ __forceinline__ void refine_sync() { __syncthreads(); }
+__device__ __forceinline__ void sums_sync() { __syncthreads(); }
 #else
-#define REFINE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+__device__ __forceinline__ void refine_sync() { lds_barrier(); }
+__device__ __forceinline__ void sums_sync() { lds_wait(); }
 #endif
 // REGION: bytes of the quad's pixel neighbourhood staged in LDS.  kRefineRegion holds the box of every quad of a 1080p-class frame; frames above 1920x1200 have quads
 // of twice the size (a diagonal strip's box is ~190 x 190 px, up to 240 x 240) and batches of them run the search kernel with kRefineRegionLarge -- three blocks per CU
@@ -589,7 +597,7 @@ __device__ __forceinline__ bool refine_quad(const RefinePtrs& P, int rows, int c
     if constexpr (MODE != 1) {
         for (int k = tid; k < kPitch; k += (int)blockDim.x) s_ones[k] = 1.0;
     }
-    REFINE_SYNC();
+    refine_sync();
     if (tid < 4) {  // :609-615
         const int a = tid, b = (tid + 1) & 3;
         const double nx = s_cy[b] - s_cy[a];
@@ -623,7 +631,7 @@ __device__ __forceinline__ bool refine_quad(const RefinePtrs& P, int rows, int c
         s_box[2] = pitch;
         s_box[3] = staged;  // rows staged, 0 = the box stays in global memory
     }
-    REFINE_SYNC();
+    refine_sync();
     const int max_ns = max(max(s_ns[0], s_ns[1]), max(s_ns[2], s_ns[3]));
     {   // which form takes this quad: an edge of more than kRefineSamples samples needs several passes -> the one-kernel form
         const bool long_quad = max_ns > kRefineSamples;
@@ -708,7 +716,7 @@ __device__ __forceinline__ bool refine_quad(const RefinePtrs& P, int rows, int c
                     same);
             }
         }
-        REFINE_SYNC();
+        refine_sync();
     }
     const int half = tid >> 7, st = tid & (kRefineSamples - 1);
     double* const n0_quad = P.n0 + ((size_t)frame * (CTAG_MAX_FEATURES * 2) + qidx) * (4 * kRefineSamples);
@@ -777,7 +785,7 @@ __device__ __forceinline__ bool refine_quad(const RefinePtrs& P, int rows, int c
             }
         }
         if constexpr (MODE == 1) return false;  // one pass: every edge of the quad has kRefineSamples samples
-        REFINE_SYNC();
+        refine_sync();
         if (tid < 48) {  // sequential (sample-order) accumulation: bit-identical to the reference's running sums
             // every sum has the form (A * B) * w with A, B in {x, y, 1} (x * 1 and 1 * 1 are exact); a sample without an
             // edge point has x = y = w = 0 and adds +0.0, which equals the reference skipping it
@@ -798,13 +806,13 @@ __device__ __forceinline__ bool refine_quad(const RefinePtrs& P, int rows, int c
             for (; k < cntS; k++) acc += (pa[k] * pb[k]) * pw[k];
             accp[tid] = acc;
         }
-        REFINE_SYNC();
+        refine_sync();
     }
     if (tid < 8) {  // line of (edge, pass)
         const int edge = tid >> 1, pass = tid & 1;
         refine_line(s_acc + edge * 12 + pass * 6, s_acc + edge * 12 + pass * 6);
     }
-    REFINE_SYNC();
+    refine_sync();
     if (tid < 4) refine_corner(s_acc, tid, off, F, P.feat2 + (size_t)frame * CTAG_MAX_FEATURES + fi);  // one refined corner per lane
     return true;
 }
@@ -829,7 +837,7 @@ void k_edge_refine(RefinePtrs P, int rows, int cols, int subpix, int nframes, in
     const double alpha128 = (15.0 + (double)((int)threadIdx.x & (kRefineSamples - 1))) / (kRefineSamples + 30);  // == (15.0 + s) / (nsamples + 30) at 128 samples
     for (int q = bx; q < nq; q += gx) {
         refine_quad<MODE, REGION>(P, rows, cols, subpix, frame, q, 0, alpha128);
-        if (q + gx < nq) REFINE_SYNC();
+        if (q + gx < nq) refine_sync();
     }
 }
 // ---- the sums kernel (round 5): TERMS in LDS.  Its round-4 form (k_edge_refine<2>, docs/history.md) kept rows of x, y, the products and the weights, and every step of
@@ -846,18 +854,6 @@ void k_edge_refine(RefinePtrs P, int rows, int cols, int subpix, int nframes, in
 #endif
 constexpr int kSumSeg = 16, kSumSegs = kRefineSamples / kSumSeg;
 constexpr int kSumPitch = kSumSeg + 2;  // doubles per row: 36 words -- an odd multiple of four, so the ds_read_b128 of 16 consecutive lanes (rows) cover the 64 banks exactly once
-// The sums kernel's block is ONE wave, and LDS serves a wave's accesses in order: its phases are ordered by a wait for LDS traffic alone.  __syncthreads() would also wait
-// for vector memory -- for the NEXT quad's n0, requested a quad ahead precisely so that nobody waits for it (with __syncthreads() the kernel ran at 0.38 of its
-// vector-issue rate: profiles/r05_pmc_instmix.json).
-// No barrier at all: correct ONLY for a block of exactly one wave64 -- k_edge_refine_sums (its only user) checks its launch size and traps otherwise.
-#if defined(CTAG_REFINE_PLAIN_SYNC) && CTAG_REFINE_PLAIN_SYNC
-#define SUMS_SYNC() __syncthreads()
-#else
-#define SUMS_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && defined(__GFX9__) && defined(__AMDGCN_WAVEFRONT_SIZE__) && __AMDGCN_WAVEFRONT_SIZE__ != 64
-#error "SUMS_SYNC assumes 64-wide wavefronts"
-#endif
 struct SumsPrefetch {
     double n0[kSumSegs];  // of sample 16 g + (tid & 15) of edge tid >> 4
     float cx, cy;
@@ -884,7 +880,7 @@ __device__ __forceinline__ bool refine_sums_quad(const SumsPrefetch& pre, const 
         s_cx[tid] = pre.cx;
         s_cy[tid] = pre.cy;
     }
-    SUMS_SYNC();
+    sums_sync();
     if (tid < 4) {  // :609-615
         const int a = tid, b = (tid + 1) & 3;
         const double nx = s_cy[b] - s_cy[a];
@@ -895,7 +891,7 @@ __device__ __forceinline__ bool refine_sums_quad(const SumsPrefetch& pre, const 
         s_nrm[tid][0] = nx / mag;
         s_nrm[tid][1] = ny / mag;
     }
-    SUMS_SYNC();
+    sums_sync();
     if (max(max(s_ns[0], s_ns[1]), max(s_ns[2], s_ns[3])) > kRefineSamples) return false;  // k_edge_refine_long's
     const int edge = tid >> 4, loc = tid & 15;
     const float ax = s_cx[edge], ay = s_cy[edge], bx = s_cx[(edge + 1) & 3], by = s_cy[(edge + 1) & 3];
@@ -914,7 +910,7 @@ __device__ __forceinline__ bool refine_sums_quad(const SumsPrefetch& pre, const 
         const double x = ok ? x0 + n0 * nx : 0.0, y = ok ? y0 + n0 * ny : 0.0;
         const double wn = ok ? 1 - alpha : 0.0, wl = ok ? alpha : 0.0;  // weights towards the next / the last corner; a sample without an edge point adds +0.0 to every sum
         const double xx = x * x, xy = x * y, yy = y * y;
-        if (g) SUMS_SYNC();  // the sums of the segment before are done with the rows
+        if (g) sums_sync();  // the sums of the segment before are done with the rows
         mine[0 * kSumPitch] = x * wn;   // (x 1) w: x 1 is exact
         mine[1 * kSumPitch] = y * wn;
         mine[2 * kSumPitch] = xx * wn;  // (A B) w: the product first, as the reference's left-to-right evaluation rounds it
@@ -927,7 +923,7 @@ __device__ __forceinline__ bool refine_sums_quad(const SumsPrefetch& pre, const 
         mine[9 * kSumPitch] = xy * wl;
         mine[10 * kSumPitch] = yy * wl;
         mine[11 * kSumPitch] = wl;
-        SUMS_SYNC();
+        sums_sync();
         if (tid < 48) {  // sequential (sample-order) accumulation: bit-identical to the reference's running sums
             double t[kSumSeg];
 #pragma unroll
@@ -940,7 +936,7 @@ __device__ __forceinline__ bool refine_sums_quad(const SumsPrefetch& pre, const 
         }
     }
     if (tid < 48) acc_out[tid] = acc;
-    SUMS_SYNC();
+    sums_sync();
     return true;
 }
 // The sums go back to global memory -- into the first 49 doubles of the quad's own n0 block, which is dead once they are formed: [0, 48) the sums, [48] 1.0 when the
@@ -949,7 +945,7 @@ __device__ __forceinline__ bool refine_sums_quad(const SumsPrefetch& pre, const 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CTAG_REFINE_SUMS2_WAVES, 8)))
 void k_edge_refine_sums(RefinePtrs P, int nframes, int per_frame) {
     // per_frame blocks per frame, blocks b and b + 8 -- one XCD -- on the same frame; a block loops over the frame's quads with the next quad's inputs in flight
-    if (blockDim.x != 64) __builtin_trap();  // SUMS_SYNC orders the phases of ONE wave; any other launch size would race silently
+    if (blockDim.x != 64) __builtin_trap();  // sums_sync orders the phases of ONE wave; any other launch size would race silently
     const int b = blockIdx.x;
     const int frame = ((b >> 3) / per_frame) * 8 + (b & 7);
     const int bx = (b >> 3) % per_frame;
@@ -964,19 +960,19 @@ void k_edge_refine_sums(RefinePtrs P, int nframes, int per_frame) {
     for (int k = tid; k < kRefineSamples; k += 64) s_alpha[k] = (15.0 + k) / (kRefineSamples + 30);
     // The loop is ROTATED so that nothing a quad needs has been requested less than a quad's time ago -- and it took the ISA to see that it was not so: with
     // "request next, work, store, cur = next" the compiler's wait-count pass, merging the loop's entry (cur's own loads outstanding) with its back edge, put
-    // s_waitcnt vmcnt(0) before the first use of `cur`, right behind the requests for the next quad (so the prefetch hid nothing, here and in round 4's kernel),
-    // and the copy at the end waited for the stores just issued.  Now: cur's first loads are awaited explicitly before the loop (the pass understands
-    // S_WAITCNT), and an iteration is work(cur) -> cur = next (a wait for loads a quad old) -> request the quad after -> store this quad's sums.
+    // a wait for all vector memory before the first use of `cur`, right behind the requests for the next quad (so the prefetch hid nothing, here and in round 4's kernel),
+    // and the copy at the end waited for the stores just issued.  Now: cur's first loads are awaited explicitly before the loop (vmem_wait: the pass
+    // understands it), and an iteration is work(cur) -> cur = next (a wait for loads a quad old) -> request the quad after -> store this quad's sums.
     SumsPrefetch cur, nxt;
     sums_prefetch(P, frame, q, cur);
-    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+    vmem_wait();
     int qn = q + per_frame;
     if (qn < nq) sums_prefetch(P, frame, qn, nxt);
     for (;;) {
         const bool have = refine_sums_quad(cur, s_alpha, s_acc);
         const double mine = tid < 48 ? s_acc[tid] : (have ? 1.0 : 0.0);
         double* const out = P.n0 + ((size_t)frame * (CTAG_MAX_FEATURES * 2) + q) * (4 * kRefineSamples);
-        SUMS_SYNC();
+        sums_sync();
         q = qn;
         qn += per_frame;
         if (q < nq) {
@@ -1046,6 +1042,12 @@ struct MarkerPtrs {
     PendingCtx pend;             // frames that exceeded this workspace's pools (device-memory calls list them for the any-frame pass)
     int big;                     // this IS the any-frame workspace: an overflow is final
 };
+static MarkerPtrs marker_ptrs(const Workspace& ws, const DetectParams& p, ctag_frame_result* out, const PendingCtx& pend, unsigned long long* stamps) {
+    MarkerPtrs P{};
+    P.nfeat = ws.nfeat, P.status = ws.status, P.frame_flags = ws.frame_flags, P.feat = ws.feat2, P.pre = ws.premarkers, P.out = out, P.stamps = stamps;
+    P.dict = p.dict, P.dict_pos = p.dict_pos, P.kp = ws.kp, P.pend = pend, P.big = ws.big ? 1 : 0;
+    return P;
+}
 
 // featureExtraction for one feature (:1056-1207); C = 8 corners (x,y), swapped in place when direction == 0
 __device__ void feature_ids(float* C, int direction, int& ID_left, int& ID_right, float& crl, float& crr, int& id, int& idl, int& idr, const float* IDc,
@@ -1088,14 +1090,14 @@ __device__ void feature_ids(float* C, int direction, int& ID_left, int& ID_right
     const P3 ll = mkline(Pt(5), Pt(0), Pt(5));
     const P3 lr = mkline(Pt(1), Pt(4), Pt(1));
     P2 vanish{0, 0}, middle{0, 0}, mleft{0, 0}, mright{0, 0};
-    solve2x2f(line1.x, line1.y, line2.x, line2.y, -line1.z, -line2.z, vanish.x, vanish.y);
-    solve2x2f(lc1.x, lc1.y, lc2.x, lc2.y, -lc1.z, -lc2.z, middle.x, middle.y);
+    ctm::solve2x2(line1.x, line1.y, line2.x, line2.y, -line1.z, -line2.z, vanish.x, vanish.y);
+    ctm::solve2x2(lc1.x, lc1.y, lc2.x, lc2.y, -lc1.z, -lc2.z, middle.x, middle.y);
     P3 ml;
     ml.x = middle.y - vanish.y;
     ml.y = vanish.x - middle.x;
     ml.z = -ml.x * middle.x - ml.y * middle.y;
-    solve2x2f(ml.x, ml.y, ll.x, ll.y, -ml.z, -ll.z, mleft.x, mleft.y);
-    solve2x2f(ml.x, ml.y, lr.x, lr.y, -ml.z, -lr.z, mright.x, mright.y);
+    ctm::solve2x2(ml.x, ml.y, ll.x, ll.y, -ml.z, -ll.z, mleft.x, mleft.y);
+    ctm::solve2x2(ml.x, ml.y, lr.x, lr.y, -ml.z, -lr.z, mright.x, mright.y);
     float d1, d2, d3, d4;
     bool is_long = false;
     d1 = dist2p(mleft, Pt(0));
@@ -1132,11 +1134,6 @@ __device__ void feature_ids(float* C, int direction, int& ID_left, int& ID_right
 // all lanes, the union-find stays on wave 0 (its state lives in that wave's registers), and the markers are decoded a wave each -- code
 // positions, dictionary coverage and the choice are independent per marker; only the places of the accepted markers in the record depend on the
 // markers before them, and those are handed out in marker order once a round of WAVES markers is decoded.
-#define WSYNC()                                                \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-    } while (0)
 template <int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void k_markers(MarkerPtrs P, int nframes, int feature_size, int drows, int dcols) {
     constexpr int NT = 64 * WAVES;
@@ -1497,7 +1494,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_markers(MarkerPtrs P, int nframe
             s_misc[3] = 0;  // no code overflow
             s_misc[5] = 0;  // not accepted
         }
-        WSYNC();
+        wave_fence();
         if (m < cnt && n >= feature_size) do {  // (wave-uniform)
         if (n <= 64) {
             // code positions (:1218-1227) a feature per lane: gap_j from features j-1 and j, position = running sum of the gaps;
@@ -1525,10 +1522,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_markers(MarkerPtrs P, int nframe
             if (j < n && pos >= CTAG_MAX_CODE_POS) bad = 1;
             const int overflow = __ballot(bad != 0) != 0ull;
             if (lane < CTAG_MAX_CODE_POS) s_code[lane] = -1;
-            WSYNC();
+            wave_fence();
             const int pos_next = __shfl_down(pos, 1);
             if (!overflow && j < n && (j == n - 1 || pos_next != pos)) s_code[pos] = idj;
-            WSYNC();
+            wave_fence();
             const unsigned long long lg = __ballot(lane < CTAG_MAX_CODE_POS && s_code[lane < CTAG_MAX_CODE_POS ? lane : 0] > -1);
             const int pos_last = __shfl(pos, n - 1);
             if (lane == 0) {
@@ -1562,7 +1559,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_markers(MarkerPtrs P, int nframe
             s_misc[3] = overflow;
             s_misc[4] = legal;
         }
-        WSYNC();
+        wave_fence();
         clk.mark(22);
         if (s_misc[3]) break;  // CTAG_FLAG_CODE_OVERFLOW (set where the round's markers are stored)
         const int length = s_misc[2], legal = s_misc[4];
@@ -1612,7 +1609,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_markers(MarkerPtrs P, int nframe
                         (uint8_t)(((b0 >> j) & 1u) | (((b1 >> j) & 1u) << 1) | (((b2 >> j) & 1u) << 2) | (((b3 >> j) & 1u) << 3) | (((b4 >> j) & 1u) << 4));
                 }
             }
-            WSYNC();
+            wave_fence();
             for (int h = h_lo; h < h_hi; h++) lane_max = max(lane_max, (int)s_cov[h]);
         } else {
             // more than 32 dictionary columns: a contiguous run of hypotheses per lane, the code and its reversed+inverted form in
@@ -1745,35 +1742,18 @@ __global__ __launch_bounds__(64 * WAVES) void k_markers(MarkerPtrs P, int nframe
 // =====================================================================================================
 // launchers
 // =====================================================================================================
-// developer aid (CTAG_FEAT_STAMPS=1): phase clocks of k_features (slots 0-5) and k_markers (16-24); `report` waits and prints
-static unsigned long long* feat_stamps(bool want, hipStream_t s, bool report) {
-    static unsigned long long* d = nullptr;
-    if (!want) return nullptr;
-    if (!d) {
-        (void)hipMalloc(reinterpret_cast<void**>(&d), 32 * 8);
-        (void)hipMemset(d, 0, 32 * 8);
-    }
-    if (report) {
-        unsigned long long h[32];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-        (void)hipMemset(d, 0, 32 * 8);
-        fprintf(stderr, "[k_features ticks] compact %llu derive %llu pairs %llu greedy %llu organise %llu obtain %llu\n", h[0], h[1], h[2], h[3], h[4], h[5]);
-        fprintf(stderr, "[k_markers ticks] load %llu pairs %llu union %llu sort %llu ids %llu carry+pre %llu | code %llu coverage %llu pick+store %llu\n", h[16], h[17], h[18],
-                h[19], h[20], h[21], h[22], h[23], h[24]);
-    }
-    return d;
-}
+// developer aid (CTAG_FEAT_STAMPS=1): phase clocks of k_features (slots 0-5) and k_markers (16-24); zeroed ahead of K7, read and printed behind K9
+static Stamps feat_stamps;
 
 hipError_t launch_features(const ChunkPlan& pl, const Workspace& ws, const DetectParams& p, hipStream_t s) {
-    FeatPtrs P{ws.ncand, ws.quads, reinterpret_cast<QuadDerived*>(ws.quad_derived), ws.quad_index, ws.nquads, ws.nfeat, ws.status, ws.frame_flags, ws.feat0, ws.feat1, ws.feat2, feat_stamps(pl.feat_stamps, s, false), ws.kp.angle, ws.frame_long, ws.cand_cap};
+    const FeatPtrs P = feat_ptrs(ws, pl.feat_stamps ? feat_stamps.zeroed(s) : nullptr);
     if (pl.latency) hipLaunchKernelGGL(k_features<512>, dim3(pl.nframes), dim3(512), 0, s, P, pl.nframes, p.feature_size);
     else hipLaunchKernelGGL(k_features<128>, dim3(pl.nframes), dim3(128), 0, s, P, pl.nframes, p.feature_size);
     return hipGetLastError();
 }
 hipError_t launch_edge_refine(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, const DetectParams& p, hipStream_t s) {
     const int nframes = pl.nframes, refine_gx = pl.refine_gx, f8 = ((nframes + 7) / 8) * 8;
-    RefinePtrs P{frames, frame_stride, row_stride, ws.nfeat, ws.status, ws.feat1, ws.feat2, ws.refine_n0, ws.frame_long, p.channels == 3 ? 3 : 1};
+    const RefinePtrs P = refine_ptrs(frames, frame_stride, row_stride, ws, p);
     if (pl.refine == RefineForm::None) return hipSuccess;
     if (pl.refine == RefineForm::One) {  // one kernel, one launch: a block per quad -- the call is as long as its longest block, and looping blocks triple it
         hipLaunchKernelGGL(k_edge_refine<0>, dim3(CTAG_MAX_FEATURES * 2, nframes), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, 0);
@@ -1790,10 +1770,16 @@ hipError_t launch_edge_refine(const ChunkPlan& pl, const uint8_t* frames, ptrdif
     return hipGetLastError();
 }
 hipError_t launch_markers(const ChunkPlan& pl, const Workspace& ws, const DetectParams& p, ctag_frame_result* out, const PendingCtx& pend, hipStream_t s) {
-    MarkerPtrs P{ws.nfeat, ws.status, ws.frame_flags, ws.feat2, p.dict, ws.premarkers, out, feat_stamps(pl.feat_stamps, s, false), p.dict_pos, ws.kp, pend, ws.big ? 1 : 0};
+    const MarkerPtrs P = marker_ptrs(ws, p, out, pend, pl.feat_stamps ? feat_stamps.d : nullptr);
     if (pl.latency) hipLaunchKernelGGL(k_markers<8>, dim3(pl.nframes), dim3(512), 0, s, P, pl.nframes, p.feature_size, p.dict_rows, p.dict_cols);
     else hipLaunchKernelGGL(k_markers<1>, dim3(pl.nframes), dim3(64), 0, s, P, pl.nframes, p.feature_size, p.dict_rows, p.dict_cols);
-    (void)feat_stamps(pl.feat_stamps, s, true);
+    if (pl.feat_stamps) {
+        unsigned long long h[25];
+        feat_stamps.read(s, h, 25);
+        fprintf(stderr, "[k_features ticks] compact %llu derive %llu pairs %llu greedy %llu organise %llu obtain %llu\n", h[0], h[1], h[2], h[3], h[4], h[5]);
+        fprintf(stderr, "[k_markers ticks] load %llu pairs %llu union %llu sort %llu ids %llu carry+pre %llu | code %llu coverage %llu pick+store %llu\n", h[16], h[17], h[18],
+                h[19], h[20], h[21], h[22], h[23], h[24]);
+    }
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 // that the reference accumulates sequentially is accumulated in the same order so results are bit-identical to the oracle.
 #include "ctag_internal.h"
 #include "ctag_math.h"
+#include "ctag_wave.h"
 #include <cstdio>
 #include <type_traits>
 #include <cstdlib>
@@ -56,6 +57,18 @@ struct QuadPtrs {
     const uint64_t* mask;             // the fused sweep's threshold mask (1 bit per half-size pixel, rows of mask_words 64-bit words), else null: k_silhouette_mask
     int mask_words;
 };
+static QuadPtrs quad_ptrs(const ChunkPlan& pl, const Workspace& ws, unsigned long long* stamps) {
+    QuadPtrs P{};
+    P.labels = ws.labels, P.tile_base = ws.tile_base, P.root_of = ws.root_of, P.ncand = ws.ncand, P.cand = ws.cand, P.quads = ws.quads, P.frame_flags = ws.frame_flags;
+    P.line_count = ws.line_count, P.clp_used = ws.clp_used, P.cl_pool = ws.cl_pool, P.line_desc = ws.line_desc, P.line_sorted = ws.line_sorted, P.line_long = ws.line_long;
+    P.line_fit = ws.line_fit, P.cand_aux = ws.cand_aux, P.pick_table = ws.pick_table, P.pick_table16 = ws.pick_table16;
+    P.pool_tile = ws.pool_tile, P.member_head = ws.member_head, P.member_next = ws.member_next;
+    P.npacks = ws.npacks, P.packs = ws.packs, P.pack_order = ws.pack_order, P.stamps = stamps;
+    P.thr_line = ws.kp.thr_line, P.thr_expand = ws.kp.thr_expand, P.rac = ws.kp.rac, P.c2_far = ws.kp.c2_far, P.c2_near = ws.kp.c2_near, P.expand_eps = ws.kp.expand_eps;
+    P.cand_cap = ws.cand_cap, P.line_cap = ws.line_cap, P.cl_cap = ws.cl_cap;
+    P.mask = pl.fused ? reinterpret_cast<const uint64_t*>(ws.half) : nullptr, P.mask_words = ws.g.hcols >> 6;  // the fused sweep's threshold mask
+    return P;
+}
 
 __device__ __forceinline__ uint32_t pack_xy(int x, int y) { return (uint32_t)x | ((uint32_t)y << 16); }
 __device__ __forceinline__ int ux(uint32_t p) { return (int)(p & 0xffffu); }
@@ -77,17 +90,6 @@ __device__ __forceinline__ void moments_to_line(double x, double y, double x2, d
     line[1] = (float)sn;
     line[2] = (float)x;
     line[3] = (float)y;
-}
-
-// determinant + solve for 2x2 CV_32F [SURVEY App. A.7]
-__device__ __forceinline__ bool solve2x2(float a00, float a01, float a10, float a11, float b0, float b1, float& x0, float& x1) {
-    double d = (double)a00 * a11 - (double)a01 * a10;
-    if (d == 0.) return false;
-    d = 1. / d;
-    const float t = (float)(((double)b0 * a11 - (double)b1 * a01) * d);
-    x1 = (float)(((double)b1 * a00 - (double)b0 * a10) * d);
-    x0 = t;
-    return true;
 }
 
 // cv::RNG (multiply-with-carry) as fitLine2D seeds it: RNG rng((uint64)-1)
@@ -369,18 +371,6 @@ __host__ __device__ __forceinline__ bool pack_big(int x_min, int w, int h, int b
            (scan_words < 0 && mask_scan_need(w, h) > -scan_words);
 }
 
-// packed 16-bit minimum (v_pk_min_u16)
-typedef unsigned short ctag_qus2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t q_pk_min_u16(uint32_t a, uint32_t b) {
-    ctag_qus2 x, y;
-    __builtin_memcpy(&x, &a, 4);
-    __builtin_memcpy(&y, &b, 4);
-    const ctag_qus2 r = __builtin_elementwise_min(x, y);
-    uint32_t o;
-    __builtin_memcpy(&o, &r, 4);
-    return o;
-}
-
 struct CornerPre {
     float x, y, dis, ang;
 };
@@ -526,13 +516,7 @@ __global__ __launch_bounds__(1024) void k_pack(QuadPtrs P, int nframes, int max_
     if (scan_words < 0) slot_prefix(nc - nbig, [&](int r) { return (int)s_ord[r]; });
 }
 
-// wave-level ordering point for the 8-lane sub-groups (no s_barrier: the sub-groups of a wave run in lockstep;
-// this only stops the compiler from moving LDS accesses across it)
-#define SG_SYNC()                                              \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-    } while (0)
+// (the 8-lane sub-groups of a wave run in lockstep: their ordering point is wave_fence, ctag_wave.h -- no barrier)
 
 #ifndef CTAG_EXPAND_INLINE
 #define CTAG_EXPAND_INLINE __forceinline__
@@ -585,82 +569,7 @@ __device__ __forceinline__ ALine approx_line(long long sx, long long sy, long lo
 // is then tested against the line of step t-1 -- by the filtered predicate above, by the reference's own fit where that is not
 // decisive -- exactly as the sequential loop does, and the prefix up to the first event (distance test fails, `left == right`,
 // or every point used) is committed.  Returns nl / nr = points added on the left / right side.  All lanes return the same values.
-// lane i <- lane i - D within its row of 16 lanes (v_mov_b32 with DPP row_shr: one vector instruction, no LDS crossbar round trip); lanes without a
-// source get 0.  The 8-lane sub-groups are halves of such rows: the lanes that would read across a sub-group's edge are the ones that ignore the value.
-template <int D>
-__device__ __forceinline__ int dpp_shr(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, 0x110 + D, 0xf, 0xf, false);
-}
-template <int D>
-__device__ __forceinline__ double dpp_shr(double v) {
-    return __hiloint2double(dpp_shr<D>(__double2hiint(v)), dpp_shr<D>(__double2loint(v)));
-}
-template <int D>
-__device__ __forceinline__ float dpp_shr(float v) {
-    return __int_as_float(dpp_shr<D>(__float_as_int(v)));
-}
-// All-reduce over a sub-group of 8 lanes or over the wave, without the LDS crossbar: lane ^ 1 and lane ^ 2 by DPP quad permutes, the other quad of
-// the 8 lanes by row_half_mirror (lane i <- 7 - i), the other half of a row of 16 by row_mirror, and the wave's four rows by four v_readlane.  The
-// operations are exact (integer sums) or a total order (best distance, ties by index), so the order of combination does not matter.  (A
-// __shfl_xor is a ds_bpermute_b32: address arithmetic, the instruction and ~100 cycles before the value can be used -- per step, and a wave's
-// reduction has six; the split loop of the RDP runs one per round.)
-template <int CTRL>
-__device__ __forceinline__ int dpp_mov(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __int_as_float(dpp_mov<CTRL>(__float_as_int(v)));
-}
-template <int CTRL>
-__device__ __forceinline__ long long dpp_mov(long long v) {
-    const unsigned lo = (unsigned)dpp_mov<CTRL>((int)(unsigned)((unsigned long long)v & 0xffffffffull)), hi = (unsigned)dpp_mov<CTRL>((int)(unsigned)((unsigned long long)v >> 32));
-    return (long long)((unsigned long long)lo | ((unsigned long long)hi << 32));
-}
-__device__ __forceinline__ long long readlane_ll(long long v, int l) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v & 0xffffffffull), l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), l);
-    return (long long)((unsigned long long)lo | ((unsigned long long)hi << 32));
-}
-constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppRowMirror = 0x140;
-template <int SG, class T>
-__device__ __forceinline__ T sg_sum(T v) {  // T: int, long long
-    v += dpp_mov<kDppXor1>(v);
-    v += dpp_mov<kDppXor2>(v);
-    v += dpp_mov<kDppHalfMirror>(v);
-    if constexpr (SG == 64) {
-        v += dpp_mov<kDppRowMirror>(v);
-        if constexpr (sizeof(T) == 8) v = (T)(readlane_ll((long long)v, 0) + readlane_ll((long long)v, 16) + readlane_ll((long long)v, 32) + readlane_ll((long long)v, 48));
-        else v = (T)(__builtin_amdgcn_readlane((int)v, 0) + __builtin_amdgcn_readlane((int)v, 16) + __builtin_amdgcn_readlane((int)v, 32) + __builtin_amdgcn_readlane((int)v, 48));
-    }
-    return v;
-}
-// the best (d, i) pair of the sub-group under `better(od, oi, d, i)` ("the other pair beats mine"): every lane ends with the same pair
-template <int SG, class Better>
-__device__ __forceinline__ void sg_best(float& bd, int& bi, Better better) {
-    auto step = [&](float od, int oi) {
-        if (better(od, oi, bd, bi)) {
-            bd = od;
-            bi = oi;
-        }
-    };
-    step(dpp_mov<kDppXor1>(bd), dpp_mov<kDppXor1>(bi));
-    step(dpp_mov<kDppXor2>(bd), dpp_mov<kDppXor2>(bi));
-    step(dpp_mov<kDppHalfMirror>(bd), dpp_mov<kDppHalfMirror>(bi));
-    if constexpr (SG == 64) {
-        step(dpp_mov<kDppRowMirror>(bd), dpp_mov<kDppRowMirror>(bi));
-        float rd[4];
-        int ri[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            rd[r] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bd), 16 * r));
-            ri[r] = __builtin_amdgcn_readlane(bi, 16 * r);
-        }
-        bd = rd[0];
-        bi = ri[0];
-#pragma unroll
-        for (int r = 1; r < 4; r++) step(rd[r], ri[r]);
-    }
-}
+// (the lane moves and reductions -- dpp_shr, dpp_mov, sg_sum, sg_best -- are ctag_wave.h's)
 // RED / rl: lanes (and this lane's index among them) that add up the moments of the initial span.  The whole-wave build speculates over its first
 // EIGHT lanes only (SG = 8, RED = 64; the other lanes repeat them): an edge rarely grows by more than a few points, and a 64-step round paid six
 // prefix-scan steps, integer divisions for the wrapped indices and a line estimate per lane for steps that were thrown away.
@@ -1266,7 +1175,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             lef[y] = 0xffffffffu;
             rig[y] = 0u;
         }
-        SG_SYNC();
+        wave_fence();
         constexpr int kChunk = 8 * SG;  // columns a sub-group covers with one 16-byte load per lane
         if constexpr (SG == 64) {
             // Whole-wave scan: 512 columns per pass, eight label rows requested together (unconditional loads from clamped
@@ -1483,13 +1392,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             if (bitmap) scan(std::false_type{});
             if (!bitmap || __ballot(redo)) {
                 if (bitmap) {  // start over
-                    SG_SYNC();
+                    wave_fence();
                     for (int x = sl; x < w + 2; x += SG) tb[x] = 0u;
                     for (int y = sl; y < h; y += SG) {
                         lef[y] = 0xffffffffu;
                         rig[y] = 0u;
                     }
-                    SG_SYNC();
+                    wave_fence();
                 }
                 scan(std::true_type{});
             }
@@ -1578,7 +1487,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                 uint32_t f[4];
 #pragma unroll
                 for (int d = 0; d < 4; d++) {
-                    const uint32_t na = q_pk_min_u16(wv[d] ^ LA2, 0x00010001u), nb = q_pk_min_u16(wv[d] ^ LB2, 0x00010001u);  // 1 per half that differs
+                    const uint32_t na = pk_min_u16(wv[d] ^ LA2, 0x00010001u), nb = pk_min_u16(wv[d] ^ LB2, 0x00010001u);  // 1 per half that differs
                     f[d] = (na & nb) ^ 0x00010001u;  // 1 per half that matches a label
                     M[d] = __umul24(f[d], 0xffffu);
                 }
@@ -1617,8 +1526,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             };
             // Unconditional loads from clamped addresses, the lanes / rows outside the box zeroed by a select: a load inside a branch makes the
             // compiler wait for EVERY load in flight where the branch rejoins, and the rows "in flight" arrived one at a time
-            // (Round 5, from the ISA: `ld_ok ? v : 0` behind the load was enough for the compiler to put the load back INSIDE a branch on ld_ok -- with s_waitcnt
-            // vmcnt(0) in front of it: a row was awaited before the next was requested, and the scan, 48 % of this kernel's phase clocks, ran at the latency of one
+            // (Round 5, from the ISA: `ld_ok ? v : 0` behind the load was enough for the compiler to put the load back INSIDE a branch on ld_ok -- with a wait
+            // for all vector memory in front of it: a row was awaited before the next was requested, and the scan, 48 % of this kernel's phase clocks, ran at the latency of one
             // L2 round trip per row.  Now nothing selects on ld_ok behind the load, an empty asm at the row's consumption reads a word of it -- so the load stays
             // above it, outside every branch --, and a lane outside the box is neutralised where its tile's labels are looked up: it matches no label.)
             const int gx0 = ld_ok ? gxf : (x_min & ~7), gx1 = ld_ok1 ? gxf + kChunk : (x_min & ~7);
@@ -1706,7 +1615,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
         }
         stamp(7);
         {
-            SG_SYNC();  // row extents (LDS atomics) complete
+            wave_fence();  // row extents (LDS atomics) complete
             for (int y = sl; y < h + 2; y += SG) {
                 uint32_t v = 0u;
                 if (y >= 1 && y <= h) {
@@ -1716,7 +1625,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                 lr[y] = v;  // lr aliases nothing that is still live: lef/rig sit in bufA/bufB
             }
         }
-        SG_SYNC();
+        wave_fence();
         }  // the scan
         if constexpr (PHASE == 3) {
             // the component's cluster space (what the packed builds reserve after their traversal) and, in it for now, the silhouette:
@@ -1751,7 +1660,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             const uint32_t* slot = P.cl_pool + (size_t)frame * P.cl_cap + p0;
             for (int x = sl; x < w + 2; x += SG) tb[x] = slot[x];
             for (int y = sl; y < h + 2; y += SG) lr[y] = slot[w + 2 + y];
-            SG_SYNC();
+            wave_fence();
         }
         // distinct silhouette pixels: two per column (one where top == bottom) plus the row ends that head no column list.  The
         // traversal below visits every listed pixel at most once, so once it has appended this many points nothing is left to
@@ -1790,7 +1699,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                     n = 1;
                 }
             }
-            SG_SYNC();
+            wave_fence();
             if (sp >= 0 && sl == 0) {
                 bufA[0] = pack_xy(x_min, fy + y_min);
                 // clear the start pixel from every list it heads
@@ -1803,7 +1712,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                 if ((r >> 16) == 2u) r &= 0xffffu;
                 lr[fy + 1] = r;
             }
-            SG_SYNC();
+            wave_fence();
             if constexpr (SG == 64) {
                 // a hit: lane `hl` of the sub-group holds the list words (c, r) of the hit pixel (nx, ny), neighbour hl & 7 of frame (fx, fy)
                 auto take_hit = [&](int hl, int nx, int ny, uint32_t c, uint32_t r) {
@@ -1822,7 +1731,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                         // the current frame moves to the hit pixel and resumes at j+1 (B7); it becomes the frame below the top
                         bufB[sp] = (uint32_t)hx | ((uint32_t)hy << 14) | ((uint32_t)(j + 1) << 28);  // sp <= n: a frame per appended point at most
                     }
-                    SG_SYNC();
+                    wave_fence();
                     n++;
                     fx = hx;
                     fy = hy;
@@ -1905,7 +1814,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                         // the current frame moves to the hit pixel and resumes at j+1 (B7); it becomes the frame below the top
                         if (sp <= C) bufB[sp] = (uint32_t)hx | ((uint32_t)hy << 14) | ((uint32_t)(j + 1) << 28);
                     }
-                    SG_SYNC();
+                    wave_fence();
                     n++;
                     fx = hx;
                     fy = hy;
@@ -1929,7 +1838,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             }
             continue;
         }
-        SG_SYNC();
+        wave_fence();
         stamp(1);
         // ---- P3: boundary centroid (:250-256), nearest point (:259-263), rotation (:264-275)
         {
@@ -1959,7 +1868,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                 bufB[k] = bufA[src];
             }
         }
-        SG_SYNC();
+        wave_fence();
         stamp(2);
         if constexpr (!PRESCAN) {
         // cluster space in the frame's pool (upper bound; the clusters are written straight to global memory)
@@ -1997,7 +1906,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             acy = aux->acy;
             const uint32_t* slot = P.cl_pool + (size_t)frame * P.cl_cap + p0;
             for (int k = sl; k < n; k += SG) bufB[k] = slot[k];
-            SG_SYNC();
+            wave_fence();
         }
         uint32_t* CLg = P.cl_pool + (size_t)frame * P.cl_cap + p0;
         // ---- P4: extended RDP (:278-349), uniform control flow inside the sub-group
@@ -2105,7 +2014,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                     const int mid = a - b - 1;
                     for (int k = sl; k < new_n; k += SG) Wn[k] = (k < mid) ? W[b + 1 + k] : W[n - 1];
                 }
-                SG_SYNC();
+                wave_fence();
                 const int back = wrap ? 0 : a;
                 cl_off[cnt_b + 1] = min(offc + m, C + 64);
                 cnt_b++;
@@ -2776,7 +2685,7 @@ __device__ __forceinline__ void quad_final_one(const QuadPtrs& P, const FrameGeo
                 CornerPre c{0.f, 0.f, 0.f, 0.f};
                 bool ok = false;
                 if (LANES == 1 || sub == q) {
-                    ok = solve2x2(a00, a01, a10, a11, b0, b1, c.x, c.y);
+                    ok = ctm::solve2x2(a00, a01, a10, a11, b0, b1, c.x, c.y);
                     if (ok) {
                         c.dis = ctm::sqrt32((c.x - acx) * (c.x - acx) + (c.y - acy) * (c.y - acy));
                         c.ang = (float)(ctm::atan2_32(c.y - acy, c.x - acx) * 180 / 3.1415926535897932384626433832795);
@@ -2919,15 +2828,7 @@ static void launch_quad_edges(const ChunkPlan& pl, const QuadPtrs& P, const Fram
         hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWords, CTAG_PACK_WAVES, false, REF>), grid, dim3(64), 0, s, P, g, nframes, 0);
     }
     if (mid) (void)hipEventRecord(mid, s);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = dev < 0 || dev >= 64 ? 0 : dev;
-    static bool have[64] = {false};
-    if (!have[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quad_edges_packed<64, kWaveWordsMax, 1, true, REF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kWaveWordsMax * 4);
-        have[dev] = true;
-    }
+    ensure_dynamic_lds(reinterpret_cast<const void*>(&k_quad_edges_packed<64, kWaveWordsMax, 1, true, REF>), kWaveWordsMax * 4);
     hipLaunchKernelGGL((k_quad_edges_packed<64, kWaveWords, 1, false, REF>), dim3(nframes, pl.big_cols), dim3(64), 0, sb, P, g, nframes, 0);
     hipLaunchKernelGGL((k_quad_edges_packed<64, kWaveWordsMax, 1, true, REF>), dim3(nframes, pl.big_max_gx), dim3(64), kWaveWordsMax * 4, s_max, P, g, nframes, kWaveWords);
 }
@@ -2938,17 +2839,8 @@ hipError_t launch_quads(const ChunkPlan& pl, const Workspace& ws, hipStream_t s,
     auto mark = [&]() {
         if (ev5) (void)hipEventRecord(ev5[evi++], s);
     };
-    QuadPtrs P{ws.labels, ws.tile_base, ws.root_of, ws.ncand, ws.cand, ws.quads, ws.frame_flags,
-               ws.line_count, ws.clp_used, ws.cl_pool, ws.line_desc, ws.line_sorted, ws.line_long, ws.line_fit, ws.cand_aux, ws.pick_table, ws.pick_table16, ws.pool_tile, ws.member_head, ws.member_next, ws.npacks, ws.packs, ws.pack_order, nullptr, ws.kp.thr_line, ws.kp.thr_expand, ws.kp.rac, ws.kp.c2_far, ws.kp.c2_near,
-               ws.cand_cap, ws.line_cap, ws.cl_cap, ws.kp.expand_eps};
-    static unsigned long long* d_stamps = nullptr;
-    if (pl.quad_stamps) {
-        if (!d_stamps) (void)hipMalloc(reinterpret_cast<void**>(&d_stamps), 32 * 8);
-        (void)hipMemsetAsync(d_stamps, 0, 32 * 8, s);
-        P.stamps = d_stamps;
-    }
-    P.mask = pl.fused ? reinterpret_cast<const uint64_t*>(ws.half) : nullptr;  // the fused sweep's threshold mask
-    P.mask_words = ws.g.hcols >> 6;
+    static Stamps stamps;
+    const QuadPtrs P = quad_ptrs(pl, ws, pl.quad_stamps ? stamps.zeroed(s) : nullptr);
     const int pack_words = pl.small_cfg ? kPackWordsSmall : kPackWords;
     const int scan_words = pl.mask_scan ? -(pl.small_cfg ? kMaskScanWords : kMaskScanWordsLarge) : pl.prescan ? kScanWords : 0;
     hipLaunchKernelGGL(k_pack, dim3(nframes), dim3(pl.latency ? 1024 : 64), 0, s, P, nframes, pl.pack_max, pl.big_points, pack_words, scan_words);
@@ -2981,8 +2873,7 @@ hipError_t launch_quads(const ChunkPlan& pl, const Workspace& ws, hipStream_t s,
     else hipLaunchKernelGGL(k_quad_final<1>, dim3(std::min(ws.cand_cap, kLdsCand) / 64, nframes), dim3(64), 0, s, P, ws.g, nframes);
     if (pl.quad_stamps) {
         unsigned long long h[32];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost);
+        stamps.read(s, h, 32);
         if (h[16] | h[17] | h[18] | h[19])
             fprintf(stderr, "[whole-wave rdp ticks] corner scan %llu split rounds %llu expand_line %llu clusters + erase %llu\n", h[16], h[17], h[18], h[19]),
             fprintf(stderr, "[whole-wave expand_line] initial sums %llu ticks, %llu rounds, %llu of them through the exact fits\n", h[20], h[21], h[22]);

@@ -7,6 +7,7 @@
 // union-find over row runs in LDS, one global atomic union-find only for the tile seams.
 // Frames are mapped to XCDs (blockIdx % 8) so a frame's intermediates stay in one XCD's L2.
 #include "ctag_internal.h"
+#include "ctag_wave.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -74,8 +75,8 @@ __device__ __forceinline__ Raw18 load_row(const uint8_t* __restrict__ rowp, int 
         }
     }
     // the neighbour lanes' edge pixels by DPP wave shifts (lane 0 / lane 63 get 0 and are replaced below), not by the LDS crossbar
-    uint32_t left = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(r.w3 >> 24), 0x138, 0xf, 0xf, false);       // wave_shr:1
-    uint32_t right2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(r.w0 & 0xffffu), 0x130, 0xf, 0xf, false);  // wave_shl:1
+    uint32_t left = wave_from_prev(r.w3 >> 24);
+    uint32_t right2 = wave_from_next(r.w0 & 0xffffu);
     if (active) {
         if (lane == 0) left = rowp[max(x0 - 1, 0)];
         if (lane == 63 || !full || x0 + 32 > cols) {
@@ -159,6 +160,11 @@ struct ZeroList {
     int32_t* one;
     int n;  // frames (<= 256); 0: nothing to zero
 };
+static ZeroList zero_list(const ChunkPlan& pl, const Workspace& ws) {
+    ZeroList Z{};  // n = 0: nothing to zero
+    if (pl.dec_zero_list) Z.a = ws.frame_ncomp, Z.b = ws.frame_flags, Z.c = ws.line_count, Z.d = ws.clp_used, Z.one = ws.ovf_count, Z.n = pl.nframes;
+    return Z;
+}
 template <bool ALIGNED, int BAND, bool HAS_TAIL>  // BAND: compile-time band height (0 = run-time band_rows_rt); HAS_TAIL: hcols % 8 != 0
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_decimate(const uint8_t* __restrict__ frames, ptrdiff_t frame_stride, ptrdiff_t row_stride,
                                                   uint8_t* __restrict__ half, FrameGeom g, int nframes, int xblocks, int yblocks, int band_rows_rt, ZeroList Z) {
@@ -247,8 +253,8 @@ __device__ __forceinline__ Raw34 load_row_wide(const uint8_t* __restrict__ rowp,
         r.w[0] = a.x, r.w[1] = a.y, r.w[2] = a.z, r.w[3] = a.w;
         r.w[4] = b.x, r.w[5] = b.y, r.w[6] = b.z, r.w[7] = b.w;
     }
-    uint32_t left = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(r.w[7] >> 24), 0x138, 0xf, 0xf, false);       // wave_shr:1
-    uint32_t right2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(r.w[0] & 0xffffu), 0x130, 0xf, 0xf, false);  // wave_shl:1
+    uint32_t left = wave_from_prev(r.w[7] >> 24);
+    uint32_t right2 = wave_from_next(r.w[0] & 0xffffu);
     if (active) {
         if (lane == 0) left = x0 > 0 ? (uint32_t)rowp[x0 - 1] : (r.w[0] & 0xffu);  // index clamp at the image border
         if (lane == 63 || x0 + 32 >= cols)
@@ -400,7 +406,7 @@ hipError_t launch_decimate(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t
                            nframes, ws.rz_xofs, ws.rz_alpha, ws.rz_yofs, ws.rz_beta);
         return hipGetLastError();
     }
-    const ZeroList Z = pl.dec_zero_list ? ZeroList{ws.frame_ncomp, ws.frame_flags, ws.line_count, ws.clp_used, ws.ovf_count, nframes} : ZeroList{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    const ZeroList Z = zero_list(pl, ws);
     const int xblocks = pl.dec_xblocks, yblocks = pl.dec_yblocks, band_rows = pl.dec_band_rows;
     const int grid = grid_for(nframes, xblocks * yblocks);
 #define CTAG_DEC_LAUNCH(AL, B, TL)                                                                                                         \
@@ -410,7 +416,7 @@ hipError_t launch_decimate(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t
         case DecForm::Wide:  // a lane owns 16 output pixels: a wave spans 1024 half-res columns
             hipLaunchKernelGGL((k_decimate_wide<135>), dim3(grid), dim3(256), 0, s, frames, frame_stride, row_stride, ws.half, g, nframes, xblocks, yblocks, band_rows);
             break;
-        case DecForm::Banded135: CTAG_DEC_LAUNCH(true, 135, false); break;  // 1080p and 4K frames
+        case DecForm::Banded135: CTAG_DEC_LAUNCH(true, 135, false); break;  // 135-row bands of a half width that is no multiple of 16 (1080p and 4K take Wide: plan_chunk)
         case DecForm::Banded: CTAG_DEC_LAUNCH(true, 0, true); break;
         default: CTAG_DEC_LAUNCH(false, 0, true); break;
     }
@@ -452,10 +458,15 @@ struct SweepPtrs {
     size_t pool_stride;    // bytes between consecutive pool arrays (parent, root_of, area, xmin, ymin, xmax, ymax, key, pool_tile, member_head, member_next)
 };
 static SweepPtrs sweep_ptrs(const Workspace& ws) {
-    return SweepPtrs{ws.half, ws.half, ws.labels, ws.tile_base, ws.tile_dirty, ws.frame_ncomp, ws.frame_flags, ws.parent, ws.root_of,
-                     ws.area, ws.xmin, ws.ymin, ws.xmax, ws.ymax, ws.key, ws.pool_tile, ws.member_head, ws.member_next, ws.ncand, ws.nroots, ws.cand, ws.cand_cap,
-                     reinterpret_cast<int2*>(ws.cand_aux), ws.ovf_count, ws.ovf_list, nullptr,
-                     (size_t)(reinterpret_cast<const char*>(ws.root_of) - reinterpret_cast<const char*>(ws.parent))};
+    SweepPtrs P{};  // (stamps stays null: launch_threshold_ccl sets it under CTAG_CCL_STAMPS)
+    P.half = ws.half, P.mask = ws.half, P.labels = ws.labels, P.tile_base = ws.tile_base, P.tile_dirty = ws.tile_dirty;
+    P.frame_ncomp = ws.frame_ncomp, P.frame_flags = ws.frame_flags;
+    P.parent = ws.parent, P.root_of = ws.root_of, P.area = ws.area, P.xmin = ws.xmin, P.ymin = ws.ymin, P.xmax = ws.xmax, P.ymax = ws.ymax, P.key = ws.key;
+    P.pool_tile = ws.pool_tile, P.member_head = ws.member_head, P.member_next = ws.member_next;
+    P.ncand = ws.ncand, P.nroots = ws.nroots, P.cand = ws.cand, P.cand_cap = ws.cand_cap, P.cand_scratch = reinterpret_cast<int2*>(ws.cand_aux);
+    P.ovf_count = ws.ovf_count, P.ovf_list = ws.ovf_list;
+    P.pool_stride = (size_t)(reinterpret_cast<const char*>(ws.root_of) - reinterpret_cast<const char*>(ws.parent));
+    return P;
 }
 
 struct CclLdsLayout {
@@ -526,25 +537,15 @@ __device__ __forceinline__ uint64_t mask_le(int b) { return b >= 63 ? ~0ull : ((
 // set bits of x at positions <= b (0 <= b <= 63): the higher ones are shifted out -- a shift and the count instead of building the mask first
 __device__ __forceinline__ int popc_le(uint64_t x, int b) { return __popcll(x << (63 - b)); }
 
-// Barrier for k_threshold_ccl: its phases exchange data through LDS only, so the barrier waits for LDS traffic
-// (lgkmcnt) and NOT for vector memory (vmcnt) -- __syncthreads() would drain the next tile's prefetch loads and the
-// label stores at every phase boundary.
-#define CCL_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+// k_threshold_ccl's phases exchange data through LDS only: their barrier is lds_barrier (ctag_wave.h), which leaves the next tile's prefetch loads and the
+// label stores in flight.
 constexpr int kCclThreads = 256;  // threads per 320x30 tile: the phases are short dependent chains, so more waves per tile
                                   // shorten every barrier-to-barrier critical path and fill the CU at the same LDS footprint
 __device__ __forceinline__ int block_excl_scan(int v, int* scratch, int& total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    // inclusive scan of the wave by DPP: shifts by 1, 2, 4, 8 inside the rows of 16 lanes (a lane without a source adds 0), then lane 15 of every even
-    // row into the odd row behind it and lane 31 into rows 2 and 3 -- six vector instructions instead of six ds_bpermute round trips
-    int inc = v;
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);   // row_shr:1
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);   // row_shr:2
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);   // row_shr:4
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, true);   // row_shr:8
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+    const int inc = wave_incl_scan(v);
     if (lane == 63) scratch[w] = inc;
-    CCL_SYNC();
+    lds_barrier();
     int base = 0;
     total = 0;
 #pragma unroll
@@ -552,7 +553,7 @@ __device__ __forceinline__ int block_excl_scan(int v, int* scratch, int& total) 
         if (i < w) base += scratch[i];
         total += scratch[i];
     }
-    CCL_SYNC();
+    lds_barrier();
     return base + inc - v;
 }
 
@@ -642,26 +643,7 @@ __device__ __forceinline__ TileRegion tile_region(int frame, int tile, const Fra
     return t;
 }
 
-// packed 16-bit min / max (v_pk_min_u16 / v_pk_max_u16): bytes are split into even / odd halves for them
-typedef unsigned short ctag_us2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
-    ctag_us2 x, y;
-    __builtin_memcpy(&x, &a, 4);
-    __builtin_memcpy(&y, &b, 4);
-    const ctag_us2 r = __builtin_elementwise_min(x, y);
-    uint32_t o;
-    __builtin_memcpy(&o, &r, 4);
-    return o;
-}
-__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
-    ctag_us2 x, y;
-    __builtin_memcpy(&x, &a, 4);
-    __builtin_memcpy(&y, &b, 4);
-    const ctag_us2 r = __builtin_elementwise_max(x, y);
-    uint32_t o;
-    __builtin_memcpy(&o, &r, 4);
-    return o;
-}
+// (the column extrema below go through pk_min_u16 / pk_max_u16, ctag_wave.h: bytes are split into even / odd halves for them)
 // four pixel < threshold tests on packed bytes -> 4 bits.  T <= 77 < 128: with the pixel's top bit handled separately the
 // per-byte subtract (0x80 | low7) - T never borrows across bytes and its bit 7 says low7 >= T; one multiply gathers the bits.
 __device__ __forceinline__ uint32_t lt4_bytes(uint32_t u, uint32_t t) {
@@ -735,9 +717,6 @@ __device__ __forceinline__ Raw32 gray_row(const RawSrc<CH>& r) {
     for (int i = 0; i < 8; i++) g.w[i] = CH == 3 ? gray4_of(r.w[(3 * i) % (8 * CH)], r.w[(3 * i + 1) % (8 * CH)], r.w[(3 * i + 2) % (8 * CH)]) : r.w[i % (8 * CH)];
     return g;
 }
-// lane i <- lane i - 1 / lane i + 1 across the whole wave (DPP wave_shr:1 / wave_shl:1)
-__device__ __forceinline__ uint32_t wave_from_prev(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ uint32_t wave_from_next(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, false); }
 // left_edge: lane 0 is at the image's left border; right_edge: lane 59 at its right border (else lanes 61 / 60 hold the pixels beyond)
 __device__ __forceinline__ void hpass_fuse(const Raw32& r, int lane, bool left_edge, bool right_edge, uint32_t q[8], int last_lane = kFuseLanes - 1) {
     Raw34 t;
@@ -824,8 +803,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(CH =
         mxE[k] = mxO[k] = 0u;
     }
     int rit = 0, slot = ys % 10;
-    // one wave, LDS only: its accesses are served in order, so a wait for LDS (NOT for the source rows in flight) orders them
-    auto wave_sync = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
+    // (the wave's phases below are ordered by lds_wait, ctag_wave.h: one wave, LDS only, and the source rows stay in flight)
     auto tile_row_done = [&](int gt) __attribute__((always_inline)) {  // the five rows of threshold-tile row gt are in the ring, their column extrema in registers
         if (active) {
             const uint4 mn = make_uint4(mnE[0] | (mnO[0] << 8), mnE[1] | (mnO[1] << 8), mnE[2] | (mnO[2] << 8), mnE[3] | (mnO[3] << 8));
@@ -839,7 +817,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(CH =
             mnE[k] = mnO[k] = 0x00ff00ffu;
             mxE[k] = mxO[k] = 0u;
         }
-        wave_sync();
+        lds_wait();
         const int r3 = gt % 3;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -852,7 +830,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(CH =
                 S.ext[r3][j] = (uint16_t)(mn | (mx << 8));
             }
         }
-        wave_sync();
+        lds_wait();
     };
     auto emit_tile_row = [&](int e) __attribute__((always_inline)) {  // tile row e's pixels are in the ring and the tile extrema of rows e - 1, e, e + 1 (as far as they exist) in `ext`
         if (e < e_lo || e >= e_hi) return;  // wave-uniform
@@ -880,7 +858,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(CH =
                 S.tt[j] = (uint8_t)T;
             }
         }
-        wave_sync();
+        lds_wait();
         if (lane < nact) {
             const uint32_t T4 = (uint32_t)S.tt[j0] | ((uint32_t)S.tt[j0 + 1] << 8) | ((uint32_t)S.tt[j0 + 2] << 16) | ((uint32_t)S.tt[min(j0 + 3, kFuseTiles - 1)] << 24);
             // (mirrored wave: its row 5 e + r is row hrows - 1 - (5 e + r) of the frame)
@@ -1058,7 +1036,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
         const unsigned long long any = __ballot(m != 0ull);
         if (lane == 0) misc_s[12 + wave] = any != 0ull ? 1 : 0;
     }
-    CCL_SYNC();
+    lds_barrier();
     stamp(0);
     if ((misc_s[12] | misc_s[13] | misc_s[14] | misc_s[15]) == 0) {
         empty_tile();
@@ -1129,7 +1107,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
         const unsigned long long any = __ballot(dark);
         if (lane == 0) misc_s[12 + wave] = any != 0ull ? 1 : 0;
     }
-    CCL_SYNC();
+    lds_barrier();
     stamp(0);
     // ---- bright tile: the reference caps the threshold at 0.3 (T <= 77 for every threshold tile, 0 on the frame border),
     // so a tile whose pixels are all >= 77 has no foreground whatever its thresholds turn out to be: its labels are zero
@@ -1151,7 +1129,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
             ext_s[r * L.ec + c] = (uint16_t)(mn | (mx << 8));
         }
     }
-    CCL_SYNC();
+    lds_barrier();
     stamp(1);
     // ---- S3: 3x3 min-of-min / max-of-max for interior tiles, zero elsewhere (corner_detector.cpp:54-67, B1)
     {
@@ -1178,7 +1156,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
             for (int x = xa; x < xb; x++) thr_s[r * (kTileW + 8) + x] = (uint8_t)T;
         }
     }
-    CCL_SYNC();
+    lds_barrier();
     stamp(2);
     // ---- binary row masks (corner_detector.cpp:69-78) from the pixels still in registers
     {
@@ -1203,7 +1181,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
             }
         }
     }
-    CCL_SYNC();
+    lds_barrier();
     stamp(3);
   } else {
         // ---- S1: stage the half-res region in LDS (16-byte chunks, coalesced along rows)
@@ -1217,7 +1195,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
                 *reinterpret_cast<uint4*>(hr_s + (size_t)r * L.rp + c * 16) = v;
             }
         }
-        CCL_SYNC();
+        lds_barrier();
         stamp(0);
         // ---- S2: per-threshold-tile min / max (corner_detector.cpp:42-53)
         {
@@ -1238,7 +1216,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
                 ext_s[r * L.ec + c] = (uint16_t)(mn | (mx << 8));
             }
         }
-        CCL_SYNC();
+        lds_barrier();
         stamp(1);
         // ---- S3: 3x3 min-of-min / max-of-max for interior tiles, zero elsewhere (corner_detector.cpp:54-67, B1)
         {
@@ -1263,7 +1241,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
                 for (int x = xa; x < xb; x++) thr_s[r * (kTileW + 8) + x] = (uint8_t)T;
             }
         }
-        CCL_SYNC();
+        lds_barrier();
         stamp(2);
         // ---- S4: binary row masks (corner_detector.cpp:69-78), 8 pixels per thread.  pixel < T is evaluated on packed bytes:
         // T <= 77 < 128, so with the pixel's top bit handled separately the per-byte subtract (0x80 | low7) - T never borrows
@@ -1302,7 +1280,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
                 mask_b[i] = (uint8_t)bits;
             }
         }
-        CCL_SYNC();
+        lds_barrier();
         stamp(3);
   }
     // ---- S5: run starts, run numbering
@@ -1332,7 +1310,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
     };
     bool overflow = nruns > RUNCAP;
     for (int i = tid; i < min(nruns, RUNCAP); i += kCclThreads) parent_s[i] = (unsigned)i;
-    CCL_SYNC();
+    lds_barrier();
     auto runid = [&](int item, int b) -> int { return runbase_s[item] + popc_le(start_s[item], b) - 1; };
 
     stamp(4);
@@ -1363,7 +1341,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
             }
         }
     }
-    CCL_SYNC();
+    lds_barrier();
     stamp(5);
     // ---- S7/S8: flatten, compact roots into slots
     int nslots = 0;
@@ -1381,7 +1359,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
                 if (parent_s[i] == (unsigned)i) lab_s[i] = (uint16_t)(s++);
     }
     if (nslots > SLOTCAP) overflow = true;
-    CCL_SYNC();
+    lds_barrier();
     if (overflow) {  // block-uniform: the tile does not fit this pass
         hand_over();
         return;
@@ -1395,7 +1373,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
         const unsigned r = lds_find(parent_s, (unsigned)i);
         if (r != (unsigned)i) lab_s[i] = lab_s[r];
     }
-    CCL_SYNC();  // the statistics below overlay the run parents
+    lds_barrier();  // the statistics below overlay the run parents
     for (int i = tid; i < nslots; i += kCclThreads) {
         st_area[i] = 0;
         st_xmin[i] = 0x7fffffff;
@@ -1403,7 +1381,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
         st_rows[i] = 0u;
         st_key[i] = 0x7fffffff;
     }
-    CCL_SYNC();
+    lds_barrier();
     // pool entries for this tile.  The first pass cannot run out: it publishes at most SLOTCAP entries per tile and the pool
     // holds twice that for every tile (FrameGeom::pool_cap); the second pass takes what is left and fails the frame when
     // that is not enough (more than ~256 components per tile that are large or touch a tile border, frame-wide).  The
@@ -1445,7 +1423,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
     if (BIG) {
         // ---- cull: a component of fewer than 30 pixels that does not touch the tile border can neither pass the area filter
         // (corner_detector.cpp:88) nor merge with anything: it is not published (its pixels keep a private label)
-        CCL_SYNC();  // S9's LDS atomics are done
+        lds_barrier();  // S9's LDS atomics are done
         constexpr int per = (SLOTCAP + kCclThreads - 1) / kCclThreads;
         const int i0 = tid * per;
         auto keep = [&](int i) -> bool {
@@ -1465,10 +1443,10 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
                 pub += kp ? 1 : 0;
             }
         }
-        CCL_SYNC();
+        lds_barrier();
         for (int i = tid; i < nruns; i += kCclThreads) lab_s[i] = final_s[lab_s[i]];
         if (tid == 0) base_reg = reserve(npub);
-        CCL_SYNC();
+        lds_barrier();
     }
     // The reservation's result goes to LDS NOW, before the label stores are issued: the vector-memory counter is served in order, so the wait for a value
     // requested before the stores, taken after them, would be a wait for every label store of wave 0 as well.  (Round 5 moved it here on the suspicion that this
@@ -1526,7 +1504,7 @@ __device__ __forceinline__ void ccl_tile(unsigned char* smem, const SweepPtrs& P
     }
     stamp(8);
     // ---- S10: publish the tile's components in the frame pool
-    CCL_SYNC();  // misc_s[9] (the pool entries' base, stored before S11); also orders the S9 LDS atomics before the reads below
+    lds_barrier();  // misc_s[9] (the pool entries' base, stored before S11); also orders the S9 LDS atomics before the reads below
     const int base = misc_s[9];
     if (base < 0) {  // second pass only: the frame's pool is exhausted
         // S11 has stored this tile's labels: the dirty bits must say so although the tile publishes nothing (the frame is rerun through the
@@ -1612,46 +1590,30 @@ hipError_t launch_threshold_ccl(const ChunkPlan& pl, const Workspace& ws, hipStr
     const size_t lds = threshold_ccl_lds_bytes(g.tw);
     const int grid = grid_for(nframes, g.tiles_x * g.tiles_y);  // one 320x30 tile per block
     SweepPtrs P = sweep_ptrs(ws);
-    static unsigned long long* d_stamps = nullptr;
-    if (pl.ccl_stamps) {
-        if (!d_stamps) (void)hipMalloc(reinterpret_cast<void**>(&d_stamps), 16 * 8);
-        (void)hipMemsetAsync(d_stamps, 0, 16 * 8, s);
-        P.stamps = d_stamps;
-    }
+    static Stamps stamps;
+    if (pl.ccl_stamps) P.stamps = stamps.zeroed(s);
     const size_t lds_big = ccl_layout(g.tw, kRunCapBig, kSlotCapBig, true).total;
     const int grid_big = 1024;  // persistent: loops over the overflow list
-    // kernels that ask for more than 64 KB of dynamic LDS need the attribute raised (per device; it only ever grows)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = dev < 0 || dev >= 64 ? 0 : dev;
-    auto want_lds = [dev](const void* fn, size_t bytes, size_t* have) {
-        if (bytes > 64 * 1024 && bytes > have[dev]) {
-            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-            have[dev] = bytes;
-        }
-    };
-    static size_t have_big5[64] = {0}, have_big0[64] = {0}, have_0[64] = {0}, have_big5m[64] = {0};
     if (pl.ccl == CclForm::Mask) {
         // (measured and not kept: K2 over work lists of the tiles with foreground, flagged by k_decimate_mask -- as looping blocks 1.33-1.55 ms, as a
         // block per list entry 1.36 ms per 4096 frames against 1.25 ms for a block per tile: the blocks of background tiles load, look and leave in the
         // shadow of their neighbours' label phases, while the lists cost two more dependent loads per tile and 0.1 ms of atomics in K1)
         hipLaunchKernelGGL((k_threshold_ccl<5, true>), dim3(grid), dim3(kCclThreads), lds, s, P, g, ws.kp, nframes);
-        want_lds(reinterpret_cast<const void*>(k_threshold_ccl_big<5, true>), lds_big, have_big5m);
+        ensure_dynamic_lds(reinterpret_cast<const void*>(k_threshold_ccl_big<5, true>), lds_big);
         hipLaunchKernelGGL((k_threshold_ccl_big<5, true>), dim3(grid_big), dim3(kCclThreads), lds_big, s, P, g, ws.kp);
     } else if (pl.ccl == CclForm::Tw5) {
         hipLaunchKernelGGL(k_threshold_ccl<5>, dim3(grid), dim3(kCclThreads), lds, s, P, g, ws.kp, nframes);
-        want_lds(reinterpret_cast<const void*>(k_threshold_ccl_big<5>), lds_big, have_big5);
+        ensure_dynamic_lds(reinterpret_cast<const void*>(k_threshold_ccl_big<5>), lds_big);
         hipLaunchKernelGGL(k_threshold_ccl_big<5>, dim3(grid_big), dim3(kCclThreads), lds_big, s, P, g, ws.kp);
     } else {
-        want_lds(reinterpret_cast<const void*>(k_threshold_ccl<0>), lds, have_0);
+        ensure_dynamic_lds(reinterpret_cast<const void*>(k_threshold_ccl<0>), lds);
         hipLaunchKernelGGL(k_threshold_ccl<0>, dim3(grid), dim3(kCclThreads), lds, s, P, g, ws.kp, nframes);
-        want_lds(reinterpret_cast<const void*>(k_threshold_ccl_big<0>), lds_big, have_big0);
+        ensure_dynamic_lds(reinterpret_cast<const void*>(k_threshold_ccl_big<0>), lds_big);
         hipLaunchKernelGGL(k_threshold_ccl_big<0>, dim3(grid_big), dim3(kCclThreads), lds_big, s, P, g, ws.kp);
     }
     if (pl.ccl_stamps) {
         unsigned long long h[16];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost);
+        stamps.read(s, h, 16);
         unsigned long long tot = 0;
         for (int i = 0; i < 10; i++) tot += h[i];
         static const char* nm[10] = {"S1 stage", "S2 minmax", "S3 dilate", "S4 masks", "S5 runs", "S6 unions", "S7-8 flatten", "S9 stats", "S11 labels", "S10 publish"};
