@@ -10,6 +10,7 @@ from scipy.optimize import least_squares
 import cylindertag_amd as ca
 import testkit as tk
 from ctag_testlib import GOLDEN, Oracle, read_bmp_gray, read_marker_file
+from pose_statement import correspondences, model_lookup
 from pose_testlib import (PoseOracle, make_camera, make_model_view, project, read_camera_yml, read_model_file, rodrigues,
                           synth_pose_results)
 
@@ -180,34 +181,19 @@ def test_ba_reaches_the_least_squares_minimum(env):
 
 
 def test_correspondence_builder_follows_the_reference(env):
-    """pose_estimation.cpp:72-95 restated in Python vs the oracle."""
+    """pose_estimation.cpp:72-95 as tests/pose_statement.py restates it (the end-feature skip, corners 0 1 4 5 [2 3 6 7]) vs the
+    oracle."""
     recs, _ = synth_pose_results(env["model"], env["K"], env["dist"], 40, 11)
     po, mv, model = env["po"], env["mv"], env["model"]
     checked = 0
     for r in recs:
         for m in range(r["n_markers"]):
-            M = r["markers"][m]
-            idx = np.where(model["ids"] == M["marker_id"])[0]
-            if idx.size == 0:
+            mi = model_lookup(model, int(r["markers"][m]["marker_id"]))
+            if mi < 0:
                 continue
-            mi = int(idx[0])
-            feats = r["features"][M["first_feature"]:M["first_feature"] + M["n_features"]]
-            img, obj = [], []
-            nf = len(feats)
-            for j, F in enumerate(feats):
-                ad = abs(int(F["id_left"]) - int(F["id_right"]))
-                if nf > 3:
-                    if j == 0 and (ad > 1 or F["id_right"] == -1):
-                        continue
-                    if j == nf - 1 and (ad > 1 or F["id_right"] == -1):
-                        continue
-                ks = [0, 1, 4, 5] + ([2, 3, 6, 7] if (ad < 3 and F["id_right"] != -1) else [])
-                for k in ks:
-                    img.append(F["corners"][2 * k:2 * k + 2])
-                    obj.append(model["corners"][mi][F["pos"] * 8 + k])
+            want_st, obj, img = correspondences(r, m, model, mi)
             st, o, i = po.correspondences(r, m, mv, mi)
-            assert st == 0 and np.array_equal(o, np.array(obj, np.float32).reshape(-1, 3))
-            assert np.array_equal(i, np.array(img, np.float32).reshape(-1, 2))
+            assert st == want_st == 0 and np.array_equal(o, obj) and np.array_equal(i, img)
             checked += 1
     assert checked > 50
 

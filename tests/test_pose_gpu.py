@@ -58,7 +58,8 @@ def test_reference_scene_pose_parity(env):
 
 def test_batch_pose_parity_device_records(env):
     """512 frames of synthetic detection records in HBM (random poses of the reference's models, every branch of the
-    correspondence builder, markers without a model, 4-point and 160-point markers) through ctag_pose_batch_device."""
+    correspondence builder, markers without a model, markers of 4 to 56 points) through ctag_pose_batch_device.  Larger
+    markers, up to the 160 points of the large form, are in test_pose_forms_gpu.py."""
     import torch
     recs, truth = synth_pose_results(env["model"], env["K"], env["dist"], 512, 1)
     d = torch.from_numpy(recs.view(np.uint8).reshape(len(recs), -1)).cuda()

@@ -150,6 +150,27 @@ def test_synthetic_batch_parity(env):
     assert len(err_t) >= 80 and np.median(err_r) < 0.1 and np.median(err_t) < 1.0, (np.median(err_r), np.median(err_t))
 
 
+@pytest.mark.parametrize("name", ["n_dist8", "n_dist12"])
+def test_synthetic_batch_parity_rational_and_thin_prism_cameras(env, name):
+    """The synthetic batch under the 8- and 12-coefficient cameras of pose_testlib.test_cameras(): k_rig_pose.hip shares
+    undistort_normalised and pose_solve with k_pose.hip, whose k[5..11] terms the golden camera leaves at zero."""
+    from pose_testlib import test_cameras
+    dist = test_cameras()[name]
+    e = dict(env, dist=dist, cam=ca.make_camera(env["K"], dist), cam_o=make_camera(env["K"], dist))
+    assert e["cam"].n_dist == len(dist) == int(name[6:]) and e["cam"].dist[len(dist) - 1] != 0
+    model, rig_of_model, recs, _ = _synthetic_batch(e, 64, 13)
+    M, mv = _model(model), make_model_view(model)
+    got = _batch(e, recs, M, ca.Rigs(M, rig_of_model))
+    want = _want(e, recs, mv, rig_of_model, 2)
+    for f in range(len(recs)):
+        assert got[2 * f:2 * f + 2].tobytes() == want[2 * f:2 * f + 2].tobytes(), "frame %d" % f
+    assert (got["status"] == 0).sum() >= 40 and (got["n_members"] >= 2).sum() >= 20
+    # and not the golden camera's records: the extra terms reach the kernel
+    plain = _batch(env, recs, M, ca.Rigs(M, rig_of_model))
+    ok = (got["status"] == 0) & (plain["status"] == 0)
+    assert np.median(np.abs(got["tvec"][ok] - plain["tvec"][ok]).max(axis=1)) > 1e-3  # millimetres
+
+
 def test_batch_equals_single_frame_calls(env):
     model, rig_of_model, recs, _ = _synthetic_batch(env, 48, 12)
     M = _model(model)
