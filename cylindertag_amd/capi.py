@@ -28,7 +28,8 @@ EXPORTS = ["ctag_create", "ctag_create_ex", "ctag_params_default", "ctag_destroy
 # ... and include/ctag_pose.h
 POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag_model_get_view", "ctag_camera_load",
                 "ctag_pose_batch_device", "ctag_estimate_pose", "ctag_pose_last_ms", "ctag_draw_axis", "ctag_draw_axis_batch_device",
-                "ctag_rigs_create", "ctag_rigs_free", "ctag_rig_pose_batch_device", "ctag_estimate_rig_pose"]
+                "ctag_rigs_create", "ctag_rigs_free", "ctag_rig_pose_batch_device", "ctag_estimate_rig_pose",
+                "ctag_camera_set_create", "ctag_camera_set_free", "ctag_mv_rig_pose_batch_device", "ctag_estimate_mv_rig_pose"]
 # ... and include/ctag_gather.h
 GATHER_EXPORTS = ["ctag_shard_range", "ctag_packed_capacity", "ctag_pack_results", "ctag_unpack_results", "ctag_comm_unique_id",
                   "ctag_comm_init", "ctag_comm_attach", "ctag_comm_destroy", "ctag_comm_native", "ctag_comm_last_error", "ctag_gather_begin",
@@ -46,6 +47,15 @@ RIG_POSE_DT = np.dtype([("status", "<i4"), ("rig", "<i4"), ("frame", "<i4"), ("n
                         ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("rvec0", "<f8", (3,)), ("tvec0", "<f8", (3,)),
                         ("cost0", "<f8"), ("cost", "<f8")])
 RIG_MAX_POINTS = 800
+# ctag_mv_pose_rec: one pose per rig from several cameras (include/ctag_pose.h)
+MV_MAX_CAMERAS = 8
+MV_POSE_DT = np.dtype([("status", "<i4"), ("rig", "<i4"), ("frame", "<i4"), ("n_cameras", "<i4"), ("start_camera", "<i4"),
+                       ("n_members", "<i4"), ("n_excluded", "<i4"), ("n_points", "<i4"), ("iterations", "<i4"), ("iterations_cam", "<i4"),
+                       ("points_of_camera", "<i4", (MV_MAX_CAMERAS,)), ("member_mask", "<u4", (MV_MAX_CAMERAS, 4)), ("reserved", "<i4", (2,)),
+                       ("rvec_epnp", "<f8", (3,)), ("tvec_epnp", "<f8", (3,)), ("rvec_cam", "<f8", (3,)), ("tvec_cam", "<f8", (3,)),
+                       ("cost_cam0", "<f8"), ("cost_cam", "<f8"), ("rvec_start", "<f8", (3,)), ("tvec_start", "<f8", (3,)), ("cost0", "<f8"),
+                       ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("cost", "<f8")])
+assert MV_POSE_DT.itemsize == 432
 
 
 class ParamsC(C.Structure):  # ctag_params (include/ctag_types.h): the reference's tunables
@@ -73,6 +83,10 @@ class CountersC(C.Structure):  # ctag_counters (include/ctag_types.h)
 
 class CameraC(C.Structure):  # ctag_camera
     _fields_ = [("K", C.c_float * 9), ("dist", C.c_float * 14), ("n_dist", C.c_int32)]
+
+
+class CameraPoseC(C.Structure):  # ctag_camera_pose: X_cam = R(rvec) X_ref + tvec
+    _fields_ = [("rvec", C.c_double * 3), ("tvec", C.c_double * 3)]
 
 
 class ModelViewC(C.Structure):  # ctag_model_view
@@ -190,6 +204,14 @@ def load_library():
     L.ctag_rig_pose_batch_device.argtypes = [vp, vp, C.c_int, vp, vp, C.POINTER(CameraC), vp]
     L.ctag_estimate_rig_pose.restype = C.c_int
     L.ctag_estimate_rig_pose.argtypes = [vp, vp, vp, vp, C.POINTER(CameraC), vp]
+    L.ctag_camera_set_create.restype = C.c_int
+    L.ctag_camera_set_create.argtypes = [C.POINTER(CameraC), C.POINTER(CameraPoseC), C.c_int, C.POINTER(vp)]
+    L.ctag_camera_set_free.restype = None
+    L.ctag_camera_set_free.argtypes = [vp]
+    L.ctag_mv_rig_pose_batch_device.restype = C.c_int
+    L.ctag_mv_rig_pose_batch_device.argtypes = [vp, C.POINTER(vp), C.c_int, vp, vp, vp, vp]
+    L.ctag_estimate_mv_rig_pose.restype = C.c_int
+    L.ctag_estimate_mv_rig_pose.argtypes = [vp, vp, vp, vp, vp, vp]
     u64p = C.POINTER(C.c_uint64)
     L.ctag_shard_range.restype = C.c_int
     L.ctag_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -329,6 +351,39 @@ class Rigs:
         if getattr(self, "r", None):
             self.L.ctag_rigs_free(self.r)
             self.r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CameraSet:
+    """ctag_camera_set: cameras (CameraC each) and poses [(rvec, tvec)] of the cameras in one reference frame,
+    X_cam = R(rvec) X_ref + tvec."""
+
+    def __init__(self, cameras, poses):
+        self.L = load_library()
+        cameras, poses = list(cameras), list(poses)
+        if len(cameras) != len(poses):
+            raise ValueError("%d cameras, %d poses" % (len(cameras), len(poses)))
+        self.n = len(cameras)
+        cams = (CameraC * max(self.n, 1))(*cameras)
+        ps = (CameraPoseC * max(self.n, 1))()
+        for c, (rv, tv) in enumerate(poses):
+            for i in range(3):
+                ps[c].rvec[i], ps[c].tvec[i] = float(rv[i]), float(tv[i])
+        s = C.c_void_p()
+        st = self.L.ctag_camera_set_create(cams, ps, self.n, C.byref(s))
+        if st != 0:
+            raise CtagError(st, "ctag_camera_set_create")
+        self.s = s
+
+    def close(self):
+        if getattr(self, "s", None):
+            self.L.ctag_camera_set_free(self.s)
+            self.s = None
 
     def __del__(self):
         try:
@@ -601,6 +656,29 @@ class Detector:
         st = self.L.ctag_rig_pose_batch_device(self.h, results_ptr, n_frames, model.m, rigs.r, C.byref(camera), out_ptr)
         if st != 0:
             raise CtagError(st, "ctag_rig_pose_batch_device")
+
+    def estimate_mv_rig_pose(self, results, model, rigs, cams):
+        """One instant: cams.n host ctag_frame_result records (record c from camera c) -> rigs.n_rigs MV_POSE_DT records."""
+        res = np.ascontiguousarray(results).reshape(-1)
+        assert res.dtype == RESULT_DT
+        if len(res) != cams.n:
+            raise ValueError("%d records for %d cameras" % (len(res), cams.n))
+        out = np.zeros(rigs.n_rigs, MV_POSE_DT)
+        st = self.L.ctag_estimate_mv_rig_pose(self.h, res.ctypes.data, model.m, rigs.r, cams.s, out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_estimate_mv_rig_pose")
+        return out
+
+    def mv_rig_pose_batch_device(self, results_ptrs, n_frames, model, rigs, cams, out_ptr):
+        """results_ptrs: one device pointer per camera of cams, n_frames result records each -> n_frames * rigs.n_rigs device
+        MV_POSE_DT records at out_ptr (record f*n_rigs + g); enqueued on the handle's stream."""
+        ptrs = list(results_ptrs)
+        if len(ptrs) != cams.n:
+            raise ValueError("%d pointers for %d cameras" % (len(ptrs), cams.n))
+        arr = (C.c_void_p * max(len(ptrs), 1))(*[C.c_void_p(int(p) if p else None) for p in ptrs])
+        st = self.L.ctag_mv_rig_pose_batch_device(self.h, arr, n_frames, model.m, rigs.r, cams.s, out_ptr)
+        if st != 0:
+            raise CtagError(st, "ctag_mv_rig_pose_batch_device")
 
     def pose_last_ms(self):
         return float(self.L.ctag_pose_last_ms(self.h))

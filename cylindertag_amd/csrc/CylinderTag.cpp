@@ -336,6 +336,77 @@ void CylinderTag::estimateRigPose(std::vector<MarkerInfo> markers, std::vector<M
     }
 }
 
+void CylinderTag::estimateMultiViewRigPose(const std::vector<std::vector<MarkerInfo>>& markersPerCamera, std::vector<ModelInfo> reconstruct_model,
+                                           const std::vector<int>& rigOfModel, const std::vector<CamInfo>& cameras,
+                                           const std::vector<ViewPose>& cameraPoses, std::vector<RigPoseInfo>& pose) {
+    pose.clear();
+    const size_t nc = cameras.size();
+    if (nc < 1 || nc > (size_t)CTAG_MV_MAX_CAMERAS) throw __FUNCTION__ + std::string(", ") + "1 to 8 cameras\n";
+    if (markersPerCamera.size() != nc || cameraPoses.size() != nc) throw __FUNCTION__ + std::string(", ") + "one marker list and one pose per camera\n";
+    if (rigOfModel.size() != reconstruct_model.size()) throw __FUNCTION__ + std::string(", ") + "one rig entry per model\n";
+    int n_rigs = 0;
+    for (int g : rigOfModel) n_rigs = g + 1 > n_rigs ? g + 1 : n_rigs;
+    if (n_rigs == 0) return;
+    std::vector<ctag_frame_result> res(nc);
+    std::vector<ctag_camera> cams(nc);
+    std::vector<ctag_camera_pose> cps(nc);
+    for (size_t c = 0; c < nc; c++) {
+        if (markersPerCamera[c].size() > (size_t)CTAG_MAX_MARKERS) throw __FUNCTION__ + std::string(", ") + "more than 100 markers\n";
+        if (flatten(markersPerCamera[c], 0, res[c]) != markersPerCamera[c].size()) throw __FUNCTION__ + std::string(", ") + "more than 100 features\n";
+        cams[c] = make_camera(cameras[c]);
+#ifdef CTAG_WITH_OPENCV
+        cv::Mat r64, t64;
+        cameraPoses[c].rvec.convertTo(r64, CV_64F);
+        cameraPoses[c].tvec.convertTo(t64, CV_64F);
+        if (r64.total() != 3 || t64.total() != 3) throw __FUNCTION__ + std::string(", ") + "a camera pose is two 3-vectors\n";
+        const double *pr = r64.ptr<double>(0), *pt = t64.ptr<double>(0);
+#else
+        const double *pr = cameraPoses[c].rvec, *pt = cameraPoses[c].tvec;
+#endif
+        for (int i = 0; i < 3; i++) {
+            cps[c].rvec[i] = pr[i];
+            cps[c].tvec[i] = pt[i];
+        }
+    }
+    ctag_camera_set* set = nullptr;
+    int st = ctag_camera_set_create(cams.data(), cps.data(), (int)nc, &set);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    ctag_model* model = nullptr;
+    try {
+        model = make_model(reconstruct_model, __FUNCTION__);
+    } catch (...) {
+        ctag_camera_set_free(set);
+        throw;
+    }
+    ctag_rigs* rigs = nullptr;
+    st = ctag_rigs_create(model, rigOfModel.data(), n_rigs, &rigs);
+    std::vector<ctag_mv_pose_rec> rec((size_t)n_rigs);
+    if (st == CTAG_OK) st = ctag_estimate_mv_rig_pose(h_, res.data(), model, rigs, set, rec.data());
+    ctag_rigs_free(rigs);
+    ctag_model_free(model);
+    ctag_camera_set_free(set);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    for (const ctag_mv_pose_rec& p : rec) {
+        if (p.status == CTAG_POSE_NOT_SEEN) continue;  // erased, as estimateRigPose erases rigs without a member
+        if (p.status != CTAG_POSE_OK) throw __FUNCTION__ + std::string(", ") + "rig without a usable point set\n";
+        RigPoseInfo ri;
+        ri.rigID = p.rig;
+#ifdef CTAG_WITH_OPENCV
+        ri.rvec = (cv::Mat_<double>(3, 1) << p.rvec[0], p.rvec[1], p.rvec[2]);
+        ri.tvec = (cv::Mat_<double>(3, 1) << p.tvec[0], p.tvec[1], p.tvec[2]);
+#else
+        for (int i = 0; i < 3; i++) {
+            ri.rvec[i] = p.rvec[i];
+            ri.tvec[i] = p.tvec[i];
+        }
+#endif
+        for (int c = 0; c < (int)nc; c++)
+            for (int k = 0; k < CTAG_MAX_MARKERS; k++)
+                if ((p.member_mask[c][k >> 5] >> (k & 31)) & 1u) ri.viewMembers.emplace_back(c, k);
+        pose.push_back(ri);
+    }
+}
+
 static void pose_vectors(const PoseInfo& p, double* r, double* t) {
 #ifdef CTAG_WITH_OPENCV
     const double *pr = p.rvec.ptr<double>(0), *pt = p.tvec.ptr<double>(0);

@@ -17,6 +17,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #ifdef CTAG_WITH_OPENCV
@@ -90,6 +91,11 @@ struct RigPoseInfo {
     int rigID;
     cv::Mat rvec, tvec;
     std::vector<int> members;
+    std::vector<std::pair<int, int>> viewMembers;  // estimateMultiViewRigPose: (camera, index into that camera's marker list)
+};
+// pose of one camera in the reference frame of a camera set (new): X_cam = R(rvec) X_ref + tvec, both 3x1 CV_64F
+struct ViewPose {
+    cv::Mat rvec, tvec;
 };
 #else
 struct CamInfo {
@@ -104,6 +110,11 @@ struct RigPoseInfo {
     int rigID = -1;
     double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
     std::vector<int> members;
+    std::vector<std::pair<int, int>> viewMembers;  // estimateMultiViewRigPose: (camera, index into that camera's marker list)
+};
+// pose of one camera in the reference frame of a camera set (new): X_cam = R(rvec) X_ref + tvec
+struct ViewPose {
+    double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
 };
 #endif
 // the annotated frame of drawAxis: rows x cols pixels of 3 bytes, channel c = Scalar component c (imgMark in the reference)
@@ -159,6 +170,15 @@ class CylinderTag {
     // <= 100 features, as detect() returns them).  Throws std::string on error or on a rig whose points do not give a pose.
     void estimateRigPose(std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, const std::vector<int>& rigOfModel,
                          CamInfo camera, std::vector<RigPoseInfo>& pose);
+
+    // One pose per rig from several calibrated cameras that saw the same instant (new; include/ctag_pose.h,
+    // ctag_estimate_mv_rig_pose): markersPerCamera[c] is camera c's marker list, cameras[c] / cameraPoses[c] its intrinsics and its
+    // pose in the reference frame (1 .. 8 cameras).  The pose of a rig maps its model frame into the REFERENCE frame.  Follows
+    // estimateRigPose: rigs no camera sees are erased, std::string is thrown on error or on a rig whose points do not give a pose;
+    // RigPoseInfo::viewMembers lists the members as (camera, marker index) pairs and `members` stays empty.
+    void estimateMultiViewRigPose(const std::vector<std::vector<MarkerInfo>>& markersPerCamera, std::vector<ModelInfo> reconstruct_model,
+                                  const std::vector<int>& rigOfModel, const std::vector<CamInfo>& cameras,
+                                  const std::vector<ViewPose>& cameraPoses, std::vector<RigPoseInfo>& pose);
 
     // Draw the axes of the posed markers (reference: header/CylinderTag.h:33, CylinderTag.cpp:211-246): pose[i] is drawn on
     // markers[i] -- the reference pairs them by list position, after estimatePose has erased the poses without a model -- with

@@ -1138,7 +1138,7 @@ void ctag_destroy(ctag_handle* h) {
     (void)hipSetDevice(h->device);
     (void)quiesce(h);
     drop_graphs(h);
-    for (auto& st : h->state)  // pose, draw, rig, gather
+    for (auto& st : h->state)  // pose, draw, rig, gather, multi-view
         if (st.p && st.free_fn) st.free_fn(st.p);
     auto drop = [](hipEvent_t e) {
         if (e) (void)hipEventDestroy(e);

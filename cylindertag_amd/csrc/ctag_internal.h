@@ -63,6 +63,14 @@ struct ctag_model {
     float* d_axis = nullptr;
 };
 
+// the rig set of include/ctag_pose.h (k_rig_pose.hip creates it; k_mv_pose.hip reads it too)
+struct ctag_rigs {
+    int n_models = 0, n_rigs = 0;
+    std::vector<int32_t> rig_of_model;
+    ctag::DevBuf<int32_t> d_rig;  // device copy, made on `device` at the first pose call
+    int device = -1;
+};
+
 namespace ctag {
 
 // ---- CCL tile geometry (half-resolution pixels) ---------------------------------------------------------
@@ -363,11 +371,12 @@ void build_pick_table(uint8_t* table, uint16_t* table16);  // kPickN*20*10 bytes
 
 
 // accessor of the opaque handle for the state of its back ends, each created on first use: the pose back end (k_pose.hip), the overlay (k_draw.hip),
-// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip).  ctag_destroy frees them in this order.
-enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kNumSiblingStates };
+// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip), the multi-view rig poses (k_mv_pose.hip).  ctag_destroy frees them in this order.
+enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kNumSiblingStates };
 void** handle_state_slot(struct ::ctag_handle* h, SiblingState which, void (*free_fn)(void*));
 // the model's device copies on `device` (k_pose.hip); the camera's distortion model is one the pose back end handles
 int model_to_device(struct ::ctag_model* m, int device);
+int rigs_to_device(struct ::ctag_rigs* r, int device);  // the same for a rig set (k_rig_pose.hip)
 bool camera_ok(const struct ::ctag_camera* c);
 bool handle_timing(const struct ::ctag_handle* h);
 // completes the frames of earlier device-memory calls that wait for the any-frame workspace (CTAG_PENDING records); waits for the

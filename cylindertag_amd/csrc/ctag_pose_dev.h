@@ -1,6 +1,8 @@
-// ctag_pose_dev.h -- device side of the pose back end shared by k_pose.hip (one pose per marker) and k_rig_pose.hip (one
-// pose per rig of markers): the LDS image of one problem, PnPSolver's correspondence rule, and EPnP + PoseBA over n points
-// in LDS (the arithmetic of the oracle's ctago_solve_pnp_epnp and ctago_pose_ba, see k_pose.hip's header for the mapping).
+// ctag_pose_dev.h -- device side of the pose back end shared by k_pose.hip (one pose per marker), k_rig_pose.hip (one pose per
+// rig of markers) and k_mv_pose.hip (one pose per rig from several cameras): the LDS image of one problem, PnPSolver's
+// correspondence rule, and EPnP + PoseBA over n points in LDS (the arithmetic of the oracle's ctago_solve_pnp_epnp and
+// ctago_pose_ba, see k_pose.hip's header for the mapping).  pose_epnp and pose_ba are the two halves; pose_ba takes the residual
+// of a point as a policy (one camera: camera_residual; a camera per point: k_mv_pose.hip); pose_solve is the two in a row.
 // Generic over the LDS capacity PTS and the block width NT: per-point loops stride over the NT lanes, while every sum over
 // the points stays with its one owner lane (lane < 144 / 34), so the result is the sequential evaluation for any n <= PTS.
 #pragma once
@@ -202,12 +204,11 @@ __device__ __forceinline__ void load_point(PoseLds<PTS>& S, const PoseCam& cam, 
     S.X[3 * i + 2] = (double)cp[2];
 }
 
-// EPnP (solvePnP SOLVEPNP_EPNP) and PoseBA over the n >= 4 points the block has loaded into S (X, OBS, u.e.US), by the NT
-// threads of the block (lane = threadIdx.x).  Lane 0 writes the pose fields of *P: rvec0 tvec0 rvec tvec iterations cost0
-// cost, or status = CTAG_POSE_DEGENERATE (the other fields untouched) for a non-finite EPnP result.  Rec is ctag_pose_rec
-// or ctag_rig_pose_rec.  Every thread of the block calls it; it synchronises the block.
-template <int PTS, int NT, class Rec>
-__device__ __forceinline__ void pose_solve(PoseLds<PTS>& S, const int lane, const int n, const PoseCam& cam, Rec* __restrict__ P) {
+// EPnP (solvePnP SOLVEPNP_EPNP) over the n >= 4 points the block has loaded into S (X, u.e.US), by the NT threads of the
+// block (lane = threadIdx.x).  True: S.x holds the pose (rvec, tvec).  False: the result is not finite.  Every thread of the
+// block calls it and gets the same answer; it synchronises the block.
+template <int PTS, int NT>
+__device__ __forceinline__ bool pose_epnp(PoseLds<PTS>& S, const int lane, const int n, const PoseCam& cam) {
 #ifdef CTAG_POSE_PROF
     unsigned long long prof_t = __builtin_readcyclecounter();
 #endif
@@ -255,10 +256,7 @@ __device__ __forceinline__ void pose_solve(PoseLds<PTS>& S, const int lane, cons
         }
     }
     wave_sync();
-    if (!S.jac_flag) {
-        if (lane == 0) P->status = CTAG_POSE_DEGENERATE;
-        return;
-    }
+    if (!S.jac_flag) return false;
     for (int i = lane; i < n; i += NT) {  // alphas
         const double p0 = S.X[3 * i] - S.cws[0], p1 = S.X[3 * i + 1] - S.cws[1], p2 = S.X[3 * i + 2] - S.cws[2];
         double a[4];
@@ -567,27 +565,27 @@ __device__ __forceinline__ void pose_solve(PoseLds<PTS>& S, const int lane, cons
         }
     }
     wave_sync();
-    if (!S.jac_flag) {
-        if (lane == 0) P->status = CTAG_POSE_DEGENERATE;
-        return;
-    }
-
+    if (!S.jac_flag) return false;
     PROF_MARK(7);
-    // =========================================== PoseBA ===========================================
-    // Ceres TrustRegionMinimizer + LevenbergMarquardtStrategy (see the oracle for the statement of the loop).
-    // All lanes carry the same x / radius / cost.  Lane = point writes its two (column-scaled) Jacobian rows and
-    // residuals to LDS; lane e < 34 owns one sequentially accumulated sum over those rows: e < 21 an entry of
-    // J^T J, 21..26 of J^T r, 27 the cost, 28..33 a squared column norm.  Every owner runs the same loop
-    // (acc += o[i0]*o[i1]; acc += o[i2]*o[i3]) with its own four offsets, so the 34 sums advance together.  The
-    // candidate point is evaluated WITH its Jacobian and normal equations, which an accepted step then keeps.
-    double x[6], xc[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) x[i] = S.x[i];
-    if (lane == 0)
-        for (int i = 0; i < 3; i++) {
-            P->rvec0[i] = x[i];
-            P->tvec0[i] = x[3 + i];
-        }
+    return true;
+}
+
+// PoseBA from the pose x over the n points of S (X, OBS), by the NT threads of the block; x is the same in every thread and
+// comes back refined.  residual(i, R, dR, y, r0, r1, j0, j1) gives point i's residuals and Jacobian rows at pose y (R, dR =
+// angle_axis_rot(y)).  Every thread of the block calls it; it synchronises the block.
+// Ceres TrustRegionMinimizer + LevenbergMarquardtStrategy (see the oracle for the statement of the loop).
+// All lanes carry the same x / radius / cost.  Lane = point writes its two (column-scaled) Jacobian rows and
+// residuals to LDS; lane e < 34 owns one sequentially accumulated sum over those rows: e < 21 an entry of
+// J^T J, 21..26 of J^T r, 27 the cost, 28..33 a squared column norm.  Every owner runs the same loop
+// (acc += o[i0]*o[i1]; acc += o[i2]*o[i3]) with its own four offsets, so the 34 sums advance together.  The
+// candidate point is evaluated WITH its Jacobian and normal equations, which an accepted step then keeps.
+template <int PTS, int NT, class Residual>
+__device__ __forceinline__ void pose_ba(PoseLds<PTS>& S, const int lane, const int n, double (&x)[6], Residual&& residual, int& iterations,
+                                        double& cost_start, double& cost_end) {
+#ifdef CTAG_POSE_PROF
+    unsigned long long prof_t = __builtin_readcyclecounter();
+#endif
+    double xc[6];
     int i0 = 12, i1 = 12, i2 = 13, i3 = 13;  // lane 27 (and the idle lanes): the cost
     {
         int e = lane, a = 0;
@@ -617,7 +615,7 @@ __device__ __forceinline__ void pose_solve(PoseLds<PTS>& S, const int lane, cons
         wave_sync();
         for (int i = lane; i < n; i += NT) {
             double r0, r1, j0[6], j1[6];
-            point_residual(R, dR, y, cam.fx, cam.fy, cam.cx, cam.cy, S.X + 3 * i, S.OBS + 2 * i, r0, r1, j0, j1, true);
+            residual(i, R, dR, y, r0, r1, j0, j1);
             double* o = S.u.b.JR + i * kJStride;
 #pragma unroll
             for (int a = 0; a < 6; a++) {
@@ -760,6 +758,39 @@ __device__ __forceinline__ void pose_solve(PoseLds<PTS>& S, const int lane, cons
         }
     }
     PROF_MARK(8);
+    iterations = iter;
+    cost_start = cost0;
+    cost_end = cost;
+}
+
+// the residual of one camera: what PoseBA fits in the per-marker and the rig pose
+template <int PTS>
+__device__ __forceinline__ auto camera_residual(const PoseLds<PTS>& S, const PoseCam& cam) {
+    return [&S, &cam](int i, const double* R, const double* dR, const double* y, double& r0, double& r1, double* j0, double* j1) {
+        point_residual(R, dR, y, cam.fx, cam.fy, cam.cx, cam.cy, S.X + 3 * i, S.OBS + 2 * i, r0, r1, j0, j1, true);
+    };
+}
+
+// EPnP, then PoseBA.  Lane 0 writes the pose fields of *P: rvec0 tvec0 rvec tvec iterations cost0 cost, or status =
+// CTAG_POSE_DEGENERATE (the other fields untouched) for a non-finite EPnP result.  Rec is ctag_pose_rec or ctag_rig_pose_rec.
+// Every thread of the block calls it; it synchronises the block.
+template <int PTS, int NT, class Rec>
+__device__ __forceinline__ void pose_solve(PoseLds<PTS>& S, const int lane, const int n, const PoseCam& cam, Rec* __restrict__ P) {
+    if (!pose_epnp<PTS, NT>(S, lane, n, cam)) {
+        if (lane == 0) P->status = CTAG_POSE_DEGENERATE;
+        return;
+    }
+    double x[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) x[i] = S.x[i];
+    if (lane == 0)
+        for (int i = 0; i < 3; i++) {
+            P->rvec0[i] = x[i];
+            P->tvec0[i] = x[3 + i];
+        }
+    int iter;
+    double cost0, cost;
+    pose_ba<PTS, NT>(S, lane, n, x, camera_residual(S, cam), iter, cost0, cost);
     if (lane == 0) {
         for (int i = 0; i < 3; i++) {
             P->rvec[i] = x[i];

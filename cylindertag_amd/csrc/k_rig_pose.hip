@@ -26,13 +26,7 @@
 static_assert(sizeof(ctag_rig_pose_rec) == 160, "ctag_rig_pose_rec layout");
 static_assert(CTAG_RIG_MAX_POINTS == CTAG_MAX_FEATURES * 8, "every valid detection record fits one rig problem");
 
-// ctag_rigs (opaque in include/ctag_pose.h)
-struct ctag_rigs {
-    int n_models = 0, n_rigs = 0;
-    std::vector<int32_t> rig_of_model;
-    ctag::DevBuf<int32_t> d_rig;  // device copy, made on `device` at the first pose call
-    int device = -1;
-};
+// struct ctag_rigs: ctag_internal.h (the multi-view poses of k_mv_pose.hip read it too)
 
 namespace ctag {
 
@@ -150,6 +144,10 @@ RigState* rig_state(ctag_handle* h) {
     return static_cast<RigState*>(*slot);
 }
 
+}  // namespace
+
+namespace ctag {
+
 int rigs_to_device(ctag_rigs* r, int device) {
     if (r->device == device && r->d_rig.p) return CTAG_OK;
     r->d_rig.release();  // (it may lie on another device)
@@ -161,7 +159,9 @@ int rigs_to_device(ctag_rigs* r, int device) {
     return CTAG_OK;
 }
 
-}  // namespace
+}  // namespace ctag
+
+using ctag::rigs_to_device;
 
 extern "C" {
 

@@ -159,6 +159,83 @@ int ctag_rig_pose_batch_device(ctag_handle* h, const ctag_frame_result* results_
 int ctag_estimate_rig_pose(ctag_handle* h, const ctag_frame_result* result, const ctag_model* model, const ctag_rigs* rigs,
                            const ctag_camera* camera, ctag_rig_pose_rec* out);
 
+/* ---- multi-view rig pose: one pose per rig from several calibrated cameras (k_mv_pose.hip) ------------------------------------
+ * A camera set holds n cameras (1 .. CTAG_MV_MAX_CAMERAS): the intrinsics of each and its pose in one reference frame,
+ * X_cam = R(rvec) X_ref + tvec (Rodrigues).  Every camera delivers one detection record per frame; frame f of every camera is
+ * the same instant.  The record of frame f and rig g gives the pose of the rig's model frame in the REFERENCE frame,
+ * X_ref = R(rvec) X_model + tvec:
+ *   1. Membership.  Cameras are visited in order c = 0 .. n-1.  A camera whose record of the frame is not CTAG_OK contributes
+ *      nothing (no error).  Inside one camera's record rule 2 of the rig section holds unchanged, duplicates judged per camera;
+ *      the bound CTAG_RIG_MAX_POINTS holds for the TOTAL over all cameras (a marker that would pass it is excluded and counted).
+ *      Bit k of member_mask[c] is set for member k of camera c.  Points are appended in camera order, then marker order, then the
+ *      builder's own order.  No member in any camera: CTAG_POSE_NOT_SEEN.  Pose fields are 0 unless the status is CTAG_POSE_OK.
+ *   2. Start camera: the camera with the most points, the lowest index on a tie.  Fewer than 4 points there: CTAG_POSE_TOO_FEW.
+ *   3. Stage 1: EPnP then PoseBA over the start camera's points alone with its intrinsics, the arithmetic of
+ *      ctag_rig_pose_batch_device: rvec_epnp tvec_epnp rvec_cam tvec_cam cost_cam0 cost_cam iterations_cam are the rvec0 tvec0
+ *      rvec tvec cost0 cost iterations bytes of that camera's own ctag_rig_pose_rec whenever its members are the same.  A
+ *      non-finite EPnP result gives CTAG_POSE_DEGENERATE.
+ *   4. Into the reference frame: R_start = Rc^T R(rvec_cam), t_start = Rc^T (tvec_cam - tc), sums in index order, rvec_start by
+ *      the inverse Rodrigues formula.  If the start camera's rvec and tvec are all exactly 0 the move is skipped: rvec_start,
+ *      tvec_start are the bytes of rvec_cam, tvec_cam.
+ *   5. Stage 2: the LM loop of PoseBA (same options, scaling and stop rules, sums in point order) over all n_points from
+ *      (rvec_start, tvec_start).  Point i of camera c: Q = Rc (R X + t) + tc, residual (fx_c Q0/Q2 + cx_c - obs_u,
+ *      fy_c Q1/Q2 + cy_c - obs_v), obs = the point's pixel undistorted with camera c's own coefficients, through its K, rounded
+ *      to float; exact analytic Jacobian.  cost0 is 0.5 * sum r^2 at the start, cost at the end.  If every point belongs to the
+ *      start camera, stage 2 is not run: rvec, tvec = rvec_start, tvec_start, iterations = 0, cost0 = cost = cost_cam.
+ *   6. With every camera pose exactly 0 and equal intrinsics, Rc P + tc is P bit for bit, and stage 2 equals PoseBA over the
+ *      concatenated points from (rvec_cam, tvec_cam) byte for byte.
+ * A rig that is its own single model gets a multi-camera marker pose: there is no separate per-marker entry point. */
+#define CTAG_MV_MAX_CAMERAS 8
+
+typedef struct ctag_camera_pose {
+    double rvec[3], tvec[3]; /* X_cam = R(rvec) X_ref + tvec */
+} ctag_camera_pose;
+
+typedef struct ctag_mv_pose_rec {
+    int32_t status;              /* CTAG_POSE_OK, _TOO_FEW, _DEGENERATE or _NOT_SEEN */
+    int32_t rig;                 /* rig index g */
+    int32_t frame;               /* frame index f in the batch */
+    int32_t n_cameras;           /* cameras with at least one member */
+    int32_t start_camera;        /* rule 2; 0 when there is no member */
+    int32_t n_members;           /* totals over all cameras */
+    int32_t n_excluded;
+    int32_t n_points;
+    int32_t iterations;          /* LM iterations of stage 2 */
+    int32_t iterations_cam;      /* ... of stage 1 */
+    int32_t points_of_camera[CTAG_MV_MAX_CAMERAS];
+    uint32_t member_mask[CTAG_MV_MAX_CAMERAS][4]; /* camera c, marker k: word k/32, bit k%32 */
+    int32_t reserved[2];         /* 0 */
+    double rvec_epnp[3];         /* EPnP pose in the start camera's frame */
+    double tvec_epnp[3];
+    double rvec_cam[3];          /* stage-1 pose in the start camera's frame */
+    double tvec_cam[3];
+    double cost_cam0;            /* stage-1 cost at the EPnP pose */
+    double cost_cam;             /* ... at the stage-1 pose */
+    double rvec_start[3];        /* stage-2 start in the reference frame */
+    double tvec_start[3];
+    double cost0;                /* cost over all points at the start */
+    double rvec[3];              /* final pose in the reference frame */
+    double tvec[3];
+    double cost;                 /* ... and its cost */
+} ctag_mv_pose_rec;              /* 432 bytes */
+
+typedef struct ctag_camera_set ctag_camera_set; /* n cameras: intrinsics + pose of each in one reference frame */
+
+/* Host only.  Copies both arrays.  CTAG_ERR_ARG for null pointers, n_cameras outside 1 .. CTAG_MV_MAX_CAMERAS or a non-finite
+ * pose entry; CTAG_ERR_UNSUPPORTED for a camera the pose back end does not handle (tilt terms). */
+int ctag_camera_set_create(const ctag_camera* cameras, const ctag_camera_pose* poses, int n_cameras, ctag_camera_set** out);
+void ctag_camera_set_free(ctag_camera_set* s);
+
+/* results_dev: HOST array of n_cameras DEVICE pointers, n_frames records each (read before the call returns).  Writes exactly
+ * n_frames x n_rigs records to out_dev, record f*n_rigs + g, and no byte outside them.  Enqueued on the handle's stream;
+ * returns without waiting.  Arguments are judged as ctag_rig_pose_batch_device judges them. */
+int ctag_mv_rig_pose_batch_device(ctag_handle* h, const ctag_frame_result* const* results_dev, int n_frames, const ctag_model* model,
+                                  const ctag_rigs* rigs, const ctag_camera_set* cams, ctag_mv_pose_rec* out_dev);
+
+/* One instant: n_cameras HOST records in (record c from camera c), n_rigs host records out.  Waits for completion. */
+int ctag_estimate_mv_rig_pose(ctag_handle* h, const ctag_frame_result* results, const ctag_model* model, const ctag_rigs* rigs,
+                              const ctag_camera_set* cams, ctag_mv_pose_rec* out);
+
 /* ---- overlay: CylinderTag::drawAxis (reference CylinderTag.cpp:211-246) ------------------------------------------------
  * Output: 8-bit, 3 channels, every channel = the gray value (cvtColor GRAY2RGB), then per drawn record, in record order,
  * what the reference paints with OpenCV 4.5.3 (k_draw.hip restates it):
