@@ -171,3 +171,11 @@ def rig_study(po, model, K, dist, cam, mv, n_frames=300, noise_px=0.2, seed=7):
             rig_r.append(rot_err_deg(R["rvec"], rv))
             rig_t.append(float(np.linalg.norm(R["tvec"] - tv)))
     return {"marker": (np.array(per_r), np.array(per_t)), "rig": (np.array(rig_r), np.array(rig_t))}
+
+
+def compose_batch(po, batch, recs=None):
+    """compose_rig_poses over the frames of one of tests/rig_shapes.py's batches (or over `recs` under its model and camera)."""
+    from pose_testlib import make_camera, make_model_view
+    recs = batch["recs"] if recs is None else recs
+    mv, cam = make_model_view(batch["model"]), make_camera(batch["K"], batch["dist"])
+    return np.concatenate([compose_rig_poses(po, recs[f], mv, cam, batch["rig_of_model"], batch["n_rigs"], f) for f in range(len(recs))])
