@@ -359,6 +359,8 @@ hipError_t launch_seam_merge(const ChunkPlan& pl, const Workspace& ws, hipStream
 hipError_t launch_resolve(const ChunkPlan& pl, const Workspace& ws, hipStream_t s);
 hipError_t launch_candidates(const ChunkPlan& pl, const Workspace& ws, hipStream_t s);
 hipError_t launch_quads(const ChunkPlan& pl, const Workspace& ws, hipStream_t s, hipEvent_t* ev5 = nullptr);  // ev5: 5 events, one after each kernel but the last
+hipError_t launch_line_fits(const ChunkPlan& pl, const Workspace& ws, hipStream_t s, unsigned long long* stamps = nullptr, hipEvent_t ev_sorted = nullptr);  // launch_quads' k_line_sort + k_welsch_lat + k_welsch; stamps: launch_quads' phase clocks
+int welsch_limits(int32_t* out, int capacity);  // the sizes at which k_line_sort / k_welsch / k_welsch_lat change form (k_quad.hip); returns their count
 hipError_t launch_features(const ChunkPlan& pl, const Workspace& ws, const DetectParams& p, hipStream_t s);
 hipError_t launch_edge_refine(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, const DetectParams& p, hipStream_t s);
 hipError_t launch_markers(const ChunkPlan& pl, const Workspace& ws, const DetectParams& p, ctag_frame_result* out, const PendingCtx& pend, hipStream_t s);

@@ -2073,6 +2073,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
 // draws, so its 20 restarts are the same computation twenty times and the selection keeps restart 0 (a later equal error
 // is not smaller).  Such edges -- 46 % of the edges of the synthetic batch -- are fitted once, a lane each (welsch_short).
 constexpr int kWShort = 10;
+constexpr int kLineSortBuckets = 2048;  // of the counting sort a frame of more than kLdsLines edges takes
 constexpr int kLineSortThreads = 1024;  // a rank sort: L / threads passes of L comparisons each; one frame has ~400 edges
 __global__ __launch_bounds__(kLineSortThreads) void k_line_sort(QuadPtrs P, int nframes) {
     __shared__ int s_n[kLdsLines];
@@ -2089,7 +2090,7 @@ __global__ __launch_bounds__(kLineSortThreads) void k_line_sort(QuadPtrs P, int 
         // kB - 1 and more in one bucket.  What the consumers rely on still holds: ranks [0, line_long) are the edges of more
         // than kWShort points; below the shared bucket the order is exact, and everything in it is longer than any length a
         // consumer compares with (kWPts, kLatPoints).
-        constexpr int kB = 2048;
+        constexpr int kB = kLineSortBuckets;
         static_assert(kB - 1 > kLatPoints && kB + 1 <= kLdsLines, "shared bucket");
         auto bucket_of = [&](int n) { return kB - 1 - min(n, kB - 1); };
         for (int b = threadIdx.x; b <= kB; b += kLineSortThreads) s_n[b] = 0;
@@ -2392,6 +2393,7 @@ __device__ __forceinline__ double ordered_sum(double a, const float* src, int n)
 // (point j in lane j & 63, register j >> 6), the terms go through LDS a chunk of kLatChunk points at a time, and the lanes that add them carry their
 // sums from chunk to chunk -- the additions of one sum are the same, in the same order, whatever the chunking.  (Two builds -- 256 and 1024
 // points of LDS -- ran side by side on two streams before; the fork and the join cost the call more than the second build saved.)
+constexpr int kLatRankBlocks = 512;  // blocks per restart and frame (grid y): a block loops over the ranks beyond
 constexpr int kLatChunk = 128;  // (256: 9.3 KB of LDS per restart, 17 per CU -- a frame's ~5000-7700 restarts took two rounds of residency; 128: one)
 static_assert(kLatPoints % kLatChunk == 0 && kLatChunk % 64 == 0, "k_welsch_lat: register / chunk layout");
 #ifndef CTAG_WLAT_WAVES
@@ -2833,6 +2835,29 @@ static void launch_quad_edges(const ChunkPlan& pl, const QuadPtrs& P, const Fram
     hipLaunchKernelGGL((k_quad_edges_packed<64, kWaveWordsMax, 1, true, REF>), dim3(nframes, pl.big_max_gx), dim3(64), kWaveWordsMax * 4, s_max, P, g, nframes, kWaveWords);
 }
 
+// K6s + K6b: the Welsch fits of the edge clusters in the workspace (line_count, line_desc, cl_pool -> line_fit).  launch_quads' tail, and all that the
+// test kit's probe of the stage runs (ctag_testkit_welsch_fit)
+hipError_t launch_line_fits(const ChunkPlan& pl, const Workspace& ws, hipStream_t s, unsigned long long* stamps, hipEvent_t ev_sorted) {
+    const int nframes = pl.nframes;
+    const QuadPtrs P = quad_ptrs(pl, ws, stamps);
+    hipLaunchKernelGGL(k_line_sort, dim3(nframes), dim3(kLineSortThreads), 0, s, P, nframes);
+    if (ev_sorted) (void)hipEventRecord(ev_sorted, s);
+    const bool welsch_lat = pl.latency && ws.welsch_rs;
+    if (welsch_lat) {  // one wave per (edge, restart); frames it declines (more edges / longer edges than it holds) fall through to k_welsch
+        hipLaunchKernelGGL(k_welsch_lat, dim3(20, kLatRankBlocks, nframes), dim3(64), 0, s, P, nframes, ws.welsch_rs);
+    }
+    hipLaunchKernelGGL(k_welsch, dim3(nframes, pl.welsch_gx + pl.welsch_gs), dim3(kWT), 0, s, P, nframes, welsch_lat ? ws.welsch_rs : (const float*)nullptr, pl.welsch_gx);
+    return hipPeekAtLastError();  // (not cleared: launch_quads reports a failed launch of any of its kernels at its own end)
+}
+
+// the limits at which the line fits change form, for the tests that build clusters at each of them (testkit.WELSCH_LIMITS names them in this order)
+int welsch_limits(int32_t* out, int capacity) {
+    const int32_t v[] = {kWShort, kWCap, kWRes, kWPts, kWPtsU, kPickN, kPickN2, kWE, kWT, kLatLines, kLatPoints, kLatChunk, kLdsLines, kLatencyFrames, kLatRankBlocks, kLineSortBuckets};
+    constexpr int n = (int)(sizeof(v) / sizeof(v[0]));
+    for (int i = 0; i < n && i < capacity; i++) out[i] = v[i];
+    return n;
+}
+
 hipError_t launch_quads(const ChunkPlan& pl, const Workspace& ws, hipStream_t s, hipEvent_t* ev5) {
     const int nframes = pl.nframes;
     int evi = 0;
@@ -2861,13 +2886,7 @@ hipError_t launch_quads(const ChunkPlan& pl, const Workspace& ws, hipStream_t s,
         (void)hipStreamWaitEvent(s, ws.ev_join, 0);
     }
     mark();
-    hipLaunchKernelGGL(k_line_sort, dim3(nframes), dim3(kLineSortThreads), 0, s, P, nframes);
-    mark();
-    const bool welsch_lat = pl.latency && ws.welsch_rs;
-    if (welsch_lat) {  // one wave per (edge, restart); frames it declines (more edges / longer edges than it holds) fall through to k_welsch
-        hipLaunchKernelGGL(k_welsch_lat, dim3(20, 512, nframes), dim3(64), 0, s, P, nframes, ws.welsch_rs);
-    }
-    hipLaunchKernelGGL(k_welsch, dim3(nframes, pl.welsch_gx + pl.welsch_gs), dim3(kWT), 0, s, P, nframes, welsch_lat ? ws.welsch_rs : (const float*)nullptr, pl.welsch_gx);
+    (void)launch_line_fits(pl, ws, s, P.stamps, ev5 ? ev5[evi++] : nullptr);
     mark();
     if (pl.latency) hipLaunchKernelGGL(k_quad_final<8>, dim3(std::min(ws.cand_cap, kLdsCand) / 8, nframes), dim3(64), 0, s, P, ws.g, nframes);
     else hipLaunchKernelGGL(k_quad_final<1>, dim3(std::min(ws.cand_cap, kLdsCand) / 64, nframes), dim3(64), 0, s, P, ws.g, nframes);

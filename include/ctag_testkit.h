@@ -33,6 +33,8 @@ extern "C" {
 #define CTAG_DBG_GRAY 9       /* uint8  [rows*cols]     gray image the BGR entry points computed (ctag_detect_batch_bgr8...) */
 #define CTAG_DBG_MASK 11      /* uint8  [hrows*hcols]   0 / 1: the adaptive-threshold mask of the fused sweep (k_decimate_mask); -1 when the last chunk took the two-kernel form */
 #define CTAG_DBG_LINES 10     /* int32  [nlines]        point count of every edge cluster handed to the Welsch fit (a4) */
+#define CTAG_DBG_LINE_POINTS 12 /* int32 [sum n][2]       x, y of those clusters' points, cluster after cluster in the order of CTAG_DBG_LINES */
+#define CTAG_DBG_LINE_FITS 13   /* float [nlines][4]      vx, vy, x0, y0 the Welsch fit gave every one of them */
 /* returns the number of ELEMENTS available (copies min(available, capacity) elements), < 0 on error */
 long ctag_debug_fetch(ctag_handle* h, int frame, int what, void* dst, size_t capacity_elems);
 
@@ -106,6 +108,24 @@ int ctag_synth3d_model(const int32_t* state, int dict_rows, int dict_cols, float
 int ctag_testkit_dense_edge_probe(ctag_handle* h, const uint8_t* gray, int rows, int cols, ptrdiff_t row_stride, const double* segments,
                                   int n_seg, const double* K, const double* dist, const double* rvec, const double* tvec,
                                   int samples_per_edge, double search_px, double min_contrast, double* out, int32_t* keep);
+
+/* ---- the Welsch line fits alone (k_line_sort + k_welsch, k_welsch_lat; cylindertag_amd/csrc/k_quad.hip: launch_line_fits) ---------
+ * Fits caller-built edge clusters with the very launcher the detection chain ends its quad stage with.  Works on the workspace of the
+ * handle's last chunk: run a detect call of at least n_frames (blank) frames of the size whose workspace is wanted first.  Frame f has
+ * edges_per_frame[f] clusters; points_per_edge lists their point counts and xy their points (host int32 [sum n][2], 0..65535), all
+ * frames back to back in input order.  The probe writes line_count, line_desc and cl_pool (clusters back to back from the start of a
+ * frame's pool, or -- tail_at_pool_end -- so that the frame's last point is the pool's last element, where the read one point past a
+ * cluster's last meets the pad of the allocation), runs the launcher on the handle's stream, waits, and copies line_fit back:
+ * lines = host float [sum edges][4] in input order.  latency: 0 = k_welsch alone, 1 = k_welsch_lat + the pick in k_welsch (the form
+ * of calls of a few frames).  welsch_gx / welsch_gs: k_welsch's blocks per frame for the long / short edges, 0 = the plan's defaults.
+ * CTAG_ERR_ARG where an input does not fit: n_frames above the last chunk's frames, latency with more than 4 frames, an edge of fewer
+ * than 2 points, more edges than the workspace's line_cap or more points than its cl_cap, a coordinate outside 16 bits. */
+int ctag_testkit_welsch_fit(ctag_handle* h, int n_frames, const int32_t* edges_per_frame, const int32_t* points_per_edge, const int32_t* xy,
+                            int latency, int welsch_gx, int welsch_gs, int tail_at_pool_end, float* lines);
+
+/* The sizes at which those kernels change form, in the order of testkit.WELSCH_LIMITS (kWShort, kWCap, ...); host only.  Writes min(capacity, count)
+ * int32 values, returns their count. */
+int ctag_testkit_welsch_limits(int32_t* out, int capacity);
 
 /* ---- the kernel forms the library picks for a chunk (plan_chunk, cylindertag_amd/csrc/ctag_api.hip) ------------------
  * For `nframes` frames of rows x cols (gray, or BGR for channels == 3) at `frames` (only its alignment is looked at) with the given

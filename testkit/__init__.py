@@ -18,19 +18,22 @@ TRUTH3D_DT = np.dtype([("n_markers", "<i4"), ("dict_row", "<i4", (8,)), ("_pad",
                        ("radius", "<f8", (8,))])
 TRUTH_DT = np.dtype([("n_markers", "<i4"), ("dict_row", "<i4", (8,)), ("strip_len", "<f4", (8,)),
                      ("corners", "<f4", (8, 8))])
-DBG_HALF, DBG_LABELS, DBG_CANDIDATES, DBG_CAND_QUADS, DBG_FEATURES0, DBG_FEATURES1, DBG_FEATURES2, DBG_PREMARKERS, DBG_GRAY, DBG_LINES, DBG_MASK = range(1, 12)
+DBG_HALF, DBG_LABELS, DBG_CANDIDATES, DBG_CAND_QUADS, DBG_FEATURES0, DBG_FEATURES1, DBG_FEATURES2, DBG_PREMARKERS, DBG_GRAY, DBG_LINES, DBG_MASK, DBG_LINE_POINTS, DBG_LINE_FITS = range(1, 14)
 SYNTH_SEED = 0x4354616753594E00  # "CTagSYN\0", SURVEY.md 8(d)
 
 # every symbol include/ctag_testkit.h declares (tests check the library exports all of them)
 EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
            "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model",
-           "ctag_testkit_dense_edge_probe", "ctag_testkit_plan"]
+           "ctag_testkit_dense_edge_probe", "ctag_testkit_plan", "ctag_testkit_welsch_fit", "ctag_testkit_welsch_limits"]
 # the fields ctag_testkit_plan writes, in order (cylindertag_amd/csrc/ctag_internal.h: ChunkPlan)
 PLAN_FIELDS = ("fused", "bgr_direct", "zero_first", "dec_zero_kernel", "dec_zero_list", "dec", "dec_xblocks", "dec_yblocks", "dec_band_rows", "dec_bands",
                "ccl", "latency", "small_cfg", "refprm", "mask_scan", "prescan", "all_wave", "fork", "pack_max", "big_points", "pack_gx", "scan_gx",
                "mscan_gx", "big_cols", "big_max_gx", "welsch_gs", "welsch_gx", "refine", "refine_gx", "refine_sums_gx")
 DEC_FORMS = ("mask", "mask_bands", "general", "wide", "banded135", "banded", "unaligned")  # ChunkPlan::dec
 CCL_FORMS = ("mask", "tw5", "any")                                                          # ChunkPlan::ccl
+# the values ctag_testkit_welsch_limits writes, in order (cylindertag_amd/csrc/k_quad.hip: welsch_limits)
+WELSCH_LIMITS = ("kWShort", "kWCap", "kWRes", "kWPts", "kWPtsU", "kPickN", "kPickN2", "kWE", "kWT", "kLatLines", "kLatPoints", "kLatChunk", "kLdsLines",
+                 "kLatencyFrames", "kLatRankBlocks", "kLineSortBuckets")
 REFINE_FORMS = ("none", "one", "split_large", "split_looping", "split")                     # ChunkPlan::refine
 
 
@@ -86,6 +89,10 @@ def load_library():
     L.ctag_testkit_dense_edge_probe.restype = C.c_int
     L.ctag_testkit_dense_edge_probe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_ssize_t, vp, C.c_int, vp, vp, vp, vp, C.c_int,
                                                 C.c_double, C.c_double, vp, vp]
+    L.ctag_testkit_welsch_fit.restype = C.c_int
+    L.ctag_testkit_welsch_fit.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.ctag_testkit_welsch_limits.restype = C.c_int
+    L.ctag_testkit_welsch_limits.argtypes = [i32p, C.c_int]
     _lib = L
     return L
 
@@ -158,6 +165,16 @@ def chunk_plan(rows, cols, nframes, adaptive_thresh=5, channels=1, corner_subpix
     return plan
 
 
+def welsch_limits():
+    """The sizes at which the Welsch fit kernels change form (ctag_testkit_welsch_limits) as a dict over WELSCH_LIMITS.  Host only."""
+    L = load_library()
+    out = np.zeros(len(WELSCH_LIMITS), np.int32)
+    n = L.ctag_testkit_welsch_limits(out.ctypes.data_as(C.POINTER(C.c_int32)), len(out))
+    if n != len(WELSCH_LIMITS):
+        raise RuntimeError("ctag_testkit_welsch_limits writes %d values, WELSCH_LIMITS names %d" % (n, len(WELSCH_LIMITS)))
+    return dict(zip(WELSCH_LIMITS, (int(v) for v in out)))
+
+
 class Detector(ca.Detector):
     """The product's Detector plus the test kit's entry points on the same handle."""
 
@@ -193,7 +210,7 @@ class Detector(ca.Detector):
             raise CtagError(-1, "ctag_debug_fetch(%d)" % what)
         if what in (DBG_HALF, DBG_GRAY, DBG_MASK):
             a = np.zeros(n, np.uint8)
-        elif what in (DBG_LABELS, DBG_CANDIDATES, DBG_LINES):
+        elif what in (DBG_LABELS, DBG_CANDIDATES, DBG_LINES, DBG_LINE_POINTS):
             a = np.zeros(n, np.int32)
         elif what == DBG_PREMARKERS:
             a = np.zeros(1, ca.RESULT_DT)
@@ -209,7 +226,25 @@ class Detector(ca.Detector):
             return a.reshape(-1, 19)
         if what == DBG_PREMARKERS:
             return a[0]
+        if what == DBG_LINE_POINTS:
+            return a.reshape(-1, 2)
+        if what == DBG_LINE_FITS:
+            return a.reshape(-1, 4)
         return a
+
+    def welsch_fit(self, frames, latency=0, welsch_gx=0, welsch_gs=0, tail_at_pool_end=False):
+        """The Welsch fit stage alone (ctag_testkit_welsch_fit) on the workspace of the last chunk: `frames` is a list of frames, each a list
+        of (n, 2) integer point clusters -> float32 [sum edges, 4] lines in input order.  Raises CtagError where the probe refuses the input."""
+        clusters = [np.asarray(c, np.int32).reshape(-1, 2) for f in frames for c in f]
+        edges = np.array([len(f) for f in frames], np.int32)
+        counts = np.array([len(c) for c in clusters], np.int32)
+        xy = np.ascontiguousarray(np.concatenate(clusters) if clusters else np.zeros((0, 2)), np.int32)
+        lines = np.zeros((len(clusters), 4), np.float32)
+        st = self.T.ctag_testkit_welsch_fit(self.h, len(frames), edges.ctypes.data, counts.ctypes.data, xy.ctypes.data, int(latency), int(welsch_gx),
+                                            int(welsch_gs), int(bool(tail_at_pool_end)), lines.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_testkit_welsch_fit")
+        return lines
 
     def dense_edge_probe(self, gray, segments, K, dist, rvec, tvec, samples_per_edge=8, search_px=3.0, min_contrast=8.0):
         """Edge search of the dense pose-refinement study on the device (ctag_testkit_dense_edge_probe): segments [n, 12]

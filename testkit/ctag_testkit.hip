@@ -374,6 +374,36 @@ long ctag_debug_fetch(ctag_handle* h, int frame, int what, void* dst, size_t cap
             }
             return (long)nl;
         }
+        case CTAG_DBG_LINE_POINTS:
+        case CTAG_DBG_LINE_FITS: {
+            int nl = 0;
+            if (!d2h(&nl, W.line_count + frame, 4)) return -2;
+            nl = std::min(nl, W.line_cap);
+            std::vector<LineDesc> d(std::max(nl, 1));
+            if (nl > 0 && !d2h(d.data(), W.line_desc + (size_t)frame * W.line_cap, sizeof(LineDesc) * nl)) return -2;
+            if (what == CTAG_DBG_LINE_FITS) {
+                if (dst && cap >= (size_t)nl * 4 && nl > 0 && !d2h(dst, W.line_fit + (size_t)frame * W.line_cap * 4, (size_t)nl * 16)) return -2;
+                return (long)nl * 4;
+            }
+            size_t total = 0, extent = 0;
+            for (int i = 0; i < nl; i++) {
+                if (d[i].n < 0 || (size_t)d[i].off + (size_t)d[i].n > (size_t)W.cl_cap) return -2;
+                total += (size_t)d[i].n;
+                extent = std::max(extent, (size_t)d[i].off + (size_t)d[i].n);
+            }
+            if (dst && cap >= total * 2 && total > 0) {
+                std::vector<uint32_t> pool(extent);
+                if (!d2h(pool.data(), W.cl_pool + (size_t)frame * W.cl_cap, extent * 4)) return -2;
+                int32_t* o = static_cast<int32_t*>(dst);
+                for (int i = 0; i < nl; i++)
+                    for (int j = 0; j < d[i].n; j++) {
+                        const uint32_t w = pool[(size_t)d[i].off + j];
+                        *o++ = (int32_t)(w & 0xffffu);
+                        *o++ = (int32_t)(w >> 16);
+                    }
+            }
+            return (long)(total * 2);
+        }
         case CTAG_DBG_PREMARKERS: {
             if (!v.keep_pre) return -1;
             if (dst && cap >= 1) {
@@ -527,6 +557,77 @@ int ctag_testkit_dense_edge_probe(ctag_handle* h, const uint8_t* gray, int rows,
     (void)hipFree(dkeep);
     return rc;
 }
+
+int ctag_testkit_welsch_fit(ctag_handle* h, int n_frames, const int32_t* edges_per_frame, const int32_t* points_per_edge, const int32_t* xy, int latency,
+                            int welsch_gx, int welsch_gs, int tail_at_pool_end, float* lines) {
+    if (!h || n_frames < 1 || !edges_per_frame || welsch_gx < 0 || welsch_gs < 0 || welsch_gx + welsch_gs > 65535) return CTAG_ERR_ARG;
+    HandleView v{};
+    handle_view(h, &v);
+    if (!v.ws || !v.ws->base || n_frames > v.last_chunk_frames) return CTAG_ERR_ARG;
+    const Workspace& W = *v.ws;
+    if (latency && (n_frames > kLatencyFrames || !W.welsch_rs)) return CTAG_ERR_ARG;
+    // the frames' descriptors and packed points as they will lie in the workspace; every limit is checked before anything is written
+    std::vector<std::vector<LineDesc>> desc(n_frames);
+    std::vector<std::vector<uint32_t>> pool(n_frames);
+    std::vector<uint32_t> base(n_frames, 0u);
+    size_t e0 = 0, p0 = 0;
+    for (int f = 0; f < n_frames; f++) {
+        const int L = edges_per_frame[f];
+        if (L < 0 || L > W.line_cap || (L > 0 && (!points_per_edge || !xy || !lines))) return CTAG_ERR_ARG;
+        size_t total = 0;
+        for (int i = 0; i < L; i++) {
+            const int n = points_per_edge[e0 + i];
+            if (n < 2 || (size_t)n > (size_t)W.cl_cap) return CTAG_ERR_ARG;
+            total += (size_t)n;
+            if (total > (size_t)W.cl_cap) return CTAG_ERR_ARG;
+        }
+        base[f] = tail_at_pool_end ? (uint32_t)(W.cl_cap - total) : 0u;
+        desc[f].resize(L);
+        pool[f].resize(total);
+        uint32_t off = 0;
+        for (int i = 0; i < L; i++) {
+            const int n = points_per_edge[e0 + i];
+            desc[f][i] = LineDesc{base[f] + off, n};
+            for (int j = 0; j < n; j++) {
+                const int32_t x = xy[(p0 + off + j) * 2], y = xy[(p0 + off + j) * 2 + 1];
+                if (x < 0 || x > 65535 || y < 0 || y > 65535) return CTAG_ERR_ARG;
+                pool[f][off + j] = (uint32_t)x | ((uint32_t)y << 16);
+            }
+            off += (uint32_t)n;
+        }
+        e0 += (size_t)L;
+        p0 += total;
+    }
+    TK_TRY(hipSetDevice(v.device));
+    hipStream_t s = static_cast<hipStream_t>(ctag_stream(h));
+    TK_TRY(hipStreamSynchronize(s));
+    TK_TRY(hipMemcpy(W.line_count, edges_per_frame, (size_t)n_frames * 4, hipMemcpyHostToDevice));
+    for (int f = 0; f < n_frames; f++) {
+        if (desc[f].empty()) continue;
+        TK_TRY(hipMemcpy(W.line_desc + (size_t)f * W.line_cap, desc[f].data(), desc[f].size() * sizeof(LineDesc), hipMemcpyHostToDevice));
+        TK_TRY(hipMemcpy(W.cl_pool + (size_t)f * W.cl_cap + base[f], pool[f].data(), pool[f].size() * 4, hipMemcpyHostToDevice));
+        TK_TRY(hipMemsetAsync(W.line_fit + (size_t)f * W.line_cap * 4, 0xff, desc[f].size() * 16, s));  // a line no kernel writes reads back as NaNs, not as an earlier call's
+    }
+    const FrameGeom& g = W.g;
+    ChunkPlan pl = plan_chunk(PlanIn{g.rows, g.cols, g.tw, n_frames, 1, 1, nullptr, 0, 0, W.kp, 0, 0, false, DevKnobs{}});
+    pl.latency = latency != 0;
+    if (welsch_gx > 0) pl.welsch_gx = welsch_gx;
+    if (welsch_gs > 0) pl.welsch_gs = welsch_gs;
+    if (launch_line_fits(pl, W, s) != hipSuccess) {
+        (void)hipGetLastError();  // (the launcher leaves it for its caller)
+        return CTAG_ERR_HIP;
+    }
+    TK_TRY(hipStreamSynchronize(s));
+    e0 = 0;
+    for (int f = 0; f < n_frames; f++) {
+        if (desc[f].empty()) continue;
+        TK_TRY(hipMemcpy(lines + e0 * 4, W.line_fit + (size_t)f * W.line_cap * 4, desc[f].size() * 16, hipMemcpyDeviceToHost));
+        e0 += desc[f].size();
+    }
+    return CTAG_OK;
+}
+
+int ctag_testkit_welsch_limits(int32_t* out, int capacity) { return welsch_limits(out, out ? std::max(capacity, 0) : 0); }
 
 int ctag_testkit_plan(int rows, int cols, int adaptive_thresh, int nframes, int channels, int corner_subpix, const void* frames, ptrdiff_t frame_stride,
                       ptrdiff_t row_stride, int fuse_mode, int wave_points, int bgr_direct, int expand_exact, int32_t* out, int capacity) {

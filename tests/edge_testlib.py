@@ -165,11 +165,15 @@ def _wods(px, py, w, f64):
     return np.stack([np.cos(t), np.sin(t), x, y], 1).astype(np.float32)
 
 
-def fitline_welsch(pts, path, site):
+def fitline_welsch(pts, path, site, trace=None):
     """cv::fitLine(points, DIST_WELSCH, 0, 0.01, 0.01) = fitLine2D: 20 restarts from random subsets, each up to 30 weighted L2
     refits with Welsch weights exp(-d^2 / 2.9846^2); the restart with the smallest error sum wins (first one on equal sums), and
     an error sum below n * FLT_EPSILON ends the search.  The restarts depend on each other only through the RNG, so they run
-    side by side here and are chosen between afterwards in order."""
+    side by side here and are chosen between afterwards in order.
+    `trace`: a dict that receives what the restarts did -- "iters" (20 ints: IRLS iterations run, i.e. error sums computed), "end" (20 of
+    "converged" / "eps" / "cap": the convergence test passed, an error sum fell below n * FLT_EPSILON, 30 iterations), "unweighted" (20
+    bools: a weight sum at or below FLT_EPSILON sent a refit to unit weights), "err" and "lines" (each restart's error sum and line as the
+    selection sees them), "chosen" (the restart whose line is returned) and "stopped" (the selection ended on an error sum below EPS)."""
     n = len(pts)
     f64 = path.f64
     dt = np.float64 if f64 else np.float32
@@ -182,6 +186,7 @@ def fitline_welsch(pts, path, site):
     prev = np.zeros_like(line)
     err = np.zeros(20)
     active = np.ones(20, bool)
+    iters, unweighted, end = np.zeros(20, int), np.zeros(20, bool), np.array(["cap"] * 20, dtype=object)
     for it in range(30):
         if it:
             t = line[:, 0] * prev[:, 0] + line[:, 1] * prev[:, 1]  # float products and sum, then widened
@@ -194,6 +199,7 @@ def fitline_welsch(pts, path, site):
                 path.note(site + ".welsch_angle", t[k], math.cos(adelta), 1.0)
                 if ang[k] < adelta:
                     path.note(site + ".welsch_shift", d[k], rdelta, abs(float(line[k, 2])) + abs(float(line[k, 3])) + 1.0)
+            end[active & (ang < adelta) & (d < rdelta)] = "converged"
             active &= ~((ang < adelta) & (d < rdelta))
             if not active.any():
                 break
@@ -202,6 +208,8 @@ def fitline_welsch(pts, path, site):
         dist = np.abs(line[:, 1:2] * xr + (-line[:, 0:1]) * yr)
         e = _seqsum(dist.astype(np.float64))
         err = np.where(active, e, err)
+        iters += active
+        end[active & (e < EPS)] = "eps"
         active &= ~(e < EPS)
         if not active.any():
             break
@@ -209,6 +217,7 @@ def fitline_welsch(pts, path, site):
         ww = np.exp(-dist * dist * c * c) if f64 else MATH.expf(-dist * dist * c * c)
         sw = _seqsum(ww.astype(np.float64))
         big = np.abs(sw) > FLT_EPSILON
+        unweighted |= active & ~big
         ww = np.where(big[:, None], (ww * (1.0 / np.where(big, sw, 1.0))[:, None]).astype(dt), dt(1))
         newline = _wods(px, py, ww, f64)
         prev = np.where(active[:, None], line, prev)
@@ -237,6 +246,9 @@ def fitline_welsch(pts, path, site):
             rivals.append(e)
     if rivals:
         path.note(site + ".welsch_min", min(rivals), min_err, n * (abs(lb[2]) + abs(lb[3]) + 1.0))
+    if trace is not None:
+        trace.update(iters=iters, end=end, unweighted=unweighted, err=np.array(err, np.float64), lines=np.array(line), chosen=best,
+                     stopped=bool(min_err < EPS))
     return [float(v) for v in line[best]]
 
 

@@ -40,6 +40,8 @@ def test_the_opencv_assumptions_are_switches_on_both_sides():
     rc, rep = _run(lib, 1, 16)
     assert rc == 0 and not rep["mismatches"], rep
     assert rep["oracle_records_that_differ_from_the_default_oracle"] > 0, "the switches change nothing on these frames: the test would not notice a missing one"
+    assert rep["probe_clusters"] > 3000 and rep["probe_mismatches"] == 0, rep
+    assert rep["probe_clusters_the_variants_disagree_on"] > 0, "the two placements agree on every probe cluster: the probe step would not notice the wrong one"
     # and the switches matter: the DEFAULT build is not the variant oracle's equal (it is the default oracle's -- every other GPU test)
     rc, rep = _run(None, 1, 16)
     assert rc == 1 and rep["mismatches"], rep
@@ -49,3 +51,4 @@ def test_plain_barriers_in_edge_refine_give_the_same_records():
     lib = _variant("plainsync", "-DCTAG_REFINE_PLAIN_SYNC=1")
     rc, rep = _run(lib, 0, 8)
     assert rc == 0 and not rep["mismatches"], rep
+    assert rep["probe_clusters"] > 3000 and rep["probe_mismatches"] == 0, rep

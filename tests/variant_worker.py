@@ -1,7 +1,9 @@
 """Child process of tests/test_variant_builds_gpu.py: ONE build of the library (CTAG_HIP_LIB, set by the parent before anything imports the
 binding) against the oracle with the matching switches.  Every record must equal the oracle's byte for byte: test.bmp and sequence frames one
 per call (the few-frame kernels), a batch of sequence frames and of synthetic frames (the batch kernels), and -- for the resize switch -- frames
-whose half width is not a multiple of 16, even and odd sized.  Prints one JSON line; exit code 1 on any difference."""
+whose half width is not a multiple of 16, even and odd sized.  Then the Welsch fit stage alone (the test kit's probe) on the size tiers and the
+branch clusters of tests/welsch_shapes.py, batch and few-frame form, against the oracle's fit with the same placement of the `err < min_err` update: the
+build with the in-loop placement has restart code of its own and never regroups.  Prints one JSON line; exit code 1 on any difference."""
 import argparse
 import json
 import os
@@ -54,9 +56,23 @@ def main():
                 differs_from_default += want != defaults["batch %d" % k]
             if got[k].tobytes() != want:
                 bad.append("batch frame %d (chunk %d)" % (k, chunk))
+    # the Welsch fits alone, on the workspace of a chunk of 32 blank frames
+    import welsch_shapes as ws
+    det.set_option(capi.OPT_MAX_CHUNK, 1024)
+    det.set_option(capi.OPT_STREAMS, 1)
+    det.detect_batch(np.full((32,) + ws.HD, 255, np.uint8))
+    fit = lambda c: orc.fitline_welsch_variant(c, a.welsch)
+    probe_clusters, probe_bad, disagree, lines = 0, [], 0, {}
+    for batch in (ws.size_edges(), ws.branch_batch()):
+        n, miss = ws.probe_mismatches(det, batch, fit, [c for c in batch["calls"] if not c["tail"]], lines)
+        probe_clusters += n
+        probe_bad += miss
+        disagree += sum(orc.fitline_welsch_variant(c, 0).tobytes() != orc.fitline_welsch_variant(c, 1).tobytes() for _, f in batch["frames"] for c in f)
+    bad += probe_bad[:10]
     det.close()
     print(json.dumps({"lib": os.environ.get("CTAG_HIP_LIB", "default"), "welsch_minerr_in_loop": a.welsch, "resize_simd_lanes": a.lanes,
                       "records": len(singles) + 2 * (len(seq) + len(syn)), "mismatches": bad[:10],
+                      "probe_clusters": probe_clusters, "probe_mismatches": len(probe_bad), "probe_clusters_the_variants_disagree_on": int(disagree),
                       "oracle_records_that_differ_from_the_default_oracle": int(differs_from_default)}), flush=True)
     return 1 if bad else 0
 
