@@ -29,7 +29,9 @@ EXPORTS = ["ctag_create", "ctag_create_ex", "ctag_params_default", "ctag_destroy
 POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag_model_get_view", "ctag_camera_load",
                 "ctag_pose_batch_device", "ctag_estimate_pose", "ctag_pose_last_ms", "ctag_draw_axis", "ctag_draw_axis_batch_device",
                 "ctag_rigs_create", "ctag_rigs_free", "ctag_rig_pose_batch_device", "ctag_estimate_rig_pose",
-                "ctag_camera_set_create", "ctag_camera_set_free", "ctag_mv_rig_pose_batch_device", "ctag_estimate_mv_rig_pose"]
+                "ctag_camera_set_create", "ctag_camera_set_free", "ctag_mv_rig_pose_batch_device", "ctag_estimate_mv_rig_pose",
+                "ctag_cov_opts_default", "ctag_pose_cov_batch_device", "ctag_rig_pose_cov_batch_device", "ctag_mv_rig_pose_cov_batch_device",
+                "ctag_estimate_pose_cov", "ctag_estimate_rig_pose_cov", "ctag_estimate_mv_rig_pose_cov"]
 # ... and include/ctag_gather.h
 GATHER_EXPORTS = ["ctag_shard_range", "ctag_packed_capacity", "ctag_pack_results", "ctag_unpack_results", "ctag_comm_unique_id",
                   "ctag_comm_init", "ctag_comm_attach", "ctag_comm_destroy", "ctag_comm_native", "ctag_comm_last_error", "ctag_gather_begin",
@@ -56,6 +58,13 @@ MV_POSE_DT = np.dtype([("status", "<i4"), ("rig", "<i4"), ("frame", "<i4"), ("n_
                        ("cost_cam0", "<f8"), ("cost_cam", "<f8"), ("rvec_start", "<f8", (3,)), ("tvec_start", "<f8", (3,)), ("cost0", "<f8"),
                        ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("cost", "<f8")])
 assert MV_POSE_DT.itemsize == 432
+# ctag_pose_cov_rec: the covariance and residual diagnostics of one pose record of any kind (include/ctag_pose.h)
+POSE_COV_DT = np.dtype([("status", "<i4"), ("n_points", "<i4"), ("dof", "<i4"), ("worst_point", "<i4"), ("n_outliers", "<i4"), ("param", "<i4"),
+                        ("cost", "<f8"), ("sigma2_hat", "<f8"), ("sigma2_used", "<f8"), ("max_residual_px", "<f8"), ("min_pivot", "<f8"),
+                        ("cov", "<f8", (6, 6))])
+assert POSE_COV_DT.itemsize == 352
+COV_OK, COV_NO_POSE, COV_BAD_RECORD, COV_SINGULAR = range(4)
+COV_PARAM_TANGENT, COV_PARAM_RVEC = 0, 1
 
 
 class ParamsC(C.Structure):  # ctag_params (include/ctag_types.h): the reference's tunables
@@ -87,6 +96,23 @@ class CameraC(C.Structure):  # ctag_camera
 
 class CameraPoseC(C.Structure):  # ctag_camera_pose: X_cam = R(rvec) X_ref + tvec
     _fields_ = [("rvec", C.c_double * 3), ("tvec", C.c_double * 3)]
+
+
+class CovOptsC(C.Structure):  # ctag_cov_opts
+    _fields_ = [("struct_size", C.c_uint32), ("param", C.c_int32), ("sigma_px", C.c_double), ("outlier_k", C.c_double)]
+
+
+def cov_opts(param=None, sigma_px=None, outlier_k=None):
+    """ctag_cov_opts_default, then the given fields."""
+    o = CovOptsC()
+    load_library().ctag_cov_opts_default(C.byref(o))
+    if param is not None:
+        o.param = int(param)
+    if sigma_px is not None:
+        o.sigma_px = float(sigma_px)
+    if outlier_k is not None:
+        o.outlier_k = float(outlier_k)
+    return o
 
 
 class ModelViewC(C.Structure):  # ctag_model_view
@@ -212,6 +238,21 @@ def load_library():
     L.ctag_mv_rig_pose_batch_device.argtypes = [vp, C.POINTER(vp), C.c_int, vp, vp, vp, vp]
     L.ctag_estimate_mv_rig_pose.restype = C.c_int
     L.ctag_estimate_mv_rig_pose.argtypes = [vp, vp, vp, vp, vp, vp]
+    optp = C.POINTER(CovOptsC)
+    L.ctag_cov_opts_default.restype = None
+    L.ctag_cov_opts_default.argtypes = [optp]
+    L.ctag_pose_cov_batch_device.restype = C.c_int
+    L.ctag_pose_cov_batch_device.argtypes = [vp, vp, C.c_int, vp, C.POINTER(CameraC), vp, vp, C.c_int, optp, vp]
+    L.ctag_rig_pose_cov_batch_device.restype = C.c_int
+    L.ctag_rig_pose_cov_batch_device.argtypes = [vp, vp, C.c_int, vp, vp, C.POINTER(CameraC), vp, optp, vp]
+    L.ctag_mv_rig_pose_cov_batch_device.restype = C.c_int
+    L.ctag_mv_rig_pose_cov_batch_device.argtypes = [vp, C.POINTER(vp), C.c_int, vp, vp, vp, vp, optp, vp]
+    L.ctag_estimate_pose_cov.restype = C.c_int
+    L.ctag_estimate_pose_cov.argtypes = [vp, vp, vp, C.POINTER(CameraC), vp, optp, vp]
+    L.ctag_estimate_rig_pose_cov.restype = C.c_int
+    L.ctag_estimate_rig_pose_cov.argtypes = [vp, vp, vp, vp, C.POINTER(CameraC), vp, optp, vp]
+    L.ctag_estimate_mv_rig_pose_cov.restype = C.c_int
+    L.ctag_estimate_mv_rig_pose_cov.argtypes = [vp, vp, vp, vp, vp, vp, optp, vp]
     u64p = C.POINTER(C.c_uint64)
     L.ctag_shard_range.restype = C.c_int
     L.ctag_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -682,6 +723,80 @@ class Detector:
 
     def pose_last_ms(self):
         return float(self.L.ctag_pose_last_ms(self.h))
+
+    # ---- pose covariance (include/ctag_pose.h): opts is a CovOptsC (cov_opts(...)) or None for the defaults
+    @staticmethod
+    def _optp(opts):
+        return C.byref(opts) if opts is not None else None
+
+    def pose_cov(self, result, poses, model, camera, opts=None):
+        """One frame: its host ctag_frame_result record and the POSE_DT records of estimate_pose -> one POSE_COV_DT record per marker."""
+        res = np.ascontiguousarray(result).reshape(1)
+        assert res.dtype == RESULT_DT
+        n = int(res[0]["n_markers"]) if res[0]["status"] == 0 else 0
+        poses = np.ascontiguousarray(poses, POSE_DT).reshape(-1)
+        if len(poses) != n:
+            raise ValueError("%d pose records for %d markers" % (len(poses), n))
+        out = np.zeros(max(n, 1), POSE_COV_DT)
+        st = self.L.ctag_estimate_pose_cov(self.h, res.ctypes.data, model.m, C.byref(camera), poses.ctypes.data if n else None,
+                                           self._optp(opts), out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_estimate_pose_cov")
+        return out[:n]
+
+    def pose_cov_batch_device(self, results_ptr, n_frames, model, camera, offsets_ptr, poses_ptr, capacity, out_ptr, opts=None):
+        """Device pointers as pose_batch_device left them -> POSE_COV_DT record w for pose record w at out_ptr; enqueued, does not wait."""
+        st = self.L.ctag_pose_cov_batch_device(self.h, results_ptr, n_frames, model.m, C.byref(camera), offsets_ptr, poses_ptr, capacity,
+                                               self._optp(opts), out_ptr)
+        if st != 0:
+            raise CtagError(st, "ctag_pose_cov_batch_device")
+
+    def rig_pose_cov(self, result, rig_poses, model, rigs, camera, opts=None):
+        """One frame: its host record and the RIG_POSE_DT records of estimate_rig_pose -> rigs.n_rigs POSE_COV_DT records."""
+        res = np.ascontiguousarray(result).reshape(1)
+        assert res.dtype == RESULT_DT
+        rig_poses = np.ascontiguousarray(rig_poses, RIG_POSE_DT).reshape(-1)
+        if len(rig_poses) != rigs.n_rigs:
+            raise ValueError("%d rig pose records for %d rigs" % (len(rig_poses), rigs.n_rigs))
+        out = np.zeros(rigs.n_rigs, POSE_COV_DT)
+        st = self.L.ctag_estimate_rig_pose_cov(self.h, res.ctypes.data, model.m, rigs.r, C.byref(camera), rig_poses.ctypes.data,
+                                               self._optp(opts), out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_estimate_rig_pose_cov")
+        return out
+
+    def rig_pose_cov_batch_device(self, results_ptr, n_frames, model, rigs, camera, rig_poses_ptr, out_ptr, opts=None):
+        """n_frames * rigs.n_rigs device RIG_POSE_DT records -> as many device POSE_COV_DT records at out_ptr; enqueued."""
+        st = self.L.ctag_rig_pose_cov_batch_device(self.h, results_ptr, n_frames, model.m, rigs.r, C.byref(camera), rig_poses_ptr,
+                                                   self._optp(opts), out_ptr)
+        if st != 0:
+            raise CtagError(st, "ctag_rig_pose_cov_batch_device")
+
+    def mv_rig_pose_cov(self, results, mv_poses, model, rigs, cams, opts=None):
+        """One instant: cams.n host records and the MV_POSE_DT records of estimate_mv_rig_pose -> rigs.n_rigs POSE_COV_DT records."""
+        res = np.ascontiguousarray(results).reshape(-1)
+        assert res.dtype == RESULT_DT
+        if len(res) != cams.n:
+            raise ValueError("%d records for %d cameras" % (len(res), cams.n))
+        mv_poses = np.ascontiguousarray(mv_poses, MV_POSE_DT).reshape(-1)
+        if len(mv_poses) != rigs.n_rigs:
+            raise ValueError("%d pose records for %d rigs" % (len(mv_poses), rigs.n_rigs))
+        out = np.zeros(rigs.n_rigs, POSE_COV_DT)
+        st = self.L.ctag_estimate_mv_rig_pose_cov(self.h, res.ctypes.data, model.m, rigs.r, cams.s, mv_poses.ctypes.data, self._optp(opts),
+                                                  out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_estimate_mv_rig_pose_cov")
+        return out
+
+    def mv_rig_pose_cov_batch_device(self, results_ptrs, n_frames, model, rigs, cams, mv_poses_ptr, out_ptr, opts=None):
+        """results_ptrs: one device pointer per camera; n_frames * rigs.n_rigs device MV_POSE_DT records -> as many POSE_COV_DT records."""
+        ptrs = list(results_ptrs)
+        if len(ptrs) != cams.n:
+            raise ValueError("%d pointers for %d cameras" % (len(ptrs), cams.n))
+        arr = (C.c_void_p * max(len(ptrs), 1))(*[C.c_void_p(int(p) if p else None) for p in ptrs])
+        st = self.L.ctag_mv_rig_pose_cov_batch_device(self.h, arr, n_frames, model.m, rigs.r, cams.s, mv_poses_ptr, self._optp(opts), out_ptr)
+        if st != 0:
+            raise CtagError(st, "ctag_mv_rig_pose_cov_batch_device")
 
     # ---- overlay (CylinderTag::drawAxis)
     def draw_axis(self, gray, result, poses, model, camera, axis_length=5, out=None):

@@ -297,6 +297,57 @@ void CylinderTag::estimatePose(const Mat& img, std::vector<MarkerInfo> markers, 
     }
 }
 
+void CylinderTag::estimatePoseCovariance(std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, CamInfo camera,
+                                         std::vector<PoseCovInfo>& covariance, bool tangent, double sigmaPx, double outlierK) {
+    covariance.clear();
+    if (markers.empty()) return;
+    for (const MarkerInfo& mi : markers)
+        if (mi.cornerLists.size() > (size_t)CTAG_MAX_FEATURES) throw std::string("estimatePoseCovariance, a marker with more than 100 features\n");
+    ctag_model* model = make_model(reconstruct_model, __FUNCTION__);
+    const ctag_camera cam = make_camera(camera);
+    ctag_cov_opts opts;
+    ctag_cov_opts_default(&opts);
+    opts.param = tangent ? CTAG_COV_PARAM_TANGENT : CTAG_COV_PARAM_RVEC;
+    opts.sigma_px = sigmaPx;
+    opts.outlier_k = outlierK;
+    std::vector<ctag_pose_rec> rec;
+    std::vector<ctag_pose_cov_rec> cov;
+    for (size_t first = 0; first < markers.size();) {  // one record (<= 100 markers / features) at a time, as estimatePose
+        ctag_frame_result res;
+        const size_t next = flatten(markers, first, res);
+        const size_t at = rec.size();
+        rec.resize(at + (size_t)res.n_markers);
+        cov.resize(at + (size_t)res.n_markers);
+        int st = ctag_estimate_pose(h_, &res, model, &cam, rec.data() + at);
+        if (st == CTAG_OK) st = ctag_estimate_pose_cov(h_, &res, model, &cam, rec.data() + at, &opts, cov.data() + at);
+        if (st != CTAG_OK) {
+            ctag_model_free(model);
+            throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+        }
+        first = next;
+    }
+    ctag_model_free(model);
+    for (size_t i = 0; i < rec.size(); i++) {
+        if (rec[i].status == CTAG_POSE_NO_MODEL) continue;  // erased, as in estimatePose
+        if (rec[i].status != CTAG_POSE_OK) throw __FUNCTION__ + std::string(", ") + "marker without a usable point set\n";
+        const ctag_pose_cov_rec& c = cov[i];
+        PoseCovInfo ci;
+        ci.markerID = rec[i].model_index;
+        ci.status = c.status;
+        ci.nPoints = c.n_points;
+        ci.dof = c.dof;
+        ci.worstPoint = c.worst_point;
+        ci.nOutliers = c.n_outliers;
+        ci.cost = c.cost;
+        ci.sigma2Hat = c.sigma2_hat;
+        ci.sigma2Used = c.sigma2_used;
+        ci.maxResidualPx = c.max_residual_px;
+        ci.minPivot = c.min_pivot;
+        for (int k = 0; k < 36; k++) ci.cov[k] = c.cov[k];
+        covariance.push_back(ci);
+    }
+}
+
 void CylinderTag::estimateRigPose(std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, const std::vector<int>& rigOfModel,
                                   CamInfo camera, std::vector<RigPoseInfo>& pose) {
     pose.clear();

@@ -117,6 +117,15 @@ struct ViewPose {
     double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
 };
 #endif
+// covariance and residual diagnostics of one per-marker pose (new): the fields of ctag_pose_cov_rec (include/ctag_pose.h, pose
+// covariance) for the PoseInfo with the same markerID at the same place of estimatePose's list
+struct PoseCovInfo {
+    int markerID = -1;
+    int status = 0;  // CTAG_COV_*; every other field is 0 unless it is CTAG_COV_OK
+    int nPoints = 0, dof = 0, worstPoint = 0, nOutliers = 0;
+    double cost = 0, sigma2Hat = 0, sigma2Used = 0, maxResidualPx = 0, minPivot = 0;
+    double cov[36] = {0};  // row-major 6x6: rows / columns 0-2 rotation (rad), 3-5 translation (model units)
+};
 // the annotated frame of drawAxis: rows x cols pixels of 3 bytes, channel c = Scalar component c (imgMark in the reference)
 struct AxisImage {
     int rows = 0, cols = 0;
@@ -162,6 +171,12 @@ class CylinderTag {
     // useDensePoseRefine is accepted and ignored: the reference's DenseSolver is empty (pose_estimation.cpp:145-148).
     void estimatePose(const ctag_host::Mat& img, std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, CamInfo camera,
                       std::vector<PoseInfo>& pose, bool useDensePoseRefine = false);
+    // Covariance of estimatePose's poses (new; ctag_estimate_pose_cov): the poses are estimated again from `markers`, and covariance[i]
+    // describes the pose estimatePose returns at place i (markers without a model are erased in both).  tangent: the unknowns are
+    // R <- Exp(dw) R, t <- t + dt with dw in the camera frame (CTAG_COV_PARAM_TANGENT), else (rvec, tvec) themselves; sigmaPx > 0:
+    // the pixel noise to assume, else the residuals' own estimate; outlierK as ctag_cov_opts::outlier_k.
+    void estimatePoseCovariance(std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, CamInfo camera,
+                                std::vector<PoseCovInfo>& covariance, bool tangent = true, double sigmaPx = 0.0, double outlierK = 3.0);
 
     // One pose per rig of markers (new; include/ctag_pose.h, ctag_estimate_rig_pose): rigOfModel[i] is the rig of model i (-1: none,
     // rigs 0 .. max), the models of one rig share one frame.  The pose of a rig is EPnP + PoseBA over the union of its member

@@ -5,6 +5,7 @@
 // of a point as a policy (one camera: camera_residual; a camera per point: k_mv_pose.hip); pose_solve is the two in a row.
 // Generic over the LDS capacity PTS and the block width NT: per-point loops stride over the NT lanes, while every sum over
 // the points stays with its one owner lane (lane < 144 / 34), so the result is the sequential evaluation for any n <= PTS.
+// k_pose_cov.hip (the covariance of a finished pose) reads the correspondence rule, the corner loader and the residuals from here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -185,23 +186,30 @@ __device__ __forceinline__ int model_lookup(const PoseModelDev& model, int marke
     return -1;
 }
 
-// lane q < cnt of an emit: corner q of feature F (order 0 1 4 5 2 3 6 7) as point i of the problem; `corners` is the model's
+// corner q of an emit (order 0 1 4 5 2 3 6 7) of feature F at model position pos: its pixel undistorted to normalised
+// coordinates (xn, yn), the BA observation ob[2] (through K, rounded to float) and the model point X[3]; `corners` is the model's
 // corner list
+__device__ __forceinline__ void corner_point(const PoseCam& cam, const float* __restrict__ corners, const ctag_feature_rec& F, int pos, int q,
+                                             double& xn, double& yn, double* ob, double* X) {
+    const int k = q < 2 ? q : q < 4 ? q + 2 : q < 6 ? q - 2 : q;  // 0 1 4 5 2 3 6 7
+    const double u = (double)F.corners[2 * k], v = (double)F.corners[2 * k + 1];
+    undistort_normalised(cam, u, v, xn, yn);
+    ob[0] = (double)(float)(cam.fx * xn + cam.cx);
+    ob[1] = (double)(float)(cam.fy * yn + cam.cy);
+    const float* cp = corners + (pos * 8 + k) * 3;
+    X[0] = (double)cp[0];
+    X[1] = (double)cp[1];
+    X[2] = (double)cp[2];
+}
+
+// lane q < cnt of an emit: that corner as point i of the problem
 template <int PTS>
 __device__ __forceinline__ void load_point(PoseLds<PTS>& S, const PoseCam& cam, const float* __restrict__ corners, const ctag_feature_rec& F,
                                            int pos, int q, int i) {
-    const int k = q < 2 ? q : q < 4 ? q + 2 : q < 6 ? q - 2 : q;  // 0 1 4 5 2 3 6 7
-    const double u = (double)F.corners[2 * k], v = (double)F.corners[2 * k + 1];
     double xn, yn;
-    undistort_normalised(cam, u, v, xn, yn);
+    corner_point(cam, corners, F, pos, q, xn, yn, S.OBS + 2 * i, S.X + 3 * i);
     S.u.e.US[2 * i] = (double)(float)xn * cam.fx + cam.cx;
     S.u.e.US[2 * i + 1] = (double)(float)yn * cam.fy + cam.cy;
-    S.OBS[2 * i] = (double)(float)(cam.fx * xn + cam.cx);
-    S.OBS[2 * i + 1] = (double)(float)(cam.fy * yn + cam.cy);
-    const float* cp = corners + (pos * 8 + k) * 3;
-    S.X[3 * i] = (double)cp[0];
-    S.X[3 * i + 1] = (double)cp[1];
-    S.X[3 * i + 2] = (double)cp[2];
 }
 
 // EPnP (solvePnP SOLVEPNP_EPNP) over the n >= 4 points the block has loaded into S (X, u.e.US), by the NT threads of the
@@ -802,4 +810,60 @@ __device__ __forceinline__ void pose_solve(PoseLds<PTS>& S, const int lane, cons
     }
 }
 
+// ---- several cameras (k_mv_pose.hip, k_pose_cov.hip) --------------------------------------------------------------------------
+constexpr int kMvCams = CTAG_MV_MAX_CAMERAS;
+
+// the camera set as the kernels take it, by value
+struct MvCams {
+    int n;
+    int at_reference[kMvCams];  // the camera's pose is exactly zero: its frame is the reference frame
+    PoseCam cam[kMvCams];
+    double R[kMvCams][9];  // Rc = R(rvec), row-major
+    double t[kMvCams][3];  // tc
+};
+
+struct MvResults {
+    const ctag_frame_result* p[kMvCams];  // device pointers, n_frames records each
+};
+
+// residual and Jacobian rows of point p seen by a camera at (Rc, tc) in the reference frame, under the rig pose (R, dR, x):
+// Q = Rc (R p + t) + tc, the projection of point_residual on Q, and Rc applied to the rows point_residual forms
+__device__ __forceinline__ void mv_point_residual(const double* R, const double* dR, const double* x, const PoseCam& cam, const double* Rc,
+                                                  const double* tc, const double* p, const double* ob, double& r0, double& r1, double* j0,
+                                                  double* j1) {
+    const double P0 = (R[0] * p[0] + R[1] * p[1] + R[2] * p[2]) + x[3];
+    const double P1 = (R[3] * p[0] + R[4] * p[1] + R[5] * p[2]) + x[4];
+    const double P2 = (R[6] * p[0] + R[7] * p[1] + R[8] * p[2]) + x[5];
+    const double Q0 = (Rc[0] * P0 + Rc[1] * P1 + Rc[2] * P2) + tc[0];
+    const double Q1 = (Rc[3] * P0 + Rc[4] * P1 + Rc[5] * P2) + tc[1];
+    const double Q2 = (Rc[6] * P0 + Rc[7] * P1 + Rc[8] * P2) + tc[2];
+    const double iz = 1.0 / Q2;
+    r0 = (cam.fx * (Q0 * iz) + cam.cx) - ob[0];
+    r1 = (cam.fy * (Q1 * iz) + cam.cy) - ob[1];
+    const double a0 = cam.fx * iz, a1 = cam.fy * iz;
+    const double b0 = cam.fx * Q0 * iz * iz, b1 = cam.fy * Q1 * iz * iz;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double* D = dR + 9 * k;
+        const double d0 = D[0] * p[0] + D[1] * p[1] + D[2] * p[2];
+        const double d1 = D[3] * p[0] + D[4] * p[1] + D[5] * p[2];
+        const double d2 = D[6] * p[0] + D[7] * p[1] + D[8] * p[2];
+        const double e0 = Rc[0] * d0 + Rc[1] * d1 + Rc[2] * d2;
+        const double e1 = Rc[3] * d0 + Rc[4] * d1 + Rc[5] * d2;
+        const double e2 = Rc[6] * d0 + Rc[7] * d1 + Rc[8] * d2;
+        j0[k] = a0 * e0 - b0 * e2;
+        j1[k] = a1 * e1 - b1 * e2;
+    }
+#pragma unroll
+    for (int m = 0; m < 3; m++) {  // dQ/dt = Rc
+        j0[3 + m] = a0 * Rc[m] - b0 * Rc[6 + m];
+        j1[3 + m] = a1 * Rc[3 + m] - b1 * Rc[6 + m];
+    }
+}
+
 }  // namespace ctag
+
+// ctag_camera_set (opaque in include/ctag_pose.h)
+struct ctag_camera_set {
+    ctag::MvCams dev;
+};

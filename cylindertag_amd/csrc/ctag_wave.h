@@ -121,6 +121,46 @@ __device__ __forceinline__ void sg_best(float& bd, int& bi, Better better) {
     }
 }
 
+// FP64 over the wave (k_pose_cov.hip).  A double moves as its two halves.  The sum is one fixed tree -- lane ^ 1, lane ^ 2, the other quad of 8, the other
+// half of the row, then the four rows' values added in row order -- and every step adds the same two numbers in both lanes of a pair, so all 64 lanes end
+// with the same bits, and the same inputs give the same bits wherever the wave runs.  It is NOT the sum in lane order.
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov(double v) { return __hiloint2double(dpp_mov<CTRL>(__double2hiint(v)), dpp_mov<CTRL>(__double2loint(v))); }
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    v += dpp_mov<kDppXor1>(v);
+    v += dpp_mov<kDppXor2>(v);
+    v += dpp_mov<kDppHalfMirror>(v);
+    v += dpp_mov<kDppRowMirror>(v);
+    return ((readlane_f64(v, 0) + readlane_f64(v, 16)) + readlane_f64(v, 32)) + readlane_f64(v, 48);
+}
+// the largest d of the wave and its index, the lowest index among equal d (a total order: the tree's shape does not matter); every lane ends with the pair
+__device__ __forceinline__ void wave_max_f64(double& bd, int& bi) {
+    auto step = [&](double od, int oi) {
+        if (od > bd || (od == bd && oi < bi)) {
+            bd = od;
+            bi = oi;
+        }
+    };
+    step(dpp_mov<kDppXor1>(bd), dpp_mov<kDppXor1>(bi));
+    step(dpp_mov<kDppXor2>(bd), dpp_mov<kDppXor2>(bi));
+    step(dpp_mov<kDppHalfMirror>(bd), dpp_mov<kDppHalfMirror>(bi));
+    step(dpp_mov<kDppRowMirror>(bd), dpp_mov<kDppRowMirror>(bi));
+    double rd[4];
+    int ri[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        rd[r] = readlane_f64(bd, 16 * r);
+        ri[r] = __builtin_amdgcn_readlane(bi, 16 * r);
+    }
+    bd = rd[0];
+    bi = ri[0];
+#pragma unroll
+    for (int r = 1; r < 4; r++) step(rd[r], ri[r]);
+}
+
 // ---- packed 16-bit min / max (v_pk_min_u16 / v_pk_max_u16) on the two halves of a word ---------------------------------------------------------------
 typedef unsigned short ctag_us2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ ctag_us2 as_us2(uint32_t a) { return __builtin_bit_cast(ctag_us2, a); }

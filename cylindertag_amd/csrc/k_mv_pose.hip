@@ -9,7 +9,8 @@
 // A solve loads the start camera's points and runs EPnP + PoseBA on them (stage 1: pose_epnp and pose_ba of ctag_pose_dev.h with
 // the one-camera residual, the bytes of k_rig_solve), moves that pose into the reference frame, then lays out the points of all
 // cameras with a per-point camera index and runs pose_ba once more with the residual that carries a camera per point (stage 2).
-// The cameras (intrinsics, Rc, tc) sit in LDS beside the problem's image.
+// The cameras (intrinsics, Rc, tc) sit in LDS beside the problem's image.  The camera set (MvCams, ctag_camera_set) and the
+// per-camera residual are stated in ctag_pose_dev.h: the covariance of k_pose_cov.hip reads them too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,32 +26,9 @@ static_assert(CTAG_MV_MAX_CAMERAS <= 255, "the per-point camera index is one byt
 
 namespace ctag {
 
-constexpr int kMvCams = CTAG_MV_MAX_CAMERAS;
 constexpr int kMvSmallPts = kPoseMaxPts;         // 160: one wave
 constexpr int kMvMaxPts = CTAG_RIG_MAX_POINTS;   // 800
 constexpr int kMvLargeThreads = 256;
-
-// the camera set as the kernels take it, by value
-struct MvCams {
-    int n;
-    int at_reference[kMvCams];  // the camera's pose is exactly zero: its frame is the reference frame
-    PoseCam cam[kMvCams];
-    double R[kMvCams][9];  // Rc = R(rvec), row-major
-    double t[kMvCams][3];  // tc
-};
-
-struct MvResults {
-    const ctag_frame_result* p[kMvCams];  // device pointers, n_frames records each
-};
-
-}  // namespace ctag
-
-// ctag_camera_set (opaque in include/ctag_pose.h)
-struct ctag_camera_set {
-    ctag::MvCams dev;
-};
-
-namespace ctag {
 
 __global__ __launch_bounds__(256) void k_mv_count(MvResults res, int n_cameras, int n_frames, PoseModelDev model, const int32_t* __restrict__ rig_of_model,
                                                   int n_rigs, ctag_mv_pose_rec* __restrict__ out, int32_t* __restrict__ lists, int32_t* __restrict__ counts) {
@@ -123,41 +101,6 @@ struct MvLds {
     double t[kMvCams][3];
     unsigned char cam_of[PTS];
 };
-
-// residual and Jacobian rows of point p seen by a camera at (Rc, tc) in the reference frame, under the rig pose (R, dR, x):
-// Q = Rc (R p + t) + tc, the projection of point_residual on Q, and Rc applied to the rows point_residual forms
-__device__ __forceinline__ void mv_point_residual(const double* R, const double* dR, const double* x, const PoseCam& cam, const double* Rc,
-                                                  const double* tc, const double* p, const double* ob, double& r0, double& r1, double* j0,
-                                                  double* j1) {
-    const double P0 = (R[0] * p[0] + R[1] * p[1] + R[2] * p[2]) + x[3];
-    const double P1 = (R[3] * p[0] + R[4] * p[1] + R[5] * p[2]) + x[4];
-    const double P2 = (R[6] * p[0] + R[7] * p[1] + R[8] * p[2]) + x[5];
-    const double Q0 = (Rc[0] * P0 + Rc[1] * P1 + Rc[2] * P2) + tc[0];
-    const double Q1 = (Rc[3] * P0 + Rc[4] * P1 + Rc[5] * P2) + tc[1];
-    const double Q2 = (Rc[6] * P0 + Rc[7] * P1 + Rc[8] * P2) + tc[2];
-    const double iz = 1.0 / Q2;
-    r0 = (cam.fx * (Q0 * iz) + cam.cx) - ob[0];
-    r1 = (cam.fy * (Q1 * iz) + cam.cy) - ob[1];
-    const double a0 = cam.fx * iz, a1 = cam.fy * iz;
-    const double b0 = cam.fx * Q0 * iz * iz, b1 = cam.fy * Q1 * iz * iz;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const double* D = dR + 9 * k;
-        const double d0 = D[0] * p[0] + D[1] * p[1] + D[2] * p[2];
-        const double d1 = D[3] * p[0] + D[4] * p[1] + D[5] * p[2];
-        const double d2 = D[6] * p[0] + D[7] * p[1] + D[8] * p[2];
-        const double e0 = Rc[0] * d0 + Rc[1] * d1 + Rc[2] * d2;
-        const double e1 = Rc[3] * d0 + Rc[4] * d1 + Rc[5] * d2;
-        const double e2 = Rc[6] * d0 + Rc[7] * d1 + Rc[8] * d2;
-        j0[k] = a0 * e0 - b0 * e2;
-        j1[k] = a1 * e1 - b1 * e2;
-    }
-#pragma unroll
-    for (int m = 0; m < 3; m++) {  // dQ/dt = Rc
-        j0[3 + m] = a0 * Rc[m] - b0 * Rc[6 + m];
-        j1[3 + m] = a1 * Rc[3 + m] - b1 * Rc[6 + m];
-    }
-}
 
 // the points of camera c's members of frame record FR (member_mask[c] of the record k_mv_count wrote) into S from index n on
 template <int PTS>

@@ -5,6 +5,7 @@
 //   ctag_classcheck errors <good.marker> <dir for scratch files>
 //   ctag_classcheck dump <dictionary.marker> <image.bmp> [model.model cameraParams.yml]
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -51,7 +52,8 @@ static ctag_host::Mat1i read_dictionary(const std::string& path, int& feature_si
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s errors <good.marker> <scratch dir> | dump <dictionary.marker> <image.bmp> [model cameraParams.yml]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s errors <good.marker> <scratch dir> | dump <dictionary.marker> <image.bmp> [model cameraParams.yml] | "
+                             "cov <dictionary.marker> <image.bmp> <model> <cameraParams.yml> <tangent 0|1> <sigma_px>\n", argv[0]);
         return 2;
     }
     const std::string mode = argv[1];
@@ -78,6 +80,26 @@ int main(int argc, char** argv) {
             CamInfo cam;
             expect_throw("missing model", [&] { ok.loadModel(dir + "/does_not_exist.model", model); });
             expect_throw("missing camera", [&] { ok.loadCamera(dir + "/does_not_exist.yml", cam); });
+            return 0;
+        }
+        if (mode == "cov") {  // estimatePoseCovariance on the image's markers, every double as a hexadecimal float
+            if (argc < 8) return 2;
+            CylinderTag t(argv[2]);
+            const ctag_host::GrayImage g = ctag_host::read_bmp_gray(argv[3]);
+            std::vector<MarkerInfo> m;
+            t.detect(ctag_host::Mat(g.rows, g.cols, g.px.data()), m, 5, true, 5);
+            std::vector<ModelInfo> model;
+            CamInfo cam;
+            t.loadModel(argv[4], model);
+            t.loadCamera(argv[5], cam);
+            std::vector<PoseCovInfo> cov;
+            t.estimatePoseCovariance(m, model, cam, cov, std::atoi(argv[6]) != 0, std::atof(argv[7]));
+            for (const PoseCovInfo& c : cov) {
+                std::printf("cov %d %d %d %d %d %d %a %a %a %a %a", c.markerID, c.status, c.nPoints, c.dof, c.worstPoint, c.nOutliers, c.cost, c.sigma2Hat,
+                            c.sigma2Used, c.maxResidualPx, c.minPivot);
+                for (int k = 0; k < 36; k++) std::printf(" %a", c.cov[k]);
+                std::printf("\n");
+            }
             return 0;
         }
         int fs = 0;

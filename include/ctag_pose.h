@@ -236,6 +236,102 @@ int ctag_mv_rig_pose_batch_device(ctag_handle* h, const ctag_frame_result* const
 int ctag_estimate_mv_rig_pose(ctag_handle* h, const ctag_frame_result* results, const ctag_model* model, const ctag_rigs* rigs,
                               const ctag_camera_set* cams, ctag_mv_pose_rec* out);
 
+/* ---- pose covariance: how far a pose record can be trusted (k_pose_cov.hip) ------------------------------------------------------
+ * One ctag_pose_cov_rec per pose record of any of the three kinds above, computed on the device from the pose records and the
+ * detection records where they lie: the 6x6 covariance of the pose under the first-order model cov = sigma^2 (J^T J)^-1 at the
+ * record's final pose, and the residuals' diagnostics.  No pose record, kernel or result above is changed by it.
+ *   1. A source record whose status is not CTAG_POSE_OK gives CTAG_COV_NO_POSE.  For every status but CTAG_COV_OK all other
+ *      fields of the covariance record are 0.
+ *   2. The points are rebuilt from the detection record(s) exactly as the pose call built them (the builder's rule and order:
+ *      the end-feature skip, corners 0 1 4 5 [2 3 6 7]):
+ *        per marker  marker poses[w].marker of frame poses[w].frame against model poses[w].model_index;
+ *        rig         frame rig_poses[w].frame: the markers whose bit is set in member_mask, in marker order, each against the
+ *                    first model with its marker_id;
+ *        multi-view  frame mv_poses[w].frame: the same per camera c from member_mask[c], in camera order; each camera's pixels
+ *                    are undistorted with that camera's own coefficients.
+ *      CTAG_COV_BAD_RECORD when the source record does not describe its detection record(s): an index lies outside its array
+ *      (frame outside the batch, marker >= the frame's marker count, model_index outside the model list, a member bit at or
+ *      past the frame's marker count, a member whose marker_id has no model, a member_mask of a camera the set does not have),
+ *      a frame that is read is not CTAG_OK, the builder rejects a member (CTAG_POSE_BAD_POS) or the total passes
+ *      CTAG_RIG_MAX_POINTS, the rebuilt point count differs from the record's n_points or is below 4, or rvec / tvec are not
+ *      finite.  Nothing outside the records' own data is ever read.  The rig set only gives n_rigs: rig_of_model is not
+ *      consulted, the member_mask is the membership.
+ *   3. The residual is PoseBA's, in undistorted pixels: rule 5 of the multi-view section for multi-view records, the same with
+ *      one camera at the reference for the other two.  The covariance describes THAT residual: the observations are the
+ *      undistorted pixels, and the Jacobian of the undistortion itself is taken as the identity (sigma_px is a noise of the
+ *      undistorted pixel).
+ *   4. Unknowns.  CTAG_COV_PARAM_RVEC: the record's own coordinates (rvec, tvec); the rotation derivatives are those of the
+ *      Rodrigues formula, as the LM loop has them.  CTAG_COV_PARAM_TANGENT: R <- Exp(dw) R, t <- t + dt, dw a small rotation
+ *      vector in the frame the pose maps INTO (the camera; the reference frame for multi-view records): dR/dw_k = [e_k]x R.
+ *      The translation columns are the same in both.
+ *   5. H = J^T J (6x6), D = diag(H)^-1/2, C = D H D (unit diagonal), C = L L^T by Cholesky; min_pivot is the smallest pivot of
+ *      that factorisation before its square root.  CTAG_COV_SINGULAR when the cost or a diagonal entry of H is not finite, a
+ *      diagonal entry of H is not positive, or a pivot is not above 1e-12 (well-posed problems of 4 to 160 points stay above
+ *      1e-6; four coincident points give -2e-16).  Otherwise cov = sigma2_used * D C^-1 D, mirrored so that it is symmetric bit
+ *      for bit.
+ *   6. Deterministic: lane l of one wavefront owns points l, l+64, ... in order, the lanes are combined in one fixed tree.  The
+ *      same source record gives the same bytes in any batch, at any place in it, in a one-frame call and on a second run. */
+#define CTAG_COV_OK 0
+#define CTAG_COV_NO_POSE 1     /* the source pose record's status is not CTAG_POSE_OK */
+#define CTAG_COV_BAD_RECORD 2  /* the source record does not describe its detection record(s): rule 2 */
+#define CTAG_COV_SINGULAR 3    /* rule 5 */
+
+#define CTAG_COV_PARAM_TANGENT 0 /* R <- Exp(dw) R, t <- t + dt: dw in the frame the pose maps INTO (camera; reference frame for mv) */
+#define CTAG_COV_PARAM_RVEC 1    /* the record's own coordinates (rvec, tvec) */
+
+typedef struct ctag_cov_opts {
+    uint32_t struct_size;  /* filled by ctag_cov_opts_default, checked */
+    int32_t param;         /* CTAG_COV_PARAM_* ; default TANGENT */
+    double sigma_px;       /* > 0: the pixel noise to assume; <= 0 (default 0): use sigma2_hat */
+    double outlier_k;      /* > 0: count points whose residual norm exceeds outlier_k * sqrt(sigma2_used); default 3 */
+} ctag_cov_opts;
+
+typedef struct ctag_pose_cov_rec {
+    int32_t status;        /* CTAG_COV_* */
+    int32_t n_points;
+    int32_t dof;           /* 2 * n_points - 6 */
+    int32_t worst_point;   /* index, in the builder's point order, of the largest residual norm; lowest index on a tie */
+    int32_t n_outliers;    /* 0 when outlier_k <= 0 */
+    int32_t param;
+    double cost;           /* 0.5 * sum r^2 at the record's final pose, recomputed */
+    double sigma2_hat;     /* 2 * cost / dof */
+    double sigma2_used;    /* sigma_px^2 if sigma_px > 0, else sigma2_hat */
+    double max_residual_px;
+    double min_pivot;      /* rule 5 */
+    double cov[36];        /* row-major, symmetric bit for bit: sigma2_used * (J^T J)^-1; rows/cols 0-2 rotation (rad), 3-5 translation (model units) */
+} ctag_pose_cov_rec;       /* 352 bytes */
+
+void ctag_cov_opts_default(ctag_cov_opts* opts);
+
+/* The three batch calls: enqueued on the handle's stream, return without waiting, write no byte outside their records.  Arguments
+ * are judged as the matching pose call judges them; opts == NULL means the defaults; a wrong struct_size, an unknown param or a
+ * sigma_px / outlier_k that is not finite gives CTAG_ERR_ARG.
+ * Per marker: offsets_dev, poses_dev and capacity as ctag_pose_batch_device left them.  Covariance record w is for pose record w,
+ * for every w < min(offsets_dev[n_frames], capacity); nothing beyond those records is written. */
+int ctag_pose_cov_batch_device(ctag_handle* h, const ctag_frame_result* results_dev, int n_frames, const ctag_model* model,
+                               const ctag_camera* camera, const int32_t* offsets_dev, const ctag_pose_rec* poses_dev, int capacity,
+                               const ctag_cov_opts* opts, ctag_pose_cov_rec* out_dev);
+/* Rig: rig_poses_dev as ctag_rig_pose_batch_device left it; writes exactly n_frames x n_rigs records, record w for pose record w. */
+int ctag_rig_pose_cov_batch_device(ctag_handle* h, const ctag_frame_result* results_dev, int n_frames, const ctag_model* model,
+                                   const ctag_rigs* rigs, const ctag_camera* camera, const ctag_rig_pose_rec* rig_poses_dev,
+                                   const ctag_cov_opts* opts, ctag_pose_cov_rec* out_dev);
+/* Multi-view: results_dev is a HOST array of n_cameras DEVICE pointers (read before the call returns), mv_poses_dev as
+ * ctag_mv_rig_pose_batch_device left it; writes exactly n_frames x n_rigs records. */
+int ctag_mv_rig_pose_cov_batch_device(ctag_handle* h, const ctag_frame_result* const* results_dev, int n_frames, const ctag_model* model,
+                                      const ctag_rigs* rigs, const ctag_camera_set* cams, const ctag_mv_pose_rec* mv_poses_dev,
+                                      const ctag_cov_opts* opts, ctag_pose_cov_rec* out_dev);
+
+/* One frame (one instant), host memory in and out, the records of the matching ctag_estimate_* call (their frame fields 0); they
+ * wait for completion.  out holds result->n_markers records (none for a frame that is not CTAG_OK), n_rigs records for the other two. */
+int ctag_estimate_pose_cov(ctag_handle* h, const ctag_frame_result* result, const ctag_model* model, const ctag_camera* camera,
+                           const ctag_pose_rec* poses, const ctag_cov_opts* opts, ctag_pose_cov_rec* out);
+int ctag_estimate_rig_pose_cov(ctag_handle* h, const ctag_frame_result* result, const ctag_model* model, const ctag_rigs* rigs,
+                               const ctag_camera* camera, const ctag_rig_pose_rec* rig_poses, const ctag_cov_opts* opts,
+                               ctag_pose_cov_rec* out);
+int ctag_estimate_mv_rig_pose_cov(ctag_handle* h, const ctag_frame_result* results, const ctag_model* model, const ctag_rigs* rigs,
+                                  const ctag_camera_set* cams, const ctag_mv_pose_rec* mv_poses, const ctag_cov_opts* opts,
+                                  ctag_pose_cov_rec* out);
+
 /* ---- overlay: CylinderTag::drawAxis (reference CylinderTag.cpp:211-246) ------------------------------------------------
  * Output: 8-bit, 3 channels, every channel = the gray value (cvtColor GRAY2RGB), then per drawn record, in record order,
  * what the reference paints with OpenCV 4.5.3 (k_draw.hip restates it):
