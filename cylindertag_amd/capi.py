@@ -31,7 +31,8 @@ POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag
                 "ctag_rigs_create", "ctag_rigs_free", "ctag_rig_pose_batch_device", "ctag_estimate_rig_pose",
                 "ctag_camera_set_create", "ctag_camera_set_free", "ctag_mv_rig_pose_batch_device", "ctag_estimate_mv_rig_pose",
                 "ctag_cov_opts_default", "ctag_pose_cov_batch_device", "ctag_rig_pose_cov_batch_device", "ctag_mv_rig_pose_cov_batch_device",
-                "ctag_estimate_pose_cov", "ctag_estimate_rig_pose_cov", "ctag_estimate_mv_rig_pose_cov"]
+                "ctag_estimate_pose_cov", "ctag_estimate_rig_pose_cov", "ctag_estimate_mv_rig_pose_cov",
+                "ctag_model_fit_opts_default", "ctag_model_fit_device", "ctag_model_fit", "ctag_model_save", "ctag_model_fit_last_ms"]
 # ... and include/ctag_gather.h
 GATHER_EXPORTS = ["ctag_shard_range", "ctag_packed_capacity", "ctag_pack_results", "ctag_unpack_results", "ctag_comm_unique_id",
                   "ctag_comm_init", "ctag_comm_attach", "ctag_comm_destroy", "ctag_comm_native", "ctag_comm_last_error", "ctag_gather_begin",
@@ -65,6 +66,10 @@ POSE_COV_DT = np.dtype([("status", "<i4"), ("n_points", "<i4"), ("dof", "<i4"), 
 assert POSE_COV_DT.itemsize == 352
 COV_OK, COV_NO_POSE, COV_BAD_RECORD, COV_SINGULAR = range(4)
 COV_PARAM_TANGENT, COV_PARAM_RVEC = 0, 1
+# ctag_model_fit_stat: one record per model of a model reconstruction (include/ctag_pose.h)
+MODEL_FIT_STAT_DT = np.dtype([("status", "<i4"), ("n_records", "<i4"), ("n_points_fitted", "<i4"), ("n_points_held", "<i4"), ("rounds", "<i4"),
+                              ("reserved", "<i4"), ("cost0", "<f8"), ("cost", "<f8"), ("lambda", "<f8"), ("rms_px", "<f8")])
+assert MODEL_FIT_STAT_DT.itemsize == 56
 
 
 class ParamsC(C.Structure):  # ctag_params (include/ctag_types.h): the reference's tunables
@@ -112,6 +117,22 @@ def cov_opts(param=None, sigma_px=None, outlier_k=None):
         o.sigma_px = float(sigma_px)
     if outlier_k is not None:
         o.outlier_k = float(outlier_k)
+    return o
+
+
+class ModelFitOptsC(C.Structure):  # ctag_model_fit_opts
+    _fields_ = [("max_rounds", C.c_int32), ("min_obs", C.c_int32), ("lambda0", C.c_double), ("lambda_max", C.c_double), ("rel_tol", C.c_double),
+                ("strip_height", C.c_double)]
+
+
+def model_fit_opts(**fields):
+    """ctag_model_fit_opts_default, then the given fields."""
+    o = ModelFitOptsC()
+    load_library().ctag_model_fit_opts_default(C.byref(o))
+    for k, v in fields.items():
+        if k not in ("max_rounds", "min_obs", "lambda0", "lambda_max", "rel_tol", "strip_height"):
+            raise TypeError("ctag_model_fit_opts has no field %r" % k)
+        setattr(o, k, v)
     return o
 
 
@@ -253,6 +274,17 @@ def load_library():
     L.ctag_estimate_rig_pose_cov.argtypes = [vp, vp, vp, vp, C.POINTER(CameraC), vp, optp, vp]
     L.ctag_estimate_mv_rig_pose_cov.restype = C.c_int
     L.ctag_estimate_mv_rig_pose_cov.argtypes = [vp, vp, vp, vp, vp, vp, optp, vp]
+    fitp = C.POINTER(ModelFitOptsC)
+    L.ctag_model_fit_opts_default.restype = None
+    L.ctag_model_fit_opts_default.argtypes = [fitp]
+    L.ctag_model_fit_device.restype = C.c_int
+    L.ctag_model_fit_device.argtypes = [vp, vp, C.c_int, vp, C.POINTER(CameraC), fitp, C.POINTER(vp), vp]
+    L.ctag_model_fit.restype = C.c_int
+    L.ctag_model_fit.argtypes = [vp, vp, C.c_int, vp, C.POINTER(CameraC), fitp, C.POINTER(vp), vp]
+    L.ctag_model_save.restype = C.c_int
+    L.ctag_model_save.argtypes = [vp, C.c_char_p]
+    L.ctag_model_fit_last_ms.restype = C.c_int
+    L.ctag_model_fit_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     u64p = C.POINTER(C.c_uint64)
     L.ctag_shard_range.restype = C.c_int
     L.ctag_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -361,6 +393,20 @@ class Model:
         return {"ids": np.ctypeslib.as_array(v.marker_id, (n,)).copy(), "size": size,
                 "base": np.ctypeslib.as_array(v.base, (n, 3)).copy(), "axis": np.ctypeslib.as_array(v.axis, (n, 3)).copy(),
                 "corners": np.ctypeslib.as_array(v.corners, (n, size * 8, 3)).copy()}
+
+    @classmethod
+    def _adopt(cls, handle):
+        """A Model around a ctag_model* the library handed out (ctag_model_fit*)."""
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.m = handle
+        return self
+
+    def save(self, path):
+        """ctag_model_save: the .model text format of CylinderTag.cpp:168-188; Model(path) reads back the same float bits."""
+        st = self.L.ctag_model_save(self.m, os.fsencode(path))
+        if st != 0:
+            raise CtagError(st, "ctag_model_save %s" % path)
 
     def close(self):
         if getattr(self, "m", None):
@@ -723,6 +769,33 @@ class Detector:
 
     def pose_last_ms(self):
         return float(self.L.ctag_pose_last_ms(self.h))
+
+    # ---- model reconstruction (include/ctag_pose.h): opts is a ModelFitOptsC (model_fit_opts(...)) or None for the defaults
+    def _fit(self, fn, name, results_arg, n_frames, seed, camera, opts):
+        n_models = int(seed.view()["ids"].size)
+        stats = np.zeros(max(n_models, 1), MODEL_FIT_STAT_DT)
+        m = C.c_void_p()
+        st = fn(self.h, results_arg, n_frames, seed.m, C.byref(camera), C.byref(opts) if opts is not None else None, C.byref(m), stats.ctypes.data)
+        if st != 0:
+            raise CtagError(st, name)
+        return Model._adopt(m), stats[:n_models]
+
+    def fit_model(self, results, seed, camera, opts=None):
+        """ctag_model_fit: host ctag_frame_result records of many frames and a seed Model -> (the Model that minimises the reprojection
+        error over them, MODEL_FIT_STAT_DT records, one per model).  Waits."""
+        res = np.ascontiguousarray(results).reshape(-1)
+        assert res.dtype == RESULT_DT
+        return self._fit(self.L.ctag_model_fit, "ctag_model_fit", res.ctypes.data if len(res) else None, len(res), seed, camera, opts)
+
+    def fit_model_device(self, results_ptr, n_frames, seed, camera, opts=None):
+        """ctag_model_fit_device: the same from n_frames result records in device memory (as detect_batch_device leaves them)."""
+        return self._fit(self.L.ctag_model_fit_device, "ctag_model_fit_device", results_ptr, n_frames, seed, camera, opts)
+
+    def model_fit_last_ms(self):
+        """Device milliseconds of the last fit call by kernel kind (needs OPT_TIMING): pose, record, assemble, solve."""
+        out = (C.c_float * 4)()
+        self.L.ctag_model_fit_last_ms(self.h, out)
+        return dict(zip(("pose", "record", "assemble", "solve"), (float(v) for v in out)))
 
     # ---- pose covariance (include/ctag_pose.h): opts is a CovOptsC (cov_opts(...)) or None for the defaults
     @staticmethod

@@ -144,9 +144,8 @@ void CylinderTag::detectBatch(const unsigned char* frames, int n, int rows, int 
 // ---------------------------------------------------------------------------------------------------------------
 
 // reference: CylinderTag::loadModel, CylinderTag.cpp:161-190
-void CylinderTag::loadModel(const std::string& path, std::vector<ModelInfo>& reconstruct_model) {
-    ctag_model* m = nullptr;
-    if (ctag_model_load(path.c_str(), &m) != CTAG_OK) throw __FUNCTION__ + std::string(", ") + "could not open the model file\n";
+// ctag_model -> vector<ModelInfo>
+static void unpack_model(const ctag_model* m, std::vector<ModelInfo>& reconstruct_model) {
     ctag_model_view v;
     ctag_model_get_view(m, &v);
     reconstruct_model.resize((size_t)v.n_models);
@@ -159,6 +158,12 @@ void CylinderTag::loadModel(const std::string& path, std::vector<ModelInfo>& rec
         const float* c = v.corners + (size_t)i * v.model_size * 24;
         for (int j = 0; j < v.model_size * 8; j++) mi.corners[(size_t)j] = Point3f(c[3 * j], c[3 * j + 1], c[3 * j + 2]);
     }
+}
+
+void CylinderTag::loadModel(const std::string& path, std::vector<ModelInfo>& reconstruct_model) {
+    ctag_model* m = nullptr;
+    if (ctag_model_load(path.c_str(), &m) != CTAG_OK) throw __FUNCTION__ + std::string(", ") + "could not open the model file\n";
+    unpack_model(m, reconstruct_model);
     ctag_model_free(m);
 }
 
@@ -251,6 +256,39 @@ static ctag_camera make_camera(const CamInfo& camera) {
     for (int i = 0; i < cam.n_dist; i++) cam.dist[i] = camera.distCoeffs[(size_t)i];
 #endif
     return cam;
+}
+
+// new: the model list from detections of the objects (include/ctag_pose.h, model reconstruction)
+void CylinderTag::reconstructModel(const std::vector<std::vector<MarkerInfo>>& framesOfMarkers, const std::vector<ModelInfo>& seedModel, CamInfo camera,
+                                   std::vector<ModelInfo>& outModel, double stripHeight) {
+    if (framesOfMarkers.empty()) throw __FUNCTION__ + std::string(", ") + "no frames\n";
+    std::vector<ctag_frame_result> recs(framesOfMarkers.size());
+    for (size_t f = 0; f < framesOfMarkers.size(); f++) {
+        for (const MarkerInfo& mi : framesOfMarkers[f])
+            if (mi.cornerLists.size() > (size_t)CTAG_MAX_FEATURES) throw __FUNCTION__ + std::string(", ") + "a marker with more than 100 features\n";
+        if (flatten(framesOfMarkers[f], 0, recs[f]) != framesOfMarkers[f].size())
+            throw __FUNCTION__ + std::string(", ") + "a frame with more markers or features than a detection record holds\n";
+        if (recs[f].n_markers == 0) recs[f].status = CTAG_NO_FEATURE;  // detect() left the list empty
+    }
+    ctag_model* seed = make_model(seedModel, __FUNCTION__);
+    const ctag_camera cam = make_camera(camera);
+    ctag_model_fit_opts opts;
+    ctag_model_fit_opts_default(&opts);
+    opts.strip_height = stripHeight;
+    std::vector<ctag_model_fit_stat> stats(seedModel.size() + 1);
+    ctag_model* fitted = nullptr;
+    const int st = ctag_model_fit(h_, recs.data(), (int)recs.size(), seed, &cam, &opts, &fitted, stats.data());
+    ctag_model_free(seed);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    unpack_model(fitted, outModel);
+    ctag_model_free(fitted);
+}
+
+void CylinderTag::saveModel(const std::string& path, const std::vector<ModelInfo>& model) {
+    ctag_model* m = make_model(model, __FUNCTION__);
+    const int st = ctag_model_save(m, path.c_str());
+    ctag_model_free(m);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + "could not write the model file\n";
 }
 
 // reference: CylinderTag::estimatePose, CylinderTag.cpp:198-209 (+ PoseEstimator::PnPSolver / PoseBA)

@@ -166,6 +166,18 @@ class CylinderTag {
     void loadModel(const std::string& path, std::vector<ModelInfo>& reconstruct_model);
     void loadCamera(const std::string& path, CamInfo& camera);
 
+    // Reconstruct the marker models themselves (new; include/ctag_pose.h, model reconstruction: ctag_model_fit).  framesOfMarkers[f] is what
+    // detect() returned for frame f of a sequence that shows the objects (a few dozen to a few thousand frames); seedModel is a rough model --
+    // an ideal cylinder of nominal radius, or an older model -- whose model size is the dictionary's column count.  outModel is the model that
+    // minimises the reprojection error over all frames, in the seed's frame and scale; stripHeight > 0 rescales it so that the strips'
+    // vertical edges have that length.  Models no frame shows come back as the seed.  A frame must fit one detection record (<= 100 markers,
+    // <= 100 features, as detect() returns them).  Throws std::string on error.
+    void reconstructModel(const std::vector<std::vector<MarkerInfo>>& framesOfMarkers, const std::vector<ModelInfo>& seedModel, CamInfo camera,
+                          std::vector<ModelInfo>& outModel, double stripHeight = 0.0);
+    // Write a model list in the text format loadModel reads (CylinderTag.cpp:168-188), floats with 9 significant digits: loadModel gives
+    // back the same values bit for bit.  Throws std::string when the file cannot be written.
+    void saveModel(const std::string& path, const std::vector<ModelInfo>& model);
+
     // Estimate the pose of the markers (reference: header/CylinderTag.h:30, CylinderTag.cpp:198-209): one PoseInfo per
     // marker that has a model, PoseInfo::markerID = index into reconstruct_model (pose_estimation.cpp:59,69).
     // useDensePoseRefine is accepted and ignored: the reference's DenseSolver is empty (pose_estimation.cpp:145-148).

@@ -183,6 +183,7 @@ void** handle_state_slot(ctag_handle* h, SiblingState which, void (*free_fn)(voi
 }
 bool handle_timing(const ctag_handle* h) { return h->timing; }
 int handle_device(const ctag_handle* h) { return h->device; }
+int handle_dict_cols(const ctag_handle* h) { return h->dict_cols; }
 void handle_view(const ctag_handle* h, HandleView* out) {
     out->device = h->device;
     out->ws = h->last_ws && h->last_ws->base ? h->last_ws : nullptr;

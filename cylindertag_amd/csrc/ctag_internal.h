@@ -21,6 +21,7 @@
 
 struct ctag_handle;
 struct ctag_camera;
+struct ctag_pose_rec;
 
 namespace ctag {
 // A device buffer the library's host code owns: pointer and capacity in elements.  grow() frees, then allocates (the old contents are gone); the
@@ -373,8 +374,8 @@ void build_pick_table(uint8_t* table, uint16_t* table16);  // kPickN*20*10 bytes
 
 
 // accessor of the opaque handle for the state of its back ends, each created on first use: the pose back end (k_pose.hip), the overlay (k_draw.hip),
-// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip), the multi-view rig poses (k_mv_pose.hip), the pose covariance (k_pose_cov.hip).  ctag_destroy frees them in this order.
-enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kCovState, kNumSiblingStates };
+// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip), the multi-view rig poses (k_mv_pose.hip), the pose covariance (k_pose_cov.hip), the model reconstruction (k_model_fit.hip).  ctag_destroy frees them in this order.
+enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kCovState, kFitState, kNumSiblingStates };
 void** handle_state_slot(struct ::ctag_handle* h, SiblingState which, void (*free_fn)(void*));
 // the model's device copies on `device` (k_pose.hip); the camera's distortion model is one the pose back end handles
 int model_to_device(struct ::ctag_model* m, int device);
@@ -390,6 +391,7 @@ int handle_finish_pending(struct ::ctag_handle* h);
 bool handle_pending_state(struct ::ctag_handle* h, const int32_t** count_dev, uint64_t* gen);
 void handle_pending_clean(struct ::ctag_handle* h, uint64_t gen);
 int handle_device(const struct ::ctag_handle* h);
+int handle_dict_cols(const struct ::ctag_handle* h);  // columns of the handle's dictionary: the model_size a reconstructed model must have
 
 // Private window for libctag_testkit.so (include/ctag_testkit.h: parity probes, synthetic frames).  Not declared in any
 // public header; the product itself never calls these two.
@@ -408,6 +410,14 @@ struct HandleView {
     ptrdiff_t gray_row_stride, gray_frame_stride;
 };
 void handle_view(const struct ::ctag_handle* h, HandleView* out);
+// the reduced system of ONE model of the model reconstruction (k_model_fit.hip; include/ctag_pose.h, model reconstruction, rule 4) at a caller-given state:
+// host detection records, host pose records (the CTAG_POSE_OK ones are the observations), a model and a lambda -> S [3P x 3P], g [3P], delta [3P], held [P]
+// (P = model_size * 8) and whether a pivot was not positive; pass_records > 0 sets how many records one pass of the workspace holds.  Waits.
+int mfit_probe_system(struct ::ctag_handle* h, const ctag_frame_result* results, int n_frames, const struct ::ctag_pose_rec* poses, int n_poses,
+                      const struct ::ctag_model* model, const struct ::ctag_camera* camera, int model_index, double lambda, int min_obs, int pass_records,
+                      double* S, double* g, double* delta, int32_t* held, int32_t* bad_pivot);
+int mfit_record_grid();   // k_mfit_record's grid
+int mfit_pass_records();  // observation records one pass of its workspace holds
 // the part of ctag_gather_end behind the payload all-gather: segment table of a `world`-rank job + unpack kernels on the
 // handle's gather stream, on a caller-supplied gathered buffer (world shards of `width` bytes); waits for completion
 int gather_unpack_gathered(struct ::ctag_handle* h, const void* gathered_dev, int n_total, int world, uint64_t width, ctag_frame_result* out_dev);

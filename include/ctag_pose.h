@@ -332,6 +332,83 @@ int ctag_estimate_mv_rig_pose_cov(ctag_handle* h, const ctag_frame_result* resul
                                   const ctag_camera_set* cams, const ctag_mv_pose_rec* mv_poses, const ctag_cov_opts* opts,
                                   ctag_pose_cov_rec* out);
 
+/* ---- model reconstruction: the corner lists themselves, from detections of the objects (k_model_fit.hip) ---------------------------
+ * Every pose call above takes a ctag_model; this call makes one.  From the detection records of a few dozen to a few thousand
+ * frames and a rough seed model (an ideal cylinder of nominal radius, cylindertag_amd/models.py, or an older model) it returns the
+ * model that minimises the reprojection error over all of them.  The problem over corners AND per-record poses separates: given the
+ * model every record's pose is the solve ctag_pose_batch_device already does, so only the corners are optimised, by
+ * Levenberg-Marquardt on the cost with the poses eliminated (the Schur complement on the 6x6 pose blocks).  Models are
+ * independent problems (a pose record belongs to one model): each has its own lambda, accept / reject and stop, inside the same
+ * launches.
+ *   1. Observations.  Every marker of every CTAG_OK frame whose pose record under the SEED (ctag_pose_batch_device) has status
+ *      CTAG_POSE_OK, in record order; its correspondences are the builder's (the end-feature skip, corners 0 1 4 5 [2 3 6 7]), its
+ *      image points undistorted as PoseBA does.  The set is fixed for the whole call.  Two markers with the same model in one
+ *      frame are two records.  A record in which two features claim the same model position (hand-built records only) is left out.
+ *   2. Held corners.  A corner of a model observed by fewer than min_obs records is held: it keeps the seed's value and leaves the
+ *      system; in the pose of a record that does see it, it still takes part with the seed's value.  A model with no fitted corner is
+ *      returned unchanged with status CTAG_POSE_NOT_SEEN.
+ *   3. Working model.  float32, as ctag_model stores it and every consumer reads it.  A trial step is computed in double, mapped
+ *      by the gauge of rule 5 and rounded to float; the cost compared and reported is the cost of exactly those floats:
+ *      stats.cost is the sum, in record order, of the cost fields ctag_pose_batch_device gives the observation records on the
+ *      returned model, byte for byte.
+ *   4. A round for model m.  All observation records are re-solved by the pose arithmetic (EPnP start included) on the trial
+ *      model; cost[m] = the sum of their cost in record order (a record that is no longer CTAG_POSE_OK makes the trial a reject).
+ *      The trial is accepted iff cost[m] decreases; on accept lambda <- max(lambda / 3, 1e-9), on reject lambda <- 4 lambda.  Reduced
+ *      normal equations at the accepted state, residual r and Jacobians Jp (pose: rvec, tvec, as CTAG_COV_PARAM_RVEC has them) and Jx
+ *      (the point) per point i of a record:  U = sum Jp_i^T Jp_i,  U = L L^T,  Z_i = L^-1 (Jp_i^T Jx_i),  y = L^-1 sum Jp_i^T r_i;
+ *      S = sum over records [ diag(Jx_i^T Jx_i) - Z^T Z ],  g = sum over records [ Jx_i^T r_i - Z_i^T y ]  on the fitted corners.
+ *      The step solves (S + lambda diag S) delta = -g by Cholesky; a pivot that is not positive counts as a reject.  Model m stops
+ *      when an accepted round lowers the cost by less than rel_tol * cost, when lambda exceeds lambda_max, or after max_rounds.
+ *   5. Gauge.  One camera cannot see the model's similarity (rotation, translation, scale: 7 degrees of freedom).  The fitted
+ *      corners of every trial are mapped by the similarity (Umeyama) that best carries them onto the seed's same corners, on the
+ *      host in double.  base, axis and marker_id are the seed's.
+ *   6. Metric scale.  strip_height > 0: each fitted model is finally scaled about the centroid of its fitted corners so that the
+ *      mean length of the strip's straight vertical edges -- corner pairs (0,5) and (1,4) of every feature whose four ends were
+ *      fitted -- is strip_height; base moves with the scaling.  stats.cost is then the cost of the scaled model (rule 3).
+ *   7. Determinism.  Every sum has a fixed order: record order across records, wave_sum_f64's tree inside one.  Two calls on the
+ *      same input return the same bytes, and the result does not depend on how many records one pass of the workspace holds.
+ *   8. CTAG_ERR_ARG: a null argument, n_frames < 1, max_rounds < 0, min_obs < 1, lambda0 / lambda_max / rel_tol that are not
+ *      positive and finite, a strip_height that is not finite, a seed whose model_size is not the handle's dictionary's column
+ *      count or is above 20 (CTAG_POSE_MAX_POINTS corners); CTAG_ERR_UNSUPPORTED: a camera the pose back end does not handle.
+ * Device memory of one call: the pose records, 216 bytes (27 doubles: Z 18, Jx^T Jx 6, g 3) per model corner per observation
+ * record of a pass -- 34 560 bytes a record at 160 corners, at most 2048 records a pass -- and 2 x (24 model_size)^2 doubles per
+ * model for S and the damped system (3.7 MB at 160 corners). */
+typedef struct ctag_model_fit_opts {
+    int32_t max_rounds;   /* default 30 */
+    int32_t min_obs;      /* default 2 */
+    double lambda0;       /* default 1e-3 */
+    double lambda_max;    /* default 1e6 */
+    double rel_tol;       /* default 2.416e-7: 4 x the relative cost change float32 rounding of the model alone causes (6.04e-8) */
+    double strip_height;  /* default 0: no metric scaling */
+} ctag_model_fit_opts;
+
+typedef struct ctag_model_fit_stat {
+    int32_t status;           /* CTAG_POSE_OK or CTAG_POSE_NOT_SEEN */
+    int32_t n_records;        /* observation records of this model */
+    int32_t n_points_fitted;  /* corners in the system */
+    int32_t n_points_held;    /* corners held at the seed */
+    int32_t rounds;           /* rounds taken (accepted + rejected) */
+    int32_t reserved;         /* 0 */
+    double cost0;             /* cost at the seed */
+    double cost;              /* cost of the returned model */
+    double lambda;            /* lambda when the model stopped */
+    double rms_px;            /* sqrt(2 cost / points of the observation records) */
+} ctag_model_fit_stat;        /* 56 bytes */
+
+void ctag_model_fit_opts_default(ctag_model_fit_opts* opts);
+/* results_dev: n_frames detection records in DEVICE memory.  *out: a new model (ctag_model_free); stats: n_models HOST records.
+ * opts == NULL means the defaults.  Waits for completion: the outer loop decides on the host. */
+int ctag_model_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, int n_frames, const ctag_model* seed,
+                          const ctag_camera* camera, const ctag_model_fit_opts* opts, ctag_model** out, ctag_model_fit_stat* stats);
+/* The same from HOST records: uploads them, then ctag_model_fit_device. */
+int ctag_model_fit(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_model* seed, const ctag_camera* camera,
+                   const ctag_model_fit_opts* opts, ctag_model** out, ctag_model_fit_stat* stats);
+/* Writes the .model text format of CylinderTag.cpp:168-188; floats with 9 significant digits, so that ctag_model_load returns the
+ * same float bits.  Host only. */
+int ctag_model_save(const ctag_model* m, const char* path);
+/* device time of the last fit call's kernels by kind (needs CTAG_OPT_TIMING), milliseconds: pose, record, assemble, solve */
+int ctag_model_fit_last_ms(ctag_handle* h, float* out4);
+
 /* ---- overlay: CylinderTag::drawAxis (reference CylinderTag.cpp:211-246) ------------------------------------------------
  * Output: 8-bit, 3 channels, every channel = the gray value (cvtColor GRAY2RGB), then per drawn record, in record order,
  * what the reference paints with OpenCV 4.5.3 (k_draw.hip restates it):

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "ctag.h"
+#include "ctag_pose.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -126,6 +127,20 @@ int ctag_testkit_welsch_fit(ctag_handle* h, int n_frames, const int32_t* edges_p
 /* The sizes at which those kernels change form, in the order of testkit.WELSCH_LIMITS (kWShort, kWCap, ...); host only.  Writes min(capacity, count)
  * int32 values, returns their count. */
 int ctag_testkit_welsch_limits(int32_t* out, int capacity);
+
+/* ---- the reduced system of the model reconstruction (cylindertag_amd/csrc/k_model_fit.hip; include/ctag_pose.h, model reconstruction) ---------
+ * k_mfit_record, k_mfit_assemble and k_mfit_solve at a caller-given state instead of inside the fit's loop.  results: n_frames HOST detection
+ * records; poses: n_poses HOST pose records over them, as ctag_pose_batch_device orders them -- the CTAG_POSE_OK ones are the observation records
+ * (rule 1) and their rvec / tvec the state; model: the corner lists; lambda: the damping (any finite value: a negative one makes the system
+ * indefinite).  For model `model_index`, with P = model_size * 8 corners: S [3P][3P] and g [3P] as assembled over ALL its corners (rule 4),
+ * held [P] (rule 2, from min_obs), delta [3P] = the solution of (S + lambda diag S) delta = -g with the held corners as identity rows (0 there),
+ * *bad_pivot = 1 when a pivot was not positive (delta is 0 then).  pass_records > 0: the workspace holds that many records a pass (rule 7);
+ * 0: the call's own size.  Host arrays out.  Runs on the handle's device and waits. */
+int ctag_testkit_model_fit_system(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_pose_rec* poses, int n_poses,
+                                  const ctag_model* model, const ctag_camera* camera, int model_index, double lambda, int min_obs, int pass_records,
+                                  double* S, double* g, double* delta, int32_t* held, int32_t* bad_pivot);
+/* k_mfit_record's grid and the records a pass holds by default (host only): out[0], out[1]; returns 2 */
+int ctag_testkit_model_fit_limits(int32_t* out, int capacity);
 
 /* ---- the kernel forms the library picks for a chunk (plan_chunk, cylindertag_amd/csrc/ctag_api.hip) ------------------
  * For `nframes` frames of rows x cols (gray, or BGR for channels == 3) at `frames` (only its alignment is looked at) with the given

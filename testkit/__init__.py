@@ -24,7 +24,8 @@ SYNTH_SEED = 0x4354616753594E00  # "CTagSYN\0", SURVEY.md 8(d)
 # every symbol include/ctag_testkit.h declares (tests check the library exports all of them)
 EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
            "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model",
-           "ctag_testkit_dense_edge_probe", "ctag_testkit_plan", "ctag_testkit_welsch_fit", "ctag_testkit_welsch_limits"]
+           "ctag_testkit_dense_edge_probe", "ctag_testkit_plan", "ctag_testkit_welsch_fit", "ctag_testkit_welsch_limits",
+           "ctag_testkit_model_fit_system", "ctag_testkit_model_fit_limits"]
 # the fields ctag_testkit_plan writes, in order (cylindertag_amd/csrc/ctag_internal.h: ChunkPlan)
 PLAN_FIELDS = ("fused", "bgr_direct", "zero_first", "dec_zero_kernel", "dec_zero_list", "dec", "dec_xblocks", "dec_yblocks", "dec_band_rows", "dec_bands",
                "ccl", "latency", "small_cfg", "refprm", "mask_scan", "prescan", "all_wave", "fork", "pack_max", "big_points", "pack_gx", "scan_gx",
@@ -93,8 +94,22 @@ def load_library():
     L.ctag_testkit_welsch_fit.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.ctag_testkit_welsch_limits.restype = C.c_int
     L.ctag_testkit_welsch_limits.argtypes = [i32p, C.c_int]
+    L.ctag_testkit_model_fit_system.restype = C.c_int
+    L.ctag_testkit_model_fit_system.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.POINTER(capi.CameraC), C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp,
+                                                vp, i32p]
+    L.ctag_testkit_model_fit_limits.restype = C.c_int
+    L.ctag_testkit_model_fit_limits.argtypes = [i32p, C.c_int]
     _lib = L
     return L
+
+
+def model_fit_limits():
+    """k_mfit_record's grid and the observation records one pass of the fit's workspace holds (ctag_testkit_model_fit_limits).  Host only."""
+    out = np.zeros(2, np.int32)
+    n = load_library().ctag_testkit_model_fit_limits(out.ctypes.data_as(C.POINTER(C.c_int32)), 2)
+    if n != 2:
+        raise RuntimeError("ctag_testkit_model_fit_limits writes %d values" % n)
+    return {"record_grid": int(out[0]), "pass_records": int(out[1])}
 
 
 def synth_frame_host(state, frame_index, rows=1080, cols=1920, seed=SYNTH_SEED, markers=4):
@@ -245,6 +260,23 @@ class Detector(ca.Detector):
         if st != 0:
             raise CtagError(st, "ctag_testkit_welsch_fit")
         return lines
+
+    def model_fit_system(self, results, poses, model, camera, model_index, lam, min_obs=2, pass_records=0):
+        """The reduced system of the model reconstruction for one model at a given state (ctag_testkit_model_fit_system): host detection
+        records, POSE_DT records over them, a Model -> dict of S [3P, 3P], g [3P], delta [3P], held [P] bool, bad_pivot bool."""
+        res = np.ascontiguousarray(results).reshape(-1)
+        assert res.dtype == ca.RESULT_DT
+        poses = np.ascontiguousarray(poses, ca.POSE_DT).reshape(-1)
+        P = int(model.view()["size"]) * 8
+        S, g, d = np.zeros((3 * P, 3 * P)), np.zeros(3 * P), np.zeros(3 * P)
+        held = np.zeros(P, np.int32)
+        bad = C.c_int32()
+        st = self.T.ctag_testkit_model_fit_system(self.h, res.ctypes.data, len(res), poses.ctypes.data, len(poses), model.m, C.byref(camera),
+                                                  int(model_index), float(lam), int(min_obs), int(pass_records), S.ctypes.data, g.ctypes.data,
+                                                  d.ctypes.data, held.ctypes.data, C.byref(bad))
+        if st != 0:
+            raise CtagError(st, "ctag_testkit_model_fit_system")
+        return {"S": S, "g": g, "delta": d, "held": held.astype(bool), "bad_pivot": bool(bad.value)}
 
     def dense_edge_probe(self, gray, segments, K, dist, rvec, tvec, samples_per_edge=8, search_px=3.0, min_contrast=8.0):
         """Edge search of the dense pose-refinement study on the device (ctag_testkit_dense_edge_probe): segments [n, 12]
