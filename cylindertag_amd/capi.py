@@ -32,7 +32,8 @@ POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag
                 "ctag_camera_set_create", "ctag_camera_set_free", "ctag_mv_rig_pose_batch_device", "ctag_estimate_mv_rig_pose",
                 "ctag_cov_opts_default", "ctag_pose_cov_batch_device", "ctag_rig_pose_cov_batch_device", "ctag_mv_rig_pose_cov_batch_device",
                 "ctag_estimate_pose_cov", "ctag_estimate_rig_pose_cov", "ctag_estimate_mv_rig_pose_cov",
-                "ctag_model_fit_opts_default", "ctag_model_fit_device", "ctag_model_fit", "ctag_model_save", "ctag_model_fit_last_ms"]
+                "ctag_model_fit_opts_default", "ctag_model_fit_device", "ctag_model_fit", "ctag_model_save", "ctag_model_fit_last_ms",
+                "ctag_rig_fit_opts_default", "ctag_rig_fit_device", "ctag_rig_fit", "ctag_rig_fit_last_ms"]
 # ... and include/ctag_gather.h
 GATHER_EXPORTS = ["ctag_shard_range", "ctag_packed_capacity", "ctag_pack_results", "ctag_unpack_results", "ctag_comm_unique_id",
                   "ctag_comm_init", "ctag_comm_attach", "ctag_comm_destroy", "ctag_comm_native", "ctag_comm_last_error", "ctag_gather_begin",
@@ -70,6 +71,14 @@ COV_PARAM_TANGENT, COV_PARAM_RVEC = 0, 1
 MODEL_FIT_STAT_DT = np.dtype([("status", "<i4"), ("n_records", "<i4"), ("n_points_fitted", "<i4"), ("n_points_held", "<i4"), ("rounds", "<i4"),
                               ("reserved", "<i4"), ("cost0", "<f8"), ("cost", "<f8"), ("lambda", "<f8"), ("rms_px", "<f8")])
 assert MODEL_FIT_STAT_DT.itemsize == 56
+# ctag_rig_fit_stat / ctag_rig_fit_model_stat: one record per rig / per model of a rig assembly (include/ctag_pose.h)
+RIG_FIT_MAX_MODELS = 16
+RIG_FIT_STAT_DT = np.dtype([("status", "<i4"), ("anchor", "<i4"), ("n_placed", "<i4"), ("n_unplaced", "<i4"), ("n_records", "<i4"), ("n_points", "<i4"),
+                            ("rounds", "<i4"), ("reserved", "<i4"), ("cost_init", "<f8"), ("cost", "<f8"), ("lambda", "<f8"), ("rms_px", "<f8")])
+assert RIG_FIT_STAT_DT.itemsize == 64
+RIG_FIT_MODEL_STAT_DT = np.dtype([("status", "<i4"), ("rig", "<i4"), ("parent", "<i4"), ("n_frames_with_parent", "<i4"), ("n_records", "<i4"),
+                                  ("reserved", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
+assert RIG_FIT_MODEL_STAT_DT.itemsize == 72
 
 
 class ParamsC(C.Structure):  # ctag_params (include/ctag_types.h): the reference's tunables
@@ -132,6 +141,21 @@ def model_fit_opts(**fields):
     for k, v in fields.items():
         if k not in ("max_rounds", "min_obs", "lambda0", "lambda_max", "rel_tol", "strip_height"):
             raise TypeError("ctag_model_fit_opts has no field %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class RigFitOptsC(C.Structure):  # ctag_rig_fit_opts
+    _fields_ = [("max_rounds", C.c_int32), ("min_frames", C.c_int32), ("lambda0", C.c_double), ("lambda_max", C.c_double), ("rel_tol", C.c_double)]
+
+
+def rig_fit_opts(**fields):
+    """ctag_rig_fit_opts_default, then the given fields."""
+    o = RigFitOptsC()
+    load_library().ctag_rig_fit_opts_default(C.byref(o))
+    for k, v in fields.items():
+        if k not in ("max_rounds", "min_frames", "lambda0", "lambda_max", "rel_tol"):
+            raise TypeError("ctag_rig_fit_opts has no field %r" % k)
         setattr(o, k, v)
     return o
 
@@ -285,6 +309,15 @@ def load_library():
     L.ctag_model_save.argtypes = [vp, C.c_char_p]
     L.ctag_model_fit_last_ms.restype = C.c_int
     L.ctag_model_fit_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    rfitp = C.POINTER(RigFitOptsC)
+    L.ctag_rig_fit_opts_default.restype = None
+    L.ctag_rig_fit_opts_default.argtypes = [rfitp]
+    L.ctag_rig_fit_device.restype = C.c_int
+    L.ctag_rig_fit_device.argtypes = [vp, vp, C.c_int, vp, vp, C.POINTER(CameraC), rfitp, C.POINTER(vp), vp, vp]
+    L.ctag_rig_fit.restype = C.c_int
+    L.ctag_rig_fit.argtypes = [vp, vp, C.c_int, vp, vp, C.POINTER(CameraC), rfitp, C.POINTER(vp), vp, vp]
+    L.ctag_rig_fit_last_ms.restype = C.c_int
+    L.ctag_rig_fit_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     u64p = C.POINTER(C.c_uint64)
     L.ctag_shard_range.restype = C.c_int
     L.ctag_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -796,6 +829,38 @@ class Detector:
         out = (C.c_float * 4)()
         self.L.ctag_model_fit_last_ms(self.h, out)
         return dict(zip(("pose", "record", "assemble", "solve"), (float(v) for v in out)))
+
+    # ---- rig assembly (include/ctag_pose.h): opts is a RigFitOptsC (rig_fit_opts(...)) or None for the defaults
+    def _fit_rigs(self, fn, name, results_arg, n_frames, model, rigs, camera, opts):
+        n_models = int(model.view()["ids"].size)
+        rig_stats = np.zeros(max(rigs.n_rigs, 1), RIG_FIT_STAT_DT)
+        model_stats = np.zeros(max(n_models, 1), RIG_FIT_MODEL_STAT_DT)
+        m = C.c_void_p()
+        st = fn(self.h, results_arg, n_frames, model.m, rigs.r, C.byref(camera), C.byref(opts) if opts is not None else None, C.byref(m),
+                rig_stats.ctypes.data, model_stats.ctypes.data)
+        if st != 0:
+            raise CtagError(st, name)
+        model_stats = model_stats[:n_models]
+        placed = np.where(model_stats["status"] == POSE_OK, rigs.rig_of_model[:n_models], -1).astype(np.int32)
+        return Model._adopt(m), rig_stats[:rigs.n_rigs], model_stats, placed
+
+    def fit_rigs(self, results, model, rigs, camera, opts=None):
+        """ctag_rig_fit: host ctag_frame_result records of many frames, a Model whose models each have their own frame and the Rigs that
+        groups them -> (the Model with every rig's models in the frame of the rig's anchor, RIG_FIT_STAT_DT records, one per rig,
+        RIG_FIT_MODEL_STAT_DT records, one per model, rig_of_model with the unplaced models at -1: what Rigs takes for the result).  Waits."""
+        res = np.ascontiguousarray(results).reshape(-1)
+        assert res.dtype == RESULT_DT
+        return self._fit_rigs(self.L.ctag_rig_fit, "ctag_rig_fit", res.ctypes.data if len(res) else None, len(res), model, rigs, camera, opts)
+
+    def fit_rigs_device(self, results_ptr, n_frames, model, rigs, camera, opts=None):
+        """ctag_rig_fit_device: the same from n_frames result records in device memory (as detect_batch_device leaves them)."""
+        return self._fit_rigs(self.L.ctag_rig_fit_device, "ctag_rig_fit_device", results_ptr, n_frames, model, rigs, camera, opts)
+
+    def rig_fit_last_ms(self):
+        """Device milliseconds of the last assembly by kernel kind (needs OPT_TIMING): marker pose, rig pose, record + assemble, solve."""
+        out = (C.c_float * 4)()
+        self.L.ctag_rig_fit_last_ms(self.h, out)
+        return dict(zip(("marker_pose", "rig_pose", "record", "solve"), (float(v) for v in out)))
 
     # ---- pose covariance (include/ctag_pose.h): opts is a CovOptsC (cov_opts(...)) or None for the defaults
     @staticmethod

@@ -284,6 +284,43 @@ void CylinderTag::reconstructModel(const std::vector<std::vector<MarkerInfo>>& f
     ctag_model_free(fitted);
 }
 
+// new: the models of every rig in one frame (include/ctag_pose.h, rig assembly)
+void CylinderTag::assembleRigModel(const std::vector<std::vector<MarkerInfo>>& framesOfMarkers, const std::vector<ModelInfo>& model,
+                                   const std::vector<int>& rigOfModel, CamInfo camera, std::vector<ModelInfo>& outModel, std::vector<int>& placedRigOfModel) {
+    if (framesOfMarkers.empty()) throw __FUNCTION__ + std::string(", ") + "no frames\n";
+    if (rigOfModel.size() != model.size()) throw __FUNCTION__ + std::string(", ") + "one rig entry per model\n";
+    int n_rigs = 1;
+    for (int g : rigOfModel) n_rigs = g + 1 > n_rigs ? g + 1 : n_rigs;
+    std::vector<ctag_frame_result> recs(framesOfMarkers.size());
+    for (size_t f = 0; f < framesOfMarkers.size(); f++) {
+        for (const MarkerInfo& mi : framesOfMarkers[f])
+            if (mi.cornerLists.size() > (size_t)CTAG_MAX_FEATURES) throw __FUNCTION__ + std::string(", ") + "a marker with more than 100 features\n";
+        if (flatten(framesOfMarkers[f], 0, recs[f]) != framesOfMarkers[f].size())
+            throw __FUNCTION__ + std::string(", ") + "a frame with more markers or features than a detection record holds\n";
+        if (recs[f].n_markers == 0) recs[f].status = CTAG_NO_FEATURE;  // detect() left the list empty
+    }
+    ctag_model* in = make_model(model, __FUNCTION__);
+    ctag_rigs* rigs = nullptr;
+    int st = ctag_rigs_create(in, rigOfModel.data(), n_rigs, &rigs);
+    if (st != CTAG_OK) {
+        ctag_model_free(in);
+        throw __FUNCTION__ + std::string(", ") + "illegal rig set\n";
+    }
+    const ctag_camera cam = make_camera(camera);
+    std::vector<ctag_rig_fit_stat> rig_stats((size_t)n_rigs);
+    std::vector<ctag_rig_fit_model_stat> model_stats(model.size() + 1);
+    ctag_model* assembled = nullptr;
+    st = ctag_rig_fit(h_, recs.data(), (int)recs.size(), in, rigs, &cam, nullptr, &assembled, rig_stats.data(), model_stats.data());
+    ctag_rigs_free(rigs);
+    ctag_model_free(in);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    unpack_model(assembled, outModel);
+    ctag_model_free(assembled);
+    placedRigOfModel.assign(rigOfModel.begin(), rigOfModel.end());
+    for (size_t m = 0; m < model.size(); m++)
+        if (model_stats[m].status != CTAG_POSE_OK) placedRigOfModel[m] = -1;
+}
+
 void CylinderTag::saveModel(const std::string& path, const std::vector<ModelInfo>& model) {
     ctag_model* m = make_model(model, __FUNCTION__);
     const int st = ctag_model_save(m, path.c_str());

@@ -174,6 +174,13 @@ class CylinderTag {
     // <= 100 features, as detect() returns them).  Throws std::string on error.
     void reconstructModel(const std::vector<std::vector<MarkerInfo>>& framesOfMarkers, const std::vector<ModelInfo>& seedModel, CamInfo camera,
                           std::vector<ModelInfo>& outModel, double stripHeight = 0.0);
+    // Carry the models of every rig into ONE frame (new; include/ctag_pose.h, rig assembly: ctag_rig_fit).  reconstructModel returns each
+    // model in its own frame; estimateRigPose needs the models of a rig in one.  framesOfMarkers[f] is what detect() returned for frame f of
+    // a sequence that shows two or more markers of a rig together; rigOfModel[i] is the rig of model i (-1: none).  outModel has the models
+    // of each rig in the frame of the rig's anchor; placedRigOfModel is rigOfModel with the models the frames never linked to their rig at
+    // -1 (they keep their corners): pass it, not rigOfModel, to estimateRigPose.  Throws std::string on error.
+    void assembleRigModel(const std::vector<std::vector<MarkerInfo>>& framesOfMarkers, const std::vector<ModelInfo>& model,
+                          const std::vector<int>& rigOfModel, CamInfo camera, std::vector<ModelInfo>& outModel, std::vector<int>& placedRigOfModel);
     // Write a model list in the text format loadModel reads (CylinderTag.cpp:168-188), floats with 9 significant digits: loadModel gives
     // back the same values bit for bit.  Throws std::string when the file cannot be written.
     void saveModel(const std::string& path, const std::vector<ModelInfo>& model);

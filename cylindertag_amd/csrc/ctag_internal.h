@@ -22,6 +22,7 @@
 struct ctag_handle;
 struct ctag_camera;
 struct ctag_pose_rec;
+struct ctag_rig_pose_rec;
 
 namespace ctag {
 // A device buffer the library's host code owns: pointer and capacity in elements.  grow() frees, then allocates (the old contents are gone); the
@@ -374,8 +375,8 @@ void build_pick_table(uint8_t* table, uint16_t* table16);  // kPickN*20*10 bytes
 
 
 // accessor of the opaque handle for the state of its back ends, each created on first use: the pose back end (k_pose.hip), the overlay (k_draw.hip),
-// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip), the multi-view rig poses (k_mv_pose.hip), the pose covariance (k_pose_cov.hip), the model reconstruction (k_model_fit.hip).  ctag_destroy frees them in this order.
-enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kCovState, kFitState, kNumSiblingStates };
+// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip), the multi-view rig poses (k_mv_pose.hip), the pose covariance (k_pose_cov.hip), the model reconstruction (k_model_fit.hip), the rig assembly (k_rig_fit.hip).  ctag_destroy frees them in this order.
+enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kCovState, kFitState, kRigFitState, kNumSiblingStates };
 void** handle_state_slot(struct ::ctag_handle* h, SiblingState which, void (*free_fn)(void*));
 // the model's device copies on `device` (k_pose.hip); the camera's distortion model is one the pose back end handles
 int model_to_device(struct ::ctag_model* m, int device);
@@ -418,6 +419,15 @@ int mfit_probe_system(struct ::ctag_handle* h, const ctag_frame_result* results,
                       double* S, double* g, double* delta, int32_t* held, int32_t* bad_pivot);
 int mfit_record_grid();   // k_mfit_record's grid
 int mfit_pass_records();  // observation records one pass of its workspace holds
+// the reduced system of ONE rig of the rig assembly (k_rig_fit.hip; include/ctag_pose.h, rig assembly, rule 5) at a caller-given state: host detection
+// records, the n_frames x n_rigs host rig-pose records over them (the CTAG_POSE_OK ones with n_members >= 2 are the observations), a model and a rig set
+// whose every model of rig `rig` is a member slot in ascending model order, the first being the anchor (its rows are dropped) -> *n_unknowns = N = 6 x the
+// rig's models, S [N x N], g [N], delta [N] and whether a pivot was not positive; pass_records > 0 sets how many records one pass of the workspace holds.  Waits.
+int rfit_probe_system(struct ::ctag_handle* h, const ctag_frame_result* results, int n_frames, const struct ::ctag_rig_pose_rec* recs,
+                      const struct ::ctag_model* model, const struct ::ctag_rigs* rigs, const struct ::ctag_camera* camera, int rig, double lambda,
+                      int pass_records, double* S, double* g, double* delta, int32_t* n_unknowns, int32_t* bad_pivot);
+int rfit_record_grid();   // k_rfit_record's grid
+int rfit_pass_records();  // observation records one pass of its workspace holds
 // the part of ctag_gather_end behind the payload all-gather: segment table of a `world`-rank job + unpack kernels on the
 // handle's gather stream, on a caller-supplied gathered buffer (world shards of `width` bytes); waits for completion
 int gather_unpack_gathered(struct ::ctag_handle* h, const void* gathered_dev, int n_total, int world, uint64_t width, ctag_frame_result* out_dev);

@@ -30,6 +30,7 @@
 #include "../../include/ctag_pose.h"
 #include "ctag_internal.h"
 #include "ctag_pose_dev.h"
+#include "ctag_schur6.h"
 #include "ctag_wave.h"
 
 static_assert(sizeof(ctag_model_fit_stat) == 56, "ctag_model_fit_stat layout");
@@ -52,49 +53,6 @@ struct MfitLds {
 
 // corner k (0 .. 7) of a feature that an emit's lane q stands for: 0 1 4 5 2 3 6 7
 __device__ __forceinline__ int mfit_corner_of(int q) { return q < 2 ? q : q < 4 ? q + 2 : q < 6 ? q - 2 : q; }
-
-// U = L L^T of a symmetric 6x6 given as its 21 upper entries in row order; false on a pivot that is not positive (or not a number)
-__device__ __forceinline__ bool mfit_chol6(const double* H, double* L) {
-    double U[36];
-    int e = 0;
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-        for (int b = a; b < 6; b++) {
-            U[a * 6 + b] = H[e];
-            U[b * 6 + a] = H[e];
-            e++;
-        }
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double d = U[j * 6 + j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= L[j * 6 + k] * L[j * 6 + k];
-        if (!(d > 0.0) || !ctl::finite64(d)) ok = false;
-        d = ctm::sqrt64(d);
-        L[j * 6 + j] = d;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double s = U[i * 6 + j];
-#pragma unroll
-            for (int k = 0; k < j; k++) s -= L[i * 6 + k] * L[j * 6 + k];
-            L[i * 6 + j] = s / d;
-        }
-    }
-    return ok;
-}
-
-// x <- L^-1 x (forward substitution, lower triangle of the row-major 6x6 L)
-__device__ __forceinline__ void mfit_forward6(const double* L, double* x) {
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double s = x[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= L[i * 6 + k] * x[k];
-        x[i] = s / L[i * 6 + i];
-    }
-}
 
 // Observation records r0 .. r1-1 (indices into ok_list, which holds pose-record indices): workspace slot r - r0 gets the 27
 // doubles of every point, table row r the corner -> local index map, flags[r] the record's state.

@@ -409,6 +409,99 @@ int ctag_model_save(const ctag_model* m, const char* path);
 /* device time of the last fit call's kernels by kind (needs CTAG_OPT_TIMING), milliseconds: pose, record, assemble, solve */
 int ctag_model_fit_last_ms(ctag_handle* h, float* out4);
 
+/* ---- rig assembly: the models of one rig into one common frame, from detections (k_rig_fit.hip) ------------------------------------
+ * ctag_model_fit returns every model in its own frame (rule 5 there pins it to its seed); the rig and multi-view calls need the
+ * models of a rig in ONE frame.  From the detection records of frames that show two or more markers of a rig together this call
+ * computes the rigid transform that carries each member model into the rig's frame -- the frame of one of its models, the anchor --
+ * and returns the assembled model.  The problem over member transforms AND per-frame rig poses separates: given the transforms a
+ * frame's rig pose is the solve ctag_rig_pose_batch_device already does, so only the transforms are optimised, by
+ * Levenberg-Marquardt on the cost with the rig poses eliminated (the Schur complement on the 6x6 pose blocks).  Rigs are
+ * independent problems: each has its own lambda, accept / reject and stop, inside the same launches.
+ *   1. Per-marker poses.  The poses of ctag_pose_batch_device under `in` are computed once, before the first round.  A frame that is not CTAG_OK and a record that is not CTAG_POSE_OK
+ *      contribute nothing.  Of two markers of a frame with one model index only the first counts (the rig section's duplicate rule:
+ *      the first marker with a model index claims it, whether or not its pose counts).
+ *   2. Initial assembly, per rig, on the host in double from those pose records (R_m, t_m of model m in a frame).  n(a,b) = the
+ *      number of frames in which models a and b of the rig both have a counted pose.  Anchor = the lowest model index of the rig
+ *      with any n(a,.) >= min_frames.  A tree grows from it: repeatedly the unplaced model b with the largest n(a,b) to a placed
+ *      model a is added with parent a (ties: the lowest b, then the lowest a) until no such count reaches min_frames.  The edge
+ *      transform X_a = E X_b has as rotation the rotation nearest (SVD, determinant fixed) to the sum, in frame order, of
+ *      R_a^T R_b and as translation the mean, in frame order, of R_a^T (t_b - t_a);  T_b = T_a o E.  model_stats' parent and
+ *      n_frames_with_parent report the tree.  Unplaced models -- never seen often enough with the rig, in no rig -- keep their
+ *      corners and get status CTAG_POSE_NOT_SEEN; a rig with no anchor gets status CTAG_POSE_NOT_SEEN.
+ *   3. Working model.  float32, as every consumer reads it.  A state applies the transforms X_rig = R X_in + t to `in`'s float
+ *      corners in double and rounds to float; base moves as a point, axis rotates only.  The anchor's transform is exactly the
+ *      identity and is skipped: its corners, base and axis are `in`'s bytes, as are an unplaced model's.  marker_id and model_size
+ *      are `in`'s.
+ *   4. Observation set.  The (frame, rig) items whose ctag_rig_pose_rec on the initial assembly is CTAG_POSE_OK with n_members >= 2,
+ *      where unplaced models are left out of their rig for the whole call (an internal rig_of_model copy has them at -1, so all
+ *      members are placed).  The set is fixed for the call.  The cost of a state = the sum, in (frame, rig) order, of the cost
+ *      field ctag_rig_pose_batch_device gives those items on that float model; stats.cost is that sum on the returned model byte
+ *      for byte, cost_init the sum on the initial assembly.
+ *   5. A round is Levenberg-Marquardt on the 6 (n_placed - 1) unknowns of a rig.  Update T_m <- Exp(d_m) T_m with d = (w, v) in
+ *      the rig frame: R <- Exp(w) R, t <- Exp(w) t + v (Exp the Rodrigues formula).  Per point i of member m with rig-frame corner Y:
+ *      Jm_i = (dr/dY) [-[Y]x | I] and Jp_i as CTAG_COV_PARAM_RVEC has it.  Per record: U = sum Jp^T Jp = L L^T, y = L^-1 sum Jp^T r,
+ *      Z_m = L^-1 sum_{i in m} Jp^T Jm;  S_mm += sum Jm^T Jm - Z_m^T Z_m,  S_mn -= Z_m^T Z_n,  g_m += sum Jm^T r - Z_m^T y;  the
+ *      anchor's rows are dropped.  The step solves (S + lambda diag S) d = -g by Cholesky; a pivot that is not positive is a reject.
+ *      The trial is accepted iff the cost of rule 4 decreases; lambda <- max(lambda / 3, 1e-9) on accept, 4 lambda on reject.  A
+ *      trial in which an observation record stops being CTAG_POSE_OK is a reject.  A rig stops when an accepted round lowers the
+ *      cost by less than rel_tol * cost, when lambda exceeds lambda_max, or after max_rounds; max_rounds = 0 returns the initial
+ *      assembly.
+ *   6. Determinism.  Every sum has a fixed order: record order across records, wave_sum_f64's tree inside one.  Two calls return
+ *      the same bytes, and the result does not depend on the pass size of the workspace or on the grid.
+ *   7. CTAG_ERR_ARG: a null argument, n_frames < 1, max_rounds < 0, min_frames < 1, lambda0 / lambda_max / rel_tol that are not
+ *      positive and finite, an `in` whose model_size is not the handle's dictionary's column count or is above 20, a `rigs` made
+ *      for another n_models, a rig of more than CTAG_RIG_FIT_MAX_MODELS models; CTAG_ERR_UNSUPPORTED: a camera the pose back end
+ *      does not handle.
+ * Device memory of one call: the pose records of both kinds, 63 doubles (Z 36, Jm^T Jm 21, g 6) per member slot -- 8064 bytes per
+ * observation record of a pass, at most 512 records a pass -- and 96 x 96 doubles per rig for S. */
+#define CTAG_RIG_FIT_MAX_MODELS 16   /* member models of one rig the assembly takes */
+typedef struct ctag_rig_fit_opts {
+    int32_t max_rounds;   /* default 30 */
+    int32_t min_frames;   /* default 2 */
+    double lambda0;       /* default 1e-3 */
+    double lambda_max;    /* default 1e6 */
+    double rel_tol;       /* default 2.479e-5: 4 x the relative cost change float32 rounding of the model alone causes (6.198e-6) */
+} ctag_rig_fit_opts;
+
+typedef struct ctag_rig_fit_stat {        /* one per rig */
+    int32_t status;       /* CTAG_POSE_OK or CTAG_POSE_NOT_SEEN */
+    int32_t anchor;       /* model index, -1 without one */
+    int32_t n_placed;     /* models in the rig's frame, the anchor included */
+    int32_t n_unplaced;   /* models of the rig left out (rule 2) */
+    int32_t n_records;    /* observation records (rule 4) */
+    int32_t n_points;     /* correspondences of those records */
+    int32_t rounds;       /* rounds taken (accepted + rejected) */
+    int32_t reserved;     /* 0 */
+    double cost_init;     /* cost of the initial assembly */
+    double cost;          /* cost of the returned model */
+    double lambda;        /* lambda when the rig stopped */
+    double rms_px;        /* sqrt(2 cost / n_points) */
+} ctag_rig_fit_stat;      /* 64 bytes */
+
+typedef struct ctag_rig_fit_model_stat {  /* one per model */
+    int32_t status;       /* CTAG_POSE_OK (placed) or CTAG_POSE_NOT_SEEN */
+    int32_t rig;          /* the rig set's entry for the model */
+    int32_t parent;       /* rule 2's tree; -1 for an anchor and an unplaced model */
+    int32_t n_frames_with_parent;
+    int32_t n_records;    /* observation records the model is a member of */
+    int32_t reserved;     /* 0 */
+    double rvec[3], tvec[3];  /* X_rig = R(rvec) X_in + tvec; exactly 0 for an anchor and for models that did not move */
+} ctag_rig_fit_model_stat;    /* 72 bytes */
+
+void ctag_rig_fit_opts_default(ctag_rig_fit_opts* opts);
+/* results_dev: n_frames detection records in DEVICE memory.  *out: a new model (ctag_model_free); rig_stats: n_rigs HOST records,
+ * model_stats: n_models HOST records.  opts == NULL means the defaults.  Waits for completion: the outer loop decides on the host.
+ * The rig calls take the result together with a rig set in which model_stats' CTAG_POSE_NOT_SEEN models are -1. */
+int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, int n_frames, const ctag_model* in, const ctag_rigs* rigs,
+                        const ctag_camera* camera, const ctag_rig_fit_opts* opts, ctag_model** out, ctag_rig_fit_stat* rig_stats,
+                        ctag_rig_fit_model_stat* model_stats);
+/* The same from HOST records: uploads them, then ctag_rig_fit_device. */
+int ctag_rig_fit(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_model* in, const ctag_rigs* rigs,
+                 const ctag_camera* camera, const ctag_rig_fit_opts* opts, ctag_model** out, ctag_rig_fit_stat* rig_stats,
+                 ctag_rig_fit_model_stat* model_stats);
+/* device time of the last assembly's kernels by kind (needs CTAG_OPT_TIMING), milliseconds: marker pose, rig pose, record + assemble, solve */
+int ctag_rig_fit_last_ms(ctag_handle* h, float* out4);
+
 /* ---- overlay: CylinderTag::drawAxis (reference CylinderTag.cpp:211-246) ------------------------------------------------
  * Output: 8-bit, 3 channels, every channel = the gray value (cvtColor GRAY2RGB), then per drawn record, in record order,
  * what the reference paints with OpenCV 4.5.3 (k_draw.hip restates it):

@@ -142,6 +142,22 @@ int ctag_testkit_model_fit_system(ctag_handle* h, const ctag_frame_result* resul
 /* k_mfit_record's grid and the records a pass holds by default (host only): out[0], out[1]; returns 2 */
 int ctag_testkit_model_fit_limits(int32_t* out, int capacity);
 
+/* ---- the reduced system of the rig assembly (cylindertag_amd/csrc/k_rig_fit.hip; include/ctag_pose.h, rig assembly) ---------------------------
+ * k_rfit_record, k_rfit_assemble and k_rfit_solve at a caller-given state instead of inside the assembly's loop.  results: n_frames HOST
+ * detection records; rig_poses: the n_frames x n_rigs HOST records ctag_rig_pose_batch_device gives over them on `model` with `rigs` -- the
+ * CTAG_POSE_OK ones with n_members >= 2 are the observation records (rule 4) and their rvec / tvec the state; model: the corner lists, already
+ * in the rig's frame; lambda: the damping (any finite value: a negative one makes the system indefinite).  For rig `rig`, whose M models (2 ..
+ * CTAG_RIG_FIT_MAX_MODELS, ascending model index) own the unknowns 6k .. 6k+5 (rotation, translation: rule 5) and whose first model is the
+ * anchor, with N = 6 M: *n_unknowns = N, S [N][N] and g [N] as assembled over ALL its models, delta [N] = the solution of
+ * (S + lambda diag S) delta = -g with the anchor's rows as identity rows (0 there), *bad_pivot = 1 when a pivot was not positive (delta is 0
+ * then).  The arrays hold 96 x 96, 96 and 96 doubles.  pass_records > 0: the workspace holds that many records a pass (rule 6); 0: the
+ * call's own size.  Host arrays out.  Runs on the handle's device and waits. */
+int ctag_testkit_rig_fit_system(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_rig_pose_rec* rig_poses,
+                                const ctag_model* model, const ctag_rigs* rigs, const ctag_camera* camera, int rig, double lambda, int pass_records,
+                                double* S, double* g, double* delta, int32_t* n_unknowns, int32_t* bad_pivot);
+/* k_rfit_record's grid and the records a pass holds by default (host only): out[0], out[1]; returns 2 */
+int ctag_testkit_rig_fit_limits(int32_t* out, int capacity);
+
 /* ---- the kernel forms the library picks for a chunk (plan_chunk, cylindertag_amd/csrc/ctag_api.hip) ------------------
  * For `nframes` frames of rows x cols (gray, or BGR for channels == 3) at `frames` (only its alignment is looked at) with the given
  * strides, the handle options CTAG_OPT_FUSED_SWEEP (-1: not set), CTAG_OPT_WAVE_POINTS, CTAG_OPT_BGR_DIRECT, CTAG_OPT_EXPAND_EXACT,

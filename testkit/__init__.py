@@ -25,7 +25,7 @@ SYNTH_SEED = 0x4354616753594E00  # "CTagSYN\0", SURVEY.md 8(d)
 EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
            "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model",
            "ctag_testkit_dense_edge_probe", "ctag_testkit_plan", "ctag_testkit_welsch_fit", "ctag_testkit_welsch_limits",
-           "ctag_testkit_model_fit_system", "ctag_testkit_model_fit_limits"]
+           "ctag_testkit_model_fit_system", "ctag_testkit_model_fit_limits", "ctag_testkit_rig_fit_system", "ctag_testkit_rig_fit_limits"]
 # the fields ctag_testkit_plan writes, in order (cylindertag_amd/csrc/ctag_internal.h: ChunkPlan)
 PLAN_FIELDS = ("fused", "bgr_direct", "zero_first", "dec_zero_kernel", "dec_zero_list", "dec", "dec_xblocks", "dec_yblocks", "dec_band_rows", "dec_bands",
                "ccl", "latency", "small_cfg", "refprm", "mask_scan", "prescan", "all_wave", "fork", "pack_max", "big_points", "pack_gx", "scan_gx",
@@ -99,6 +99,10 @@ def load_library():
                                                 vp, i32p]
     L.ctag_testkit_model_fit_limits.restype = C.c_int
     L.ctag_testkit_model_fit_limits.argtypes = [i32p, C.c_int]
+    L.ctag_testkit_rig_fit_system.restype = C.c_int
+    L.ctag_testkit_rig_fit_system.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.POINTER(capi.CameraC), C.c_int, C.c_double, C.c_int, vp, vp, vp, i32p, i32p]
+    L.ctag_testkit_rig_fit_limits.restype = C.c_int
+    L.ctag_testkit_rig_fit_limits.argtypes = [i32p, C.c_int]
     _lib = L
     return L
 
@@ -109,6 +113,15 @@ def model_fit_limits():
     n = load_library().ctag_testkit_model_fit_limits(out.ctypes.data_as(C.POINTER(C.c_int32)), 2)
     if n != 2:
         raise RuntimeError("ctag_testkit_model_fit_limits writes %d values" % n)
+    return {"record_grid": int(out[0]), "pass_records": int(out[1])}
+
+
+def rig_fit_limits():
+    """k_rfit_record's grid and the observation records one pass of the rig assembly's workspace holds (ctag_testkit_rig_fit_limits).  Host only."""
+    out = np.zeros(2, np.int32)
+    n = load_library().ctag_testkit_rig_fit_limits(out.ctypes.data_as(C.POINTER(C.c_int32)), 2)
+    if n != 2:
+        raise RuntimeError("ctag_testkit_rig_fit_limits writes %d values" % n)
     return {"record_grid": int(out[0]), "pass_records": int(out[1])}
 
 
@@ -277,6 +290,23 @@ class Detector(ca.Detector):
         if st != 0:
             raise CtagError(st, "ctag_testkit_model_fit_system")
         return {"S": S, "g": g, "delta": d, "held": held.astype(bool), "bad_pivot": bool(bad.value)}
+
+    def rig_fit_system(self, results, rig_poses, model, rigs, camera, rig, lam, pass_records=0):
+        """The reduced system of the rig assembly for one rig at a given state (ctag_testkit_rig_fit_system): host detection records, the
+        RIG_POSE_DT records over them on `model` with `rigs` -> dict of S [N, N], g [N], delta [N] (N = 6 x the rig's models, the first
+        model's rows being the dropped anchor's), bad_pivot bool."""
+        res = np.ascontiguousarray(results).reshape(-1)
+        assert res.dtype == ca.RESULT_DT
+        recs = np.ascontiguousarray(rig_poses, ca.RIG_POSE_DT).reshape(-1)
+        assert len(recs) == len(res) * rigs.n_rigs
+        S, g, d = np.zeros(96 * 96), np.zeros(96), np.zeros(96)
+        n, bad = C.c_int32(), C.c_int32()
+        st = self.T.ctag_testkit_rig_fit_system(self.h, res.ctypes.data, len(res), recs.ctypes.data, model.m, rigs.r, C.byref(camera), int(rig),
+                                                float(lam), int(pass_records), S.ctypes.data, g.ctypes.data, d.ctypes.data, C.byref(n), C.byref(bad))
+        if st != 0:
+            raise CtagError(st, "ctag_testkit_rig_fit_system")
+        N = int(n.value)
+        return {"S": S[:N * N].reshape(N, N).copy(), "g": g[:N].copy(), "delta": d[:N].copy(), "bad_pivot": bool(bad.value)}
 
     def dense_edge_probe(self, gray, segments, K, dist, rvec, tvec, samples_per_edge=8, search_px=3.0, min_contrast=8.0):
         """Edge search of the dense pose-refinement study on the device (ctag_testkit_dense_edge_probe): segments [n, 12]
