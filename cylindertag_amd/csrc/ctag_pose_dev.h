@@ -5,7 +5,8 @@
 // of a point as a policy (one camera: camera_residual; a camera per point: k_mv_pose.hip); pose_solve is the two in a row.
 // Generic over the LDS capacity PTS and the block width NT: per-point loops stride over the NT lanes, while every sum over
 // the points stays with its one owner lane (lane < 144 / 34), so the result is the sequential evaluation for any n <= PTS.
-// k_pose_cov.hip (the covariance of a finished pose) reads the correspondence rule, the corner loader and the residuals from here.
+// k_pose_cov.hip (the covariance of a finished pose), k_model_fit.hip and k_rig_fit.hip read the correspondence rule, the corner
+// loader, the residuals, the point descriptor and load_state6 from here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -200,6 +201,29 @@ __device__ __forceinline__ void corner_point(const PoseCam& cam, const float* __
     X[0] = (double)cp[0];
     X[1] = (double)cp[1];
     X[2] = (double)cp[2];
+}
+
+// Where a point of a record comes from, in one word, for the kernels that walk a record once and visit its points afterwards
+// (k_pose_cov.hip, k_model_fit.hip, k_rig_fit.hip): feature index in its frame record (7 bits) | corner q of the emit << 7 (3 bits) |
+// camera << 10 (3 bits) | model position << 13 (positions are below 2^16)
+static_assert(CTAG_MAX_FEATURES <= 128 && CTAG_MV_MAX_CAMERAS <= 8, "the point descriptor's bit fields");
+__device__ __forceinline__ int32_t point_desc(int feature, int q, int cam, int pos) { return feature | (q << 7) | (cam << 10) | (pos << 13); }
+__device__ __forceinline__ int desc_feature(int32_t s) { return s & 127; }
+__device__ __forceinline__ int desc_q(int32_t s) { return (s >> 7) & 7; }
+__device__ __forceinline__ int desc_cam(int32_t s) { return (s >> 10) & 7; }
+__device__ __forceinline__ int desc_pos(int32_t s) { return s >> 13; }
+
+// x = (rvec, tvec) of a pose record of any kind; false when one of the six is not finite
+template <class Rec>
+__device__ __forceinline__ bool load_state6(const Rec& P, double* x) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        x[i] = P.rvec[i];
+        x[3 + i] = P.tvec[i];
+        ok = ok && ctl::finite64(x[i]) && ctl::finite64(x[3 + i]);
+    }
+    return ok;
 }
 
 // lane q < cnt of an emit: that corner as point i of the problem

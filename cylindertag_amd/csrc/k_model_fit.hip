@@ -18,16 +18,22 @@
 //             zero right-hand side, the two triangular solves, delta and a flag for a pivot that is not positive.
 // The host decides (accept / reject, lambda, stop, gauge, metric scale) per model between the launches.  FP64 VALU like the pose
 // kernels; the largest system is 480 x 480, nothing here is MFMA-shaped enough to pay for a second arithmetic.
+//
+// What this fit shares with the rig assembly (k_rig_fit.hip) is not here: the pose block of a record (pass 1 of the record kernel, a
+// column through L^-1, the point Jacobian) is ctag_schur6.h's, the point descriptor and load_state6 are ctag_pose_dev.h's, and the
+// host side of a fit -- timed state, call context, working model, systems with their pass loop and solve, the accept / reject rule
+// -- is ctag_fit_host.h's.  This file keeps its kernels' own walk, tables and pass 2, find_held, gauge_to_seed,
+// metric_scale, the probe, and its round loop.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/ctag_pose.h"
+#include "ctag_fit_host.h"
 #include "ctag_internal.h"
 #include "ctag_pose_dev.h"
 #include "ctag_schur6.h"
@@ -43,11 +49,10 @@ constexpr int kMfitPassRecords = 2048;   // observation records one pass of the 
 constexpr int kMfitDoubles = 27;         // per point of a record: Z (18), Jx^T Jx (6), Jx^T r - Z^T y (3)
 constexpr int kMfitMaxN = 3 * kPoseMaxPts;  // 480 unknowns per model at most
 constexpr int kMfitSolveThreads = 1024;
-constexpr int kMfitLeftOut = 1;          // flags: the record is not an observation (rule 1; set on its first visit, never changes)
-constexpr int kMfitSingular = 2;         // flags: U of the record has a pivot that is not positive at this state
+// flags of a record: kRecLeftOut (it is not an observation: rule 1; set on its first visit, never changes) and kRecSingular
 
 struct MfitLds {
-    int32_t src[kPoseMaxPts];    // point i: feature index in its frame record | corner q of the emit << 7 | model position << 13
+    int32_t src[kPoseMaxPts];    // point i: its descriptor (point_desc, ctag_pose_dev.h; camera 0)
     int16_t table[kPoseMaxPts];  // model corner -> local point index, -1 where absent
 };
 
@@ -76,7 +81,7 @@ __global__ __launch_bounds__(64) void k_mfit_record(const ctag_frame_result* __r
                 const ctag_feature_rec* F0 = FR.features;
                 const int st = marker_points(FR, FR.markers[P.marker], model.model_size, kPoseMaxPts, n, [&](const ctag_feature_rec& F, int pos, int cnt, int i0) {
                     if (lane < cnt) {
-                        L.src[i0 + lane] = (int32_t)(&F - F0) | (lane << 7) | (pos << 13);
+                        L.src[i0 + lane] = point_desc((int)(&F - F0), lane, 0, pos);
                         L.table[pos * 8 + mfit_corner_of(lane)] = (int16_t)(i0 + lane);
                     }
                 });
@@ -88,21 +93,16 @@ __global__ __launch_bounds__(64) void k_mfit_record(const ctag_frame_result* __r
             int dup = 0;
             for (int i = lane; i < n; i += 64) {
                 const int s = L.src[i];
-                dup += L.table[(s >> 13) * 8 + mfit_corner_of((s >> 7) & 7)] != i ? 1 : 0;
+                dup += L.table[desc_pos(s) * 8 + mfit_corner_of(desc_q(s))] != i ? 1 : 0;
             }
             ok = sg_sum<64>(dup) == 0;
         }
         double x[6];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            x[i] = P.rvec[i];
-            x[3 + i] = P.tvec[i];
-            ok = ok && ctl::finite64(x[i]) && ctl::finite64(x[3 + i]);
-        }
+        ok = load_state6(P, x) && ok;
         int16_t* T = table + (size_t)r * pm;
         if (!ok) {  // wave-uniform
             for (int c = lane; c < pm; c += 64) T[c] = -1;
-            if (lane == 0) flags[r] = kMfitLeftOut;
+            if (lane == 0) flags[r] = kRecLeftOut;
             continue;
         }
         for (int c = lane; c < pm; c += 64) T[c] = L.table[c];
@@ -119,44 +119,24 @@ __global__ __launch_bounds__(64) void k_mfit_record(const ctag_frame_result* __r
         for (int i = lane; i < n; i += 64) {
             const int s = L.src[i];
             double xn, yn, ob[2], X[3], q0, q1, j0[6], j1[6];
-            corner_point(cam, corners, FR.features[s & 127], s >> 13, (s >> 7) & 7, xn, yn, ob, X);
+            corner_point(cam, corners, FR.features[desc_feature(s)], desc_pos(s), desc_q(s), xn, yn, ob, X);
             point_residual(R, dR, x, cam.fx, cam.fy, cam.cx, cam.cy, X, ob, q0, q1, j0, j1, true);
-            int e = 0;
-#pragma unroll
-            for (int a = 0; a < 6; a++) {
-#pragma unroll
-                for (int c = a; c < 6; c++) {
-                    H[e] += j0[a] * j0[c];
-                    H[e] += j1[a] * j1[c];
-                    e++;
-                }
-                b[a] += j0[a] * q0;
-                b[a] += j1[a] * q1;
-            }
+            gram6_add(j0, j1, H);
+            grad6_add(j0, j1, q0, q1, b);
         }
-#pragma unroll
-        for (int e = 0; e < 21; e++) H[e] = wave_sum_f64(H[e]);
-#pragma unroll
-        for (int a = 0; a < 6; a++) b[a] = wave_sum_f64(b[a]);
         double Lc[36];
-        const bool pd = mfit_chol6(H, Lc);  // the same in every lane
-        if (lane == 0) flags[r] = pd ? 0 : kMfitSingular;
+        const bool pd = pose_block6(H, b, Lc);  // the same in every lane; b is y from here on
+        if (lane == 0) flags[r] = pd ? 0 : kRecSingular;
         if (!pd) continue;
-        mfit_forward6(Lc, b);  // y
         // ---- pass 2: the 27 doubles of every point
         double* W = ws + (size_t)(r - r0) * pm * kMfitDoubles;
         for (int i = lane; i < n; i += 64) {
             const int s = L.src[i];
             double xn, yn, ob[2], X[3], q0, q1, j0[6], j1[6];
-            corner_point(cam, corners, FR.features[s & 127], s >> 13, (s >> 7) & 7, xn, yn, ob, X);
+            corner_point(cam, corners, FR.features[desc_feature(s)], desc_pos(s), desc_q(s), xn, yn, ob, X);
             point_residual(R, dR, x, cam.fx, cam.fy, cam.cx, cam.cy, X, ob, q0, q1, j0, j1, true);
-            // d residual / d X = (a0 R0 - b0 R2, a1 R1 - b1 R2) with the a0, b0, a1, b1 of point_residual: j0[3] = a0, j0[5] = -b0, j1[4] = a1, j1[5] = -b1
             double x0[3], x1[3];
-#pragma unroll
-            for (int m = 0; m < 3; m++) {
-                x0[m] = j0[3] * R[m] + j0[5] * R[6 + m];
-                x1[m] = j1[4] * R[3 + m] + j1[5] * R[6 + m];
-            }
+            point_dX(R, j0, j1, x0, x1);
             double* O = W + (size_t)i * kMfitDoubles;
             double gi[3];
 #pragma unroll
@@ -164,13 +144,9 @@ __global__ __launch_bounds__(64) void k_mfit_record(const ctag_frame_result* __r
                 double z[6];
 #pragma unroll
                 for (int a = 0; a < 6; a++) z[a] = j0[a] * x0[m] + j1[a] * x1[m];
-                mfit_forward6(Lc, z);
-                double zy = 0.0;
+                const double zy = forward6_dot(Lc, z, b);
 #pragma unroll
-                for (int a = 0; a < 6; a++) {
-                    O[a * 3 + m] = z[a];
-                    zy += z[a] * b[a];
-                }
+                for (int a = 0; a < 6; a++) O[a * 3 + m] = z[a];
                 gi[m] = (x0[m] * q0 + x1[m] * q1) - zy;
             }
             O[18] = x0[0] * x0[0] + x1[0] * x1[0];
@@ -337,131 +313,71 @@ __global__ __launch_bounds__(kMfitSolveThreads) void k_mfit_solve(const double* 
 }  // namespace ctag
 
 // =====================================================================================================
-// host side
+// host side: the parts a fit shares with the rig assembly are ctag_fit_host.h's (namespace ctag::fit)
 // =====================================================================================================
 namespace {
 
-struct FitState {
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    float ms[4] = {0.f, 0.f, 0.f, 0.f};  // pose, record, assemble, solve
-};
+namespace fit = ctag::fit;
 
-void fit_state_free(void* p) {
-    FitState* s = static_cast<FitState*>(p);
-    for (auto& e : s->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete s;
-}
-
-FitState* fit_state(ctag_handle* h) {
-    void** slot = ctag::handle_state_slot(h, ctag::kFitState, fit_state_free);
-    if (!*slot) {
-        FitState* s = new (std::nothrow) FitState();
-        if (!s) return nullptr;
-        for (auto& e : s->ev)
-            if (hipEventCreate(&e) != hipSuccess) {
-                fit_state_free(s);
-                return nullptr;
-            }
-        *slot = s;
-    }
-    return static_cast<FitState*>(*slot);
-}
-
-#define FIT_HIP(call)                              \
-    do {                                           \
-        if ((call) != hipSuccess) return CTAG_ERR_HIP; \
-    } while (0)
-
-// The device side of one call: the observation list, the record workspace and the per-model systems.
-struct FitWork {
-    ctag_handle* h = nullptr;
-    hipStream_t s = nullptr;
-    FitState* st = nullptr;
-    bool timing = false;
-    const ctag_frame_result* res = nullptr;
-    int n_frames = 0, n_models = 0, pm = 0, N = 0, R = 0, pass = 0;
-    ctag::PoseCam cam{};
-    std::vector<int32_t> ok, rec_model, flags;  // [R]
-    std::vector<int16_t> table;                 // [R][pm]
-    std::vector<uint8_t> held;                  // [n_models][pm]
-    ctag::DevBuf<int32_t> d_ok, d_rec_model, d_flags, d_active, d_bad;
+// The device side of one call: the models' systems (a group is a model), the record workspace, and which corners do not move.
+struct FitWork : fit::Systems {
+    fit::Call c;
+    int pm = 0;
+    std::vector<int16_t> table;  // [R][pm]
+    std::vector<uint8_t> held;   // [n_models][pm]
     ctag::DevBuf<int16_t> d_table;
-    ctag::DevBuf<double> d_ws, d_S, d_g, d_A, d_delta, d_lambda;
+    ctag::DevBuf<double> d_ws, d_A;
     ctag::DevBuf<uint8_t> d_held;
 
-    int setup(int n_models_, int pm_, int pass_records) {
-        n_models = n_models_;
+    int setup(int n_models, int pm_, int pass_records) {
         pm = pm_;
-        N = 3 * pm;
-        R = (int)ok.size();
-        pass = std::max(1, std::min(R, pass_records > 0 ? pass_records : ctag::kMfitPassRecords));
-        const size_t nn = (size_t)n_models * N * N;
+        const size_t nn = (size_t)n_models * 9 * pm * pm;
         if (nn * 16 > ((size_t)6 << 30)) return CTAG_ERR_LIMIT;
-        FIT_HIP(d_ok.grow(R));
-        FIT_HIP(d_rec_model.grow(R));
-        FIT_HIP(d_flags.grow(R));
+        const int rc = Systems::setup(c, n_models, 3 * pm, pass_records, ctag::kMfitPassRecords);
+        if (rc != CTAG_OK) return rc;
         FIT_HIP(d_table.grow((size_t)R * pm));
         FIT_HIP(d_ws.grow((size_t)pass * pm * ctag::kMfitDoubles));
-        FIT_HIP(d_S.grow(nn));
         FIT_HIP(d_A.grow(nn));
-        FIT_HIP(d_g.grow((size_t)n_models * N));
-        FIT_HIP(d_delta.grow((size_t)n_models * N));
-        FIT_HIP(d_lambda.grow(n_models));
-        FIT_HIP(d_active.grow(n_models));
-        FIT_HIP(d_bad.grow(n_models));
         FIT_HIP(d_held.grow((size_t)n_models * pm));
-        FIT_HIP(hipMemcpyAsync(d_ok.p, ok.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, s));
-        FIT_HIP(hipMemcpyAsync(d_rec_model.p, rec_model.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, s));
-        flags.assign(R, 0);
         table.assign((size_t)R * pm, -1);
         return CTAG_OK;
     }
 
-    // S and g of every model at (corners_dev, poses_dev), pass by pass; flags come back to the host.  Waits.
+    // S and g of every model at (corners_dev, poses_dev); slot 1 times the record kernel, slot 2 the assemble kernel.  Waits.
     int build_system(const float* corners_dev, const int32_t* ids_dev, const ctag_pose_rec* poses_dev, bool fetch_table) {
-        const ctag::PoseModelDev md{n_models, pm / 8, ids_dev, corners_dev};
-        FIT_HIP(hipMemsetAsync(d_S.p, 0, sizeof(double) * (size_t)n_models * N * N, s));
-        FIT_HIP(hipMemsetAsync(d_g.p, 0, sizeof(double) * (size_t)n_models * N, s));
+        const ctag::PoseModelDev md{n_groups, pm / 8, ids_dev, corners_dev};
         const int pairs = pm * (pm + 1) / 2;
-        for (int r0 = 0; r0 < R; r0 += pass) {
-            const int r1 = std::min(R, r0 + pass);
-            if (timing) FIT_HIP(hipEventRecord(st->ev[0], s));
-            hipLaunchKernelGGL(ctag::k_mfit_record, dim3(std::min(r1 - r0, ctag::kMfitGrid)), dim3(64), 0, s, res, n_frames, poses_dev, d_ok.p, r0, r1, md, cam,
+        const int rc = build(c, [&](int r0, int r1) {
+            if (c.mark(0) != CTAG_OK) return CTAG_ERR_HIP;
+            hipLaunchKernelGGL(ctag::k_mfit_record, dim3(std::min(r1 - r0, ctag::kMfitGrid)), dim3(64), 0, c.s, c.res, c.n_frames, poses_dev, d_obs.p, r0, r1, md, c.cam,
                                d_ws.p, d_table.p, d_flags.p);
-            if (timing) FIT_HIP(hipEventRecord(st->ev[1], s));
-            hipLaunchKernelGGL(ctag::k_mfit_assemble, dim3((pairs + pm + 255) / 256, n_models), dim3(256), 0, s, d_ws.p, d_table.p, d_rec_model.p, d_flags.p, r0,
+            if (c.mark(1) != CTAG_OK) return CTAG_ERR_HIP;
+            hipLaunchKernelGGL(ctag::k_mfit_assemble, dim3((pairs + pm + 255) / 256, n_groups), dim3(256), 0, c.s, d_ws.p, d_table.p, d_rec_group.p, d_flags.p, r0,
                                r1, pm, d_S.p, d_g.p);
-            FIT_HIP(hipGetLastError());
-            if (timing) {
-                FIT_HIP(hipEventRecord(st->ev[2], s));
-                FIT_HIP(hipEventSynchronize(st->ev[2]));
-                float a = 0.f, b = 0.f;
-                (void)hipEventElapsedTime(&a, st->ev[0], st->ev[1]);
-                (void)hipEventElapsedTime(&b, st->ev[1], st->ev[2]);
-                st->ms[1] += a;
-                st->ms[2] += b;
-            }
-        }
-        FIT_HIP(hipMemcpyAsync(flags.data(), d_flags.p, sizeof(int32_t) * R, hipMemcpyDeviceToHost, s));
-        if (fetch_table) FIT_HIP(hipMemcpyAsync(table.data(), d_table.p, sizeof(int16_t) * (size_t)R * pm, hipMemcpyDeviceToHost, s));
-        FIT_HIP(hipStreamSynchronize(s));
+            if (fit::launched() != CTAG_OK || c.mark(2) != CTAG_OK || c.reached(2) != CTAG_OK) return CTAG_ERR_HIP;
+            c.add_ms(1, 0);
+            c.add_ms(2, 1);
+            return CTAG_OK;
+        });
+        if (rc != CTAG_OK || !fetch_table) return rc;
+        FIT_HIP(hipMemcpyAsync(table.data(), d_table.p, sizeof(int16_t) * (size_t)R * pm, hipMemcpyDeviceToHost, c.s));
+        FIT_HIP(hipStreamSynchronize(c.s));
         return CTAG_OK;
     }
 
     // held[m][c] = corner c of model m is seen by fewer than min_obs observation records
     void find_held(int min_obs, std::vector<int>& n_records, std::vector<int>& n_fitted) {
-        std::vector<int> count((size_t)n_models * pm, 0);
-        n_records.assign(n_models, 0);
-        n_fitted.assign(n_models, 0);
+        std::vector<int> count((size_t)n_groups * pm, 0);
+        n_records.assign(n_groups, 0);
+        n_fitted.assign(n_groups, 0);
         for (int r = 0; r < R; r++) {
-            if (flags[r] & ctag::kMfitLeftOut) continue;
-            const int m = rec_model[r];
+            if (flags[r] & ctag::kRecLeftOut) continue;
+            const int m = rec_group[r];
             n_records[m]++;
             for (int c = 0; c < pm; c++) count[(size_t)m * pm + c] += table[(size_t)r * pm + c] >= 0 ? 1 : 0;
         }
-        held.assign((size_t)n_models * pm, 1);
-        for (int m = 0; m < n_models; m++)
+        held.assign((size_t)n_groups * pm, 1);
+        for (int m = 0; m < n_groups; m++)
             for (int c = 0; c < pm; c++)
                 if (count[(size_t)m * pm + c] >= min_obs) {
                     held[(size_t)m * pm + c] = 0;
@@ -469,30 +385,14 @@ struct FitWork {
                 }
     }
 
-    int upload_held() { return hipMemcpyAsync(d_held.p, held.data(), held.size(), hipMemcpyHostToDevice, s) == hipSuccess ? CTAG_OK : CTAG_ERR_HIP; }
+    int upload_held() { return hipMemcpyAsync(d_held.p, held.data(), held.size(), hipMemcpyHostToDevice, c.s) == hipSuccess ? CTAG_OK : CTAG_ERR_HIP; }
 
-    // delta[n_models][N] and bad[n_models] for the models with active[m] != 0.  Waits.
+    // a model with a singular record is bad; a left-out record is no observation and says nothing
     int solve(const std::vector<double>& lambda, const std::vector<int32_t>& active, std::vector<double>& delta, std::vector<int32_t>& bad) {
-        FIT_HIP(hipMemcpyAsync(d_lambda.p, lambda.data(), sizeof(double) * n_models, hipMemcpyHostToDevice, s));
-        FIT_HIP(hipMemcpyAsync(d_active.p, active.data(), sizeof(int32_t) * n_models, hipMemcpyHostToDevice, s));
-        FIT_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int32_t) * n_models, s));
-        FIT_HIP(hipMemsetAsync(d_delta.p, 0, sizeof(double) * (size_t)n_models * N, s));
-        if (timing) FIT_HIP(hipEventRecord(st->ev[0], s));
-        hipLaunchKernelGGL(ctag::k_mfit_solve, dim3(n_models), dim3(ctag::kMfitSolveThreads), 0, s, d_S.p, d_g.p, d_held.p, d_lambda.p, d_active.p, pm, d_A.p,
-                           d_delta.p, d_bad.p);
-        FIT_HIP(hipGetLastError());
-        if (timing) FIT_HIP(hipEventRecord(st->ev[1], s));
-        delta.resize((size_t)n_models * N);
-        bad.resize(n_models);
-        FIT_HIP(hipMemcpyAsync(delta.data(), d_delta.p, sizeof(double) * delta.size(), hipMemcpyDeviceToHost, s));
-        FIT_HIP(hipMemcpyAsync(bad.data(), d_bad.p, sizeof(int32_t) * n_models, hipMemcpyDeviceToHost, s));
-        FIT_HIP(hipStreamSynchronize(s));
-        if (timing) {
-            float a = 0.f;
-            (void)hipEventElapsedTime(&a, st->ev[0], st->ev[1]);
-            st->ms[3] += a;
-        }
-        return CTAG_OK;
+        return Systems::solve(c, lambda, active, ctag::kRecSingular, delta, bad, [&]() {
+            hipLaunchKernelGGL(ctag::k_mfit_solve, dim3(n_groups), dim3(ctag::kMfitSolveThreads), 0, c.s, d_S.p, d_g.p, d_held.p, d_lambda.p, d_active.p, pm, d_A.p,
+                               d_delta.p, d_bad.p);
+        });
     }
 };
 
@@ -518,15 +418,8 @@ void gauge_to_seed(std::vector<double>& X, const std::vector<double>& Y) {
             for (int b = 0; b < 3; b++) C[b * 3 + a] += (Y[3 * i + b] - my[b]) * xa;
         }
     if (!(vx > 0.0)) return;
-    double U[9], sv[3], V[9];
-    ctl::svd3(C, U, sv, V);
-    auto det3 = [](const double* M) {
-        return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
-    };
-    const double sg = det3(U) * det3(V) < 0.0 ? -1.0 : 1.0;
-    double Rm[9];
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) Rm[a * 3 + b] = U[a * 3] * V[b * 3] + U[a * 3 + 1] * V[b * 3 + 1] + sg * U[a * 3 + 2] * V[b * 3 + 2];
+    double sv[3], Rm[9];
+    const double sg = fit::nearest_rotation(C, Rm, sv);
     const double scale = (sv[0] + sv[1] + sg * sv[2]) / vx;
     if (!std::isfinite(scale) || !(scale > 0.0)) return;
     for (int i = 0; i < n; i++) {
@@ -574,55 +467,6 @@ int fit_opts(const ctag_model_fit_opts* o, ctag_model_fit_opts& r) {
     return CTAG_OK;
 }
 
-int clone_model(const ctag_model* seed, ctag_model** out) {
-    ctag_model_view v;
-    if (ctag_model_get_view(seed, &v) != CTAG_OK) return CTAG_ERR_ARG;
-    return ctag_model_create(&v, out);
-}
-
-struct ModelGuard {  // frees the working model unless it is handed out
-    ctag_model* m = nullptr;
-    ~ModelGuard() {
-        if (m) ctag_model_free(m);
-    }
-};
-
-// pose records of the working model W (its device corners are current) into poses_dev, then to the host.  Waits.
-int pose_pass(FitWork& w, ctag_model* W, const ctag_camera* camera, int32_t* offsets_dev, ctag_pose_rec* poses_dev, int total, std::vector<ctag_pose_rec>& host) {
-    if (w.timing) FIT_HIP(hipEventRecord(w.st->ev[0], w.s));
-    const int rc = ctag_pose_batch_device(w.h, w.res, w.n_frames, W, camera, offsets_dev, poses_dev, total);
-    if (rc != CTAG_OK) return rc;
-    if (w.timing) FIT_HIP(hipEventRecord(w.st->ev[1], w.s));
-    host.resize(total);
-    FIT_HIP(hipMemcpyAsync(host.data(), poses_dev, sizeof(ctag_pose_rec) * (size_t)total, hipMemcpyDeviceToHost, w.s));
-    FIT_HIP(hipStreamSynchronize(w.s));
-    if (w.timing) {
-        float a = 0.f;
-        (void)hipEventElapsedTime(&a, w.st->ev[0], w.st->ev[1]);
-        w.st->ms[0] += a;
-    }
-    return CTAG_OK;
-}
-
-// the working model's corners to its device copy, behind what is enqueued on the stream
-int push_corners(FitWork& w, ctag_model* W) {
-    return hipMemcpyAsync(W->d_corners.p, W->corners.data(), sizeof(float) * W->corners.size(), hipMemcpyHostToDevice, w.s) == hipSuccess ? CTAG_OK : CTAG_ERR_HIP;
-}
-
-int fit_prepare(FitWork& w, ctag_handle* h, const ctag_frame_result* results_dev, int n_frames, const ctag_camera* camera) {
-    w.h = h;
-    FIT_HIP(hipSetDevice(ctag::handle_device(h)));
-    w.st = fit_state(h);
-    if (!w.st) return CTAG_ERR_HIP;
-    w.s = static_cast<hipStream_t>(ctag_stream(h));
-    w.timing = ctag::handle_timing(h);
-    for (float& v : w.st->ms) v = 0.f;
-    w.res = results_dev;
-    w.n_frames = n_frames;
-    w.cam = ctag::make_pose_cam(camera);
-    return CTAG_OK;
-}
-
 }  // namespace
 
 namespace ctag {
@@ -639,23 +483,20 @@ int mfit_probe_system(ctag_handle* h, const ctag_frame_result* results, int n_fr
     if (!camera_ok(camera)) return CTAG_ERR_UNSUPPORTED;
     ctag_model* model = const_cast<ctag_model*>(model_c);
     FitWork w;
-    int rc = fit_prepare(w, h, nullptr, n_frames, camera);
+    int rc = w.c.prepare(h, kFitState, nullptr, n_frames, camera);
     if (rc != CTAG_OK) return rc;
     if (model_to_device(model, handle_device(h)) != CTAG_OK) return CTAG_ERR_HIP;
     DevBuf<ctag_frame_result> d_res;
     DevBuf<ctag_pose_rec> d_poses;
-    FIT_HIP(d_res.grow(n_frames));
-    FIT_HIP(d_poses.grow(n_poses));
-    FIT_HIP(hipMemcpyAsync(d_res.p, results, sizeof(ctag_frame_result) * (size_t)n_frames, hipMemcpyHostToDevice, w.s));
-    FIT_HIP(hipMemcpyAsync(d_poses.p, poses, sizeof(ctag_pose_rec) * (size_t)n_poses, hipMemcpyHostToDevice, w.s));
-    w.res = d_res.p;
+    rc = fit::upload_probe_inputs(w.c, results, d_res, poses, (size_t)n_poses, d_poses);
+    if (rc != CTAG_OK) return rc;
     for (int i = 0; i < n_poses; i++)
         if (poses[i].status == CTAG_POSE_OK && poses[i].model_index >= 0 && poses[i].model_index < model->n_models) {
-            w.ok.push_back(i);
-            w.rec_model.push_back(poses[i].model_index);
+            w.obs.push_back(i);
+            w.rec_group.push_back(poses[i].model_index);
         }
     const int pm = model->model_size * 8, N = 3 * pm;
-    if (w.ok.empty()) return CTAG_ERR_ARG;
+    if (w.obs.empty()) return CTAG_ERR_ARG;
     rc = w.setup(model->n_models, pm, pass_records);
     if (rc != CTAG_OK) return rc;
     rc = w.build_system(model->d_corners.p, model->d_ids.p, d_poses.p, true);
@@ -674,8 +515,6 @@ int mfit_probe_system(ctag_handle* h, const ctag_frame_result* results, int n_fr
     std::memcpy(delta, d.data() + (size_t)model_index * N, sizeof(double) * N);
     for (int c = 0; c < pm; c++) held[c] = w.held[(size_t)model_index * pm + c];
     *bad_pivot = bad[model_index];
-    for (int r = 0; r < w.R; r++)
-        if (w.rec_model[r] == model_index && (w.flags[r] & kMfitSingular)) *bad_pivot = 1;
     return CTAG_OK;
 }
 
@@ -693,13 +532,7 @@ void ctag_model_fit_opts_default(ctag_model_fit_opts* o) {
     o->strip_height = 0.0;
 }
 
-int ctag_model_fit_last_ms(ctag_handle* h, float* out4) {
-    if (!h || !out4) return CTAG_ERR_ARG;
-    FitState* st = fit_state(h);
-    if (!st) return CTAG_ERR_HIP;
-    for (int i = 0; i < 4; i++) out4[i] = st->ms[i];
-    return CTAG_OK;
-}
+int ctag_model_fit_last_ms(ctag_handle* h, float* out4) { return fit::last_ms(h, ctag::kFitState, out4); }  // pose, record, assemble, solve
 
 int ctag_model_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, int n_frames, const ctag_model* seed, const ctag_camera* camera,
                           const ctag_model_fit_opts* opts_in, ctag_model** out, ctag_model_fit_stat* stats) {
@@ -710,10 +543,10 @@ int ctag_model_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, 
     if (!ctag::camera_ok(camera)) return CTAG_ERR_UNSUPPORTED;
     if ((long long)n_frames * CTAG_MAX_MARKERS > (1ll << 30)) return CTAG_ERR_LIMIT;
     FitWork w;
-    int rc = fit_prepare(w, h, results_dev, n_frames, camera);
+    int rc = w.c.prepare(h, ctag::kFitState, results_dev, n_frames, camera);
     if (rc != CTAG_OK) return rc;
-    ModelGuard guard;
-    rc = clone_model(seed, &guard.m);
+    fit::ModelGuard guard;
+    rc = fit::clone_model(seed, &guard.m);
     if (rc != CTAG_OK) return rc;
     ctag_model* W = guard.m;
     const int nm = W->n_models, pm = W->model_size * 8, N = 3 * pm;
@@ -733,32 +566,31 @@ int ctag_model_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, 
     // ---- rule 1: the observation records are the CTAG_POSE_OK records under the seed
     ctag::DevBuf<int32_t> d_off;
     ctag::DevBuf<ctag_pose_rec> d_poses;
-    FIT_HIP(d_off.grow((size_t)n_frames + 1));
-    FIT_HIP(d_poses.grow(1));
-    // capacity 1: the call is made for offsets[n_frames], the record count, and for W's device copy; the one pose it solves is discarded
-    rc = ctag_pose_batch_device(h, results_dev, n_frames, W, camera, d_off.p, d_poses.p, 1);
+    std::vector<int32_t> off;
+    rc = fit::count_pose_records(w.c, W, camera, d_off, d_poses, off);
     if (rc != CTAG_OK) return rc;
-    int32_t total = 0;
-    FIT_HIP(hipMemcpyAsync(&total, d_off.p + n_frames, sizeof(int32_t), hipMemcpyDeviceToHost, w.s));
-    FIT_HIP(hipStreamSynchronize(w.s));
+    const int32_t total = off[n_frames];
     if (total <= 0) return hand_out();
-    FIT_HIP(d_poses.grow((size_t)total));
     std::vector<ctag_pose_rec> acc, trial;
-    rc = pose_pass(w, W, camera, d_off.p, d_poses.p, total, acc);
+    // pose records of W (its device corners are current) to the host, timed in slot 0
+    auto pose_pass = [&](std::vector<ctag_pose_rec>& host) {
+        return w.c.pose_pass(0, [&]() { return ctag_pose_batch_device(h, results_dev, n_frames, W, camera, d_off.p, d_poses.p, total); }, d_poses.p, (size_t)total, host);
+    };
+    rc = pose_pass(acc);
     if (rc != CTAG_OK) return rc;
     for (int i = 0; i < total; i++)
         if (acc[i].status == CTAG_POSE_OK) {
-            w.ok.push_back(i);
-            w.rec_model.push_back(acc[i].model_index);
+            w.obs.push_back(i);
+            w.rec_group.push_back(acc[i].model_index);
         }
-    if (w.ok.empty()) return hand_out();
+    if (w.obs.empty()) return hand_out();
     rc = w.setup(nm, pm, 0);
     if (rc != CTAG_OK) return rc;
     rc = w.build_system(W->d_corners.p, W->d_ids.p, d_poses.p, true);
     if (rc != CTAG_OK) return rc;
     const int R = w.R;
     std::vector<uint8_t> left_out(R);
-    for (int r = 0; r < R; r++) left_out[r] = (w.flags[r] & ctag::kMfitLeftOut) ? 1 : 0;
+    for (int r = 0; r < R; r++) left_out[r] = (w.flags[r] & ctag::kRecLeftOut) ? 1 : 0;
 
     // ---- rule 2
     std::vector<int> n_records, n_fitted;
@@ -766,60 +598,47 @@ int ctag_model_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, 
     rc = w.upload_held();
     if (rc != CTAG_OK) return rc;
 
-    // cost of model m over its observation records, in record order; false when one of them is not CTAG_POSE_OK
+    fit::Lm lm;
+    lm.start(nm, opts.lambda0);
+    std::vector<uint8_t> ok_cur;
+    w.costs_of(acc, &left_out, lm.cost, ok_cur);
     std::vector<long long> n_points(nm, 0);
-    auto costs_of = [&](const std::vector<ctag_pose_rec>& P, std::vector<double>& cost, std::vector<uint8_t>& all_ok) {
-        cost.assign(nm, 0.0);
-        all_ok.assign(nm, 1);
-        for (int r = 0; r < R; r++) {
-            if (left_out[r]) continue;
-            const ctag_pose_rec& p = P[w.ok[r]];
-            const int m = w.rec_model[r];
-            if (p.status != CTAG_POSE_OK) all_ok[m] = 0;
-            cost[m] += p.cost;
-        }
-    };
-    std::vector<double> cost_cur, cost_trial, lambda(nm, opts.lambda0), delta;
-    std::vector<uint8_t> ok_cur, ok_trial;
-    std::vector<int32_t> active(nm, 0), bad;
-    costs_of(acc, cost_cur, ok_cur);
     for (int r = 0; r < R; r++)
-        if (!left_out[r]) n_points[w.rec_model[r]] += acc[w.ok[r]].n_points;
-    bool any = false;
+        if (!left_out[r]) n_points[w.rec_group[r]] += acc[w.obs[r]].n_points;
     for (int m = 0; m < nm; m++) {
         stats[m].n_records = n_records[m];
         stats[m].n_points_fitted = n_fitted[m];
         stats[m].n_points_held = pm - n_fitted[m];
-        stats[m].cost0 = stats[m].cost = cost_cur[m];
+        stats[m].cost0 = stats[m].cost = lm.cost[m];
         if (n_records[m] > 0 && n_fitted[m] > 0) {
             stats[m].status = CTAG_POSE_OK;
-            active[m] = opts.max_rounds > 0 ? 1 : 0;
-            any = any || active[m];
+            lm.active[m] = opts.max_rounds > 0 ? 1 : 0;
         }
     }
 
-    // ---- rules 3-5: the rounds.  `accepted` is the accepted state of every model; W carries the trial during a round
+    // ---- rules 3-5: the rounds.  `accepted` is the accepted state of every model; W carries the trial during a round.  The loop is
+    // the rig assembly's (k_rig_fit.hip, rule 5) but for the steps marked "model"; the two are kept in step by hand
     std::vector<float> accepted = W->corners;
     const std::vector<float>& seed_corners = seed->corners;
-    bool need_system = false;
-    std::vector<double> X, Y;
-    while (any) {
+    bool need_system = false;  // the system of the first round is the one built above
+    std::vector<double> X, Y, delta, cost_trial(nm, 0.0);
+    std::vector<uint8_t> ok_trial(nm, 0);
+    std::vector<int32_t> bad;
+    while (lm.any_active()) {
         if (need_system) {
             W->corners = accepted;
-            if (push_corners(w, W) != CTAG_OK) return CTAG_ERR_HIP;
-            FIT_HIP(hipMemcpyAsync(d_poses.p, acc.data(), sizeof(ctag_pose_rec) * (size_t)total, hipMemcpyHostToDevice, w.s));
+            if (fit::push_corners(w.c, W) != CTAG_OK) return CTAG_ERR_HIP;
+            FIT_HIP(hipMemcpyAsync(d_poses.p, acc.data(), sizeof(ctag_pose_rec) * (size_t)total, hipMemcpyHostToDevice, w.c.s));
             rc = w.build_system(W->d_corners.p, W->d_ids.p, d_poses.p, false);
             if (rc != CTAG_OK) return rc;
             need_system = false;
         }
-        rc = w.solve(lambda, active, delta, bad);
+        rc = w.solve(lm.lambda, lm.active, delta, bad);
         if (rc != CTAG_OK) return rc;
-        for (int r = 0; r < R; r++)
-            if (!left_out[r] && (w.flags[r] & ctag::kMfitSingular)) bad[w.rec_model[r]] = 1;
         W->corners = accepted;
         bool any_trial = false;
-        for (int m = 0; m < nm; m++) {
-            if (!active[m] || bad[m]) continue;
+        for (int m = 0; m < nm; m++) {  // model: the step on the corners that move, then rule 5
+            if (!lm.active[m] || bad[m]) continue;
             X.clear();
             Y.clear();
             for (int c = 0; c < pm; c++) {
@@ -844,30 +663,18 @@ int ctag_model_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, 
             any_trial = true;
         }
         if (any_trial) {
-            if (push_corners(w, W) != CTAG_OK) return CTAG_ERR_HIP;
-            rc = pose_pass(w, W, camera, d_off.p, d_poses.p, total, trial);
+            if (fit::push_corners(w.c, W) != CTAG_OK) return CTAG_ERR_HIP;
+            rc = pose_pass(trial);
             if (rc != CTAG_OK) return rc;
-            costs_of(trial, cost_trial, ok_trial);
+            w.costs_of(trial, &left_out, cost_trial, ok_trial);
         }
-        any = false;
         for (int m = 0; m < nm; m++) {
-            if (!active[m]) continue;
-            stats[m].rounds++;
-            if (!bad[m] && ok_trial[m] && cost_trial[m] < cost_cur[m]) {
-                const double drop = cost_cur[m] - cost_trial[m];
-                cost_cur[m] = cost_trial[m];
-                std::memcpy(&accepted[(size_t)m * pm * 3], &W->corners[(size_t)m * pm * 3], sizeof(float) * (size_t)pm * 3);
-                for (int r = 0; r < R; r++)
-                    if (w.rec_model[r] == m) acc[w.ok[r]] = trial[w.ok[r]];
-                lambda[m] = std::max(lambda[m] / 3.0, 1e-9);
-                need_system = true;
-                if (drop < opts.rel_tol * cost_cur[m]) active[m] = 0;
-            } else {
-                lambda[m] *= 4.0;
-                if (lambda[m] > opts.lambda_max) active[m] = 0;
-            }
-            if (stats[m].rounds >= opts.max_rounds) active[m] = 0;
-            any = any || active[m];
+            if (!lm.active[m]) continue;
+            // an active model that is not bad has made a trial, so `any_trial &&` (the rig loop's guard) changes no decision here
+            if (!lm.decide(m, any_trial && !bad[m] && ok_trial[m], cost_trial[m], opts)) continue;
+            std::memcpy(&accepted[(size_t)m * pm * 3], &W->corners[(size_t)m * pm * 3], sizeof(float) * (size_t)pm * 3);  // model
+            w.take_records(m, trial, acc);
+            need_system = true;
         }
     }
 
@@ -890,34 +697,28 @@ int ctag_model_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, 
             scaled = true;
         }
     if (scaled) {
-        if (push_corners(w, W) != CTAG_OK) return CTAG_ERR_HIP;
-        rc = pose_pass(w, W, camera, d_off.p, d_poses.p, total, trial);
+        if (fit::push_corners(w.c, W) != CTAG_OK) return CTAG_ERR_HIP;
+        rc = pose_pass(trial);
         if (rc != CTAG_OK) return rc;
-        costs_of(trial, cost_cur, ok_cur);
+        w.costs_of(trial, &left_out, lm.cost, ok_cur);
     }
     for (int m = 0; m < nm; m++) {
         if (stats[m].status != CTAG_POSE_OK) continue;
-        stats[m].cost = cost_cur[m];
-        stats[m].lambda = lambda[m];
-        stats[m].rms_px = n_points[m] > 0 ? std::sqrt(2.0 * cost_cur[m] / (double)n_points[m]) : 0.0;
+        stats[m].rounds = lm.rounds[m];
+        stats[m].cost = lm.cost[m];
+        stats[m].lambda = lm.lambda[m];
+        stats[m].rms_px = n_points[m] > 0 ? std::sqrt(2.0 * lm.cost[m] / (double)n_points[m]) : 0.0;
     }
-    // the device copies belong to the trial states of the call: the model handed out makes its own at its first use
-    W->d_ids.release();
-    W->d_corners.release();
-    W->d_base_axis.release();
-    W->d_base = W->d_axis = nullptr;
-    W->device = -1;
+    fit::release_device_copies(W);
     return hand_out();
 }
 
 int ctag_model_fit(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_model* seed, const ctag_camera* camera,
                    const ctag_model_fit_opts* opts, ctag_model** out, ctag_model_fit_stat* stats) {
     if (!h || !results || n_frames < 1 || !seed || !camera || !out || !stats) return CTAG_ERR_ARG;
-    if (hipSetDevice(ctag::handle_device(h)) != hipSuccess) return CTAG_ERR_HIP;
-    ctag::DevBuf<ctag_frame_result> d_res;
-    FIT_HIP(d_res.grow((size_t)n_frames));
-    FIT_HIP(hipMemcpy(d_res.p, results, sizeof(ctag_frame_result) * (size_t)n_frames, hipMemcpyHostToDevice));
-    return ctag_model_fit_device(h, d_res.p, n_frames, seed, camera, opts, out, stats);
+    return fit::with_results_on_device(h, results, n_frames, [&](const ctag_frame_result* results_dev) {
+        return ctag_model_fit_device(h, results_dev, n_frames, seed, camera, opts, out, stats);
+    });
 }
 
 // CylinderTag.cpp:168-188 read backwards: "model_num model_size", then per model its id, base, axis and model_size * 8 lines

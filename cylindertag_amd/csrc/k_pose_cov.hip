@@ -23,11 +23,11 @@
 #include "../../include/ctag_pose.h"
 #include "ctag_internal.h"
 #include "ctag_pose_dev.h"
+#include "ctag_schur6.h"
 #include "ctag_wave.h"
 
 static_assert(sizeof(ctag_pose_cov_rec) == 352, "ctag_pose_cov_rec layout");
 static_assert(sizeof(ctag_cov_opts) == 24, "ctag_cov_opts layout");
-static_assert(CTAG_MAX_FEATURES <= 128 && CTAG_MV_MAX_CAMERAS <= 8, "the point descriptor's bit fields");
 
 namespace ctag {
 
@@ -44,8 +44,7 @@ struct CovLds {
     PoseCam cam[kMvCams];
     double R[kMvCams][9];
     double t[kMvCams][3];
-    // where point i comes from: src = feature index in its frame record | corner q of the emit << 7 | camera << 10 | model
-    // position << 13 (positions are below 2^16); model = the model index
+    // where point i comes from: src = its descriptor (point_desc, ctag_pose_dev.h); model = the model index
     int32_t src[kCovMaxPts];
     int32_t model[kCovMaxPts];
     double norm[kCovMaxPts];  // residual norm of point i, written and read by its owner lane
@@ -62,7 +61,7 @@ __device__ __forceinline__ bool cov_add_marker(CovLds& L, const int lane, const 
     int nl = 0;
     const int st = marker_points(FR, M, model.model_size, kPoseMaxPts, nl, [&](const ctag_feature_rec& F, int pos, int cnt, int i0) {
         if (lane < cnt && base + i0 + cnt <= kCovMaxPts) {
-            L.src[base + i0 + lane] = (int32_t)(&F - F0) | (lane << 7) | (c << 10) | (pos << 13);
+            L.src[base + i0 + lane] = point_desc((int)(&F - F0), lane, c, pos);
             L.model[base + i0 + lane] = mi;
         }
     });
@@ -221,12 +220,7 @@ __global__ __launch_bounds__(64) void k_pose_cov(Src src, PoseModelDev model, Co
         int n = 0;
         double x[6];
         bool ok = src.build(P, model, L, lane, n) && n == P.n_points && n >= 4;
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            x[i] = P.rvec[i];
-            x[3 + i] = P.tvec[i];
-            ok = ok && ctl::finite64(x[i]) && ctl::finite64(x[3 + i]);
-        }
+        ok = load_state6(P, x) && ok;
         if (!ok) {
             cov_store_status(O, CTAG_COV_BAD_RECORD, lane);
             continue;
@@ -255,23 +249,15 @@ __global__ __launch_bounds__(64) void k_pose_cov(Src src, PoseModelDev model, Co
         for (int e = 0; e < 21; e++) H[e] = 0.0;
         for (int i = lane; i < n; i += 64) {
             const int s = L.src[i], mi = L.model[i];
-            const int c = (s >> 10) & 7;
+            const int c = desc_cam(s);
             const ctag_frame_result& FR = src.frame(P, c);
             double xn, yn, ob[2], X[3], r0, r1, j0[6], j1[6];
-            corner_point(L.cam[c], model.corners + (size_t)mi * model.model_size * 24, FR.features[s & 127], s >> 13, (s >> 7) & 7, xn, yn, ob, X);
+            corner_point(L.cam[c], model.corners + (size_t)mi * model.model_size * 24, FR.features[desc_feature(s)], desc_pos(s), desc_q(s), xn, yn, ob, X);
             if constexpr (Src::kMultiView)
                 mv_point_residual(R, dR, x, L.cam[c], L.R[c], L.t[c], X, ob, r0, r1, j0, j1);
             else
                 point_residual(R, dR, x, L.cam[c].fx, L.cam[c].fy, L.cam[c].cx, L.cam[c].cy, X, ob, r0, r1, j0, j1, true);
-            int e = 0;
-#pragma unroll
-            for (int a = 0; a < 6; a++)
-#pragma unroll
-                for (int b = a; b < 6; b++) {
-                    H[e] += j0[a] * j0[b];
-                    H[e] += j1[a] * j1[b];
-                    e++;
-                }
+            gram6_add(j0, j1, H);
             const double r2 = r0 * r0 + r1 * r1;
             ss += r2;
             const double nrm = ctm::sqrt64(r2);

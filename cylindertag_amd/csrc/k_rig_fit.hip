@@ -20,15 +20,21 @@
 //             right-hand side, the two triangular solves, delta and a flag for a pivot that is not positive.
 // The host decides (initial assembly, accept / reject, lambda, stop) per rig between the launches.  FP64 VALU like the pose kernels;
 // the largest system is 90 x 90, nothing here is MFMA-shaped.
+//
+// What the assembly shares with the model reconstruction (k_model_fit.hip) is not here: the pose block of a record (pass 1, a column
+// through L^-1, the point Jacobian) is ctag_schur6.h's, the point descriptor and load_state6 are ctag_pose_dev.h's, and the host side
+// of a fit -- timed state, call context, working model, systems with their pass loop and solve, the accept / reject rule --
+// is ctag_fit_host.h's.  This file keeps its kernels' own walk, tables and pass 2, the initial assembly of rules 1-4,
+// apply_rigid, report_transforms, the probe, and its round loop.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/ctag_pose.h"
+#include "ctag_fit_host.h"
 #include "ctag_internal.h"
 #include "ctag_pose_dev.h"
 #include "ctag_schur6.h"
@@ -47,11 +53,10 @@ constexpr int kRfitDoubles = 63;          // per member slot of a record: Z (36)
 constexpr int kRfitN = 6 * kRfitSlots;    // 96: row stride of S, delta and g
 constexpr int kRfitMaxPts = CTAG_RIG_MAX_POINTS;
 constexpr int kRfitSolveThreads = 256;
-constexpr int kRfitLeftOut = 1;           // flags: the record does not describe its detection record (never for records k_rig_solve wrote)
-constexpr int kRfitSingular = 2;          // flags: U of the record has a pivot that is not positive at this state
+// flags of a record: kRecLeftOut (it does not describe its detection record: never for records k_rig_solve wrote) and kRecSingular
 
 struct RfitLds {
-    int32_t src[kRfitMaxPts];        // point i: feature index in its frame record | corner q of the emit << 7 | model position << 13
+    int32_t src[kRfitMaxPts];        // point i: its descriptor (point_desc, ctag_pose_dev.h; camera 0)
     int32_t mstart[kRfitSlots + 1];  // member k owns the points mstart[k] .. mstart[k + 1] - 1
     int32_t mmodel[kRfitSlots];      // its model index
     int8_t table[kRfitSlots];        // model slot of the rig -> member, -1 where absent
@@ -88,7 +93,7 @@ __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __r
                 const int base = n;
                 int nl = 0;
                 const int st = marker_points(FR, FR.markers[k], model.model_size, kPoseMaxPts, nl, [&](const ctag_feature_rec& F, int pos, int cnt, int i0) {
-                    if (lane < cnt && base + i0 + cnt <= kRfitMaxPts) L.src[base + i0 + lane] = (int32_t)(&F - F0) | (lane << 7) | (pos << 13);
+                    if (lane < cnt && base + i0 + cnt <= kRfitMaxPts) L.src[base + i0 + lane] = point_desc((int)(&F - F0), lane, 0, pos);
                 });
                 if (st != CTAG_POSE_OK || base + nl > kRfitMaxPts) {
                     ok = false;
@@ -106,16 +111,11 @@ __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __r
         if (lane == 0) L.mstart[min(nmem, kRfitSlots)] = n;
         ok = ok && n == P.n_points && n >= 4 && nmem >= 2;
         double x[6];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            x[i] = P.rvec[i];
-            x[3 + i] = P.tvec[i];
-            ok = ok && ctl::finite64(x[i]) && ctl::finite64(x[3 + i]);
-        }
+        ok = load_state6(P, x) && ok;
         wave_sync();
         if (!ok) {  // wave-uniform
             if (lane < kRfitSlots) T[lane] = -1;
-            if (lane == 0) flags[r] = kRfitLeftOut;
+            if (lane == 0) flags[r] = kRecLeftOut;
             continue;
         }
         if (lane < kRfitSlots) T[lane] = L.table[lane];
@@ -134,31 +134,16 @@ __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __r
             for (int i = L.mstart[k] + lane; i < i1; i += 64) {
                 const int s = L.src[i];
                 double xn, yn, ob[2], X[3], q0, q1, j0[6], j1[6];
-                corner_point(cam, corners, FR.features[s & 127], s >> 13, (s >> 7) & 7, xn, yn, ob, X);
+                corner_point(cam, corners, FR.features[desc_feature(s)], desc_pos(s), desc_q(s), xn, yn, ob, X);
                 point_residual(R, dR, x, cam.fx, cam.fy, cam.cx, cam.cy, X, ob, q0, q1, j0, j1, true);
-                int e = 0;
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-#pragma unroll
-                    for (int c = a; c < 6; c++) {
-                        H[e] += j0[a] * j0[c];
-                        H[e] += j1[a] * j1[c];
-                        e++;
-                    }
-                    b[a] += j0[a] * q0;
-                    b[a] += j1[a] * q1;
-                }
+                gram6_add(j0, j1, H);
+                grad6_add(j0, j1, q0, q1, b);
             }
         }
-#pragma unroll
-        for (int e = 0; e < 21; e++) H[e] = wave_sum_f64(H[e]);
-#pragma unroll
-        for (int a = 0; a < 6; a++) b[a] = wave_sum_f64(b[a]);
         double Lc[36];
-        const bool pd = mfit_chol6(H, Lc);  // the same in every lane
-        if (lane == 0) flags[r] = pd ? 0 : kRfitSingular;
+        const bool pd = pose_block6(H, b, Lc);  // the same in every lane; b is y from here on
+        if (lane == 0) flags[r] = pd ? 0 : kRecSingular;
         if (!pd) continue;
-        mfit_forward6(Lc, b);  // y
         // ---- pass 2: the 63 doubles of every member
         double* W = ws + (size_t)(r - r0) * kRfitSlots * kRfitDoubles;
         for (int k = 0; k < nmem; k++) {
@@ -174,15 +159,10 @@ __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __r
             for (int i = L.mstart[k] + lane; i < i1; i += 64) {
                 const int s = L.src[i];
                 double xn, yn, ob[2], Y[3], q0, q1, j0[6], j1[6];
-                corner_point(cam, corners, FR.features[s & 127], s >> 13, (s >> 7) & 7, xn, yn, ob, Y);
+                corner_point(cam, corners, FR.features[desc_feature(s)], desc_pos(s), desc_q(s), xn, yn, ob, Y);
                 point_residual(R, dR, x, cam.fx, cam.fy, cam.cx, cam.cy, Y, ob, q0, q1, j0, j1, true);
-                // d residual / d Y = (a0 R0 - b0 R2, a1 R1 - b1 R2) with the a0, b0, a1, b1 of point_residual: j0[3] = a0, j0[5] = -b0, j1[4] = a1, j1[5] = -b1
                 double x0[3], x1[3], m0[6], m1[6];
-#pragma unroll
-                for (int m = 0; m < 3; m++) {
-                    x0[m] = j0[3] * R[m] + j0[5] * R[6 + m];
-                    x1[m] = j1[4] * R[3 + m] + j1[5] * R[6 + m];
-                }
+                point_dX(R, j0, j1, x0, x1);  // d residual / d Y
                 // Jm = (dr/dY) [-[Y]x | I]: the rotation columns are Y x (dr/dY)
                 m0[0] = Y[1] * x0[2] - Y[2] * x0[1];
                 m0[1] = Y[2] * x0[0] - Y[0] * x0[2];
@@ -224,14 +204,9 @@ __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __r
                 double z[6];
 #pragma unroll
                 for (int a = 0; a < 6; a++) z[a] = Z[a * 6 + c];
-                mfit_forward6(Lc, z);
-                double zy = 0.0;
+                gm[c] -= forward6_dot(Lc, z, b);
 #pragma unroll
-                for (int a = 0; a < 6; a++) {
-                    Z[a * 6 + c] = z[a];
-                    zy += z[a] * b[a];
-                }
-                gm[c] -= zy;
+                for (int a = 0; a < 6; a++) Z[a * 6 + c] = z[a];
             }
             if (lane == 0) {
                 double* O = W + (size_t)k * kRfitDoubles;
@@ -352,41 +327,11 @@ __global__ __launch_bounds__(kRfitSolveThreads) void k_rfit_solve(const double* 
 }  // namespace ctag
 
 // =====================================================================================================
-// host side
+// host side: the parts the assembly shares with the model reconstruction are ctag_fit_host.h's (namespace ctag::fit)
 // =====================================================================================================
 namespace {
 
-struct RfitState {
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    float ms[4] = {0.f, 0.f, 0.f, 0.f};  // marker pose, rig pose, record + assemble, solve
-};
-
-void rfit_state_free(void* p) {
-    RfitState* s = static_cast<RfitState*>(p);
-    for (auto& e : s->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete s;
-}
-
-RfitState* rfit_state(ctag_handle* h) {
-    void** slot = ctag::handle_state_slot(h, ctag::kRigFitState, rfit_state_free);
-    if (!*slot) {
-        RfitState* s = new (std::nothrow) RfitState();
-        if (!s) return nullptr;
-        for (auto& e : s->ev)
-            if (hipEventCreate(&e) != hipSuccess) {
-                rfit_state_free(s);
-                return nullptr;
-            }
-        *slot = s;
-    }
-    return static_cast<RfitState*>(*slot);
-}
-
-#define RFIT_HIP(call)                                 \
-    do {                                               \
-        if ((call) != hipSuccess) return CTAG_ERR_HIP; \
-    } while (0)
+namespace fit = ctag::fit;
 
 struct Rigid {  // X_rig = R X_in + t
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
@@ -401,111 +346,52 @@ void mat_vec(const double* A, const double* v, double* o) {
     for (int i = 0; i < 3; i++) o[i] = A[i * 3] * v[0] + A[i * 3 + 1] * v[1] + A[i * 3 + 2] * v[2];
 }
 
-double det3(const double* M) { return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]); }
-
-// the rotation nearest to M (Frobenius): U diag(1, 1, det(U V^T)) V^T of M = U s V^T
-void nearest_rotation(const double* M, double* R) {
-    double U[9], sv[3], V[9];
-    ctl::svd3(M, U, sv, V);
-    const double sg = det3(U) * det3(V) < 0.0 ? -1.0 : 1.0;
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) R[a * 3 + b] = U[a * 3] * V[b * 3] + U[a * 3 + 1] * V[b * 3 + 1] + sg * U[a * 3 + 2] * V[b * 3 + 2];
-}
-
-// The device side of one call: the observation list, the record workspace and the per-rig systems.
-struct RfitWork {
-    ctag_handle* h = nullptr;
-    hipStream_t s = nullptr;
-    RfitState* st = nullptr;
-    bool timing = false;
-    const ctag_frame_result* res = nullptr;
-    int n_frames = 0, n_models = 0, n_rigs = 0, R = 0, pass = 0;
-    ctag::PoseCam cam{};
-    std::vector<int32_t> obs, rec_rig, flags;        // [R]: rig-pose record index, its rig, the record kernel's verdict
-    std::vector<int32_t> slot_of_model;              // [n_models]: the model's slot in its rig's system, -1 outside every system
-    std::vector<int32_t> n_slots, drop;              // [n_rigs]
-    ctag::DevBuf<int32_t> d_obs, d_rec_rig, d_flags, d_slot, d_n_slots, d_drop, d_active, d_bad;
+// The device side of one call: the rigs' systems (a group is a rig), the record workspace, and the slots of the models in them.
+struct RfitWork : fit::Systems {
+    fit::Call c;
+    std::vector<int32_t> slot_of_model;  // [n_models]: the model's slot in its rig's system, -1 outside every system
+    std::vector<int32_t> n_slots, drop;  // [n_rigs]
+    ctag::DevBuf<int32_t> d_slot, d_n_slots, d_drop;
     ctag::DevBuf<int8_t> d_table;
-    ctag::DevBuf<double> d_ws, d_S, d_g, d_delta, d_lambda;
+    ctag::DevBuf<double> d_ws;
 
     int setup(int pass_records) {
-        R = (int)obs.size();
-        pass = std::max(1, std::min(R, pass_records > 0 ? pass_records : ctag::kRfitPassRecords));
-        const size_t nn = (size_t)n_rigs * ctag::kRfitN * ctag::kRfitN;
-        if (nn * 8 > ((size_t)2 << 30)) return CTAG_ERR_LIMIT;
-        RFIT_HIP(d_obs.grow(std::max(R, 1)));
-        RFIT_HIP(d_rec_rig.grow(std::max(R, 1)));
-        RFIT_HIP(d_flags.grow(std::max(R, 1)));
-        RFIT_HIP(d_table.grow((size_t)std::max(R, 1) * ctag::kRfitSlots));
-        RFIT_HIP(d_ws.grow((size_t)pass * ctag::kRfitSlots * ctag::kRfitDoubles));
-        RFIT_HIP(d_S.grow(nn));
-        RFIT_HIP(d_g.grow((size_t)n_rigs * ctag::kRfitN));
-        RFIT_HIP(d_delta.grow((size_t)n_rigs * ctag::kRfitN));
-        RFIT_HIP(d_lambda.grow(n_rigs));
-        RFIT_HIP(d_active.grow(n_rigs));
-        RFIT_HIP(d_bad.grow(n_rigs));
-        RFIT_HIP(d_n_slots.grow(n_rigs));
-        RFIT_HIP(d_drop.grow(n_rigs));
-        RFIT_HIP(d_slot.grow(std::max(n_models, 1)));
-        if (R > 0) {
-            RFIT_HIP(hipMemcpyAsync(d_obs.p, obs.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, s));
-            RFIT_HIP(hipMemcpyAsync(d_rec_rig.p, rec_rig.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, s));
-        }
-        if (n_models > 0) RFIT_HIP(hipMemcpyAsync(d_slot.p, slot_of_model.data(), sizeof(int32_t) * n_models, hipMemcpyHostToDevice, s));
-        RFIT_HIP(hipMemcpyAsync(d_n_slots.p, n_slots.data(), sizeof(int32_t) * n_rigs, hipMemcpyHostToDevice, s));
-        RFIT_HIP(hipMemcpyAsync(d_drop.p, drop.data(), sizeof(int32_t) * n_rigs, hipMemcpyHostToDevice, s));
-        flags.assign(R, 0);
+        const int n_rigs = (int)n_slots.size(), n_models = (int)slot_of_model.size();
+        if ((size_t)n_rigs * ctag::kRfitN * ctag::kRfitN * 8 > ((size_t)2 << 30)) return CTAG_ERR_LIMIT;
+        const int rc = Systems::setup(c, n_rigs, ctag::kRfitN, pass_records, ctag::kRfitPassRecords);
+        if (rc != CTAG_OK) return rc;
+        FIT_HIP(d_table.grow((size_t)std::max(R, 1) * ctag::kRfitSlots));
+        FIT_HIP(d_ws.grow((size_t)pass * ctag::kRfitSlots * ctag::kRfitDoubles));
+        FIT_HIP(d_n_slots.grow(n_rigs));
+        FIT_HIP(d_drop.grow(n_rigs));
+        FIT_HIP(d_slot.grow(std::max(n_models, 1)));
+        if (n_models > 0) FIT_HIP(hipMemcpyAsync(d_slot.p, slot_of_model.data(), sizeof(int32_t) * n_models, hipMemcpyHostToDevice, c.s));
+        FIT_HIP(hipMemcpyAsync(d_n_slots.p, n_slots.data(), sizeof(int32_t) * n_rigs, hipMemcpyHostToDevice, c.s));
+        FIT_HIP(hipMemcpyAsync(d_drop.p, drop.data(), sizeof(int32_t) * n_rigs, hipMemcpyHostToDevice, c.s));
         return CTAG_OK;
     }
 
-    // S and g of every rig at (model, recs_dev), pass by pass; flags come back to the host.  Waits.
-    int build_system(const ctag::PoseModelDev& md, const ctag_rig_pose_rec* recs_dev) {
-        RFIT_HIP(hipMemsetAsync(d_S.p, 0, sizeof(double) * (size_t)n_rigs * ctag::kRfitN * ctag::kRfitN, s));
-        RFIT_HIP(hipMemsetAsync(d_g.p, 0, sizeof(double) * (size_t)n_rigs * ctag::kRfitN, s));
+    // S and g of every rig at (model, recs_dev); slot 2 times the record and the assemble kernel together.  Waits.
+    int build_system(const ctag_model* model, const ctag_rig_pose_rec* recs_dev) {
+        const ctag::PoseModelDev md{model->n_models, model->model_size, model->d_ids.p, model->d_corners.p};
         constexpr int kThreads = ctag::kRfitN * ctag::kRfitN + ctag::kRfitN;
-        for (int r0 = 0; r0 < R; r0 += pass) {
-            const int r1 = std::min(R, r0 + pass);
-            if (timing) RFIT_HIP(hipEventRecord(st->ev[0], s));
-            hipLaunchKernelGGL(ctag::k_rfit_record, dim3(std::min(r1 - r0, ctag::kRfitGrid)), dim3(64), 0, s, res, n_frames, recs_dev, d_obs.p, r0, r1, md,
-                               d_slot.p, cam, d_ws.p, d_table.p, d_flags.p);
-            hipLaunchKernelGGL(ctag::k_rfit_assemble, dim3((kThreads + 255) / 256, n_rigs), dim3(256), 0, s, d_ws.p, d_table.p, d_rec_rig.p, d_flags.p, r0, r1,
+        return build(c, [&](int r0, int r1) {
+            if (c.mark(0) != CTAG_OK) return CTAG_ERR_HIP;
+            hipLaunchKernelGGL(ctag::k_rfit_record, dim3(std::min(r1 - r0, ctag::kRfitGrid)), dim3(64), 0, c.s, c.res, c.n_frames, recs_dev, d_obs.p, r0, r1, md,
+                               d_slot.p, c.cam, d_ws.p, d_table.p, d_flags.p);
+            hipLaunchKernelGGL(ctag::k_rfit_assemble, dim3((kThreads + 255) / 256, n_groups), dim3(256), 0, c.s, d_ws.p, d_table.p, d_rec_group.p, d_flags.p, r0, r1,
                                d_S.p, d_g.p);
-            RFIT_HIP(hipGetLastError());
-            if (timing) {
-                RFIT_HIP(hipEventRecord(st->ev[1], s));
-                RFIT_HIP(hipEventSynchronize(st->ev[1]));
-                float a = 0.f;
-                (void)hipEventElapsedTime(&a, st->ev[0], st->ev[1]);
-                st->ms[2] += a;
-            }
-        }
-        if (R > 0) RFIT_HIP(hipMemcpyAsync(flags.data(), d_flags.p, sizeof(int32_t) * R, hipMemcpyDeviceToHost, s));
-        RFIT_HIP(hipStreamSynchronize(s));
-        return CTAG_OK;
+            if (fit::launched() != CTAG_OK || c.mark(1) != CTAG_OK || c.reached(1) != CTAG_OK) return CTAG_ERR_HIP;
+            c.add_ms(2, 0);
+            return CTAG_OK;
+        });
     }
 
-    // delta[n_rigs][96] and bad[n_rigs] for the rigs with active[g] != 0.  Waits.
-    int solve(const std::vector<double>& lambda, const std::vector<int32_t>& active, std::vector<double>& delta, std::vector<int32_t>& bad) {
-        RFIT_HIP(hipMemcpyAsync(d_lambda.p, lambda.data(), sizeof(double) * n_rigs, hipMemcpyHostToDevice, s));
-        RFIT_HIP(hipMemcpyAsync(d_active.p, active.data(), sizeof(int32_t) * n_rigs, hipMemcpyHostToDevice, s));
-        RFIT_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int32_t) * n_rigs, s));
-        RFIT_HIP(hipMemsetAsync(d_delta.p, 0, sizeof(double) * (size_t)n_rigs * ctag::kRfitN, s));
-        if (timing) RFIT_HIP(hipEventRecord(st->ev[0], s));
-        hipLaunchKernelGGL(ctag::k_rfit_solve, dim3(n_rigs), dim3(ctag::kRfitSolveThreads), 0, s, d_S.p, d_g.p, d_n_slots.p, d_drop.p, d_lambda.p, d_active.p,
-                           d_delta.p, d_bad.p);
-        RFIT_HIP(hipGetLastError());
-        if (timing) RFIT_HIP(hipEventRecord(st->ev[1], s));
-        delta.resize((size_t)n_rigs * ctag::kRfitN);
-        bad.resize(n_rigs);
-        RFIT_HIP(hipMemcpyAsync(delta.data(), d_delta.p, sizeof(double) * delta.size(), hipMemcpyDeviceToHost, s));
-        RFIT_HIP(hipMemcpyAsync(bad.data(), d_bad.p, sizeof(int32_t) * n_rigs, hipMemcpyDeviceToHost, s));
-        RFIT_HIP(hipStreamSynchronize(s));
-        if (timing) {
-            float a = 0.f;
-            (void)hipEventElapsedTime(&a, st->ev[0], st->ev[1]);
-            st->ms[3] += a;
-        }
-        return CTAG_OK;
+    int solve(const std::vector<double>& lambda, const std::vector<int32_t>& active, int bad_flags, std::vector<double>& delta, std::vector<int32_t>& bad) {
+        return Systems::solve(c, lambda, active, bad_flags, delta, bad, [&]() {
+            hipLaunchKernelGGL(ctag::k_rfit_solve, dim3(n_groups), dim3(ctag::kRfitSolveThreads), 0, c.s, d_S.p, d_g.p, d_n_slots.p, d_drop.p, d_lambda.p, d_active.p,
+                               d_delta.p, d_bad.p);
+        });
     }
 };
 
@@ -518,50 +404,12 @@ int rfit_opts(const ctag_rig_fit_opts* o, ctag_rig_fit_opts& r) {
     return CTAG_OK;
 }
 
-struct ModelGuard {  // frees the working model unless it is handed out
-    ctag_model* m = nullptr;
-    ~ModelGuard() {
-        if (m) ctag_model_free(m);
-    }
-};
-
 struct RigsGuard {
     ctag_rigs* r = nullptr;
     ~RigsGuard() {
         if (r) ctag_rigs_free(r);
     }
 };
-
-int rfit_prepare(RfitWork& w, ctag_handle* h, const ctag_frame_result* results_dev, int n_frames, const ctag_camera* camera) {
-    w.h = h;
-    RFIT_HIP(hipSetDevice(ctag::handle_device(h)));
-    w.st = rfit_state(h);
-    if (!w.st) return CTAG_ERR_HIP;
-    w.s = static_cast<hipStream_t>(ctag_stream(h));
-    w.timing = ctag::handle_timing(h);
-    for (float& v : w.st->ms) v = 0.f;
-    w.res = results_dev;
-    w.n_frames = n_frames;
-    w.cam = ctag::make_pose_cam(camera);
-    return CTAG_OK;
-}
-
-// rig-pose records of the working model W (its device corners are current) into recs_dev, then to the host.  Waits.
-int rig_pose_pass(RfitWork& w, ctag_model* W, const ctag_rigs* rigs, const ctag_camera* camera, ctag_rig_pose_rec* recs_dev, std::vector<ctag_rig_pose_rec>& host) {
-    if (w.timing) RFIT_HIP(hipEventRecord(w.st->ev[0], w.s));
-    const int rc = ctag_rig_pose_batch_device(w.h, w.res, w.n_frames, W, rigs, camera, recs_dev);
-    if (rc != CTAG_OK) return rc;
-    if (w.timing) RFIT_HIP(hipEventRecord(w.st->ev[1], w.s));
-    host.resize((size_t)w.n_frames * w.n_rigs);
-    RFIT_HIP(hipMemcpyAsync(host.data(), recs_dev, sizeof(ctag_rig_pose_rec) * host.size(), hipMemcpyDeviceToHost, w.s));
-    RFIT_HIP(hipStreamSynchronize(w.s));
-    if (w.timing) {
-        float a = 0.f;
-        (void)hipEventElapsedTime(&a, w.st->ev[0], w.st->ev[1]);
-        w.st->ms[1] += a;
-    }
-    return CTAG_OK;
-}
 
 // rule 3: model m of W = T applied to model m of `in`, in double, rounded to float
 void apply_rigid(const ctag_model* in, ctag_model* W, int m, const Rigid& T) {
@@ -582,10 +430,6 @@ void apply_rigid(const ctag_model* in, ctag_model* W, int m, const Rigid& T) {
     for (int k = 0; k < 3; k++) W->axis[3 * m + k] = (float)Y[k];
 }
 
-int push_corners(RfitWork& w, ctag_model* W) {
-    return hipMemcpyAsync(W->d_corners.p, W->corners.data(), sizeof(float) * W->corners.size(), hipMemcpyHostToDevice, w.s) == hipSuccess ? CTAG_OK : CTAG_ERR_HIP;
-}
-
 }  // namespace
 
 namespace ctag {
@@ -603,14 +447,13 @@ int rfit_probe_system(ctag_handle* h, const ctag_frame_result* results, int n_fr
     if (!camera_ok(camera)) return CTAG_ERR_UNSUPPORTED;
     ctag_model* model = const_cast<ctag_model*>(model_c);
     RfitWork w;
-    int rc = rfit_prepare(w, h, nullptr, n_frames, camera);
+    int rc = w.c.prepare(h, kRigFitState, nullptr, n_frames, camera);
     if (rc != CTAG_OK) return rc;
-    w.n_models = model->n_models;
-    w.n_rigs = rigs->n_rigs;
-    w.slot_of_model.assign(w.n_models, -1);
-    w.n_slots.assign(w.n_rigs, 0);
-    w.drop.assign(w.n_rigs, 0);
-    for (int m = 0; m < w.n_models; m++) {
+    const int n_rigs = rigs->n_rigs;
+    w.slot_of_model.assign(model->n_models, -1);
+    w.n_slots.assign(n_rigs, 0);
+    w.drop.assign(n_rigs, 0);
+    for (int m = 0; m < model->n_models; m++) {
         const int gi = rigs->rig_of_model[m];
         if (gi < 0) continue;
         if (w.n_slots[gi] >= kRfitSlots) return CTAG_ERR_ARG;
@@ -618,34 +461,30 @@ int rfit_probe_system(ctag_handle* h, const ctag_frame_result* results, int n_fr
     }
     if (w.n_slots[rig] < 2) return CTAG_ERR_ARG;
     if (model_to_device(model, handle_device(h)) != CTAG_OK) return CTAG_ERR_HIP;
-    const size_t n_items = (size_t)n_frames * rigs->n_rigs;
+    const size_t n_items = (size_t)n_frames * n_rigs;
     DevBuf<ctag_frame_result> d_res;
     DevBuf<ctag_rig_pose_rec> d_recs;
-    RFIT_HIP(d_res.grow(n_frames));
-    RFIT_HIP(d_recs.grow(n_items));
-    RFIT_HIP(hipMemcpyAsync(d_res.p, results, sizeof(ctag_frame_result) * (size_t)n_frames, hipMemcpyHostToDevice, w.s));
-    RFIT_HIP(hipMemcpyAsync(d_recs.p, recs, sizeof(ctag_rig_pose_rec) * n_items, hipMemcpyHostToDevice, w.s));
-    w.res = d_res.p;
+    rc = fit::upload_probe_inputs(w.c, results, d_res, recs, n_items, d_recs);
+    if (rc != CTAG_OK) return rc;
     for (size_t i = 0; i < n_items; i++)
-        if (recs[i].status == CTAG_POSE_OK && recs[i].n_members >= 2 && recs[i].rig >= 0 && recs[i].rig < rigs->n_rigs) {
+        if (recs[i].status == CTAG_POSE_OK && recs[i].n_members >= 2 && recs[i].rig >= 0 && recs[i].rig < n_rigs) {
             w.obs.push_back((int32_t)i);
-            w.rec_rig.push_back(recs[i].rig);
+            w.rec_group.push_back(recs[i].rig);
         }
     if (w.obs.empty()) return CTAG_ERR_ARG;
     rc = w.setup(pass_records);
     if (rc != CTAG_OK) return rc;
-    const PoseModelDev md{model->n_models, model->model_size, model->d_ids.p, model->d_corners.p};
-    rc = w.build_system(md, d_recs.p);
+    rc = w.build_system(model, d_recs.p);
     if (rc != CTAG_OK) return rc;
-    std::vector<double> lam(w.n_rigs, lambda), d;
-    std::vector<int32_t> active(w.n_rigs, 0), bad;
+    std::vector<double> lam(n_rigs, lambda), d;
+    std::vector<int32_t> active(n_rigs, 0), bad;
     active[rig] = 1;
-    rc = w.solve(lam, active, d, bad);
+    rc = w.solve(lam, active, kRecSingular, d, bad);  // a caller's record may be left out; that does not make the rig bad here
     if (rc != CTAG_OK) return rc;
     const int N = 6 * w.n_slots[rig];
     std::vector<double> Sf((size_t)kRfitN * kRfitN), gf(kRfitN);
-    RFIT_HIP(hipMemcpy(Sf.data(), w.d_S.p + (size_t)rig * kRfitN * kRfitN, sizeof(double) * Sf.size(), hipMemcpyDeviceToHost));
-    RFIT_HIP(hipMemcpy(gf.data(), w.d_g.p + (size_t)rig * kRfitN, sizeof(double) * kRfitN, hipMemcpyDeviceToHost));
+    FIT_HIP(hipMemcpy(Sf.data(), w.d_S.p + (size_t)rig * kRfitN * kRfitN, sizeof(double) * Sf.size(), hipMemcpyDeviceToHost));
+    FIT_HIP(hipMemcpy(gf.data(), w.d_g.p + (size_t)rig * kRfitN, sizeof(double) * kRfitN, hipMemcpyDeviceToHost));
     for (int i = 0; i < N; i++) {
         for (int j = 0; j < N; j++) S[(size_t)i * N + j] = Sf[(size_t)i * kRfitN + j];
         g[i] = gf[i];
@@ -653,8 +492,6 @@ int rfit_probe_system(ctag_handle* h, const ctag_frame_result* results, int n_fr
     }
     *n_unknowns = N;
     *bad_pivot = bad[rig];
-    for (int r = 0; r < w.R; r++)
-        if (w.rec_rig[r] == rig && (w.flags[r] & kRfitSingular)) *bad_pivot = 1;
     return CTAG_OK;
 }
 
@@ -671,13 +508,7 @@ void ctag_rig_fit_opts_default(ctag_rig_fit_opts* o) {
     o->rel_tol = 2.479e-5;  // 4 x 6.198e-6: what float32 rounding of the model alone does to the cost
 }
 
-int ctag_rig_fit_last_ms(ctag_handle* h, float* out4) {
-    if (!h || !out4) return CTAG_ERR_ARG;
-    RfitState* st = rfit_state(h);
-    if (!st) return CTAG_ERR_HIP;
-    for (int i = 0; i < 4; i++) out4[i] = st->ms[i];
-    return CTAG_OK;
-}
+int ctag_rig_fit_last_ms(ctag_handle* h, float* out4) { return fit::last_ms(h, ctag::kRigFitState, out4); }  // marker pose, rig pose, record + assemble, solve
 
 int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, int n_frames, const ctag_model* in, const ctag_rigs* rigs,
                         const ctag_camera* camera, const ctag_rig_fit_opts* opts_in, ctag_model** out, ctag_rig_fit_stat* rig_stats,
@@ -696,17 +527,11 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
     if (!ctag::camera_ok(camera)) return CTAG_ERR_UNSUPPORTED;
     if ((long long)n_frames * CTAG_MAX_MARKERS > (1ll << 30) || (long long)n_frames * ng > (1ll << 28)) return CTAG_ERR_LIMIT;
     RfitWork w;
-    int rc = rfit_prepare(w, h, results_dev, n_frames, camera);
+    int rc = w.c.prepare(h, ctag::kRigFitState, results_dev, n_frames, camera);
     if (rc != CTAG_OK) return rc;
-    w.n_models = nm;
-    w.n_rigs = ng;
-    ModelGuard guard;
-    {
-        ctag_model_view v;
-        if (ctag_model_get_view(in, &v) != CTAG_OK) return CTAG_ERR_ARG;
-        rc = ctag_model_create(&v, &guard.m);
-        if (rc != CTAG_OK) return rc;
-    }
+    fit::ModelGuard guard;
+    rc = fit::clone_model(in, &guard.m);
+    if (rc != CTAG_OK) return rc;
     ctag_model* W = guard.m;
     for (int m = 0; m < nm; m++) {
         std::memset(&model_stats[m], 0, sizeof(model_stats[m]));
@@ -722,12 +547,7 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
         rig_stats[g].lambda = opts.lambda0;
     }
     auto hand_out = [&]() {
-        // the device copies belong to the trial states of the call: the model handed out makes its own at its first use
-        W->d_ids.release();
-        W->d_corners.release();
-        W->d_base_axis.release();
-        W->d_base = W->d_axis = nullptr;
-        W->device = -1;
+        fit::release_device_copies(W);
         *out = guard.m;
         guard.m = nullptr;
         return CTAG_OK;
@@ -737,25 +557,14 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
     // ---- rule 1: the per-marker poses under `in`
     ctag::DevBuf<int32_t> d_off;
     ctag::DevBuf<ctag_pose_rec> d_poses;
-    RFIT_HIP(d_off.grow((size_t)n_frames + 1));
-    RFIT_HIP(d_poses.grow(1));
-    // capacity 1: the call is made for offsets[n_frames], the record count; the one pose it solves is discarded
-    rc = ctag_pose_batch_device(h, results_dev, n_frames, in, camera, d_off.p, d_poses.p, 1);
+    std::vector<int32_t> off;
+    rc = fit::count_pose_records(w.c, in, camera, d_off, d_poses, off);
     if (rc != CTAG_OK) return rc;
-    std::vector<int32_t> off((size_t)n_frames + 1);
-    RFIT_HIP(hipMemcpyAsync(off.data(), d_off.p, sizeof(int32_t) * off.size(), hipMemcpyDeviceToHost, w.s));
-    RFIT_HIP(hipStreamSynchronize(w.s));
     const int32_t total = off[n_frames];
     if (total <= 0) return hand_out();
-    RFIT_HIP(d_poses.grow((size_t)total));
-    std::vector<ctag_pose_rec> poses((size_t)total);
-    if (w.timing) RFIT_HIP(hipEventRecord(w.st->ev[0], w.s));
-    rc = ctag_pose_batch_device(h, results_dev, n_frames, in, camera, d_off.p, d_poses.p, total);
+    std::vector<ctag_pose_rec> poses;
+    rc = w.c.pose_pass(0, [&]() { return ctag_pose_batch_device(h, results_dev, n_frames, in, camera, d_off.p, d_poses.p, total); }, d_poses.p, (size_t)total, poses);
     if (rc != CTAG_OK) return rc;
-    if (w.timing) RFIT_HIP(hipEventRecord(w.st->ev[1], w.s));
-    RFIT_HIP(hipMemcpyAsync(poses.data(), d_poses.p, sizeof(ctag_pose_rec) * (size_t)total, hipMemcpyDeviceToHost, w.s));
-    RFIT_HIP(hipStreamSynchronize(w.s));
-    if (w.timing) (void)hipEventElapsedTime(&w.st->ms[0], w.st->ev[0], w.st->ev[1]);
     // seen[f][m]: the pose record of frame f that counts for model m, -1 if none
     std::vector<int32_t> seen((size_t)n_frames * nm, -1);
     {
@@ -831,7 +640,8 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
                 for (int i = 0; i < 3; i++) sumt[i] += e[i];
             }
             Rigid E;
-            nearest_rotation(sumR, E.R);
+            double sv[3];
+            fit::nearest_rotation(sumR, E.R, sv);
             for (int i = 0; i < 3; i++) E.t[i] = sumt[i] / (double)best;
             Rigid& Tb = T[mb];
             const Rigid& Ta = T[ma];
@@ -856,17 +666,17 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
                 model_stats[M[a]].status = CTAG_POSE_OK;
             }
     }
-    auto is_anchor = [&](int m) { return placed[m] && rig_stats[rigs->rig_of_model[m]].anchor == m; };
+    auto moves = [&](int m) { return placed[m] && rig_stats[rigs->rig_of_model[m]].anchor != m; };  // placed and not its rig's anchor
     auto report_transforms = [&](const std::vector<Rigid>& TT) {
         for (int m = 0; m < nm; m++) {
-            if (!placed[m] || is_anchor(m)) continue;
+            if (!moves(m)) continue;
             ctl::rodrigues_from_matrix(TT[m].R, model_stats[m].rvec);
             for (int i = 0; i < 3; i++) model_stats[m].tvec[i] = TT[m].t[i];
         }
     };
     // ---- rule 3: the working model at the initial assembly; rule 4: the rig set without the unplaced models
     for (int m = 0; m < nm; m++)
-        if (placed[m] && !is_anchor(m)) apply_rigid(in, W, m, T[m]);
+        if (moves(m)) apply_rigid(in, W, m, T[m]);
     report_transforms(T);
     std::vector<int32_t> rig_placed(nm);
     bool any_placed = false;
@@ -880,35 +690,29 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
     if (rc != CTAG_OK) return rc;
     const size_t n_items = (size_t)n_frames * ng;
     ctag::DevBuf<ctag_rig_pose_rec> d_recs;
-    RFIT_HIP(d_recs.grow(n_items));
+    FIT_HIP(d_recs.grow(n_items));
     std::vector<ctag_rig_pose_rec> acc, trial;
-    rc = rig_pose_pass(w, W, rg.r, camera, d_recs.p, acc);
+    // rig-pose records of W (its device corners are current) to the host, timed in slot 1
+    auto rig_pose_pass = [&](std::vector<ctag_rig_pose_rec>& host) {
+        return w.c.pose_pass(1, [&]() { return ctag_rig_pose_batch_device(h, results_dev, n_frames, W, rg.r, camera, d_recs.p); }, d_recs.p, n_items, host);
+    };
+    rc = rig_pose_pass(acc);
     if (rc != CTAG_OK) return rc;
     for (size_t i = 0; i < n_items; i++)
         if (acc[i].status == CTAG_POSE_OK && acc[i].n_members >= 2) {
             w.obs.push_back((int32_t)i);
-            w.rec_rig.push_back(acc[i].rig);
+            w.rec_group.push_back(acc[i].rig);
         }
     rc = w.setup(0);
     if (rc != CTAG_OK) return rc;
     const int R = w.R;
-    // cost of rig g over its observation records, in (frame, rig) order; all_ok[g] = 0 when one of them is not CTAG_POSE_OK
-    auto costs_of = [&](const std::vector<ctag_rig_pose_rec>& P, std::vector<double>& cost, std::vector<uint8_t>& all_ok) {
-        cost.assign(ng, 0.0);
-        all_ok.assign(ng, 1);
-        for (int r = 0; r < R; r++) {
-            const ctag_rig_pose_rec& p = P[w.obs[r]];
-            if (p.status != CTAG_POSE_OK) all_ok[w.rec_rig[r]] = 0;
-            cost[w.rec_rig[r]] += p.cost;
-        }
-    };
-    std::vector<double> cost_cur, cost_trial, lambda(ng, opts.lambda0), delta;
-    std::vector<uint8_t> ok_cur, ok_trial(ng, 0);
-    std::vector<int32_t> active(ng, 0), bad;
-    costs_of(acc, cost_cur, ok_cur);
+    fit::Lm lm;
+    lm.start(ng, opts.lambda0);
+    std::vector<uint8_t> ok_cur;
+    w.costs_of(acc, nullptr, lm.cost, ok_cur);
     for (int r = 0; r < R; r++) {
         const ctag_rig_pose_rec& p = acc[w.obs[r]];
-        ctag_rig_fit_stat& s = rig_stats[w.rec_rig[r]];
+        ctag_rig_fit_stat& s = rig_stats[w.rec_group[r]];
         s.n_records++;
         s.n_points += p.n_points;
         for (int k = 0; k < CTAG_MAX_MARKERS; k++)  // pose record k of a frame is its marker k
@@ -917,42 +721,40 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
                 if (i < off[p.frame + 1] && poses[i].model_index >= 0 && poses[i].model_index < nm) model_stats[poses[i].model_index].n_records++;
             }
     }
-    bool any = false;
     for (int g = 0; g < ng; g++) {
-        rig_stats[g].cost_init = rig_stats[g].cost = cost_cur[g];
-        if (rig_stats[g].status == CTAG_POSE_OK && rig_stats[g].n_records > 0 && rig_stats[g].n_placed > 1) {
-            active[g] = opts.max_rounds > 0 ? 1 : 0;
-            any = any || active[g];
-        }
+        rig_stats[g].cost_init = rig_stats[g].cost = lm.cost[g];
+        if (rig_stats[g].status == CTAG_POSE_OK && rig_stats[g].n_records > 0 && rig_stats[g].n_placed > 1) lm.active[g] = opts.max_rounds > 0 ? 1 : 0;
     }
 
-    // ---- rule 5: the rounds.  T is the accepted state of every model; W carries the trial during a round
+    // ---- rule 5: the rounds.  T and acc_* are the accepted state of every model; W carries the trial during a round.  The loop is
+    // the model reconstruction's (k_model_fit.hip, rules 3-5) but for the steps marked "rig"; the two are kept in step by hand
     std::vector<Rigid> Tt(nm);
     std::vector<float> acc_corners = W->corners, acc_base = W->base, acc_axis = W->axis;
-    bool need_system = true;
+    bool need_system = true;  // none has been built yet
     const int pm = W->model_size * 8;
-    while (any) {
+    std::vector<double> delta, cost_trial(ng, 0.0);
+    std::vector<uint8_t> ok_trial(ng, 0);
+    std::vector<int32_t> bad;
+    while (lm.any_active()) {
         if (need_system) {
             W->corners = acc_corners;
-            if (push_corners(w, W) != CTAG_OK) return CTAG_ERR_HIP;
-            RFIT_HIP(hipMemcpyAsync(d_recs.p, acc.data(), sizeof(ctag_rig_pose_rec) * n_items, hipMemcpyHostToDevice, w.s));
-            const ctag::PoseModelDev md{W->n_models, W->model_size, W->d_ids.p, W->d_corners.p};
-            rc = w.build_system(md, d_recs.p);
+            if (fit::push_corners(w.c, W) != CTAG_OK) return CTAG_ERR_HIP;
+            FIT_HIP(hipMemcpyAsync(d_recs.p, acc.data(), sizeof(ctag_rig_pose_rec) * n_items, hipMemcpyHostToDevice, w.c.s));
+            rc = w.build_system(W, d_recs.p);
             if (rc != CTAG_OK) return rc;
             need_system = false;
         }
-        rc = w.solve(lambda, active, delta, bad);
+        // rig: every observation record was solved by k_rig_solve on this state, so one that is flagged at all makes its rig bad
+        rc = w.solve(lm.lambda, lm.active, ~0, delta, bad);
         if (rc != CTAG_OK) return rc;
-        for (int r = 0; r < R; r++)
-            if (w.flags[r] != 0) bad[w.rec_rig[r]] = 1;
         W->corners = acc_corners;
         W->base = acc_base;
         W->axis = acc_axis;
         bool any_trial = false;
-        for (int m = 0; m < nm; m++) {
-            if (!placed[m] || is_anchor(m)) continue;
+        for (int m = 0; m < nm; m++) {  // rig: T <- Exp(delta) T for the models that move
+            if (!moves(m)) continue;
             const int g = rigs->rig_of_model[m];
-            if (!active[g] || bad[g]) continue;
+            if (!lm.active[g] || bad[g]) continue;
             const double* d = &delta[(size_t)g * ctag::kRfitN + 6 * w.slot_of_model[m]];
             bool finite = true;
             for (int i = 0; i < 6; i++) finite = finite && std::isfinite(d[i]);
@@ -969,38 +771,26 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
             any_trial = true;
         }
         if (any_trial) {
-            if (push_corners(w, W) != CTAG_OK) return CTAG_ERR_HIP;
-            rc = rig_pose_pass(w, W, rg.r, camera, d_recs.p, trial);
+            if (fit::push_corners(w.c, W) != CTAG_OK) return CTAG_ERR_HIP;
+            rc = rig_pose_pass(trial);
             if (rc != CTAG_OK) return rc;
-            costs_of(trial, cost_trial, ok_trial);
+            w.costs_of(trial, nullptr, cost_trial, ok_trial);
         }
-        any = false;
         for (int g = 0; g < ng; g++) {
-            if (!active[g]) continue;
-            rig_stats[g].rounds++;
-            if (any_trial && !bad[g] && ok_trial[g] && cost_trial[g] < cost_cur[g]) {
-                const double drop = cost_cur[g] - cost_trial[g];
-                cost_cur[g] = cost_trial[g];
-                for (int m : members[g]) {
-                    if (!placed[m] || is_anchor(m)) continue;
-                    T[m] = Tt[m];
-                    std::memcpy(&acc_corners[(size_t)m * pm * 3], &W->corners[(size_t)m * pm * 3], sizeof(float) * (size_t)pm * 3);
-                    for (int k = 0; k < 3; k++) {
-                        acc_base[3 * m + k] = W->base[3 * m + k];
-                        acc_axis[3 * m + k] = W->axis[3 * m + k];
-                    }
+            if (!lm.active[g]) continue;
+            // without a trial, cost_trial and ok_trial are an earlier round's
+            if (!lm.decide(g, any_trial && !bad[g] && ok_trial[g], cost_trial[g], opts)) continue;
+            for (int m : members[g]) {  // rig
+                if (!moves(m)) continue;
+                T[m] = Tt[m];
+                std::memcpy(&acc_corners[(size_t)m * pm * 3], &W->corners[(size_t)m * pm * 3], sizeof(float) * (size_t)pm * 3);
+                for (int k = 0; k < 3; k++) {
+                    acc_base[3 * m + k] = W->base[3 * m + k];
+                    acc_axis[3 * m + k] = W->axis[3 * m + k];
                 }
-                for (int r = 0; r < R; r++)
-                    if (w.rec_rig[r] == g) acc[w.obs[r]] = trial[w.obs[r]];
-                lambda[g] = std::max(lambda[g] / 3.0, 1e-9);
-                need_system = true;
-                if (drop < opts.rel_tol * cost_cur[g]) active[g] = 0;
-            } else {
-                lambda[g] *= 4.0;
-                if (lambda[g] > opts.lambda_max) active[g] = 0;
             }
-            if (rig_stats[g].rounds >= opts.max_rounds) active[g] = 0;
-            any = any || active[g];
+            w.take_records(g, trial, acc);
+            need_system = true;
         }
     }
     W->corners = acc_corners;
@@ -1009,9 +799,10 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
     report_transforms(T);
     for (int g = 0; g < ng; g++) {
         if (rig_stats[g].status != CTAG_POSE_OK) continue;
-        rig_stats[g].cost = cost_cur[g];
-        rig_stats[g].lambda = lambda[g];
-        rig_stats[g].rms_px = rig_stats[g].n_points > 0 ? std::sqrt(2.0 * cost_cur[g] / (double)rig_stats[g].n_points) : 0.0;
+        rig_stats[g].rounds = lm.rounds[g];
+        rig_stats[g].cost = lm.cost[g];
+        rig_stats[g].lambda = lm.lambda[g];
+        rig_stats[g].rms_px = rig_stats[g].n_points > 0 ? std::sqrt(2.0 * lm.cost[g] / (double)rig_stats[g].n_points) : 0.0;
     }
     return hand_out();
 }
@@ -1019,11 +810,9 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
 int ctag_rig_fit(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_model* in, const ctag_rigs* rigs, const ctag_camera* camera,
                  const ctag_rig_fit_opts* opts, ctag_model** out, ctag_rig_fit_stat* rig_stats, ctag_rig_fit_model_stat* model_stats) {
     if (!h || !results || n_frames < 1 || !in || !rigs || !camera || !out || !rig_stats || !model_stats) return CTAG_ERR_ARG;
-    if (hipSetDevice(ctag::handle_device(h)) != hipSuccess) return CTAG_ERR_HIP;
-    ctag::DevBuf<ctag_frame_result> d_res;
-    RFIT_HIP(d_res.grow((size_t)n_frames));
-    RFIT_HIP(hipMemcpy(d_res.p, results, sizeof(ctag_frame_result) * (size_t)n_frames, hipMemcpyHostToDevice));
-    return ctag_rig_fit_device(h, d_res.p, n_frames, in, rigs, camera, opts, out, rig_stats, model_stats);
+    return fit::with_results_on_device(h, results, n_frames, [&](const ctag_frame_result* results_dev) {
+        return ctag_rig_fit_device(h, results_dev, n_frames, in, rigs, camera, opts, out, rig_stats, model_stats);
+    });
 }
 
 }  // extern "C"
