@@ -33,7 +33,8 @@ POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag
                 "ctag_cov_opts_default", "ctag_pose_cov_batch_device", "ctag_rig_pose_cov_batch_device", "ctag_mv_rig_pose_cov_batch_device",
                 "ctag_estimate_pose_cov", "ctag_estimate_rig_pose_cov", "ctag_estimate_mv_rig_pose_cov",
                 "ctag_model_fit_opts_default", "ctag_model_fit_device", "ctag_model_fit", "ctag_model_save", "ctag_model_fit_last_ms",
-                "ctag_rig_fit_opts_default", "ctag_rig_fit_device", "ctag_rig_fit", "ctag_rig_fit_last_ms"]
+                "ctag_rig_fit_opts_default", "ctag_rig_fit_device", "ctag_rig_fit", "ctag_rig_fit_last_ms",
+                "ctag_camera_fit_opts_default", "ctag_camera_fit_device", "ctag_camera_fit", "ctag_camera_fit_last_ms", "ctag_camera_set_get"]
 # ... and include/ctag_gather.h
 GATHER_EXPORTS = ["ctag_shard_range", "ctag_packed_capacity", "ctag_pack_results", "ctag_unpack_results", "ctag_comm_unique_id",
                   "ctag_comm_init", "ctag_comm_attach", "ctag_comm_destroy", "ctag_comm_native", "ctag_comm_last_error", "ctag_gather_begin",
@@ -79,6 +80,13 @@ assert RIG_FIT_STAT_DT.itemsize == 64
 RIG_FIT_MODEL_STAT_DT = np.dtype([("status", "<i4"), ("rig", "<i4"), ("parent", "<i4"), ("n_frames_with_parent", "<i4"), ("n_records", "<i4"),
                                   ("reserved", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
 assert RIG_FIT_MODEL_STAT_DT.itemsize == 72
+# ctag_camera_fit_stat / ctag_camera_fit_cam_stat: one record per call / per camera of a camera set fit (include/ctag_pose.h)
+CAMERA_FIT_STAT_DT = np.dtype([("status", "<i4"), ("anchor", "<i4"), ("n_placed", "<i4"), ("n_unplaced", "<i4"), ("n_records", "<i4"), ("n_points", "<i4"),
+                               ("rounds", "<i4"), ("reserved", "<i4"), ("cost_init", "<f8"), ("cost", "<f8"), ("lambda", "<f8"), ("rms_px", "<f8")])
+assert CAMERA_FIT_STAT_DT.itemsize == 64
+CAMERA_FIT_CAM_STAT_DT = np.dtype([("status", "<i4"), ("parent", "<i4"), ("n_items_with_parent", "<i4"), ("n_records", "<i4"), ("n_points", "<i4"),
+                                   ("reserved", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
+assert CAMERA_FIT_CAM_STAT_DT.itemsize == 72
 
 
 class ParamsC(C.Structure):  # ctag_params (include/ctag_types.h): the reference's tunables
@@ -156,6 +164,22 @@ def rig_fit_opts(**fields):
     for k, v in fields.items():
         if k not in ("max_rounds", "min_frames", "lambda0", "lambda_max", "rel_tol"):
             raise TypeError("ctag_rig_fit_opts has no field %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class CameraFitOptsC(C.Structure):  # ctag_camera_fit_opts
+    _fields_ = [("max_rounds", C.c_int32), ("min_items", C.c_int32), ("min_points", C.c_int32), ("reserved", C.c_int32), ("lambda0", C.c_double),
+                ("lambda_max", C.c_double), ("rel_tol", C.c_double)]
+
+
+def camera_fit_opts(**fields):
+    """ctag_camera_fit_opts_default, then the given fields."""
+    o = CameraFitOptsC()
+    load_library().ctag_camera_fit_opts_default(C.byref(o))
+    for k, v in fields.items():
+        if k not in ("max_rounds", "min_items", "min_points", "lambda0", "lambda_max", "rel_tol"):
+            raise TypeError("ctag_camera_fit_opts has no field %r" % k)
         setattr(o, k, v)
     return o
 
@@ -318,6 +342,17 @@ def load_library():
     L.ctag_rig_fit.argtypes = [vp, vp, C.c_int, vp, vp, C.POINTER(CameraC), rfitp, C.POINTER(vp), vp, vp]
     L.ctag_rig_fit_last_ms.restype = C.c_int
     L.ctag_rig_fit_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    cfitp = C.POINTER(CameraFitOptsC)
+    L.ctag_camera_fit_opts_default.restype = None
+    L.ctag_camera_fit_opts_default.argtypes = [cfitp]
+    L.ctag_camera_fit_device.restype = C.c_int
+    L.ctag_camera_fit_device.argtypes = [vp, C.POINTER(vp), C.c_int, C.c_int, vp, vp, C.POINTER(CameraC), cfitp, C.POINTER(vp), vp, vp]
+    L.ctag_camera_fit.restype = C.c_int
+    L.ctag_camera_fit.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(CameraC), cfitp, C.POINTER(vp), vp, vp]
+    L.ctag_camera_fit_last_ms.restype = C.c_int
+    L.ctag_camera_fit_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ctag_camera_set_get.restype = C.c_int
+    L.ctag_camera_set_get.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(CameraC), C.POINTER(CameraPoseC)]
     u64p = C.POINTER(C.c_uint64)
     L.ctag_shard_range.restype = C.c_int
     L.ctag_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -499,6 +534,38 @@ class CameraSet:
         if st != 0:
             raise CtagError(st, "ctag_camera_set_create")
         self.s = s
+
+    @classmethod
+    def _adopt(cls, s):
+        """The CameraSet that owns the ctag_camera_set* a C call handed out."""
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.s = s
+        self.n = len(self.poses())
+        return self
+
+    def _get(self):
+        n = C.c_int()
+        cams, ps = (CameraC * MV_MAX_CAMERAS)(), (CameraPoseC * MV_MAX_CAMERAS)()
+        st = self.L.ctag_camera_set_get(self.s, C.byref(n), cams, ps)
+        if st != 0:
+            raise CtagError(st, "ctag_camera_set_get")
+        return n.value, cams, ps
+
+    def poses(self):
+        """ctag_camera_set_get: [(rvec, tvec)] of the set's cameras, the doubles it was created from."""
+        n, _, ps = self._get()
+        return [(np.array(ps[c].rvec[:], np.float64), np.array(ps[c].tvec[:], np.float64)) for c in range(n)]
+
+    def cameras(self):
+        """ctag_camera_set_get: the CameraC of every camera of the set."""
+        n, cams, _ = self._get()
+        out = []
+        for c in range(n):
+            cam = CameraC()
+            C.memmove(C.byref(cam), C.byref(cams[c]), C.sizeof(CameraC))
+            out.append(cam)
+        return out
 
     def close(self):
         if getattr(self, "s", None):
@@ -861,6 +928,45 @@ class Detector:
         out = (C.c_float * 4)()
         self.L.ctag_rig_fit_last_ms(self.h, out)
         return dict(zip(("marker_pose", "rig_pose", "record", "solve"), (float(v) for v in out)))
+
+    # ---- camera set fit (include/ctag_pose.h): opts is a CameraFitOptsC (camera_fit_opts(...)), or its fields as keywords
+    def _fit_camera_set(self, fn, name, results_arg, n_cameras, n_frames, model, rigs, cameras, opts, fields):
+        if fields:
+            if opts is not None:
+                raise TypeError("opts and option keywords together")
+            opts = camera_fit_opts(**fields)
+        cameras = list(cameras)
+        if len(cameras) != n_cameras:
+            raise ValueError("%d cameras for %d record arrays" % (len(cameras), n_cameras))
+        cams = (CameraC * max(n_cameras, 1))(*cameras)
+        stat = np.zeros(1, CAMERA_FIT_STAT_DT)
+        cam_stats = np.zeros(max(n_cameras, 1), CAMERA_FIT_CAM_STAT_DT)
+        s = C.c_void_p()
+        st = fn(self.h, results_arg, n_cameras, n_frames, model.m, rigs.r, cams, C.byref(opts) if opts is not None else None, C.byref(s),
+                stat.ctypes.data, cam_stats.ctypes.data)
+        if st != 0:
+            raise CtagError(st, name)
+        return (CameraSet._adopt(s) if s.value else None), stat[0], cam_stats[:n_cameras]
+
+    def fit_camera_set(self, records_per_camera, model, rigs, cameras, opts=None, **fields):
+        """ctag_camera_fit: records_per_camera[c][f] = the host ctag_frame_result record of camera c at instant f, and the cameras'
+        intrinsics (CameraC each) -> (the CameraSet with every camera's pose in the anchor camera's frame, or None when a camera could
+        not be placed; one CAMERA_FIT_STAT_DT record; CAMERA_FIT_CAM_STAT_DT records, one per camera).  Waits."""
+        res = np.ascontiguousarray(records_per_camera)
+        assert res.dtype == RESULT_DT and res.ndim == 2
+        return self._fit_camera_set(self.L.ctag_camera_fit, "ctag_camera_fit", res.ctypes.data if res.size else None, res.shape[0], res.shape[1], model, rigs,
+                                    cameras, opts, fields)
+
+    def fit_camera_set_device(self, results_ptrs, n_frames, model, rigs, cameras, opts=None, **fields):
+        """ctag_camera_fit_device: the same from one device pointer per camera, n_frames result records each."""
+        ptrs = (C.c_void_p * max(len(results_ptrs), 1))(*[int(p) for p in results_ptrs])
+        return self._fit_camera_set(self.L.ctag_camera_fit_device, "ctag_camera_fit_device", ptrs, len(results_ptrs), n_frames, model, rigs, cameras, opts, fields)
+
+    def camera_fit_last_ms(self):
+        """Device milliseconds of the last camera set fit by kernel kind (needs OPT_TIMING): per-camera rig pose, multi-view pose, record + assemble, solve."""
+        out = (C.c_float * 4)()
+        self.L.ctag_camera_fit_last_ms(self.h, out)
+        return dict(zip(("rig_pose", "mv_pose", "record", "solve"), (float(v) for v in out)))
 
     # ---- pose covariance (include/ctag_pose.h): opts is a CovOptsC (cov_opts(...)) or None for the defaults
     @staticmethod

@@ -321,6 +321,66 @@ void CylinderTag::assembleRigModel(const std::vector<std::vector<MarkerInfo>>& f
         if (model_stats[m].status != CTAG_POSE_OK) placedRigOfModel[m] = -1;
 }
 
+// new: the poses of the cameras of a set (include/ctag_pose.h, camera set fit)
+bool CylinderTag::calibrateCameraSet(const std::vector<std::vector<std::vector<MarkerInfo>>>& markersPerCamera, const std::vector<ModelInfo>& model,
+                                     const std::vector<int>& rigOfModel, const std::vector<CamInfo>& cameras, std::vector<ViewPose>& cameraPoses,
+                                     std::vector<int>& placed) {
+    const size_t nc = cameras.size();
+    if (nc < 2 || nc > (size_t)CTAG_MV_MAX_CAMERAS) throw __FUNCTION__ + std::string(", ") + "2 to 8 cameras\n";
+    if (markersPerCamera.size() != nc) throw __FUNCTION__ + std::string(", ") + "one list of instants per camera\n";
+    const size_t nf = markersPerCamera[0].size();
+    if (nf == 0) throw __FUNCTION__ + std::string(", ") + "no instants\n";
+    if (rigOfModel.size() != model.size()) throw __FUNCTION__ + std::string(", ") + "one rig entry per model\n";
+    int n_rigs = 1;
+    for (int g : rigOfModel) n_rigs = g + 1 > n_rigs ? g + 1 : n_rigs;
+    std::vector<ctag_frame_result> recs(nc * nf);  // camera-major
+    std::vector<ctag_camera> cams(nc);
+    for (size_t c = 0; c < nc; c++) {
+        if (markersPerCamera[c].size() != nf) throw __FUNCTION__ + std::string(", ") + "every camera has the same instants\n";
+        cams[c] = make_camera(cameras[c]);
+        for (size_t f = 0; f < nf; f++) {
+            const std::vector<MarkerInfo>& list = markersPerCamera[c][f];
+            ctag_frame_result& r = recs[c * nf + f];
+            for (const MarkerInfo& mi : list)
+                if (mi.cornerLists.size() > (size_t)CTAG_MAX_FEATURES) throw __FUNCTION__ + std::string(", ") + "a marker with more than 100 features\n";
+            if (flatten(list, 0, r) != list.size()) throw __FUNCTION__ + std::string(", ") + "an instant with more markers or features than a detection record holds\n";
+            if (r.n_markers == 0) r.status = CTAG_NO_FEATURE;  // detect() left the list empty
+        }
+    }
+    ctag_model* in = make_model(model, __FUNCTION__);
+    ctag_rigs* rigs = nullptr;
+    int st = ctag_rigs_create(in, rigOfModel.data(), n_rigs, &rigs);
+    if (st != CTAG_OK) {
+        ctag_model_free(in);
+        throw __FUNCTION__ + std::string(", ") + "illegal rig set\n";
+    }
+    ctag_camera_fit_stat stat;
+    std::vector<ctag_camera_fit_cam_stat> cam_stats(nc);
+    ctag_camera_set* set = nullptr;
+    st = ctag_camera_fit(h_, recs.data(), (int)nc, (int)nf, in, rigs, cams.data(), nullptr, &set, &stat, cam_stats.data());
+    ctag_rigs_free(rigs);
+    ctag_model_free(in);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    if (set) ctag_camera_set_free(set);
+    cameraPoses.assign(nc, ViewPose());
+    placed.assign(nc, 0);
+    for (size_t c = 0; c < nc; c++) {
+        placed[c] = cam_stats[c].status == CTAG_POSE_OK ? 1 : 0;
+#ifdef CTAG_WITH_OPENCV
+        cameraPoses[c].rvec = cv::Mat(3, 1, CV_64F);
+        cameraPoses[c].tvec = cv::Mat(3, 1, CV_64F);
+        double *pr = cameraPoses[c].rvec.ptr<double>(0), *pt = cameraPoses[c].tvec.ptr<double>(0);
+#else
+        double *pr = cameraPoses[c].rvec, *pt = cameraPoses[c].tvec;
+#endif
+        for (int i = 0; i < 3; i++) {
+            pr[i] = cam_stats[c].pose.rvec[i];
+            pt[i] = cam_stats[c].pose.tvec[i];
+        }
+    }
+    return stat.n_unplaced == 0 && stat.status == CTAG_POSE_OK;
+}
+
 void CylinderTag::saveModel(const std::string& path, const std::vector<ModelInfo>& model) {
     ctag_model* m = make_model(model, __FUNCTION__);
     const int st = ctag_model_save(m, path.c_str());

@@ -181,6 +181,15 @@ class CylinderTag {
     // -1 (they keep their corners): pass it, not rigOfModel, to estimateRigPose.  Throws std::string on error.
     void assembleRigModel(const std::vector<std::vector<MarkerInfo>>& framesOfMarkers, const std::vector<ModelInfo>& model,
                           const std::vector<int>& rigOfModel, CamInfo camera, std::vector<ModelInfo>& outModel, std::vector<int>& placedRigOfModel);
+    // Fit the poses of the cameras of a set from detections they share (new; include/ctag_pose.h, camera set fit: ctag_camera_fit with
+    // the defaults).  markersPerCamera[c][f] is what camera c's detect() returned at instant f -- the same f is the same instant in every
+    // camera -- while a rig of rigOfModel is carried through the volume the cameras watch; cameras[c] are the intrinsics, which stay as
+    // given.  cameraPoses[c] is camera c's pose in the frame of the anchor camera (the lowest-numbered camera that shares enough instants
+    // with another; its pose is zero): what estimateMultiViewRigPose takes.  placed[c] is 0 for a camera the instants never linked to the
+    // others (its pose is zero and means nothing).  Returns whether every camera was placed.  Throws std::string on error.
+    bool calibrateCameraSet(const std::vector<std::vector<std::vector<MarkerInfo>>>& markersPerCamera, const std::vector<ModelInfo>& model,
+                            const std::vector<int>& rigOfModel, const std::vector<CamInfo>& cameras, std::vector<ViewPose>& cameraPoses,
+                            std::vector<int>& placed);
     // Write a model list in the text format loadModel reads (CylinderTag.cpp:168-188), floats with 9 significant digits: loadModel gives
     // back the same values bit for bit.  Throws std::string when the file cannot be written.
     void saveModel(const std::string& path, const std::vector<ModelInfo>& model);

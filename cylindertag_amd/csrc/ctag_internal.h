@@ -23,6 +23,8 @@ struct ctag_handle;
 struct ctag_camera;
 struct ctag_pose_rec;
 struct ctag_rig_pose_rec;
+struct ctag_mv_pose_rec;
+struct ctag_camera_set;
 
 namespace ctag {
 // A device buffer the library's host code owns: pointer and capacity in elements.  grow() frees, then allocates (the old contents are gone); the
@@ -375,8 +377,8 @@ void build_pick_table(uint8_t* table, uint16_t* table16);  // kPickN*20*10 bytes
 
 
 // accessor of the opaque handle for the state of its back ends, each created on first use: the pose back end (k_pose.hip), the overlay (k_draw.hip),
-// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip), the multi-view rig poses (k_mv_pose.hip), the pose covariance (k_pose_cov.hip), the model reconstruction (k_model_fit.hip) and the rig assembly (k_rig_fit.hip), whose states are both a fit::Timed of ctag_fit_host.h.  ctag_destroy frees them in this order.
-enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kCovState, kFitState, kRigFitState, kNumSiblingStates };
+// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip), the multi-view rig poses (k_mv_pose.hip), the pose covariance (k_pose_cov.hip), the model reconstruction (k_model_fit.hip) the rig assembly (k_rig_fit.hip) and the camera set fit (k_cam_fit.hip), whose states are each a fit::Timed of ctag_fit_host.h.  ctag_destroy frees them in this order.
+enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kCovState, kFitState, kRigFitState, kCamFitState, kNumSiblingStates };
 void** handle_state_slot(struct ::ctag_handle* h, SiblingState which, void (*free_fn)(void*));
 // the model's device copies on `device` (k_pose.hip); the camera's distortion model is one the pose back end handles
 int model_to_device(struct ::ctag_model* m, int device);
@@ -426,6 +428,15 @@ int mfit_pass_records();  // observation records one pass of its workspace holds
 int rfit_probe_system(struct ::ctag_handle* h, const ctag_frame_result* results, int n_frames, const struct ::ctag_rig_pose_rec* recs,
                       const struct ::ctag_model* model, const struct ::ctag_rigs* rigs, const struct ::ctag_camera* camera, int rig, double lambda,
                       int pass_records, double* S, double* g, double* delta, int32_t* n_unknowns, int32_t* bad_pivot);
+// The reduced system of the camera set fit at a caller-given state (k_cam_fit.hip; the probe of libctag_testkit.so): n_cameras x n_frames host detection
+// records camera-major, the n_frames x n_rigs host multi-view records over them under `cams` (the CTAG_POSE_OK ones with n_cameras >= 2 are the
+// observations), camera `anchor` of the set dropped -> *n_unknowns = N = 6 x the set's cameras, S [N x N], g [N], delta [N] and whether a pivot was
+// not positive; pass_records > 0 sets how many records one pass of the workspace holds.  Waits.
+int cfit_probe_system(struct ::ctag_handle* h, const ctag_frame_result* results, int n_frames, const struct ::ctag_mv_pose_rec* recs,
+                      const struct ::ctag_model* model, const struct ::ctag_rigs* rigs, const struct ::ctag_camera_set* cams, int anchor, double lambda,
+                      int pass_records, double* S, double* g, double* delta, int32_t* n_unknowns, int32_t* bad_pivot);
+int cfit_record_grid();   // k_cfit_record's grid
+int cfit_pass_records();  // observation records one pass of its workspace holds
 int rfit_record_grid();   // k_rfit_record's grid
 int rfit_pass_records();  // observation records one pass of its workspace holds
 // the part of ctag_gather_end behind the payload all-gather: segment table of a `world`-rank job + unpack kernels on the

@@ -890,4 +890,6 @@ __device__ __forceinline__ void mv_point_residual(const double* R, const double*
 // ctag_camera_set (opaque in include/ctag_pose.h)
 struct ctag_camera_set {
     ctag::MvCams dev;
+    ctag_camera cameras[CTAG_MV_MAX_CAMERAS];  // what the set was created from, for ctag_camera_set_get: entries 0 .. dev.n - 1
+    ctag_camera_pose poses[CTAG_MV_MAX_CAMERAS];
 };

@@ -280,8 +280,20 @@ int ctag_camera_set_create(const ctag_camera* cameras, const ctag_camera_pose* p
             zero = zero && poses[src].rvec[i] == 0.0 && poses[src].tvec[i] == 0.0;
         }
         d.at_reference[c] = zero ? 1 : 0;
+        s->cameras[c] = cameras[src];
+        s->poses[c] = poses[src];
     }
     *out = s;
+    return CTAG_OK;
+}
+
+int ctag_camera_set_get(const ctag_camera_set* s, int* n_cameras, ctag_camera* cameras, ctag_camera_pose* poses) {
+    if (!s || !n_cameras) return CTAG_ERR_ARG;
+    *n_cameras = s->dev.n;
+    for (int c = 0; c < s->dev.n; c++) {
+        if (cameras) cameras[c] = s->cameras[c];
+        if (poses) poses[c] = s->poses[c];
+    }
     return CTAG_OK;
 }
 

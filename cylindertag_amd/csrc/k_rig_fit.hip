@@ -15,7 +15,7 @@
 //             (other rigs' records skipped by a block-uniform branch), subtracts Z_a^T Z_b and adds Jm^T Jm on the diagonal blocks;
 //             g the same way.  The running sums live in global memory between passes of the record workspace, so the result does not
 //             depend on the pass size;
-//   solve     k_rfit_solve: one block per rig, the damped system (S + lambda diag S) as a packed lower triangle in LDS (at most
+//   solve     k_fit_solve<96> (ctag_fit_solve.h): one block per rig, the damped system (S + lambda diag S) as a packed lower triangle in LDS (at most
 //             96 x 97 / 2 doubles, 37 KB), right-looking Cholesky, the dropped rows (the anchor's) as identity rows with a zero
 //             right-hand side, the two triangular solves, delta and a flag for a pivot that is not positive.
 // The host decides (initial assembly, accept / reject, lambda, stop) per rig between the launches.  FP64 VALU like the pose kernels;
@@ -35,6 +35,7 @@
 
 #include "../../include/ctag_pose.h"
 #include "ctag_fit_host.h"
+#include "ctag_fit_solve.h"
 #include "ctag_internal.h"
 #include "ctag_pose_dev.h"
 #include "ctag_schur6.h"
@@ -52,7 +53,6 @@ constexpr int kRfitSlots = CTAG_RIG_FIT_MAX_MODELS;  // member slots of a record
 constexpr int kRfitDoubles = 63;          // per member slot of a record: Z (36), Jm^T Jm (21, upper triangle in row order), g (6)
 constexpr int kRfitN = 6 * kRfitSlots;    // 96: row stride of S, delta and g
 constexpr int kRfitMaxPts = CTAG_RIG_MAX_POINTS;
-constexpr int kRfitSolveThreads = 256;
 // flags of a record: kRecLeftOut (it does not describe its detection record: never for records k_rig_solve wrote) and kRecSingular
 
 struct RfitLds {
@@ -259,71 +259,6 @@ __global__ __launch_bounds__(256) void k_rfit_assemble(const double* __restrict_
     if (is_s && i != j) S[(size_t)rig * NN + (size_t)j * kRfitN + i] = acc;
 }
 
-// (S + lambda diag S) delta = -g of rig blockIdx.x by Cholesky over its first N = 6 n_slots[rig] rows, the rows of model slot
-// drop[rig] as identity rows with a zero right-hand side.  bad[rig] = 1 and delta = 0 for a pivot that is not positive.
-__global__ __launch_bounds__(kRfitSolveThreads) void k_rfit_solve(const double* __restrict__ S, const double* __restrict__ g, const int32_t* __restrict__ n_slots,
-                                                                  const int32_t* __restrict__ drop, const double* __restrict__ lambda,
-                                                                  const int32_t* __restrict__ active, double* __restrict__ delta, int32_t* __restrict__ bad) {
-    __shared__ double A[kRfitN * (kRfitN + 1) / 2], rhs[kRfitN], z[kRfitN], diag[kRfitN];
-    const int rig = blockIdx.x, tid = threadIdx.x;
-    if (!active[rig]) return;  // block-uniform
-    const int N = 6 * min(max(n_slots[rig], 0), kRfitSlots), dr = drop[rig];
-    const double* Sm = S + (size_t)rig * kRfitN * kRfitN;
-    const double lam = lambda[rig];
-    auto at = [](int i, int k) { return i * (i + 1) / 2 + k; };  // k <= i
-    for (int e = tid; e < N * N; e += kRfitSolveThreads) {
-        const int i = e / N, k = e - i * N;
-        if (k > i) continue;
-        double v;
-        if (i / 6 == dr || k / 6 == dr) v = i == k ? 1.0 : 0.0;
-        else {
-            v = Sm[(size_t)i * kRfitN + k];
-            if (i == k) v += lam * v;
-        }
-        A[at(i, k)] = v;
-    }
-    for (int i = tid; i < N; i += kRfitSolveThreads) rhs[i] = i / 6 == dr ? 0.0 : -g[(size_t)rig * kRfitN + i];
-    __syncthreads();
-    bool ok = true;
-    for (int j = 0; j < N; j++) {
-        const double d = A[at(j, j)];           // written before the last barrier; not written again
-        if (!(d > 0.0) || !ctl::finite64(d)) {  // the same in every thread
-            ok = false;
-            break;
-        }
-        const double sd = ctm::sqrt64(d);
-        if (tid == 0) diag[j] = sd;
-        for (int i = j + 1 + tid; i < N; i += kRfitSolveThreads) A[at(i, j)] /= sd;
-        __syncthreads();
-        for (int i = j + 1 + (tid >> 4); i < N; i += kRfitSolveThreads / 16) {  // row i of the trailing block, 16 threads along the row
-            const double lij = A[at(i, j)];
-            for (int k = j + 1 + (tid & 15); k <= i; k += 16) A[at(i, k)] -= lij * A[at(k, j)];
-        }
-        __syncthreads();
-    }
-    if (!ok) {
-        for (int i = tid; i < kRfitN; i += kRfitSolveThreads) delta[(size_t)rig * kRfitN + i] = 0.0;
-        if (tid == 0) bad[rig] = 1;
-        return;
-    }
-    for (int j = 0; j < N; j++) {  // L z = rhs, column by column
-        const double zj = rhs[j] / diag[j];
-        __syncthreads();  // every thread has read rhs[j]
-        if (tid == 0) z[j] = zj;
-        for (int i = j + 1 + tid; i < N; i += kRfitSolveThreads) rhs[i] -= A[at(i, j)] * zj;
-        __syncthreads();
-    }
-    for (int j = N - 1; j >= 0; j--) {  // L^T delta = z, row j of L is column j of L^T
-        const double dj = z[j] / diag[j];
-        __syncthreads();
-        if (tid == 0) rhs[j] = dj;
-        for (int k = tid; k < j; k += kRfitSolveThreads) z[k] -= A[at(j, k)] * dj;
-        __syncthreads();
-    }
-    for (int i = tid; i < kRfitN; i += kRfitSolveThreads) delta[(size_t)rig * kRfitN + i] = (i < N && i / 6 != dr) ? rhs[i] : 0.0;
-    if (tid == 0) bad[rig] = 0;
-}
-
 }  // namespace ctag
 
 // =====================================================================================================
@@ -389,7 +324,7 @@ struct RfitWork : fit::Systems {
 
     int solve(const std::vector<double>& lambda, const std::vector<int32_t>& active, int bad_flags, std::vector<double>& delta, std::vector<int32_t>& bad) {
         return Systems::solve(c, lambda, active, bad_flags, delta, bad, [&]() {
-            hipLaunchKernelGGL(ctag::k_rfit_solve, dim3(n_groups), dim3(ctag::kRfitSolveThreads), 0, c.s, d_S.p, d_g.p, d_n_slots.p, d_drop.p, d_lambda.p, d_active.p,
+            hipLaunchKernelGGL(ctag::k_fit_solve<ctag::kRfitN>, dim3(n_groups), dim3(ctag::kFitSolveThreads), 0, c.s, d_S.p, d_g.p, d_n_slots.p, d_drop.p, d_lambda.p, d_active.p,
                                d_delta.p, d_bad.p);
         });
     }

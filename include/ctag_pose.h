@@ -502,6 +502,101 @@ int ctag_rig_fit(ctag_handle* h, const ctag_frame_result* results, int n_frames,
 /* device time of the last assembly's kernels by kind (needs CTAG_OPT_TIMING), milliseconds: marker pose, rig pose, record + assemble, solve */
 int ctag_rig_fit_last_ms(ctag_handle* h, float* out4);
 
+/* ---- camera set fit: the poses of the cameras of a set, from detections they share (k_cam_fit.hip) -----------------------------------
+ * The multi-view call takes a ctag_camera_set; this call makes one.  Two to CTAG_MV_MAX_CAMERAS cameras with known intrinsics watch
+ * one working volume; frame f of every camera is the same instant, and a rig of the rig set is carried through the volume.  The call
+ * returns every camera's pose in the frame of one of them, the anchor.  The problem over camera poses AND the rig's pose at every
+ * instant separates: given the camera poses an instant's rig pose is the solve ctag_mv_rig_pose_batch_device already does, so only the
+ * camera poses are optimised, by Levenberg-Marquardt on the cost with the rig poses eliminated (the Schur complement on the 6x6 pose
+ * blocks).  Intrinsics are an input and stay as given.  One problem per call.
+ *   1. Per-camera rig poses.  ctag_rig_pose_batch_device runs once per camera, on that camera's records with its intrinsics, before
+ *      the first round.  The record of (instant f, rig g) -- an item -- counts for the start in camera c when it is CTAG_POSE_OK with
+ *      n_points >= min_points (a lone 4-corner marker ends in its mirrored minimum nine times in ten: DESIGN.md section 16).
+ *   2. Initial assembly, on the host in double, from those records (R_c, t_c of the item in camera c).  n(a,b) = the number of items
+ *      counted in both cameras a and b.  Anchor = the lowest camera index with any n(a,.) >= min_items.  A tree grows from it:
+ *      repeatedly the unplaced camera b with the largest n(a,b) to a placed camera a is added with parent a (ties: the lowest b, then
+ *      the lowest a) until no such count reaches min_items.  The edge X_b = E X_a has as rotation Rbar, the rotation nearest (SVD,
+ *      determinant fixed) to the sum, in item order, of R_b R_a^T, and as translation the mean, in item order, of t_b - Rbar t_a;
+ *      T_b = E o T_a.  The reference frame is the anchor camera's: its pose is exactly zero in the output and is never updated.
+ *      Cameras the tree does not reach are unplaced: they leave the call (the multi-view solves of rules 3-4 run on the placed
+ *      cameras only) and get status CTAG_POSE_NOT_SEEN and a zero pose; cam_stats carry the caller's camera indices.  Without an
+ *      anchor the call's status is CTAG_POSE_NOT_SEEN and every camera is unplaced.
+ *   3. Observation set.  The items whose ctag_mv_pose_rec on the initial set is CTAG_POSE_OK with n_cameras >= 2.  The set is fixed
+ *      for the call.  The cost of a state = the sum, in item order, of the cost fields ctag_mv_rig_pose_batch_device gives those items
+ *      under that state's camera set; stat.cost is that sum on the returned set byte for byte (the set made by
+ *      ctag_camera_set_create from the placed cameras' intrinsics and cam_stats' poses, in camera order), cost_init the sum on the
+ *      initial set.
+ *   4. A round is Levenberg-Marquardt on the 6 (n_placed - 1) unknowns.  Update of camera c by d = (w, v) in its own frame:
+ *      Rc <- Exp(w) Rc, tc <- Exp(w) tc + v (Exp the Rodrigues formula; the state is (rvec, tvec), rvec by the inverse formula).  Per
+ *      point of camera c with Q = Rc (R X + t) + tc: Jc = (dr/dQ) [-[Q]x | I], Jp the point's derivative in the rig pose's
+ *      (rvec, tvec) as stage 2 of the multi-view section forms it.  Per record: U = sum Jp^T Jp = L L^T, y = L^-1 sum Jp^T r,
+ *      Z_c = L^-1 sum_{i in c} Jp^T Jc;  S_cc += sum Jc^T Jc - Z_c^T Z_c,  S_cd -= Z_c^T Z_d,  g_c += sum Jc^T r - Z_c^T y;  the
+ *      anchor's rows are dropped.  The step solves (S + lambda diag S) d = -g by Cholesky; a pivot that is not positive is a reject.
+ *      The trial is accepted iff the cost of rule 3 decreases; lambda <- max(lambda / 3, 1e-9) on accept, 4 lambda on reject.  A
+ *      trial in which an observation record stops being CTAG_POSE_OK is a reject.  The call stops when an accepted round lowers the
+ *      cost by less than rel_tol * cost, when lambda exceeds lambda_max, or after max_rounds; max_rounds = 0 returns the initial set.
+ *   5. Determinism.  Every sum has a fixed order: record order across records, wave_sum_f64's tree inside one (lane l of one
+ *      wavefront owns points l, l + 64, ... of the record).  Two calls return the same bytes, and the result does not depend on the
+ *      pass size of the workspace or on the grid.
+ *   6. CTAG_ERR_ARG: a null argument (a null entry of results_dev included), n_frames < 1, n_cameras outside
+ *      2 .. CTAG_MV_MAX_CAMERAS, max_rounds < 0, min_items < 1, min_points < 1, lambda0 / lambda_max / rel_tol that are not positive
+ *      and finite, a model whose model_size is not the handle's dictionary's column count or is above 20, a `rigs` made for another
+ *      n_models; CTAG_ERR_UNSUPPORTED: a camera the pose back end does not handle.
+ * Device memory of one call: the rig-pose records of one camera and the multi-view records, 63 doubles (Z 36, Jc^T Jc 21, g 6) per
+ * camera slot -- 4032 bytes per observation record of a pass, at most 512 records a pass -- and 48 x 48 doubles for S. */
+typedef struct ctag_camera_fit_opts {
+    int32_t max_rounds;   /* default 30 */
+    int32_t min_items;    /* default 2: (instant, rig) items a camera pair must share to become a tree edge */
+    int32_t min_points;   /* default 8: a per-camera rig record counts for the start only from this many points */
+    int32_t reserved;     /* 0 */
+    double lambda0;       /* default 1e-3 */
+    double lambda_max;    /* default 1e6 */
+    double rel_tol;       /* default 6.14e-13: 4 x the relative cost change a one-ulp change of a camera pose causes through the inner solves (1.535e-13) */
+} ctag_camera_fit_opts;   /* 40 bytes */
+
+typedef struct ctag_camera_fit_stat {     /* one per call */
+    int32_t status;       /* CTAG_POSE_OK or CTAG_POSE_NOT_SEEN (no anchor) */
+    int32_t anchor;       /* camera index, -1 without one */
+    int32_t n_placed;     /* cameras with a pose, the anchor included */
+    int32_t n_unplaced;   /* cameras left out (rule 2) */
+    int32_t n_records;    /* observation records (rule 3) */
+    int32_t n_points;     /* correspondences of those records */
+    int32_t rounds;       /* rounds taken (accepted + rejected) */
+    int32_t reserved;     /* 0 */
+    double cost_init;     /* cost of the initial set */
+    double cost;          /* cost of the returned set */
+    double lambda;        /* lambda when the call stopped */
+    double rms_px;        /* sqrt(2 cost / n_points) */
+} ctag_camera_fit_stat;   /* 64 bytes */
+
+typedef struct ctag_camera_fit_cam_stat { /* one per camera */
+    int32_t status;       /* CTAG_POSE_OK (placed) or CTAG_POSE_NOT_SEEN */
+    int32_t parent;       /* rule 2's tree, a camera index; -1 for the anchor and an unplaced camera */
+    int32_t n_items_with_parent;
+    int32_t n_records;    /* observation records in which the camera has points */
+    int32_t n_points;     /* its correspondences in them */
+    int32_t reserved;     /* 0 */
+    ctag_camera_pose pose; /* X_cam = R(rvec) X_anchor + tvec; exactly 0 for the anchor and for an unplaced camera */
+} ctag_camera_fit_cam_stat; /* 72 bytes */
+
+void ctag_camera_fit_opts_default(ctag_camera_fit_opts* opts);
+/* results_dev: HOST array of n_cameras DEVICE pointers, n_frames records each (the multi-view call's layout); cameras: n_cameras
+ * intrinsics.  *out: a new camera set (ctag_camera_set_free) when every camera is placed, NULL otherwise -- the call still returns
+ * CTAG_OK and the placed poses are in cam_stats; *out is NULL after every error too.  stat: one HOST record, cam_stats: n_cameras
+ * HOST records.  opts == NULL means the defaults.  Waits for completion: the outer loop decides on the host. */
+int ctag_camera_fit_device(ctag_handle* h, const ctag_frame_result* const* results_dev, int n_cameras, int n_frames, const ctag_model* model,
+                           const ctag_rigs* rigs, const ctag_camera* cameras, const ctag_camera_fit_opts* opts, ctag_camera_set** out,
+                           ctag_camera_fit_stat* stat, ctag_camera_fit_cam_stat* cam_stats);
+/* The same from n_cameras x n_frames HOST records, camera-major (record c * n_frames + f): uploads them, then ctag_camera_fit_device. */
+int ctag_camera_fit(ctag_handle* h, const ctag_frame_result* results, int n_cameras, int n_frames, const ctag_model* model, const ctag_rigs* rigs,
+                    const ctag_camera* cameras, const ctag_camera_fit_opts* opts, ctag_camera_set** out, ctag_camera_fit_stat* stat,
+                    ctag_camera_fit_cam_stat* cam_stats);
+/* device time of the last fit's kernels by kind (needs CTAG_OPT_TIMING), milliseconds: per-camera rig pose, multi-view pose, record + assemble, solve */
+int ctag_camera_fit_last_ms(ctag_handle* h, float* out4);
+/* Reads a camera set back: *n_cameras, and the intrinsics and poses it was created from (either array may be NULL; each holds
+ * CTAG_MV_MAX_CAMERAS entries at most, n_cameras are written).  Host only. */
+int ctag_camera_set_get(const ctag_camera_set* s, int* n_cameras, ctag_camera* cameras, ctag_camera_pose* poses);
+
 /* ---- overlay: CylinderTag::drawAxis (reference CylinderTag.cpp:211-246) ------------------------------------------------
  * Output: 8-bit, 3 channels, every channel = the gray value (cvtColor GRAY2RGB), then per drawn record, in record order,
  * what the reference paints with OpenCV 4.5.3 (k_draw.hip restates it):

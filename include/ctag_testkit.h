@@ -158,6 +158,21 @@ int ctag_testkit_rig_fit_system(ctag_handle* h, const ctag_frame_result* results
 /* k_rfit_record's grid and the records a pass holds by default (host only): out[0], out[1]; returns 2 */
 int ctag_testkit_rig_fit_limits(int32_t* out, int capacity);
 
+/* ---- the reduced system of the camera set fit (cylindertag_amd/csrc/k_cam_fit.hip; include/ctag_pose.h, camera set fit) -------------------
+ * k_cfit_record, k_cfit_assemble and k_fit_solve<48> at a caller-given state instead of inside the fit's loop.  results: n_cameras x n_frames
+ * HOST detection records, camera-major (n_cameras is the set's); mv_poses: the n_frames x n_rigs HOST records
+ * ctag_mv_rig_pose_batch_device gives over them under `cams` -- the CTAG_POSE_OK ones with n_cameras >= 2 are the observation records
+ * (rule 3) and their rvec / tvec the state; lambda: the damping (any finite value: a negative one makes the system indefinite).  Camera c of
+ * the set owns the unknowns 6c .. 6c+5 (rotation, translation: rule 4), camera `anchor` is dropped; with N = 6 n_cameras: *n_unknowns = N,
+ * S [N][N] and g [N] as assembled over ALL cameras, delta [N] = the solution of (S + lambda diag S) delta = -g with the anchor's rows as
+ * identity rows (0 there), *bad_pivot = 1 when a pivot was not positive (delta is 0 then).  The arrays hold 48 x 48, 48 and 48 doubles.
+ * pass_records > 0: the workspace holds that many records a pass (rule 5); 0: the call's own size.  Runs on the handle's device and waits. */
+int ctag_testkit_camera_fit_system(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_mv_pose_rec* mv_poses,
+                                   const ctag_model* model, const ctag_rigs* rigs, const ctag_camera_set* cams, int anchor, double lambda,
+                                   int pass_records, double* S, double* g, double* delta, int32_t* n_unknowns, int32_t* bad_pivot);
+/* k_cfit_record's grid and the records a pass holds by default (host only): out[0], out[1]; returns 2 */
+int ctag_testkit_camera_fit_limits(int32_t* out, int capacity);
+
 /* ---- the kernel forms the library picks for a chunk (plan_chunk, cylindertag_amd/csrc/ctag_api.hip) ------------------
  * For `nframes` frames of rows x cols (gray, or BGR for channels == 3) at `frames` (only its alignment is looked at) with the given
  * strides, the handle options CTAG_OPT_FUSED_SWEEP (-1: not set), CTAG_OPT_WAVE_POINTS, CTAG_OPT_BGR_DIRECT, CTAG_OPT_EXPAND_EXACT,

@@ -25,7 +25,8 @@ SYNTH_SEED = 0x4354616753594E00  # "CTagSYN\0", SURVEY.md 8(d)
 EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
            "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model",
            "ctag_testkit_dense_edge_probe", "ctag_testkit_plan", "ctag_testkit_welsch_fit", "ctag_testkit_welsch_limits",
-           "ctag_testkit_model_fit_system", "ctag_testkit_model_fit_limits", "ctag_testkit_rig_fit_system", "ctag_testkit_rig_fit_limits"]
+           "ctag_testkit_model_fit_system", "ctag_testkit_model_fit_limits", "ctag_testkit_rig_fit_system", "ctag_testkit_rig_fit_limits",
+           "ctag_testkit_camera_fit_system", "ctag_testkit_camera_fit_limits"]
 # the fields ctag_testkit_plan writes, in order (cylindertag_amd/csrc/ctag_internal.h: ChunkPlan)
 PLAN_FIELDS = ("fused", "bgr_direct", "zero_first", "dec_zero_kernel", "dec_zero_list", "dec", "dec_xblocks", "dec_yblocks", "dec_band_rows", "dec_bands",
                "ccl", "latency", "small_cfg", "refprm", "mask_scan", "prescan", "all_wave", "fork", "pack_max", "big_points", "pack_gx", "scan_gx",
@@ -103,6 +104,10 @@ def load_library():
     L.ctag_testkit_rig_fit_system.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.POINTER(capi.CameraC), C.c_int, C.c_double, C.c_int, vp, vp, vp, i32p, i32p]
     L.ctag_testkit_rig_fit_limits.restype = C.c_int
     L.ctag_testkit_rig_fit_limits.argtypes = [i32p, C.c_int]
+    L.ctag_testkit_camera_fit_system.restype = C.c_int
+    L.ctag_testkit_camera_fit_system.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, i32p, i32p]
+    L.ctag_testkit_camera_fit_limits.restype = C.c_int
+    L.ctag_testkit_camera_fit_limits.argtypes = [i32p, C.c_int]
     _lib = L
     return L
 
@@ -122,6 +127,15 @@ def rig_fit_limits():
     n = load_library().ctag_testkit_rig_fit_limits(out.ctypes.data_as(C.POINTER(C.c_int32)), 2)
     if n != 2:
         raise RuntimeError("ctag_testkit_rig_fit_limits writes %d values" % n)
+    return {"record_grid": int(out[0]), "pass_records": int(out[1])}
+
+
+def camera_fit_limits():
+    """k_cfit_record's grid and the observation records one pass of the camera set fit's workspace holds (ctag_testkit_camera_fit_limits).  Host only."""
+    out = np.zeros(2, np.int32)
+    n = load_library().ctag_testkit_camera_fit_limits(out.ctypes.data_as(C.POINTER(C.c_int32)), 2)
+    if n != 2:
+        raise RuntimeError("ctag_testkit_camera_fit_limits writes %d values" % n)
     return {"record_grid": int(out[0]), "pass_records": int(out[1])}
 
 
@@ -305,6 +319,23 @@ class Detector(ca.Detector):
                                                 float(lam), int(pass_records), S.ctypes.data, g.ctypes.data, d.ctypes.data, C.byref(n), C.byref(bad))
         if st != 0:
             raise CtagError(st, "ctag_testkit_rig_fit_system")
+        N = int(n.value)
+        return {"S": S[:N * N].reshape(N, N).copy(), "g": g[:N].copy(), "delta": d[:N].copy(), "bad_pivot": bool(bad.value)}
+
+    def camera_fit_system(self, results, mv_poses, model, rigs, camera_set, anchor, lam, pass_records=0):
+        """The reduced system of the camera set fit at a given state (ctag_testkit_camera_fit_system): host detection records [camera][frame],
+        the MV_POSE_DT records over them under `camera_set` -> dict of S [N, N], g [N], delta [N] (N = 6 x the set's cameras, camera
+        `anchor`'s rows dropped), bad_pivot bool."""
+        res = np.ascontiguousarray(results)
+        assert res.dtype == ca.RESULT_DT and res.ndim == 2 and res.shape[0] == camera_set.n
+        recs = np.ascontiguousarray(mv_poses, ca.MV_POSE_DT).reshape(-1)
+        assert len(recs) == res.shape[1] * rigs.n_rigs
+        S, g, d = np.zeros(48 * 48), np.zeros(48), np.zeros(48)
+        n, bad = C.c_int32(), C.c_int32()
+        st = self.T.ctag_testkit_camera_fit_system(self.h, res.ctypes.data, res.shape[1], recs.ctypes.data, model.m, rigs.r, camera_set.s, int(anchor),
+                                                   float(lam), int(pass_records), S.ctypes.data, g.ctypes.data, d.ctypes.data, C.byref(n), C.byref(bad))
+        if st != 0:
+            raise CtagError(st, "ctag_testkit_camera_fit_system")
         N = int(n.value)
         return {"S": S[:N * N].reshape(N, N).copy(), "g": g[:N].copy(), "delta": d[:N].copy(), "bad_pivot": bool(bad.value)}
 

@@ -653,6 +653,18 @@ int ctag_testkit_rig_fit_limits(int32_t* out, int capacity) {
     return 2;
 }
 
+int ctag_testkit_camera_fit_system(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_mv_pose_rec* mv_poses,
+                                   const ctag_model* model, const ctag_rigs* rigs, const ctag_camera_set* cams, int anchor, double lambda,
+                                   int pass_records, double* S, double* g, double* delta, int32_t* n_unknowns, int32_t* bad_pivot) {
+    return cfit_probe_system(h, results, n_frames, mv_poses, model, rigs, cams, anchor, lambda, pass_records, S, g, delta, n_unknowns, bad_pivot);
+}
+
+int ctag_testkit_camera_fit_limits(int32_t* out, int capacity) {
+    const int32_t v[2] = {cfit_record_grid(), cfit_pass_records()};
+    if (out) std::memcpy(out, v, sizeof(int32_t) * (size_t)std::min(std::max(capacity, 0), 2));
+    return 2;
+}
+
 int ctag_testkit_plan(int rows, int cols, int adaptive_thresh, int nframes, int channels, int corner_subpix, const void* frames, ptrdiff_t frame_stride,
                       ptrdiff_t row_stride, int fuse_mode, int wave_points, int bgr_direct, int expand_exact, int32_t* out, int capacity) {
     // KParams of ctag_params_default as far as the plan reads them (threshold_line 1.8, threshold_expand 1.2, collinear_cost 1.05)
