@@ -34,7 +34,8 @@ POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag
                 "ctag_estimate_pose_cov", "ctag_estimate_rig_pose_cov", "ctag_estimate_mv_rig_pose_cov",
                 "ctag_model_fit_opts_default", "ctag_model_fit_device", "ctag_model_fit", "ctag_model_save", "ctag_model_fit_last_ms",
                 "ctag_rig_fit_opts_default", "ctag_rig_fit_device", "ctag_rig_fit", "ctag_rig_fit_last_ms",
-                "ctag_camera_fit_opts_default", "ctag_camera_fit_device", "ctag_camera_fit", "ctag_camera_fit_last_ms", "ctag_camera_set_get"]
+                "ctag_camera_fit_opts_default", "ctag_camera_fit_device", "ctag_camera_fit", "ctag_camera_fit_last_ms", "ctag_camera_set_get",
+                "ctag_intrinsics_fit_opts_default", "ctag_intrinsics_fit_device", "ctag_intrinsics_fit", "ctag_intrinsics_fit_last_ms"]
 # ... and include/ctag_gather.h
 GATHER_EXPORTS = ["ctag_shard_range", "ctag_packed_capacity", "ctag_pack_results", "ctag_unpack_results", "ctag_comm_unique_id",
                   "ctag_comm_init", "ctag_comm_attach", "ctag_comm_destroy", "ctag_comm_native", "ctag_comm_last_error", "ctag_gather_begin",
@@ -87,6 +88,13 @@ assert CAMERA_FIT_STAT_DT.itemsize == 64
 CAMERA_FIT_CAM_STAT_DT = np.dtype([("status", "<i4"), ("parent", "<i4"), ("n_items_with_parent", "<i4"), ("n_records", "<i4"), ("n_points", "<i4"),
                                    ("reserved", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
 assert CAMERA_FIT_CAM_STAT_DT.itemsize == 72
+# ctag_intrinsics_fit_stat: one record per intrinsics fit (include/ctag_pose.h); parameter order fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4
+INTR_PARAMS = 16
+INTR_PARAM_NAMES = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6", "s1", "s2", "s3", "s4")
+INTRINSICS_FIT_STAT_DT = np.dtype([("status", "<i4"), ("n_records", "<i4"), ("n_points", "<i4"), ("n_free", "<i4"), ("rounds", "<i4"), ("free_mask", "<u4"),
+                                   ("cost0", "<f8"), ("cost", "<f8"), ("lambda", "<f8"), ("rms_px", "<f8"), ("sigma2_hat", "<f8"), ("pose_cost", "<f8"),
+                                   ("sigma", "<f8", (INTR_PARAMS,))])
+assert INTRINSICS_FIT_STAT_DT.itemsize == 200
 
 
 class ParamsC(C.Structure):  # ctag_params (include/ctag_types.h): the reference's tunables
@@ -180,6 +188,22 @@ def camera_fit_opts(**fields):
     for k, v in fields.items():
         if k not in ("max_rounds", "min_items", "min_points", "lambda0", "lambda_max", "rel_tol"):
             raise TypeError("ctag_camera_fit_opts has no field %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class IntrinsicsFitOptsC(C.Structure):  # ctag_intrinsics_fit_opts
+    _fields_ = [("max_rounds", C.c_int32), ("min_points", C.c_int32), ("free_mask", C.c_uint32), ("tie_focal", C.c_int32), ("lambda0", C.c_double),
+                ("lambda_max", C.c_double), ("rel_tol", C.c_double)]
+
+
+def intrinsics_fit_opts(**fields):
+    """ctag_intrinsics_fit_opts_default, then the given fields."""
+    o = IntrinsicsFitOptsC()
+    load_library().ctag_intrinsics_fit_opts_default(C.byref(o))
+    for k, v in fields.items():
+        if k not in ("max_rounds", "min_points", "free_mask", "tie_focal", "lambda0", "lambda_max", "rel_tol"):
+            raise TypeError("ctag_intrinsics_fit_opts has no field %r" % k)
         setattr(o, k, v)
     return o
 
@@ -351,6 +375,14 @@ def load_library():
     L.ctag_camera_fit.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(CameraC), cfitp, C.POINTER(vp), vp, vp]
     L.ctag_camera_fit_last_ms.restype = C.c_int
     L.ctag_camera_fit_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    ifitp = C.POINTER(IntrinsicsFitOptsC)
+    L.ctag_intrinsics_fit_opts_default.restype = None
+    L.ctag_intrinsics_fit_opts_default.argtypes = [ifitp]
+    for fn in (L.ctag_intrinsics_fit_device, L.ctag_intrinsics_fit):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, C.c_int, vp, vp, C.POINTER(CameraC), ifitp, C.POINTER(CameraC), vp, vp]
+    L.ctag_intrinsics_fit_last_ms.restype = C.c_int
+    L.ctag_intrinsics_fit_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ctag_camera_set_get.restype = C.c_int
     L.ctag_camera_set_get.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(CameraC), C.POINTER(CameraPoseC)]
     u64p = C.POINTER(C.c_uint64)
@@ -967,6 +999,42 @@ class Detector:
         out = (C.c_float * 4)()
         self.L.ctag_camera_fit_last_ms(self.h, out)
         return dict(zip(("rig_pose", "mv_pose", "record", "solve"), (float(v) for v in out)))
+
+    # ---- intrinsics fit (include/ctag_pose.h): opts is an IntrinsicsFitOptsC (intrinsics_fit_opts(...)), or its fields as keywords
+    def _fit_intrinsics(self, fn, name, results_arg, n_frames, model, rigs, seed, opts, fields):
+        if fields:
+            if opts is not None:
+                raise TypeError("opts and option keywords together")
+            opts = intrinsics_fit_opts(**fields)
+        if rigs is None:  # every model a rig of its own
+            n_models = int(model.view()["ids"].size)
+            rigs = Rigs(model, np.arange(n_models, dtype=np.int32), n_models)
+        out = CameraC()
+        stat = np.zeros(1, INTRINSICS_FIT_STAT_DT)
+        poses = np.zeros(max(n_frames * rigs.n_rigs, 1), RIG_POSE_DT)
+        st = fn(self.h, results_arg, n_frames, model.m, rigs.r, C.byref(seed), C.byref(opts) if opts is not None else None, C.byref(out), stat.ctypes.data,
+                poses.ctypes.data)
+        if st != 0:
+            raise CtagError(st, name)
+        return out, stat[0], poses[:n_frames * rigs.n_rigs]
+
+    def fit_intrinsics(self, results, model, rigs, seed, opts=None, **fields):
+        """ctag_intrinsics_fit: host ctag_frame_result records of many views of rigs whose models are known, and a rough seed CameraC ->
+        (the fitted CameraC, one INTRINSICS_FIT_STAT_DT record with the parameters' sigmas, the RIG_POSE_DT records of every view under
+        it, record f * n_rigs + g).  rigs=None makes every model a rig of its own.  Waits."""
+        res = np.ascontiguousarray(results).reshape(-1)
+        assert res.dtype == RESULT_DT
+        return self._fit_intrinsics(self.L.ctag_intrinsics_fit, "ctag_intrinsics_fit", res.ctypes.data if len(res) else None, len(res), model, rigs, seed, opts, fields)
+
+    def fit_intrinsics_device(self, results_ptr, n_frames, model, rigs, seed, opts=None, **fields):
+        """ctag_intrinsics_fit_device: the same from n_frames result records in device memory (as detect_batch_device leaves them)."""
+        return self._fit_intrinsics(self.L.ctag_intrinsics_fit_device, "ctag_intrinsics_fit_device", results_ptr, n_frames, model, rigs, seed, opts, fields)
+
+    def intrinsics_fit_last_ms(self):
+        """Device milliseconds of the last intrinsics fit by kernel kind (needs OPT_TIMING): rig pose, view pose, record + assemble, solve."""
+        out = (C.c_float * 4)()
+        self.L.ctag_intrinsics_fit_last_ms(self.h, out)
+        return dict(zip(("rig_pose", "view_pose", "record", "solve"), (float(v) for v in out)))
 
     # ---- pose covariance (include/ctag_pose.h): opts is a CovOptsC (cov_opts(...)) or None for the defaults
     @staticmethod

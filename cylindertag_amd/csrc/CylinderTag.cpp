@@ -381,6 +381,54 @@ bool CylinderTag::calibrateCameraSet(const std::vector<std::vector<std::vector<M
     return stat.n_unplaced == 0 && stat.status == CTAG_POSE_OK;
 }
 
+// new: the camera's intrinsics from views of known rigs (include/ctag_pose.h, intrinsics fit)
+bool CylinderTag::calibrateCamera(const std::vector<std::vector<MarkerInfo>>& markersPerFrame, const std::vector<ModelInfo>& model, const std::vector<int>& rigOfModel,
+                                  CamInfo seed, CamInfo& camera, std::vector<double>* sigma, unsigned freeMask, bool tieFocal) {
+    if (markersPerFrame.empty()) throw __FUNCTION__ + std::string(", ") + "no frames\n";
+    std::vector<int> rig(rigOfModel);
+    if (rig.empty())
+        for (size_t m = 0; m < model.size(); m++) rig.push_back((int)m);
+    if (rig.size() != model.size()) throw __FUNCTION__ + std::string(", ") + "one rig entry per model\n";
+    int n_rigs = 1;
+    for (int g : rig) n_rigs = g + 1 > n_rigs ? g + 1 : n_rigs;
+    std::vector<ctag_frame_result> recs(markersPerFrame.size());
+    for (size_t f = 0; f < markersPerFrame.size(); f++) {
+        for (const MarkerInfo& mi : markersPerFrame[f])
+            if (mi.cornerLists.size() > (size_t)CTAG_MAX_FEATURES) throw __FUNCTION__ + std::string(", ") + "a marker with more than 100 features\n";
+        if (flatten(markersPerFrame[f], 0, recs[f]) != markersPerFrame[f].size())
+            throw __FUNCTION__ + std::string(", ") + "a frame with more markers or features than a detection record holds\n";
+        if (recs[f].n_markers == 0) recs[f].status = CTAG_NO_FEATURE;  // detect() left the list empty
+    }
+    ctag_model* in = make_model(model, __FUNCTION__);
+    ctag_rigs* rigs = nullptr;
+    int st = ctag_rigs_create(in, rig.data(), n_rigs, &rigs);
+    if (st != CTAG_OK) {
+        ctag_model_free(in);
+        throw __FUNCTION__ + std::string(", ") + "illegal rig set\n";
+    }
+    const ctag_camera cam0 = make_camera(seed);
+    ctag_intrinsics_fit_opts opts;
+    ctag_intrinsics_fit_opts_default(&opts);
+    opts.free_mask = freeMask;
+    opts.tie_focal = tieFocal ? 1 : 0;
+    ctag_camera cam;
+    ctag_intrinsics_fit_stat stat;
+    st = ctag_intrinsics_fit(h_, recs.data(), (int)recs.size(), in, rigs, &cam0, &opts, &cam, &stat, nullptr);
+    ctag_rigs_free(rigs);
+    ctag_model_free(in);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    camera = seed;
+#ifdef CTAG_WITH_OPENCV
+    camera.Intrinsic = cv::Mat(3, 3, CV_32F, cam.K).clone();  // float, as cameraParams.yml stores them
+    if (cam.n_dist > 0) camera.distCoeffs = cv::Mat(cam.n_dist, 1, CV_32F, cam.dist).clone();
+#else
+    std::memcpy(camera.Intrinsic, cam.K, sizeof(cam.K));
+    for (int i = 0; i < cam.n_dist; i++) camera.distCoeffs[(size_t)i] = cam.dist[i];
+#endif
+    if (sigma) sigma->assign(stat.sigma, stat.sigma + CTAG_INTR_PARAMS);
+    return stat.status == CTAG_POSE_OK;
+}
+
 void CylinderTag::saveModel(const std::string& path, const std::vector<ModelInfo>& model) {
     ctag_model* m = make_model(model, __FUNCTION__);
     const int st = ctag_model_save(m, path.c_str());

@@ -190,6 +190,18 @@ class CylinderTag {
     bool calibrateCameraSet(const std::vector<std::vector<std::vector<MarkerInfo>>>& markersPerCamera, const std::vector<ModelInfo>& model,
                             const std::vector<int>& rigOfModel, const std::vector<CamInfo>& cameras, std::vector<ViewPose>& cameraPoses,
                             std::vector<int>& placed);
+    // Fit the camera itself from views of rigs whose models are known (new; include/ctag_pose.h, intrinsics fit: ctag_intrinsics_fit with
+    // the defaults but freeMask and tieFocal).  markersPerFrame[f] is what detect() returned for view f of a sequence that carries a rig of
+    // rigOfModel (empty: every model a rig of its own) through the whole image at several distances and tilts; seed is a rough camera --
+    // the focal length off by several per cent, the principal point by tens of pixels, no distortion will do -- whose number of
+    // distortion coefficients is the result's.  camera is the fitted camera (its matrices are float, as cameraParams.yml stores them); sigma, if given, gets the sixteen standard deviations
+    // fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 (0 for a parameter that was not fitted): look at them, a single small marker cannot
+    // fix a principal point and they say so.  freeMask: bit i = parameter i is fitted, 0 = fx fy cx cy and every coefficient the seed
+    // has; tieFocal: fy = fx x (seed fy / seed fx).  Returns whether a camera was fitted (false: no usable view, too few points, or a
+    // degenerate set; camera is the seed then).  Models and rig layout stay as given: alternate with reconstructModel /
+    // assembleRigModel.  Throws std::string on error.
+    bool calibrateCamera(const std::vector<std::vector<MarkerInfo>>& markersPerFrame, const std::vector<ModelInfo>& model, const std::vector<int>& rigOfModel,
+                         CamInfo seed, CamInfo& camera, std::vector<double>* sigma = nullptr, unsigned freeMask = 0, bool tieFocal = false);
     // Write a model list in the text format loadModel reads (CylinderTag.cpp:168-188), floats with 9 significant digits: loadModel gives
     // back the same values bit for bit.  Throws std::string when the file cannot be written.
     void saveModel(const std::string& path, const std::vector<ModelInfo>& model);

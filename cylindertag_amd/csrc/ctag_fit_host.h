@@ -1,11 +1,12 @@
-// ctag_fit_host.h -- the host side that the three fits share (k_model_fit.hip: the corners of a model against marker poses;
+// ctag_fit_host.h -- the host side that the four fits share (k_model_fit.hip: the corners of a model against marker poses;
 // k_rig_fit.hip: the member transforms of a rig against rig poses; k_cam_fit.hip: the camera poses of a set against multi-view rig
-// poses, one group; nothing else includes it).  All minimise a reprojection cost over per-group unknowns (group = model / rig /
+// poses, one group; k_intr_fit.hip: the intrinsics of a camera against its own view poses, one group of 16 rows; nothing else
+// includes it).  All minimise a reprojection cost over per-group unknowns (group = model / rig /
 // the camera set) by Levenberg-Marquardt rounds on a Schur-reduced system: a pose pass, a record
 // kernel and an assemble kernel over the observation records, a damped solve per group, and a decision per group.  Stated here
 // once: the timed state on the handle, the context of a call, the working model, the systems on the device with their pass loop
 // and solve, and the LM bookkeeping with its constants and its decision.  Each fit keeps its kernels and its own round loop: the
-// three loops have the same shape (rebuild the systems if a trial was accepted, solve, make the trials, one pose pass, decide per
+// four loops have the same shape (rebuild the systems if a trial was accepted, solve, make the trials, one pose pass, decide per
 // group) and differ in what a trial and an accepted state are; stated once with five callbacks the loop came out longer than the
 // plain loops together (tried with the first two) and harder to follow, so the shape is repeated and everything the loops call is shared.
 #pragma once

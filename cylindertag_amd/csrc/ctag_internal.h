@@ -377,8 +377,8 @@ void build_pick_table(uint8_t* table, uint16_t* table16);  // kPickN*20*10 bytes
 
 
 // accessor of the opaque handle for the state of its back ends, each created on first use: the pose back end (k_pose.hip), the overlay (k_draw.hip),
-// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip), the multi-view rig poses (k_mv_pose.hip), the pose covariance (k_pose_cov.hip), the model reconstruction (k_model_fit.hip) the rig assembly (k_rig_fit.hip) and the camera set fit (k_cam_fit.hip), whose states are each a fit::Timed of ctag_fit_host.h.  ctag_destroy frees them in this order.
-enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kCovState, kFitState, kRigFitState, kCamFitState, kNumSiblingStates };
+// the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip), the multi-view rig poses (k_mv_pose.hip), the pose covariance (k_pose_cov.hip), the model reconstruction (k_model_fit.hip) the rig assembly (k_rig_fit.hip), the camera set fit (k_cam_fit.hip) and the intrinsics fit (k_intr_fit.hip), whose states are each a fit::Timed of ctag_fit_host.h.  ctag_destroy frees them in this order.
+enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kCovState, kFitState, kRigFitState, kCamFitState, kIntrFitState, kNumSiblingStates };
 void** handle_state_slot(struct ::ctag_handle* h, SiblingState which, void (*free_fn)(void*));
 // the model's device copies on `device` (k_pose.hip); the camera's distortion model is one the pose back end handles
 int model_to_device(struct ::ctag_model* m, int device);
@@ -435,6 +435,15 @@ int rfit_probe_system(struct ::ctag_handle* h, const ctag_frame_result* results,
 int cfit_probe_system(struct ::ctag_handle* h, const ctag_frame_result* results, int n_frames, const struct ::ctag_mv_pose_rec* recs,
                       const struct ::ctag_model* model, const struct ::ctag_rigs* rigs, const struct ::ctag_camera_set* cams, int anchor, double lambda,
                       int pass_records, double* S, double* g, double* delta, int32_t* n_unknowns, int32_t* bad_pivot);
+// the intrinsics fit's kernels at a caller-given state (k_intr_fit.hip; include/ctag_testkit.h says what each argument is).  Wait.
+int ifit_probe_system(struct ::ctag_handle* h, const ctag_frame_result* results, int n_frames, const struct ::ctag_rig_pose_rec* recs,
+                      const struct ::ctag_model* model, const struct ::ctag_rigs* rigs, const struct ::ctag_camera* camera, uint32_t free_mask, int tie_focal,
+                      double lambda, int pass_records, double* S, double* g, double* delta, int32_t* n_free, int32_t* bad_pivot);
+int ifit_probe_poses(struct ::ctag_handle* h, const ctag_frame_result* results, int n_frames, const struct ::ctag_rig_pose_rec* recs,
+                     const struct ::ctag_model* model, const struct ::ctag_rigs* rigs, const struct ::ctag_camera* camera, struct ::ctag_rig_pose_rec* out,
+                     int32_t* usable);
+int ifit_record_grid();   // k_ifit_record's and k_ifit_pose's grid
+int ifit_pass_records();  // observation records one pass of its workspace holds
 int cfit_record_grid();   // k_cfit_record's grid
 int cfit_pass_records();  // observation records one pass of its workspace holds
 int rfit_record_grid();   // k_rfit_record's grid

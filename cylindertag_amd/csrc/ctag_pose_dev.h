@@ -5,8 +5,8 @@
 // of a point as a policy (one camera: camera_residual; a camera per point: k_mv_pose.hip); pose_solve is the two in a row.
 // Generic over the LDS capacity PTS and the block width NT: per-point loops stride over the NT lanes, while every sum over
 // the points stays with its one owner lane (lane < 144 / 34), so the result is the sequential evaluation for any n <= PTS.
-// k_pose_cov.hip (the covariance of a finished pose), k_model_fit.hip and k_rig_fit.hip read the correspondence rule, the corner
-// loader, the residuals, the point descriptor and load_state6 from here.
+// k_pose_cov.hip (the covariance of a finished pose), k_model_fit.hip, k_rig_fit.hip, k_cam_fit.hip and k_intr_fit.hip read the
+// correspondence rule, the corner loaders, the residuals, the point descriptor and load_state6 from here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -203,8 +203,19 @@ __device__ __forceinline__ void corner_point(const PoseCam& cam, const float* __
     X[2] = (double)cp[2];
 }
 
+// the same corner as detected: its raw pixel uv[2], never undistorted, and the model point X[3] (the intrinsics fit, k_intr_fit.hip)
+__device__ __forceinline__ void corner_pixel(const float* __restrict__ corners, const ctag_feature_rec& F, int pos, int q, double* uv, double* X) {
+    const int k = q < 2 ? q : q < 4 ? q + 2 : q < 6 ? q - 2 : q;  // 0 1 4 5 2 3 6 7
+    uv[0] = (double)F.corners[2 * k];
+    uv[1] = (double)F.corners[2 * k + 1];
+    const float* cp = corners + (pos * 8 + k) * 3;
+    X[0] = (double)cp[0];
+    X[1] = (double)cp[1];
+    X[2] = (double)cp[2];
+}
+
 // Where a point of a record comes from, in one word, for the kernels that walk a record once and visit its points afterwards
-// (k_pose_cov.hip, k_model_fit.hip, k_rig_fit.hip): feature index in its frame record (7 bits) | corner q of the emit << 7 (3 bits) |
+// (k_pose_cov.hip, k_model_fit.hip, k_rig_fit.hip, k_cam_fit.hip, k_intr_fit.hip): feature index in its frame record (7 bits) | corner q of the emit << 7 (3 bits) |
 // camera << 10 (3 bits) | model position << 13 (positions are below 2^16)
 static_assert(CTAG_MAX_FEATURES <= 128 && CTAG_MV_MAX_CAMERAS <= 8, "the point descriptor's bit fields");
 __device__ __forceinline__ int32_t point_desc(int feature, int q, int cam, int pos) { return feature | (q << 7) | (cam << 10) | (pos << 13); }

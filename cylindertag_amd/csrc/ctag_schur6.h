@@ -1,6 +1,7 @@
 // ctag_schur6.h -- the 6x6 pose block of a Schur complement, as the record kernels that eliminate a record's pose use it
 // (k_model_fit.hip: corners against marker poses; k_rig_fit.hip: member transforms against rig poses; k_cam_fit.hip: camera poses
-// against multi-view rig poses): the sums of U = sum Jp^T Jp
+// against multi-view rig poses; k_intr_fit.hip: a camera's intrinsics against its view poses, which sums U in LDS and takes chol6,
+// forward6 and forward6_dot from here): the sums of U = sum Jp^T Jp
 // and sum Jp^T r over a record's points (k_pose_cov.hip sums the same U), U = L L^T, y = L^-1 sum Jp^T r, a column through L^-1 and
 // the point Jacobian.  Every accumulator sees its additions in the order written here: the fits' results are held byte for byte.
 #pragma once

@@ -597,6 +597,108 @@ int ctag_camera_fit_last_ms(ctag_handle* h, float* out4);
  * CTAG_MV_MAX_CAMERAS entries at most, n_cameras are written).  Host only. */
 int ctag_camera_set_get(const ctag_camera_set* s, int* n_cameras, ctag_camera* cameras, ctag_camera_pose* poses);
 
+/* ---- intrinsics fit: the camera itself, from detections of rigs whose models are known (k_intr_fit.hip) ------------------------------
+ * Every pose call takes a ctag_camera; this call makes one from a rough seed.  A rig of the rig set (a one-marker rig is the special
+ * case) is shown to ONE camera in many views; models and rig layout are inputs and stay as given.  The problem over the camera AND the
+ * rig's pose in every view separates: given the camera a view's pose is a 6-parameter minimisation of its own, so only the camera's
+ * parameters are optimised, by Levenberg-Marquardt on the cost with the view poses eliminated (the Schur complement on the 6x6 pose
+ * blocks).  Parameter i of CTAG_INTR_PARAMS: fx fy cx cy = K[0] K[4] K[2] K[5], then dist[0..11] = k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4.
+ *   1. Observations.  ctag_rig_pose_batch_device runs once under the SEED camera; its records, in record order f * n_rigs + g, are the
+ *      seed pass.  A record is an observation when it is CTAG_POSE_OK with n_points >= min_points.  Its members, correspondences and
+ *      point order are that record's (member_mask, the builder's order), and the set is fixed for the whole call.  The image point of
+ *      a correspondence is the feature's corner AS DETECTED (float pixels), never undistorted.
+ *   2. Cost: the forward reprojection error, what a camera calibration minimises.  Per point with P = R X + t, x = P0/P2, y = P1/P2,
+ *      r2 = x^2 + y^2: rad = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3),
+ *        xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2) + s1 r2 + s2 r2^2,   yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y + s3 r2 + s4 r2^2,
+ *        r = (fx xd + cx - u, fy yd + cy - v)                          (cv::projectPoints' model without tilt, as the overlay has it);
+ *      cost of a record = 0.5 sum |r|^2, cost of a state = the record costs summed in record order.  It is NOT the sum of the pose
+ *      calls' cost fields: PoseBA's residual lives in the undistorted image, which shrinks or grows with the very coefficients being
+ *      fitted (a camera that maps everything towards one point would win), and its observations are rounded to float, so that cost is
+ *      not smooth in the camera.  stat.pose_cost is that sum all the same, byte for byte, over the observation records of ONE
+ *      ctag_rig_pose_batch_device call under the returned camera -- for comparison only.  A point with P2 <= 0, a rational
+ *      denominator that is not positive, or a value that is not finite makes the state unusable.
+ *   3. Working camera.  ctag_camera is float32: a trial is formed in double (camera + delta) and rounded to float, and the cost that
+ *      is compared and reported is the cost of exactly those floats, read back as every pose call reads a ctag_camera.  n_dist is the
+ *      seed's; coefficients at or beyond n_dist are zero and cannot be free (CTAG_ERR_ARG).  K's other entries are the seed's.  A
+ *      trial whose fx or fy is not positive and finite is unusable.
+ *   4. View poses.  Given the camera, a record's pose is the minimiser of rule 2's cost over its own (rvec, tvec), additive in those six
+ *      numbers (CTAG_COV_PARAM_RVEC's parametrisation), found by damped Gauss-Newton from the record's accepted pose (in round 0 the
+ *      seed pass's): (U + mu diag U) d = -sum Jp^T r by Cholesky; mu starts at 1e-4, mu / 3 after an accepted step (the cost fell),
+ *      4 mu after a rejected one (cost not lower, unusable trial, pivot not positive); at most 40 steps; it stops after an accepted
+ *      step that lowers the cost by less than 1e-15 of it, at a cost of exactly 0, and when mu passes 1e8.  There is no EPnP restart:
+ *      a restart moves small records between minima from one trial to the next (case (e)).  A record whose
+ *      start is unusable makes the state unusable.
+ *   5. A round.  At the accepted state, per point Jp (2 x 6, in rvec, tvec) and Jc (2 x 16, analytic; with tie_focal the fx column is
+ *      dr/dfx + ratio dr/dfy, ratio = seed fy / seed fx).  Per record: U = sum Jp^T Jp = L L^T, Z = L^-1 sum Jp^T Jc,
+ *      y = L^-1 sum Jp^T r, S_r = sum Jc^T Jc - Z^T Z, g_r = sum Jc^T r - Z^T y; S and g are the sums over the records in record
+ *      order.  The step solves (S + lambda diag S) delta = -g over the free rows by Cholesky (fixed parameters are identity rows); a
+ *      pivot that is not positive is a reject.  Trial = camera + delta (rule 3; a tied fy = ratio x the new fx), then the view poses
+ *      (rule 4, from the accepted poses), then the cost.  The trial is accepted iff it is usable and its cost is lower;
+ *      lambda <- max(lambda / 3, 1e-9) on accept, 4 lambda on reject.  The call stops when an accepted round lowers the cost by less
+ *      than rel_tol x cost, when lambda exceeds lambda_max, or after max_rounds; max_rounds = 0 returns the seed with the view poses
+ *      of rule 4 under it.
+ *   6. Result.  *out is the accepted camera.  poses_out (n_frames x n_rigs, may be NULL): an observation's record carries the final
+ *      rvec / tvec / cost under rule 2 with rvec0 / tvec0 / cost0 (and every other field) the seed pass's; every other record is the
+ *      seed pass's unchanged.  stat.cost is the sum of the observations' cost fields in record order, cost0 the same after round 0's
+ *      view poses under the seed.  sigma2_hat = 2 cost / (2 n_points - 6 n_records - n_free); sigma[i] = sqrt(sigma2_hat (S^-1)_ii)
+ *      from the undamped S at the returned state over the free rows, on the host in double; 0 for a fixed parameter, ratio x
+ *      sigma[fx] for a tied fy; all 0 when the system at the returned state cannot be formed or factored (a record flagged there, a
+ *      pivot that is not positive).  A weak data set shows in them: a single marker cannot fix a principal point.
+ *      Status: CTAG_POSE_NOT_SEEN (no observation), CTAG_POSE_TOO_FEW (2 n_points - 6 n_records <= n_free), CTAG_POSE_DEGENERATE (the
+ *      seed state is unusable, or the undamped S has a pivot that is not positive at the start); *out is the seed in all three, and
+ *      poses_out the seed pass.
+ *   7. Determinism.  Every sum has a fixed order: record order across records; inside a record the points in point order for the
+ *      sums of rule 5 (one owner lane per entry), lane l's points l, l + 64, ... then wave_sum_f64's tree for rule 4.  Two calls on
+ *      the same input return the same bytes, and the result does not depend on the pass size of the workspace or on the grid.
+ *   8. CTAG_ERR_ARG: a null argument (poses_out excepted), n_frames < 1, max_rounds < 0, min_points < 1, lambda0 / lambda_max / rel_tol
+ *      that are not positive and finite, a free_mask bit at or above CTAG_INTR_PARAMS or on a coefficient at or beyond the seed's
+ *      n_dist, no free parameter, a model whose model_size is not the handle's dictionary's column count or is above 20, a `rigs`
+ *      made for another n_models; CTAG_ERR_UNSUPPORTED: a seed the pose back end does not handle; CTAG_ERR_LIMIT: n_frames x
+ *      CTAG_MAX_MARKERS above 2^30 or n_frames x n_rigs above 2^28, and for the host entry n_frames above 2^24.
+ * Out of scope: tilt terms, several cameras in one call, fitting models or layout together with the camera (alternate with
+ * ctag_model_fit / ctag_rig_fit).  Device memory of one call: two sets of rig pose records, 152 doubles per observation record of a
+ * pass (at most 512 records a pass), 16 x 16 doubles for S. */
+#define CTAG_INTR_PARAMS 16
+
+typedef struct ctag_intrinsics_fit_opts {
+    int32_t max_rounds;   /* default 30 */
+    int32_t min_points;   /* default 8: a rig record with fewer points is no observation */
+    uint32_t free_mask;   /* bit i: parameter i is fitted; 0 = fx fy cx cy and the first min(seed n_dist, 12) coefficients */
+    int32_t tie_focal;    /* != 0: fy = fx * (seed fy / seed fx), one unknown; bit 1 of free_mask is ignored */
+    double lambda0;       /* default 1e-3 */
+    double lambda_max;    /* default 1e6 */
+    double rel_tol;       /* default 7.71e-9: 4 x the relative cost change a one-ulp move of one camera field causes at a returned state (1.928e-9) */
+} ctag_intrinsics_fit_opts; /* 40 bytes */
+
+typedef struct ctag_intrinsics_fit_stat {  /* one per call */
+    int32_t status;       /* CTAG_POSE_OK, _NOT_SEEN, _TOO_FEW or _DEGENERATE (rule 6) */
+    int32_t n_records;    /* observation records (rule 1) */
+    int32_t n_points;     /* correspondences of those records */
+    int32_t n_free;       /* unknowns of the camera */
+    int32_t rounds;       /* rounds taken (accepted + rejected) */
+    uint32_t free_mask;   /* the mask in use: the default resolved, bit 1 cleared under tie_focal */
+    double cost0;         /* cost under the seed, view poses by rule 4 */
+    double cost;          /* cost of the returned camera */
+    double lambda;        /* lambda when the call stopped */
+    double rms_px;        /* sqrt(2 cost / n_points) */
+    double sigma2_hat;    /* rule 6 */
+    double pose_cost;     /* rule 2: the pose back end's own cost under the returned camera, for comparison */
+    double sigma[CTAG_INTR_PARAMS]; /* rule 6, in parameter order */
+} ctag_intrinsics_fit_stat; /* 200 bytes */
+
+void ctag_intrinsics_fit_opts_default(ctag_intrinsics_fit_opts* opts);
+/* results_dev: n_frames detection records in DEVICE memory.  out, stat: HOST; poses_out: n_frames x n_rigs HOST records or NULL.
+ * opts == NULL means the defaults.  Waits for completion: the outer loop decides on the host. */
+int ctag_intrinsics_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, int n_frames, const ctag_model* model, const ctag_rigs* rigs,
+                               const ctag_camera* seed, const ctag_intrinsics_fit_opts* opts, ctag_camera* out, ctag_intrinsics_fit_stat* stat,
+                               ctag_rig_pose_rec* poses_out);
+/* The same from HOST records: uploads them, then ctag_intrinsics_fit_device. */
+int ctag_intrinsics_fit(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_model* model, const ctag_rigs* rigs,
+                        const ctag_camera* seed, const ctag_intrinsics_fit_opts* opts, ctag_camera* out, ctag_intrinsics_fit_stat* stat,
+                        ctag_rig_pose_rec* poses_out);
+/* device time of the last fit's kernels by kind (needs CTAG_OPT_TIMING), milliseconds: rig pose, view pose, record + assemble, solve */
+int ctag_intrinsics_fit_last_ms(ctag_handle* h, float* out4);
+
 /* ---- overlay: CylinderTag::drawAxis (reference CylinderTag.cpp:211-246) ------------------------------------------------
  * Output: 8-bit, 3 channels, every channel = the gray value (cvtColor GRAY2RGB), then per drawn record, in record order,
  * what the reference paints with OpenCV 4.5.3 (k_draw.hip restates it):

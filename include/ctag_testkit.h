@@ -173,6 +173,23 @@ int ctag_testkit_camera_fit_system(ctag_handle* h, const ctag_frame_result* resu
 /* k_cfit_record's grid and the records a pass holds by default (host only): out[0], out[1]; returns 2 */
 int ctag_testkit_camera_fit_limits(int32_t* out, int capacity);
 
+/* ---- the intrinsics fit's kernels at a caller-given state (cylindertag_amd/csrc/k_intr_fit.hip; include/ctag_pose.h, intrinsics fit) -----------
+ * results: n_frames HOST detection records; poses: n_frames x n_rigs HOST rig pose records -- the CTAG_POSE_OK ones are the observation
+ * records and their rvec / tvec the state.
+ * ctag_testkit_intrinsics_fit_system: k_ifit_record, k_ifit_assemble and k_ifit_solve at (camera, poses): S [16 x 16], g [16] over all sixteen
+ * parameters (with tie_focal the fx row and column carry the tied fy), delta [16] of (S + lambda diag S) delta = -g over the free rows
+ * (0 elsewhere; any finite lambda: a negative one makes the system indefinite), *n_free and whether a pivot was not positive.  free_mask and
+ * tie_focal as ctag_intrinsics_fit_opts has them; pass_records > 0 sets how many records one pass of the workspace holds.
+ * ctag_testkit_intrinsics_fit_poses: k_ifit_pose (rule 4) alone from the records' poses under `camera`: out gets the n_frames x n_rigs
+ * records with rvec, tvec and cost of the observation records replaced, *usable = every observation record could be evaluated.  Both wait. */
+int ctag_testkit_intrinsics_fit_system(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_rig_pose_rec* poses,
+                                       const ctag_model* model, const ctag_rigs* rigs, const ctag_camera* camera, uint32_t free_mask, int tie_focal,
+                                       double lambda, int pass_records, double* S, double* g, double* delta, int32_t* n_free, int32_t* bad_pivot);
+int ctag_testkit_intrinsics_fit_poses(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_rig_pose_rec* poses,
+                                      const ctag_model* model, const ctag_rigs* rigs, const ctag_camera* camera, ctag_rig_pose_rec* out, int32_t* usable);
+/* the record and pose kernels' grid and the records a pass holds by default (host only): out[0], out[1]; returns 2 */
+int ctag_testkit_intrinsics_fit_limits(int32_t* out, int capacity);
+
 /* ---- the kernel forms the library picks for a chunk (plan_chunk, cylindertag_amd/csrc/ctag_api.hip) ------------------
  * For `nframes` frames of rows x cols (gray, or BGR for channels == 3) at `frames` (only its alignment is looked at) with the given
  * strides, the handle options CTAG_OPT_FUSED_SWEEP (-1: not set), CTAG_OPT_WAVE_POINTS, CTAG_OPT_BGR_DIRECT, CTAG_OPT_EXPAND_EXACT,

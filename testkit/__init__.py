@@ -26,7 +26,8 @@ EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_unpack_gathered"
            "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model",
            "ctag_testkit_dense_edge_probe", "ctag_testkit_plan", "ctag_testkit_welsch_fit", "ctag_testkit_welsch_limits",
            "ctag_testkit_model_fit_system", "ctag_testkit_model_fit_limits", "ctag_testkit_rig_fit_system", "ctag_testkit_rig_fit_limits",
-           "ctag_testkit_camera_fit_system", "ctag_testkit_camera_fit_limits"]
+           "ctag_testkit_camera_fit_system", "ctag_testkit_camera_fit_limits",
+           "ctag_testkit_intrinsics_fit_system", "ctag_testkit_intrinsics_fit_poses", "ctag_testkit_intrinsics_fit_limits"]
 # the fields ctag_testkit_plan writes, in order (cylindertag_amd/csrc/ctag_internal.h: ChunkPlan)
 PLAN_FIELDS = ("fused", "bgr_direct", "zero_first", "dec_zero_kernel", "dec_zero_list", "dec", "dec_xblocks", "dec_yblocks", "dec_band_rows", "dec_bands",
                "ccl", "latency", "small_cfg", "refprm", "mask_scan", "prescan", "all_wave", "fork", "pack_max", "big_points", "pack_gx", "scan_gx",
@@ -108,6 +109,13 @@ def load_library():
     L.ctag_testkit_camera_fit_system.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, i32p, i32p]
     L.ctag_testkit_camera_fit_limits.restype = C.c_int
     L.ctag_testkit_camera_fit_limits.argtypes = [i32p, C.c_int]
+    L.ctag_testkit_intrinsics_fit_system.restype = C.c_int
+    L.ctag_testkit_intrinsics_fit_system.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.POINTER(capi.CameraC), C.c_uint32, C.c_int, C.c_double, C.c_int, vp, vp, vp,
+                                                     i32p, i32p]
+    L.ctag_testkit_intrinsics_fit_poses.restype = C.c_int
+    L.ctag_testkit_intrinsics_fit_poses.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.POINTER(capi.CameraC), vp, i32p]
+    L.ctag_testkit_intrinsics_fit_limits.restype = C.c_int
+    L.ctag_testkit_intrinsics_fit_limits.argtypes = [i32p, C.c_int]
     _lib = L
     return L
 
@@ -136,6 +144,16 @@ def camera_fit_limits():
     n = load_library().ctag_testkit_camera_fit_limits(out.ctypes.data_as(C.POINTER(C.c_int32)), 2)
     if n != 2:
         raise RuntimeError("ctag_testkit_camera_fit_limits writes %d values" % n)
+    return {"record_grid": int(out[0]), "pass_records": int(out[1])}
+
+
+def intrinsics_fit_limits():
+    """The grid of k_ifit_record / k_ifit_pose and the observation records one pass of the intrinsics fit's workspace holds
+    (ctag_testkit_intrinsics_fit_limits).  Host only."""
+    out = np.zeros(2, np.int32)
+    n = load_library().ctag_testkit_intrinsics_fit_limits(out.ctypes.data_as(C.POINTER(C.c_int32)), 2)
+    if n != 2:
+        raise RuntimeError("ctag_testkit_intrinsics_fit_limits writes %d values" % n)
     return {"record_grid": int(out[0]), "pass_records": int(out[1])}
 
 
@@ -338,6 +356,38 @@ class Detector(ca.Detector):
             raise CtagError(st, "ctag_testkit_camera_fit_system")
         N = int(n.value)
         return {"S": S[:N * N].reshape(N, N).copy(), "g": g[:N].copy(), "delta": d[:N].copy(), "bad_pivot": bool(bad.value)}
+
+    def intrinsics_fit_system(self, results, rig_poses, model, rigs, camera, lam, free_mask=0, tie_focal=0, pass_records=0):
+        """The reduced system of the intrinsics fit at a given state (ctag_testkit_intrinsics_fit_system): host detection records, the
+        RIG_POSE_DT records over them (the CTAG_POSE_OK ones are the observations, their rvec / tvec the view poses) and the camera ->
+        dict of S [16, 16], g [16], delta [16], n_free, bad_pivot bool."""
+        res = np.ascontiguousarray(results).reshape(-1)
+        assert res.dtype == ca.RESULT_DT
+        recs = np.ascontiguousarray(rig_poses, ca.RIG_POSE_DT).reshape(-1)
+        assert len(recs) == len(res) * rigs.n_rigs
+        S, g, d = np.zeros((16, 16)), np.zeros(16), np.zeros(16)
+        n, bad = C.c_int32(), C.c_int32()
+        st = self.T.ctag_testkit_intrinsics_fit_system(self.h, res.ctypes.data, len(res), recs.ctypes.data, model.m, rigs.r, C.byref(camera), int(free_mask),
+                                                       int(tie_focal), float(lam), int(pass_records), S.ctypes.data, g.ctypes.data, d.ctypes.data, C.byref(n),
+                                                       C.byref(bad))
+        if st != 0:
+            raise CtagError(st, "ctag_testkit_intrinsics_fit_system")
+        return {"S": S, "g": g, "delta": d, "n_free": int(n.value), "bad_pivot": bool(bad.value)}
+
+    def intrinsics_fit_poses(self, results, rig_poses, model, rigs, camera):
+        """Rule 4 of the intrinsics fit alone (ctag_testkit_intrinsics_fit_poses): every CTAG_POSE_OK record's view pose under `camera`,
+        started from the record's own -> (RIG_POSE_DT records with rvec, tvec, cost replaced, usable bool)."""
+        res = np.ascontiguousarray(results).reshape(-1)
+        assert res.dtype == ca.RESULT_DT
+        recs = np.ascontiguousarray(rig_poses, ca.RIG_POSE_DT).reshape(-1)
+        assert len(recs) == len(res) * rigs.n_rigs
+        out = np.zeros(len(recs), ca.RIG_POSE_DT)
+        usable = C.c_int32()
+        st = self.T.ctag_testkit_intrinsics_fit_poses(self.h, res.ctypes.data, len(res), recs.ctypes.data, model.m, rigs.r, C.byref(camera), out.ctypes.data,
+                                                      C.byref(usable))
+        if st != 0:
+            raise CtagError(st, "ctag_testkit_intrinsics_fit_poses")
+        return out, bool(usable.value)
 
     def dense_edge_probe(self, gray, segments, K, dist, rvec, tvec, samples_per_edge=8, search_px=3.0, min_contrast=8.0):
         """Edge search of the dense pose-refinement study on the device (ctag_testkit_dense_edge_probe): segments [n, 12]

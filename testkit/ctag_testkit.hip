@@ -659,6 +659,23 @@ int ctag_testkit_camera_fit_system(ctag_handle* h, const ctag_frame_result* resu
     return cfit_probe_system(h, results, n_frames, mv_poses, model, rigs, cams, anchor, lambda, pass_records, S, g, delta, n_unknowns, bad_pivot);
 }
 
+int ctag_testkit_intrinsics_fit_system(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_rig_pose_rec* poses,
+                                       const ctag_model* model, const ctag_rigs* rigs, const ctag_camera* camera, uint32_t free_mask, int tie_focal,
+                                       double lambda, int pass_records, double* S, double* g, double* delta, int32_t* n_free, int32_t* bad_pivot) {
+    return ifit_probe_system(h, results, n_frames, poses, model, rigs, camera, free_mask, tie_focal, lambda, pass_records, S, g, delta, n_free, bad_pivot);
+}
+
+int ctag_testkit_intrinsics_fit_poses(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_rig_pose_rec* poses,
+                                      const ctag_model* model, const ctag_rigs* rigs, const ctag_camera* camera, ctag_rig_pose_rec* out, int32_t* usable) {
+    return ifit_probe_poses(h, results, n_frames, poses, model, rigs, camera, out, usable);
+}
+
+int ctag_testkit_intrinsics_fit_limits(int32_t* out, int capacity) {
+    const int32_t v[2] = {ifit_record_grid(), ifit_pass_records()};
+    if (out) std::memcpy(out, v, sizeof(int32_t) * (size_t)std::min(std::max(capacity, 0), 2));
+    return 2;
+}
+
 int ctag_testkit_camera_fit_limits(int32_t* out, int capacity) {
     const int32_t v[2] = {cfit_record_grid(), cfit_pass_records()};
     if (out) std::memcpy(out, v, sizeof(int32_t) * (size_t)std::min(std::max(capacity, 0), 2));
