@@ -269,6 +269,24 @@ CTM_HD float exp32_nonpos(float x) {
     return e * bits_to_f32((uint32_t)((int)k + 127) << 23);
 #endif
 }
+// exp32_nonpos where its range reduction does nothing.  For x <= 0, not NaN: true exactly when exp32_nonpos's k = rint(x log2e) is zero -- the product
+// below is the very one exp32_nonpos rounds, and rint of a value in [-0.5, 0] is -0 (the tie at -0.5 goes to the even neighbour, which is -0).  It also
+// says x >= -87 (x log2e >= -0.5 puts x above -0.35).
+CTM_HD bool exp32_k_is_zero(float x) { return x * 1.44269502162933349609375f >= -0.5f; }
+// exp32_nonpos(x) for an x with exp32_k_is_zero(x): the same polynomial in the same order with r = x; no range test, no rint, no Cody-Waite products,
+// no ldexp.  Equal bits: k = +-0 makes both of exp32_nonpos's products k ln2_hi and k ln2_lo +-0, so its r = (x - +-0) - +-0 == x and its scale is
+// ldexp(e, 0) = e * 2^0 = e.  The one argument whose r differs is x = -0.0, where exp32_nonpos has r = (-0 - -0) - -0 = +0.0: p r is then +-0, r r is +0,
+// (p r r + r) is +-0 and e = +-0 + 1 = 1.0f with either sign.  tests/test_exp32_k0_cpu.py holds it against exp32_nonpos over every float of the binades
+// around the boundary and every 64th below.
+CTM_HD float exp32_nonpos_k0(float x) {
+    const float r = x;
+    float p = 1.3933733571320772171020508e-03f;
+    p = p * r + 8.3632357418537139892578125e-03f;
+    p = p * r + 4.1666463017463684082031250e-02f;
+    p = p * r + 1.6666576266288757324218750e-01f;
+    p = p * r + 0.5f;
+    return (p * (r * r) + r) + 1.0f;
+}
 // Several quotients with ONE denominator (the five moments over their weight in fitLine and in edgeRefine): IEEE division, so a / d
 // on the host; on the device the compiler's own expansion of a double division -- v_rcp_f64, two Newton steps on the reciprocal, then
 // per numerator q = a r, e = a - d q, q + e r (correctly rounded: it is the sequence v_div_fmas / v_div_fixup finish) -- with the

@@ -1,4 +1,4 @@
-// ctag_wave.h -- what the kernels say to the wave itself, each stated once: the ordering points that are cheaper than __syncthreads(), the DPP lane moves
+// ctag_wave.h -- what the kernels say to the wave itself, each stated once: the ordering points that are cheaper than __syncthreads(), the vote, the DPP lane moves
 // and the reductions / scans built from them, and the packed 16-bit min / max.  Device only (gfx9, 64-wide wavefronts); every function is one or a few
 // instructions and is inlined.
 #pragma once
@@ -29,6 +29,12 @@ __device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_A
 // Wait for every vector-memory access the wave has issued (vmcnt(0)) and for nothing else: placed by hand where the compiler's own wait would come later
 // and in a worse place (k_edge_refine_sums).
 __device__ __forceinline__ void vmem_wait() { __builtin_amdgcn_s_waitcnt(0x0f70); }
+
+// ---- votes ----------------------------------------------------------------------------------------------------------------------------------------------
+// True when `p` holds on EVERY ACTIVE lane of the wave: one v_cmp into a scalar pair (the ballot of !p has no bit set) and a scalar compare, so a branch on
+// it is a scalar branch -- the whole wave takes one side.  Nothing is waited for.  Lanes that are inactive where it is called -- they left the loop, or sit in
+// the other side of a divergent branch -- do not vote: a ballot carries no bit for them.  With no lane active it is true.
+__device__ __forceinline__ bool wave_all(bool p) { return __builtin_amdgcn_ballot_w64(!p) == 0ull; }
 
 // ---- DPP lane moves: a v_mov_b32 with a data-parallel-primitive control, one vector instruction, no LDS crossbar round trip -----------------------
 // (A __shfl is a ds_bpermute_b32: address arithmetic, the instruction and ~100 cycles before the value can be used.)

@@ -177,13 +177,33 @@ __device__ __forceinline__ void welsch_first_fit(const Pts pts, const Picks pick
     }
     moments_to_line(x, y, x2, y2, xy, w, line);
 }
+// The Welsch weight exp32_nonpos(a), a = -(r c)^2.  A point less than ~1.76 px from the restart's line has a >= -0.35, where exp32_nonpos's k is 0 and its
+// range reduction, its flush below -87 and its ldexp do nothing (ctag_math.h: exp32_k_is_zero, exp32_nonpos_k0) -- and the points of an edge were admitted
+// within 1.8 / 1.2 px of a line.  So the WAVE votes: when every active lane's argument is that small all of them take the bare polynomial, else all take the
+// general form; a scalar branch, the same bits on either side.  (Per lane the test would only add exec-mask code.)  Lanes that have left the point loop --
+// a shorter edge, a restart that has ended -- are inactive here and do not vote.
+// COUNT (developer aid, CTAG_QUAD_STAMPS): the wave's trips by side, each counted on the first active lane.
+struct WeightTrips {
+    unsigned fast = 0, general = 0;
+};
+template <bool COUNT>
+__device__ __forceinline__ float welsch_weight(float a, WeightTrips& trips) {
+    const bool fast = wave_all(ctm::exp32_k_is_zero(a));
+    if constexpr (COUNT) {
+        const bool first = (int)__lane_id() == __ffsll((unsigned long long)__ballot(1)) - 1;
+        trips.fast += first && fast ? 1u : 0u;
+        trips.general += first && !fast ? 1u : 0u;
+    }
+    if (fast) return ctm::exp32_nonpos_k0(a);
+    return ctm::exp32_nonpos(a);
+}
 // IRLS iterations it0, it0 + 1, ... of one restart from `line` (the body of fitLine2D's inner loop).  Returns true when the restart has ENDED -- converged,
 // err < EPS, or 30 iterations -- with (line, err) as the reference leaves them; returns false at iteration it_stop, AFTER that iteration's convergence test
 // has failed: the caller goes on later (on any lane) with welsch_rounds(.., it0 = it_stop, resume = true), which skips the test it already knows the
 // outcome of -- so neither the previous line nor err has to travel.  it_stop = 30: to the end.
 // wc: this lane's column of a [rows][WS] float array in LDS (element j at wc[j * WS]) for the weights of the first `ncache` points between the two passes.
-template <int WS, class Pts>
-__device__ __forceinline__ bool welsch_rounds(const Pts pts, int n, double EPS, float* line, double& err, int it0, int it_stop, bool resume, float* wc, int ncache) {
+template <int WS, bool COUNT, class Pts>
+__device__ __forceinline__ bool welsch_rounds(const Pts pts, int n, double EPS, float* line, double& err, int it0, int it_stop, bool resume, float* wc, int ncache, WeightTrips& trips) {
     float prev[4] = {0.f, 0.f, 0.f, 0.f};
     const float c = 1 / 2.9846f;
 #ifdef CTAG_WELSCH_MINERR_IN_LOOP
@@ -224,26 +244,26 @@ __device__ __forceinline__ bool welsch_rounds(const Pts pts, int n, double EPS, 
         // (the point after the last is requested too and never used: the staged rows and the cluster pool are padded by one element, which
         // spares every trip the clamp of its index -- v_min_i32, sign extension and a 64-bit address per point and pass)
         float2 pn0 = pts(min(0, n - 1));  // next point, loaded one trip ahead
-        CTAG_PRAGMA(unroll CTAG_WUNROLL)
+        // (the three loops that vote are not unrolled: a loop with a wave vote in it cannot be given a remainder loop, and the kernel's time was flat in
+        // CTAG_WUNROLL)
         for (int j = 0; j < ncache; j++) {
             const float2 p = pn0;
             pn0 = pts(j + 1);
             const float x = p.x - lx, y = p.y - ly;
             const float r = ctm::fabs32(nx * x + ny * y);
             err += r;
-            const float wj = ctm::exp32_nonpos(-r * r * c * c);
+            const float wj = welsch_weight<COUNT>(-r * r * c * c, trips);
             wc[j * WS] = wj;
             sum_w += wj;
         }
         float2 pn1 = pts(min(ncache, n - 1));  // next point, loaded one trip ahead
-        CTAG_PRAGMA(unroll CTAG_WUNROLL)
         for (int j = ncache; j < n; j++) {
             const float2 p = pn1;
             pn1 = pts(j + 1);
             const float x = p.x - lx, y = p.y - ly;
             const float r = ctm::fabs32(nx * x + ny * y);
             err += r;
-            sum_w += ctm::exp32_nonpos(-r * r * c * c);
+            sum_w += welsch_weight<COUNT>(-r * r * c * c, trips);
         }
 #ifdef CTAG_WELSCH_MINERR_IN_LOOP
         if (err < berr) {
@@ -272,13 +292,12 @@ __device__ __forceinline__ bool welsch_rounds(const Pts pts, int n, double EPS, 
                 w += wj;
             }
             float2 pn3 = pts(min(ncache, n - 1));  // next point, loaded one trip ahead
-            CTAG_PRAGMA(unroll CTAG_WUNROLL)
             for (int j = ncache; j < n; j++) {
                 const float2 p = pn3;
                 pn3 = pts(j + 1);
                 const float px = p.x, py = p.y;
                 const float r = ctm::fabs32(nx * (px - lx) + ny * (py - ly));
-                const float wj = (float)(ctm::exp32_nonpos(-r * r * c * c) * inv);
+                const float wj = (float)(welsch_weight<COUNT>(-r * r * c * c, trips) * inv);
                 x += wj * px;
                 y += wj * py;
                 x2 += wj * px * px;
@@ -319,12 +338,12 @@ __device__ __forceinline__ void restart_store(float* res, int rstride, const flo
 }
 // One whole Welsch restart (the body of fitLine2D's `for k` loop) on one lane; with res = wc and rstride = WS the result lands in the lane's own
 // weight column, which is dead by then (needs kWCap >= 6).
-template <int WS, class Pts, class Picks>
-__device__ __forceinline__ void welsch_restart(const Pts pts, int n, const Picks picks, int npick, double EPS, float* res, int rstride, float* wc) {
+template <int WS, bool COUNT, class Pts, class Picks>
+__device__ __forceinline__ void welsch_restart(const Pts pts, int n, const Picks picks, int npick, double EPS, float* res, int rstride, float* wc, WeightTrips& trips) {
     float line[4];
     double err = 0;
     welsch_first_fit(pts, picks, npick, line);
-    (void)welsch_rounds<WS>(pts, n, EPS, line, err, 0, 30, false, wc, min(n, kWCap));
+    (void)welsch_rounds<WS, COUNT>(pts, n, EPS, line, err, 0, 30, false, wc, min(n, kWCap), trips);
     restart_store(res, rstride, line, err);
 }
 
@@ -2212,7 +2231,13 @@ struct WelschLds {
     int cnt[kWB];
 };
 
-template <int MODE>  // 0: float pairs in LDS, 1: packed words in LDS, 2: global memory
+// developer aid (CTAG_QUAD_STAMPS): the wave trips of the weight evaluations by side (welsch_weight), stamps 27 and 28
+__device__ __forceinline__ void welsch_trips_add(const QuadPtrs& P, const WeightTrips& trips) {
+    if (trips.fast) atomicAdd(&P.stamps[27], (unsigned long long)trips.fast);
+    if (trips.general) atomicAdd(&P.stamps[28], (unsigned long long)trips.general);
+}
+
+template <int MODE, bool COUNT>  // MODE 0: float pairs in LDS, 1: packed words in LDS, 2: global memory; COUNT: P.stamps is set, count the weight trips
 __device__ __forceinline__ void welsch_block_run(const QuadPtrs& P, WelschLds& S, int frame) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr bool STAGED = MODE != 2;
@@ -2226,6 +2251,7 @@ __device__ __forceinline__ void welsch_block_run(const QuadPtrs& P, WelschLds& S
     double err = 0;
     bool fin = true;
     int item = tid;
+    WeightTrips trips;
     for (int phase = 0; phase < 2; phase++) {
         bool run;
         if (phase == 0) {
@@ -2299,17 +2325,19 @@ __device__ __forceinline__ void welsch_block_run(const QuadPtrs& P, WelschLds& S
                     welsch_first_fit(pts, ListPicks{pk}, 10, line);
                 }
             }
-            fin = welsch_rounds<kWT>(pts, n, EPS, line, err, phase == 0 ? 0 : kWRegroupAt, phase == 0 ? kWRegroupAt : 30, phase != 0, S.wc + tid, min(n, phase == 0 ? kWCap : kWRes));
+            fin = welsch_rounds<kWT, COUNT>(pts, n, EPS, line, err, phase == 0 ? 0 : kWRegroupAt, phase == 0 ? kWRegroupAt : 30, phase != 0, S.wc + tid, min(n, phase == 0 ? kWCap : kWRes), trips);
             if (fin) restart_store(S.wc + kWRes * kWT + item, kWT, line, err);
         } else {
             fin = true;
         }
     }
+    if constexpr (COUNT) welsch_trips_add(P, trips);
     __syncthreads();
     if (tid < kWE && S.n[tid] > 0) welsch_select(P, frame, S.lid[tid], S.n[tid], S.wc + kWRes * kWT + tid * 20, 1, kWT, 20);
 }
 
 // the edges of sorted ranks [first, first + kWE) of the frame (ranks below L: the edges of more than kWShort points)
+template <bool COUNT>
 __device__ __forceinline__ void welsch_block(const QuadPtrs& P, WelschLds& S, int frame, int first, int L) {
     const int tid = threadIdx.x;
     if (tid < kWE) {
@@ -2337,27 +2365,30 @@ __device__ __forceinline__ void welsch_block(const QuadPtrs& P, WelschLds& S, in
             }
         }
         __syncthreads();
-        welsch_block_run<0>(P, S, frame);
+        welsch_block_run<0, COUNT>(P, S, frame);
     } else if (n0 <= kWPtsU) {
         for (int idx = tid; idx < kWE * kWPtsU; idx += kWT) {
             const int e = idx / kWPtsU, j = idx - e * kWPtsU;
             if (j < S.n[e]) S.ptu[e][j] = S.gpts[e][j];
         }
         __syncthreads();
-        welsch_block_run<1>(P, S, frame);
+        welsch_block_run<1, COUNT>(P, S, frame);
     } else {
-        welsch_block_run<2>(P, S, frame);
+        welsch_block_run<2, COUNT>(P, S, frame);
     }
 }
 
 // Edges of at most kWShort points, a lane each: ONE restart on all of the edge's points (see kWShort)
+template <bool COUNT>
 __device__ __forceinline__ void welsch_short(const QuadPtrs& P, WelschLds& S, int frame, int first, int L) {
     const int tid = threadIdx.x;
     if (first + tid >= L) return;
     const int lid = P.line_sorted[(size_t)frame * P.line_cap + first + tid];
     const LineDesc d = P.line_desc[(size_t)frame * P.line_cap + lid];
     const int n = d.n;  // 2 <= n <= kWShort <= kWCap: every weight stays in LDS
-    welsch_restart<kWT>(GlobalPts{P.cl_pool + (size_t)frame * P.cl_cap + d.off}, n, AllPicks{}, n, n * 1.1920928955078125e-07, S.wc + tid, kWT, S.wc + tid);
+    WeightTrips trips;
+    welsch_restart<kWT, COUNT>(GlobalPts{P.cl_pool + (size_t)frame * P.cl_cap + d.off}, n, AllPicks{}, n, n * 1.1920928955078125e-07, S.wc + tid, kWT, S.wc + tid, trips);
+    if constexpr (COUNT) welsch_trips_add(P, trips);
     welsch_select(P, frame, lid, n, S.wc + tid, 0, kWT, 1);
 }
 
@@ -2605,6 +2636,8 @@ __device__ __forceinline__ void welsch_pick(const QuadPtrs& P, int frame, int ra
 #ifndef CTAG_WELSCH_WAVES
 #define CTAG_WELSCH_WAVES 5
 #endif
+// COUNT: the build launched when P.stamps is set (CTAG_QUAD_STAMPS); it also counts the weight evaluations' wave trips by side
+template <bool COUNT>
 __global__ __launch_bounds__(kWT) __attribute__((amdgpu_waves_per_eu(CTAG_WELSCH_WAVES, CTAG_WELSCH_WAVES))) void k_welsch(QuadPtrs P, int nframes, const float* lat_rs, int gy_long) {
     // Longest first across the WHOLE batch: blockIdx.x (the fast dispatch index) is the frame, blockIdx.y the rank of the
     // group of kWE edges in the frame's list sorted by descending point count.  The longest groups of all frames are dispatched
@@ -2625,11 +2658,11 @@ __global__ __launch_bounds__(kWT) __attribute__((amdgpu_waves_per_eu(CTAG_WELSCH
     const int nlong = min(P.line_long[frame], L);  // ranks [0, nlong): edges of more than kWShort points, kWE per block x 20 restarts
     if ((int)blockIdx.y < gy_long) {
         for (int first = (int)blockIdx.y * kWE; first < nlong; first += gy_long * kWE) {
-            welsch_block(P, S, frame, first, nlong);
+            welsch_block<COUNT>(P, S, frame, first, nlong);
             __syncthreads();
         }
     } else {  // ranks [nlong, L): kWT short edges per block, one restart each
-        for (int first = nlong + ((int)blockIdx.y - gy_long) * kWT; first < L; first += ((int)gridDim.y - gy_long) * kWT) welsch_short(P, S, frame, first, L);
+        for (int first = nlong + ((int)blockIdx.y - gy_long) * kWT; first < L; first += ((int)gridDim.y - gy_long) * kWT) welsch_short<COUNT>(P, S, frame, first, L);
     }
 }
 
@@ -2846,7 +2879,7 @@ hipError_t launch_line_fits(const ChunkPlan& pl, const Workspace& ws, hipStream_
     if (welsch_lat) {  // one wave per (edge, restart); frames it declines (more edges / longer edges than it holds) fall through to k_welsch
         hipLaunchKernelGGL(k_welsch_lat, dim3(20, kLatRankBlocks, nframes), dim3(64), 0, s, P, nframes, ws.welsch_rs);
     }
-    hipLaunchKernelGGL(k_welsch, dim3(nframes, pl.welsch_gx + pl.welsch_gs), dim3(kWT), 0, s, P, nframes, welsch_lat ? ws.welsch_rs : (const float*)nullptr, pl.welsch_gx);
+    hipLaunchKernelGGL(stamps ? k_welsch<true> : k_welsch<false>, dim3(nframes, pl.welsch_gx + pl.welsch_gs), dim3(kWT), 0, s, P, nframes, welsch_lat ? ws.welsch_rs : (const float*)nullptr, pl.welsch_gx);
     return hipPeekAtLastError();  // (not cleared: launch_quads reports a failed launch of any of its kernels at its own end)
 }
 
@@ -2896,7 +2929,10 @@ hipError_t launch_quads(const ChunkPlan& pl, const Workspace& ws, hipStream_t s,
         if (h[16] | h[17] | h[18] | h[19])
             fprintf(stderr, "[whole-wave rdp ticks] corner scan %llu split rounds %llu expand_line %llu clusters + erase %llu\n", h[16], h[17], h[18], h[19]),
             fprintf(stderr, "[whole-wave expand_line] initial sums %llu ticks, %llu rounds, %llu of them through the exact fits\n", h[20], h[21], h[22]);
-        if (h[26]) fprintf(stderr, "[k_welsch] %llu restarts in %llu blocks, %llu (%.1f %%) went on after the regroup at iteration %d\n", h[24], h[26], h[25], 100.0 * h[25] / (h[24] ? h[24] : 1), kWRegroupAt);
+        if (h[26])
+            fprintf(stderr, "[k_welsch] %llu restarts in %llu blocks, %llu (%.1f %%) went on after the regroup at iteration %d\n", h[24], h[26], h[25], 100.0 * h[25] / (h[24] ? h[24] : 1), kWRegroupAt),
+            fprintf(stderr, "[k_welsch] weight evaluations: %llu wave trips took the bare polynomial (every active lane's k = 0), %llu the general exp32_nonpos: %.2f %% fast\n", h[27], h[28],
+                    100.0 * h[27] / (h[27] + h[28] ? h[27] + h[28] : 1));
         else if (h[24]) fprintf(stderr, "[k_welsch_lat ticks] restart 0 of the edges of rank 0 / 2 / 4 / 6: %llu %llu %llu %llu; restart 19: %llu %llu %llu %llu\n", h[24], h[25], h[26], h[27], h[28], h[29], h[30], h[31]);
         for (int b = 0; b < 16; b += 8) {
             unsigned long long tot = 0;

@@ -43,6 +43,13 @@ long ctag_debug_fetch(ctag_handle* h, int frame, int what, void* dst, size_t cap
  * Host arrays in/out. */
 int ctag_math_probe(ctag_handle* h, int op, int n, const double* a, const double* b, double* out);
 
+/* exp32_nonpos_k0 and exp32_k_is_zero (cylindertag_amd/csrc/ctag_math.h) against exp32_nonpos on the HOST, over the floats of bit patterns first_bits,
+ * first_bits + step, ... up to last_bits (all of them <= 0 and not NaN, else CTAG_ERR_ARG; among negative floats a larger pattern lies further from zero).
+ * counts[0] = values visited, counts[1] = those with exp32_k_is_zero, counts[2] = those where exp32_k_is_zero(x) != (rintf(x * log2e) == 0) with the product
+ * exp32_nonpos rounds, counts[3] = those with exp32_k_is_zero whose exp32_nonpos_k0 and exp32_nonpos differ in bits; *first_bad (may be null) = the bit
+ * pattern of the first value counted in [2] or [3].  Host only. */
+int ctag_testkit_exp32_k0_sweep(uint32_t first_bits, uint32_t last_bits, uint32_t step, uint64_t* counts, uint32_t* first_bad);
+
 /* ---- the multi-rank unpack on one GPU -----------------------------------------------------------------------
  * Runs exactly what ctag_gather_end runs after the payload all-gather (include/ctag_gather.h): the segment table of a
  * `world`-rank job over n_total frames (shard r = the ctag_shard_range of rank r, placed at r * width in the

@@ -22,7 +22,7 @@ DBG_HALF, DBG_LABELS, DBG_CANDIDATES, DBG_CAND_QUADS, DBG_FEATURES0, DBG_FEATURE
 SYNTH_SEED = 0x4354616753594E00  # "CTagSYN\0", SURVEY.md 8(d)
 
 # every symbol include/ctag_testkit.h declares (tests check the library exports all of them)
-EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
+EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_exp32_k0_sweep", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
            "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model",
            "ctag_testkit_dense_edge_probe", "ctag_testkit_plan", "ctag_testkit_welsch_fit", "ctag_testkit_welsch_limits",
            "ctag_testkit_model_fit_system", "ctag_testkit_model_fit_limits", "ctag_testkit_rig_fit_system", "ctag_testkit_rig_fit_limits",
@@ -38,6 +38,8 @@ CCL_FORMS = ("mask", "tw5", "any")                                              
 WELSCH_LIMITS = ("kWShort", "kWCap", "kWRes", "kWPts", "kWPtsU", "kPickN", "kPickN2", "kWE", "kWT", "kLatLines", "kLatPoints", "kLatChunk", "kLdsLines",
                  "kLatencyFrames", "kLatRankBlocks", "kLineSortBuckets")
 REFINE_FORMS = ("none", "one", "split_large", "split_looping", "split")                     # ChunkPlan::refine
+# op codes of Detector.math (ctag_math_probe; oracle/ctag_oracle.h lists 0..16) that tests name
+MATH_EXP32_NONPOS, MATH_EXP32_NONPOS_K0 = 15, 17
 
 
 def lib_path():
@@ -66,6 +68,8 @@ def load_library():
     L.ctag_debug_fetch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L.ctag_math_probe.restype = C.c_int
     L.ctag_math_probe.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    L.ctag_testkit_exp32_k0_sweep.restype = C.c_int
+    L.ctag_testkit_exp32_k0_sweep.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.ctag_testkit_unpack_gathered.restype = C.c_int
     L.ctag_testkit_unpack_gathered.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint64, vp]
     L.ctag_testkit_stall_stream.restype = C.c_int
@@ -118,6 +122,19 @@ def load_library():
     L.ctag_testkit_intrinsics_fit_limits.argtypes = [i32p, C.c_int]
     _lib = L
     return L
+
+
+def exp32_k0_sweep(first_bits, last_bits, step=1):
+    """exp32_nonpos_k0 / exp32_k_is_zero against exp32_nonpos on the host over the floats of bit patterns first_bits, first_bits + step, ... <= last_bits
+    (ctag_testkit_exp32_k0_sweep) -> dict of visited, k_is_zero, predicate_mismatches, bit_mismatches, first_bad (a bit pattern, or None).  Host only."""
+    counts = (C.c_uint64 * 4)()
+    first_bad = C.c_uint32()
+    st = load_library().ctag_testkit_exp32_k0_sweep(int(first_bits), int(last_bits), int(step), counts, C.byref(first_bad))
+    if st != 0:
+        raise CtagError(st, "ctag_testkit_exp32_k0_sweep")
+    out = dict(zip(("visited", "k_is_zero", "predicate_mismatches", "bit_mismatches"), (int(v) for v in counts)))
+    out["first_bad"] = int(first_bad.value) if out["predicate_mismatches"] or out["bit_mismatches"] else None
+    return out
 
 
 def model_fit_limits():

@@ -44,6 +44,7 @@ __global__ void k_math_probe(int op, int n, const double* a, const double* b, do
         case 14: r = ctm::round32((float)x); break;
         case 15: r = ctm::exp32_nonpos((float)x); break;  // x <= 0, not NaN
         case 16: r = ctm::div64(x, ctm::recip64(y)); break;  // x / y through the shared-reciprocal form (device) or `/` (host)
+        case 17: r = ctm::exp32_nonpos_k0((float)x); break;  // x <= 0 with ctm::exp32_k_is_zero(x)
         default: break;
     }
     out[i] = r;
@@ -438,6 +439,26 @@ int ctag_math_probe(ctag_handle* h, int op, int n, const double* a, const double
     (void)hipFree(db);
     (void)hipFree(dout);
     return rc;
+}
+
+int ctag_testkit_exp32_k0_sweep(uint32_t first_bits, uint32_t last_bits, uint32_t step, uint64_t* counts, uint32_t* first_bad) {
+    if (!counts || step == 0 || first_bits > last_bits) return CTAG_ERR_ARG;
+    uint64_t visited = 0, k0 = 0, bad_pred = 0, bad_bits = 0;
+    uint32_t bad_at = 0;
+    for (uint64_t u = first_bits; u <= last_bits; u += step) {
+        const float x = ctm::bits_to_f32((uint32_t)u);
+        if (!(x <= 0.0f)) return CTAG_ERR_ARG;  // positive or NaN: outside exp32_nonpos's domain
+        const bool is_zero = ctm::exp32_k_is_zero(x);
+        bool bad = is_zero != (__builtin_rintf(x * 1.44269502162933349609375f) == 0.0f);
+        bad_pred += bad ? 1 : 0;
+        if (is_zero && ctm::f32_to_bits(ctm::exp32_nonpos_k0(x)) != ctm::f32_to_bits(ctm::exp32_nonpos(x))) bad_bits++, bad = true;
+        if (bad && bad_pred + bad_bits == 1) bad_at = (uint32_t)u;
+        visited++;
+        k0 += is_zero ? 1 : 0;
+    }
+    counts[0] = visited, counts[1] = k0, counts[2] = bad_pred, counts[3] = bad_bits;
+    if (first_bad) *first_bad = bad_at;
+    return CTAG_OK;
 }
 
 int ctag_testkit_unpack_gathered(ctag_handle* h, const void* gathered_dev, int n_total, int world, uint64_t width, ctag_frame_result* out_dev) {
