@@ -5,7 +5,9 @@
 // the camera set) by Levenberg-Marquardt rounds on a Schur-reduced system: a pose pass, a record
 // kernel and an assemble kernel over the observation records, a damped solve per group, and a decision per group.  Stated here
 // once: the timed state on the handle, the context of a call, the working model, the systems on the device with their pass loop
-// and solve, and the LM bookkeeping with its constants and its decision.  Each fit keeps its kernels and its own round loop: the
+// and solve, and the LM bookkeeping with its constants, its options check and its decision; for the two fits whose unknowns are
+// 6-parameter slots (rig, camera set) also the slot systems with their workspace, assemble and solve launches and the probe's
+// hand-out, and the co-visibility tree of their initial assembly.  Each fit keeps its kernels and its own round loop: the
 // four loops have the same shape (rebuild the systems if a trial was accepted, solve, make the trials, one pose pass, decide per
 // group) and differ in what a trial and an accepted state are; stated once with five callbacks the loop came out longer than the
 // plain loops together (tried with the first two) and harder to follow, so the shape is repeated and everything the loops call is shared.
@@ -18,6 +20,7 @@
 #include <vector>
 
 #include "../../include/ctag_pose.h"
+#include "ctag_fit_solve.h"
 #include "ctag_internal.h"
 #include "ctag_pose_dev.h"
 #include "ctag_schur6.h"
@@ -197,6 +200,48 @@ inline double nearest_rotation(const double* M, double* R, double* sv) {
     return sg;
 }
 
+inline void mat_mul(const double* A, const double* B, double* C) {  // C = A B, 3x3 row-major, sums in index order
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
+}
+
+inline void mat_vec(const double* A, const double* v, double* o) {
+    for (int i = 0; i < 3; i++) o[i] = A[i * 3] * v[0] + A[i * 3 + 1] * v[1] + A[i * 3 + 2] * v[2];
+}
+
+// ---- the initial assembly's tree (rule 2 of the rig assembly and of the camera set fit) over k nodes with the symmetric co-visibility
+// counts cnt[k x k]: the anchor is the first node with an edge of at least min_count, and the tree grows from it by the edge of the
+// largest count (at least min_count) between a node in it and one outside.  edge(parent, child, count) is called for every edge in
+// the order the tree grows, in_tree[k] marks its nodes.  Returns the anchor, -1 when no edge counts.
+template <class Edge>
+int covisibility_tree(int k, const std::vector<int>& cnt, int min_count, std::vector<uint8_t>& in_tree, Edge&& edge) {
+    in_tree.assign(k, 0);
+    int anchor = -1;
+    for (int a = 0; a < k && anchor < 0; a++)
+        for (int b = 0; b < k; b++)
+            if (cnt[(size_t)a * k + b] >= min_count) {
+                anchor = a;
+                break;
+            }
+    if (anchor < 0) return -1;
+    in_tree[anchor] = 1;
+    for (;;) {
+        int best = min_count - 1, ba = -1, bb = -1;
+        for (int b = 0; b < k; b++) {  // ascending b, then ascending a: the first of equal counts stays
+            if (in_tree[b]) continue;
+            for (int a = 0; a < k; a++)
+                if (in_tree[a] && cnt[(size_t)a * k + b] > best) {
+                    best = cnt[(size_t)a * k + b];
+                    ba = a;
+                    bb = b;
+                }
+        }
+        if (bb < 0) return anchor;
+        edge(ba, bb, best);
+        in_tree[bb] = 1;
+    }
+}
+
 // ---- the observation records and the reduced systems of every group, on the device
 struct Systems {
     int n_groups = 0, N = 0, R = 0, pass = 0;    // N: rows of a group's S, g and delta
@@ -240,6 +285,18 @@ struct Systems {
         if (R > 0) FIT_HIP(hipMemcpyAsync(flags.data(), d_flags.p, sizeof(int32_t) * R, hipMemcpyDeviceToHost, c.s));
         FIT_HIP(hipStreamSynchronize(c.s));
         return CTAG_OK;
+    }
+
+    // build() for a fit whose record and assemble kernel are timed together in slot 2: enqueue(r0, r1) launches the two
+    template <class Enqueue>
+    int build_timed(Call& c, Enqueue&& enqueue) {
+        return build(c, [&](int r0, int r1) {
+            if (c.mark(0) != CTAG_OK) return CTAG_ERR_HIP;
+            enqueue(r0, r1);
+            if (launched() != CTAG_OK || c.mark(1) != CTAG_OK || c.reached(1) != CTAG_OK) return CTAG_ERR_HIP;
+            c.add_ms(2, 0);
+            return CTAG_OK;
+        });
     }
 
     // delta[n_groups][N] and bad[n_groups] of the groups with active[g] != 0: launch() enqueues the solve kernel (timed in slot 3).
@@ -286,6 +343,75 @@ struct Systems {
             if (rec_group[r] == g) acc[obs[r]] = trial[obs[r]];
     }
 };
+
+// ---- the systems of a fit whose unknowns are 6-parameter slots (the rig assembly: a group per rig, a slot per placed model; the camera
+// set fit: one group, a slot per placed camera): STRIDE = 6 x the most slots of a group is the row stride of S, g and delta, and a
+// record's workspace holds STRIDE / 6 slot blocks (ctag_schur6.h) for k_fit_assemble<STRIDE> and k_fit_solve<STRIDE>
+template <int STRIDE>
+struct SlotSystems : Systems {
+    Call c;
+    std::vector<int32_t> n_slots, drop;  // [n_groups]: the slots of a group's system, and the one whose rows are dropped (the anchor's)
+    DevBuf<int32_t> d_n_slots, d_drop;
+    DevBuf<double> d_ws;
+
+    // after obs, rec_group, n_slots and drop are filled
+    int setup(int pass_records, int default_pass) {
+        const int ng = (int)n_slots.size();
+        if ((size_t)ng * STRIDE * STRIDE * 8 > ((size_t)2 << 30)) return CTAG_ERR_LIMIT;
+        const int rc = Systems::setup(c, ng, STRIDE, pass_records, default_pass);
+        if (rc != CTAG_OK) return rc;
+        FIT_HIP(d_ws.grow((size_t)pass * (STRIDE / 6) * kSlotDoubles));
+        FIT_HIP(d_n_slots.grow(ng));
+        FIT_HIP(d_drop.grow(ng));
+        FIT_HIP(hipMemcpyAsync(d_n_slots.p, n_slots.data(), sizeof(int32_t) * ng, hipMemcpyHostToDevice, c.s));
+        FIT_HIP(hipMemcpyAsync(d_drop.p, drop.data(), sizeof(int32_t) * ng, hipMemcpyHostToDevice, c.s));
+        return CTAG_OK;
+    }
+
+    // the launch of the assemble kernel behind the record kernel of records r0 .. r1-1
+    template <class SlotOf>
+    void assemble(SlotOf slot_of, int r0, int r1) {
+        hipLaunchKernelGGL((k_fit_assemble<STRIDE, SlotOf>), dim3(fit_assemble_blocks<STRIDE>(), n_groups), dim3(kFitAssembleThreads), 0, c.s, d_ws.p, slot_of, d_flags.p,
+                           r0, r1, d_S.p, d_g.p);
+    }
+
+    int solve(const std::vector<double>& lambda, const std::vector<int32_t>& active, int bad_flags, std::vector<double>& delta, std::vector<int32_t>& bad) {
+        return Systems::solve(c, lambda, active, bad_flags, delta, bad, [&]() {
+            hipLaunchKernelGGL(k_fit_solve<STRIDE>, dim3(n_groups), dim3(kFitSolveThreads), 0, c.s, d_S.p, d_g.p, d_n_slots.p, d_drop.p, d_lambda.p, d_active.p, d_delta.p,
+                               d_bad.p);
+        });
+    }
+
+    // what a probe hands out: group grp's system at `lambda` solved alone (a caller's record may be left out; that does not make the
+    // group bad here), its S, g and delta compacted from row stride STRIDE to N = 6 n_slots[grp]
+    int probe(int grp, double lambda, double* S, double* g, double* delta, int32_t* n_unknowns, int32_t* bad_pivot) {
+        std::vector<double> lam(n_groups, lambda), d;
+        std::vector<int32_t> active(n_groups, 0), bad;
+        active[grp] = 1;
+        const int rc = solve(lam, active, kRecSingular, d, bad);
+        if (rc != CTAG_OK) return rc;
+        const int N = 6 * n_slots[grp];
+        std::vector<double> Sf((size_t)STRIDE * STRIDE), gf(STRIDE);
+        FIT_HIP(hipMemcpy(Sf.data(), d_S.p + (size_t)grp * STRIDE * STRIDE, sizeof(double) * Sf.size(), hipMemcpyDeviceToHost));
+        FIT_HIP(hipMemcpy(gf.data(), d_g.p + (size_t)grp * STRIDE, sizeof(double) * STRIDE, hipMemcpyDeviceToHost));
+        for (int i = 0; i < N; i++) {
+            for (int j = 0; j < N; j++) S[(size_t)i * N + j] = Sf[(size_t)i * STRIDE + j];
+            g[i] = gf[i];
+            delta[i] = d[(size_t)grp * STRIDE + i];
+        }
+        *n_unknowns = N;
+        *bad_pivot = bad[grp];
+        return CTAG_OK;
+    }
+};
+
+// the options every fit's Levenberg-Marquardt takes: lambda0, lambda_max and rel_tol are positive and finite
+template <class Opts>
+bool lm_opts_ok(const Opts& o) {
+    for (double v : {o.lambda0, o.lambda_max, o.rel_tol})
+        if (!std::isfinite(v) || !(v > 0.0)) return false;
+    return true;
+}
 
 // ---- Levenberg-Marquardt per group
 struct Lm {

@@ -224,6 +224,36 @@ __device__ __forceinline__ int desc_q(int32_t s) { return (s >> 7) & 7; }
 __device__ __forceinline__ int desc_cam(int32_t s) { return (s >> 10) & 7; }
 __device__ __forceinline__ int desc_pos(int32_t s) { return s >> 13; }
 
+constexpr int kFitMaxPts = CTAG_RIG_MAX_POINTS;  // points of an observation record of a fit at most
+
+// The member walk of the fits' record kernels (k_rfit_record; k_cfit_record, once per camera; k_ifit_pose and k_ifit_record): the
+// markers k < min(max(n_markers, 0), CTAG_MAX_MARKERS) of FR whose bit is set in mask[4], in marker order, each with the model
+// model_lookup gives it and its points in the builder's order (marker_points).  member(mi, base) is called for a member of model mi
+// whose points start at n = base, before them, and may turn it down; point(i, desc, mi) is called in lane q < cnt of an emit for the
+// lane's point i with its point_desc under camera `cam`.  n is advanced.  False -- the record does not describe its detection record
+// -- for a member without a model or turned down, a marker marker_points rejects, or more than kFitMaxPts points; what member and
+// point have written by then is not to be used.  A mask bit at or above the frame's marker count is ignored (k_pose_cov.hip's
+// cov_add_members rejects it, and k_rig_count and k_mv_count load points as they walk: those walks are their own).  Wave-uniform.
+template <class Member, class Point>
+__device__ __forceinline__ bool fit_member_walk(const ctag_frame_result& FR, const uint32_t* mask, const PoseModelDev& model, int lane, int cam, int& n,
+                                                Member&& member, Point&& point) {
+    const int nm = min(max(FR.n_markers, 0), CTAG_MAX_MARKERS);
+    const ctag_feature_rec* F0 = FR.features;
+    for (int k = 0; k < nm; k++) {
+        if (!((mask[k >> 5] >> (k & 31)) & 1u)) continue;
+        const int mi = model_lookup(model, FR.markers[k].marker_id);
+        if (mi < 0 || !member(mi, n)) return false;
+        const int base = n;
+        int nl = 0;
+        const int st = marker_points(FR, FR.markers[k], model.model_size, kPoseMaxPts, nl, [&](const ctag_feature_rec& F, int pos, int cnt, int i0) {
+            if (lane < cnt && base + i0 + cnt <= kFitMaxPts) point(base + i0 + lane, point_desc((int)(&F - F0), lane, cam, pos), mi);
+        });
+        if (st != CTAG_POSE_OK || base + nl > kFitMaxPts) return false;
+        n += nl;
+    }
+    return true;
+}
+
 // x = (rvec, tvec) of a pose record of any kind; false when one of the six is not finite
 template <class Rec>
 __device__ __forceinline__ bool load_state6(const Rec& P, double* x) {

@@ -4,22 +4,25 @@
 // Mapping.  The reprojection problem over camera poses and per-instant rig poses separates: given the camera
 // poses an instant's rig pose is the solve k_mv_solve already does, so a round is
 //   pose      ctag_mv_rig_pose_batch_device under the trial camera set (k_mv_pose.hip, untouched);
-//   record    k_cfit_record: one wavefront per observation record, grid-stride.  The walk is k_mv_count's / k_mv_solve's: camera,
-//             marker, builder order (marker_points over member_mask[c]); corner_point and mv_point_residual are the pose kernels',
+//   record    k_cfit_record: one wavefront per observation record, grid-stride.  The walk is k_mv_count's / k_mv_solve's order: camera,
+//             then fit_member_walk (ctag_pose_dev.h) over member_mask[c]; corner_point and mv_point_residual are the pose kernels',
 //             every camera's pixels undistorted with its own coefficients.  Lane l owns the points l, l + 64, ... of the record.
 //             Pass 1: the 21 entries of U = sum Jp^T Jp and the 6 of sum Jp^T r over all points, pose_block6 (ctag_schur6.h).  Pass 2,
 //             camera by camera: a camera's points are one contiguous run, so the 36 + 21 + 6 sums of Jp^T Jc, Jc^T Jc and Jc^T r over
 //             it are wave sums in which the lanes without a point of the run add zeros; then Z = L^-1 (Jp^T Jc) and
-//             g = Jc^T r - Z^T y: 63 doubles per camera slot, 8 slots, plus the record's mask of cameras with points;
-//   assemble  k_cfit_assemble: one thread per entry (i <= j) of the 48 x 48 S and of g; it walks the records in record order,
-//             subtracts Z_a^T Z_b and adds Jc^T Jc on the diagonal blocks.  The running sums live in global memory between passes of
-//             the record workspace, so the result does not depend on the pass size;
+//             g = Jc^T r - Z^T y: the slot block of ctag_schur6.h, 63 doubles per camera slot, 8 slots, plus the record's mask of
+//             cameras with points;
+//   assemble  k_fit_assemble<48> (ctag_fit_solve.h, the rig assembly's kernel) with CfitSlotOf: one thread per entry (i <= j) of the
+//             48 x 48 S and of g; it walks the records in record order, subtracts Z_a^T Z_b and adds Jc^T Jc on the diagonal blocks.
+//             The running sums live in global memory between passes of the record workspace, so the result does not depend on the
+//             pass size;
 //   solve     k_fit_solve<48> (ctag_fit_solve.h, the rig assembly's kernel): one block, at most 42 unknowns, the anchor's rows as
 //             identity rows.
 // The host decides (initial assembly, accept / reject, lambda, stop) between the launches.  FP64 VALU like the pose kernels.
-// The pose block of a record is ctag_schur6.h's, the host side of a fit (timed state, call context, systems with their pass loop and
-// solve, the accept / reject rule) is ctag_fit_host.h's.  This file keeps its kernels' walk and pass 2, the initial assembly of
-// rule 2, the probe, and its round loop.
+// The pose block and the slot block of a record are ctag_schur6.h's, the host side of a fit (timed state, call context, the slot
+// systems with their pass loop, solve and probe hand-out, the co-visibility tree of rule 2, the accept / reject rule) is
+// ctag_fit_host.h's.  This file keeps its record kernel with its point evaluation and its lane-to-point assignment, the counts and
+// the edge of rule 2's tree, and its round loop.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,21 +46,19 @@ namespace ctag {
 
 constexpr int kCfitGrid = 256;            // wavefronts of one k_cfit_record launch at most
 constexpr int kCfitPassRecords = 512;     // observation records one pass of the workspace holds
-constexpr int kCfitDoubles = 63;          // per camera slot of a record: Z (36), Jc^T Jc (21, upper triangle in row order), g (6)
 constexpr int kCfitN = 6 * kMvCams;       // 48: row stride of S, delta and g
-constexpr int kCfitMaxPts = CTAG_RIG_MAX_POINTS;
 
 struct CfitLds {
     PoseCam cam[kMvCams];            // the camera table, once per block
     double R[kMvCams][9];
     double t[kMvCams][3];
-    int32_t src[kCfitMaxPts];        // point i: its descriptor (point_desc, ctag_pose_dev.h)
-    int16_t mdl[kCfitMaxPts];        // ... and its model index
+    int32_t src[kFitMaxPts];        // point i: its descriptor (point_desc, ctag_pose_dev.h)
+    int16_t mdl[kFitMaxPts];        // ... and its model index
     int32_t cstart[kMvCams + 1];     // camera c owns the points cstart[c] .. cstart[c + 1] - 1
 };
 
-// Observation records r0 .. r1-1 (indices into obs, which holds multi-view record indices): workspace slot r - r0 gets the 63 doubles
-// of every camera with points, cmask[r] the mask of those cameras, flags[r] the record's state (kRec*).
+// Observation records r0 .. r1-1 (indices into obs, which holds multi-view record indices): workspace slot r - r0 gets the slot block
+// (ctag_schur6.h) of every camera with points, cmask[r] the mask of those cameras, flags[r] the record's state (kRec*).
 __global__ __launch_bounds__(64) void k_cfit_record(MvResults res, int n_frames, const ctag_mv_pose_rec* __restrict__ recs, const int32_t* __restrict__ obs,
                                                     int r0, int r1, PoseModelDev model, MvCams cams, double* __restrict__ ws,
                                                     int32_t* __restrict__ cmask, int32_t* __restrict__ flags) {
@@ -83,33 +84,11 @@ __global__ __launch_bounds__(64) void k_cfit_record(MvResults res, int n_frames,
                 break;
             }
             const ctag_frame_result& FR = res.p[c][f];
-            if (FR.status != CTAG_OK) {
-                ok = false;
-                break;
-            }
-            const int nm = min(max(FR.n_markers, 0), CTAG_MAX_MARKERS);
-            const ctag_feature_rec* F0 = FR.features;
-            for (int k = 0; k < nm && ok; k++) {
-                if (!((mask[k >> 5] >> (k & 31)) & 1u)) continue;
-                const int mi = model_lookup(model, FR.markers[k].marker_id);
-                if (mi < 0) {
-                    ok = false;
-                    break;
-                }
-                const int base = n;
-                int nl = 0;
-                const int st = marker_points(FR, FR.markers[k], model.model_size, kPoseMaxPts, nl, [&](const ctag_feature_rec& F, int pos, int cnt, int i0) {
-                    if (lane < cnt && base + i0 + cnt <= kCfitMaxPts) {
-                        L.src[base + i0 + lane] = point_desc((int)(&F - F0), lane, c, pos);
-                        L.mdl[base + i0 + lane] = (int16_t)mi;
-                    }
-                });
-                if (st != CTAG_POSE_OK || base + nl > kCfitMaxPts) {
-                    ok = false;
-                    break;
-                }
-                n += nl;
-            }
+            ok = FR.status == CTAG_OK && fit_member_walk(FR, mask, model, lane, c, n, [](int, int) { return true; }, [&](int i, int32_t desc, int mi) {
+                     L.src[i] = desc;
+                     L.mdl[i] = (int16_t)mi;
+                 });
+            if (!ok) break;
         }
         if (lane == 0) L.cstart[kMvCams] = n;
         ok = ok && n == P.n_points && n >= 4;
@@ -164,8 +143,8 @@ __global__ __launch_bounds__(64) void k_cfit_record(MvResults res, int n_frames,
             cmask[r] = pd ? present : 0;
         }
         if (!pd) continue;
-        // ---- pass 2: the 63 doubles of every camera with points
-        double* W = ws + (size_t)(r - r0) * kMvCams * kCfitDoubles;
+        // ---- pass 2: the slot block of every camera with points, Jc = (dr/dQ) [-[Q]x | I]
+        double* W = ws + (size_t)(r - r0) * kMvCams * kSlotDoubles;
         for (int c = 0; c < kMvCams; c++) {
             if (!((present >> c) & 1)) continue;
             const int i0 = L.cstart[c], i1 = L.cstart[c + 1];
@@ -177,104 +156,36 @@ __global__ __launch_bounds__(64) void k_cfit_record(MvResults res, int n_frames,
             for (int e = 0; e < 21; e++) A[e] = 0.0;
 #pragma unroll
             for (int e = 0; e < 6; e++) gm[e] = 0.0;
-            for (int i = i0 + ((lane - i0) & 63); i < i1; i += 64) {  // the lane's own points (i = lane mod 64) inside the run
+            // the lane's own points (i = lane mod 64) inside the run: the same lanes as in pass 1, they decide the order of the wave sums
+            for (int i = i0 + ((lane - i0) & 63); i < i1; i += 64) {
                 int cc;
-                double Q[3], q0, q1, j0[6], j1[6];
+                double Q[3], q0, q1, j0[6], j1[6], m0[6], m1[6];
                 point(i, cc, Q, q0, q1, j0, j1);
-                // d residual / d Q = (a0, 0, -b0), (0, a1, -b1); Jc = (dr/dQ) [-[Q]x | I]: the rotation columns are Q x (dr/dQ)
+                // d residual / d Q = (a0, 0, -b0), (0, a1, -b1)
                 const double iz = 1.0 / Q[2];
                 const double x0[3] = {fx * iz, 0.0, -(fx * Q[0] * iz * iz)};
                 const double x1[3] = {0.0, fy * iz, -(fy * Q[1] * iz * iz)};
-                double m0[6], m1[6];
-                m0[0] = Q[1] * x0[2] - Q[2] * x0[1];
-                m0[1] = Q[2] * x0[0] - Q[0] * x0[2];
-                m0[2] = Q[0] * x0[1] - Q[1] * x0[0];
-                m1[0] = Q[1] * x1[2] - Q[2] * x1[1];
-                m1[1] = Q[2] * x1[0] - Q[0] * x1[2];
-                m1[2] = Q[0] * x1[1] - Q[1] * x1[0];
-#pragma unroll
-                for (int m = 0; m < 3; m++) {
-                    m0[3 + m] = x0[m];
-                    m1[3 + m] = x1[m];
-                }
-                int e = 0;
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-#pragma unroll
-                    for (int d = 0; d < 6; d++) {
-                        Z[a * 6 + d] += j0[a] * m0[d];
-                        Z[a * 6 + d] += j1[a] * m1[d];
-                    }
-#pragma unroll
-                    for (int d = a; d < 6; d++) {
-                        A[e] += m0[a] * m0[d];
-                        A[e] += m1[a] * m1[d];
-                        e++;
-                    }
-                    gm[a] += m0[a] * q0;
-                    gm[a] += m1[a] * q1;
-                }
+                slot_rows(Q, x0, x1, m0, m1);
+                cross6_add(j0, j1, m0, m1, Z);
+                gram6_add(m0, m1, A);
+                grad6_add(m0, m1, q0, q1, gm);
             }
-#pragma unroll
-            for (int e = 0; e < 36; e++) Z[e] = wave_sum_f64(Z[e]);
-#pragma unroll
-            for (int e = 0; e < 21; e++) A[e] = wave_sum_f64(A[e]);
-#pragma unroll
-            for (int e = 0; e < 6; e++) gm[e] = wave_sum_f64(gm[e]);
-#pragma unroll
-            for (int d = 0; d < 6; d++) {  // column d of Z <- L^-1 (column d), g_d -= Z_d . y
-                double z[6];
-#pragma unroll
-                for (int a = 0; a < 6; a++) z[a] = Z[a * 6 + d];
-                gm[d] -= forward6_dot(Lc, z, b);
-#pragma unroll
-                for (int a = 0; a < 6; a++) Z[a * 6 + d] = z[a];
-            }
-            if (lane == 0) {
-                double* O = W + (size_t)c * kCfitDoubles;
-#pragma unroll
-                for (int e = 0; e < 36; e++) O[e] = Z[e];
-#pragma unroll
-                for (int e = 0; e < 21; e++) O[36 + e] = A[e];
-#pragma unroll
-                for (int e = 0; e < 6; e++) O[57 + e] = gm[e];
-            }
+            slot_finish(Z, A, gm, Lc, b, lane, W + (size_t)c * kSlotDoubles);
         }
     }
 }
 
-// Adds records r0 .. r1-1 to S and g.  Thread t < 48 x 48: entry (i, j) = (t / 48, t % 48) of S, the threads with i <= j work and
-// write both triangles; 48 x 48 <= t < 48 x 48 + 48: entry t - 48 x 48 of g.  Camera slot a owns rows 6a .. 6a + 5.
-__global__ __launch_bounds__(256) void k_cfit_assemble(const double* __restrict__ ws, const int32_t* __restrict__ cmask, const int32_t* __restrict__ flags, int r0,
-                                                       int r1, double* __restrict__ S, double* __restrict__ g) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    constexpr int NN = kCfitN * kCfitN;
-    const int i = t < NN ? t / kCfitN : t - NN, j = t < NN ? t - i * kCfitN : 0;
-    const bool is_s = t < NN && i <= j, is_g = t >= NN && t < NN + kCfitN;
-    if (!is_s && !is_g) return;
-    const int a = i / 6, p = i - 6 * a, bs = j / 6, q = j - 6 * bs;
-    double* dst = is_s ? S + (size_t)i * kCfitN + j : g + i;
-    double acc = *dst;
-    int ea = 0;  // index of (p, q) in the upper triangle's row order
-    if (is_s && a == bs) ea = p * 6 - p * (p - 1) / 2 + (q - p);
-    const int need = is_g ? (1 << a) : ((1 << a) | (1 << bs));
-    for (int r = r0; r < r1; r++) {
-        if (flags[r] != 0 || (cmask[r] & need) != need) continue;
-        const double* za = ws + ((size_t)(r - r0) * kMvCams + a) * kCfitDoubles;
-        if (is_g) {
-            acc += za[57 + p];
-            continue;
-        }
-        const double* zb = ws + ((size_t)(r - r0) * kMvCams + bs) * kCfitDoubles;
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; k++) s += za[k * 6 + p] * zb[k * 6 + q];
-        acc -= s;
-        if (a == bs) acc += za[36 + ea];
+// k_fit_assemble's SlotOf: one group; a camera's slot block lies at the slot itself, when the camera has points in the record
+struct CfitSlotOf {
+    const int32_t* cmask;
+    __device__ int group() const { return 0; }
+    __device__ bool operator()(int r, int a, int b, int& ka, int& kb) const {
+        const int need = (1 << a) | (1 << b);
+        ka = a;
+        kb = b;
+        return (cmask[r] & need) == need;
     }
-    *dst = acc;
-    if (is_s && i != j) S[(size_t)j * kCfitN + i] = acc;
-}
+};
 
 }  // namespace ctag
 
@@ -285,15 +196,6 @@ namespace {
 
 namespace fit = ctag::fit;
 
-void mat_mul(const double* A, const double* B, double* C) {  // C = A B, 3x3 row-major, sums in index order
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
-}
-
-void mat_vec(const double* A, const double* v, double* o) {
-    for (int i = 0; i < 3; i++) o[i] = A[i * 3] * v[0] + A[i * 3 + 1] * v[1] + A[i * 3 + 2] * v[2];
-}
-
 struct SetGuard {  // frees a camera set unless it is handed out
     ctag_camera_set* s = nullptr;
     ~SetGuard() { reset(nullptr); }
@@ -303,46 +205,26 @@ struct SetGuard {  // frees a camera set unless it is handed out
     }
 };
 
-// The device side of one call: the one system (group 0), the record workspace and the cameras' detection records.
-struct CfitWork : fit::Systems {
-    fit::Call c;
+// The device side of one call: the one system (group 0: its slots are the placed cameras, the anchor's dropped), the record workspace
+// and the cameras' detection records.
+struct CfitWork : fit::SlotSystems<ctag::kCfitN> {
     ctag::MvResults res{};
-    int32_t n_slots = 0, drop = 0;  // cameras of the set; the anchor's slot
-    ctag::DevBuf<int32_t> d_n_slots, d_drop, d_cmask;
-    ctag::DevBuf<double> d_ws;
+    ctag::DevBuf<int32_t> d_cmask;
 
     int setup(int pass_records) {
-        const int rc = Systems::setup(c, 1, ctag::kCfitN, pass_records, ctag::kCfitPassRecords);
+        const int rc = SlotSystems::setup(pass_records, ctag::kCfitPassRecords);
         if (rc != CTAG_OK) return rc;
         FIT_HIP(d_cmask.grow((size_t)std::max(R, 1)));
-        FIT_HIP(d_ws.grow((size_t)pass * ctag::kMvCams * ctag::kCfitDoubles));
-        FIT_HIP(d_n_slots.grow(1));
-        FIT_HIP(d_drop.grow(1));
-        FIT_HIP(hipMemcpyAsync(d_n_slots.p, &n_slots, sizeof(int32_t), hipMemcpyHostToDevice, c.s));
-        FIT_HIP(hipMemcpyAsync(d_drop.p, &drop, sizeof(int32_t), hipMemcpyHostToDevice, c.s));
-        FIT_HIP(hipStreamSynchronize(c.s));  // n_slots and drop are read from this object
         return CTAG_OK;
     }
 
-    // S and g at (cams, recs_dev); slot 2 times the record and the assemble kernel together.  Waits.
+    // S and g at (cams, recs_dev).  Waits.
     int build_system(const ctag_model* model, const ctag_camera_set* cams, const ctag_mv_pose_rec* recs_dev) {
         const ctag::PoseModelDev md{model->n_models, model->model_size, model->d_ids.p, model->d_corners.p};
-        constexpr int kThreads = ctag::kCfitN * ctag::kCfitN + ctag::kCfitN;
-        return build(c, [&](int r0, int r1) {
-            if (c.mark(0) != CTAG_OK) return CTAG_ERR_HIP;
+        return build_timed(c, [&](int r0, int r1) {
             hipLaunchKernelGGL(ctag::k_cfit_record, dim3(std::min(r1 - r0, ctag::kCfitGrid)), dim3(64), 0, c.s, res, c.n_frames, recs_dev, d_obs.p, r0, r1, md,
                                cams->dev, d_ws.p, d_cmask.p, d_flags.p);
-            hipLaunchKernelGGL(ctag::k_cfit_assemble, dim3((kThreads + 255) / 256), dim3(256), 0, c.s, d_ws.p, d_cmask.p, d_flags.p, r0, r1, d_S.p, d_g.p);
-            if (fit::launched() != CTAG_OK || c.mark(1) != CTAG_OK || c.reached(1) != CTAG_OK) return CTAG_ERR_HIP;
-            c.add_ms(2, 0);
-            return CTAG_OK;
-        });
-    }
-
-    int solve(const std::vector<double>& lambda, const std::vector<int32_t>& active, int bad_flags, std::vector<double>& delta, std::vector<int32_t>& bad) {
-        return Systems::solve(c, lambda, active, bad_flags, delta, bad, [&]() {
-            hipLaunchKernelGGL(ctag::k_fit_solve<ctag::kCfitN>, dim3(1), dim3(ctag::kFitSolveThreads), 0, c.s, d_S.p, d_g.p, d_n_slots.p, d_drop.p, d_lambda.p,
-                               d_active.p, d_delta.p, d_bad.p);
+            assemble(ctag::CfitSlotOf{d_cmask.p}, r0, r1);
         });
     }
 };
@@ -350,10 +232,7 @@ struct CfitWork : fit::Systems {
 int cfit_opts(const ctag_camera_fit_opts* o, ctag_camera_fit_opts& r) {
     ctag_camera_fit_opts_default(&r);
     if (o) r = *o;
-    if (r.max_rounds < 0 || r.min_items < 1 || r.min_points < 1) return CTAG_ERR_ARG;
-    for (double v : {r.lambda0, r.lambda_max, r.rel_tol})
-        if (!std::isfinite(v) || !(v > 0.0)) return CTAG_ERR_ARG;
-    return CTAG_OK;
+    return r.max_rounds >= 0 && r.min_items >= 1 && r.min_points >= 1 && fit::lm_opts_ok(r) ? CTAG_OK : CTAG_ERR_ARG;
 }
 
 }  // namespace
@@ -389,28 +268,13 @@ int cfit_probe_system(ctag_handle* h, const ctag_frame_result* results, int n_fr
             w.rec_group.push_back(0);
         }
     if (w.obs.empty()) return CTAG_ERR_ARG;
-    w.n_slots = nc;
-    w.drop = anchor;
+    w.n_slots.assign(1, nc);
+    w.drop.assign(1, anchor);
     rc = w.setup(pass_records);
     if (rc != CTAG_OK) return rc;
     rc = w.build_system(model, cams, d_recs.p);
     if (rc != CTAG_OK) return rc;
-    std::vector<double> lam(1, lambda), d;
-    std::vector<int32_t> active(1, 1), bad;
-    rc = w.solve(lam, active, kRecSingular, d, bad);  // a caller's record may be left out; that does not make the system bad here
-    if (rc != CTAG_OK) return rc;
-    const int N = 6 * nc;
-    std::vector<double> Sf((size_t)kCfitN * kCfitN), gf(kCfitN);
-    FIT_HIP(hipMemcpy(Sf.data(), w.d_S.p, sizeof(double) * Sf.size(), hipMemcpyDeviceToHost));
-    FIT_HIP(hipMemcpy(gf.data(), w.d_g.p, sizeof(double) * kCfitN, hipMemcpyDeviceToHost));
-    for (int i = 0; i < N; i++) {
-        for (int j = 0; j < N; j++) S[(size_t)i * N + j] = Sf[(size_t)i * kCfitN + j];
-        g[i] = gf[i];
-        delta[i] = d[i];
-    }
-    *n_unknowns = N;
-    *bad_pivot = bad[0];
-    return CTAG_OK;
+    return w.probe(0, lambda, S, g, delta, n_unknowns, bad_pivot);
 }
 
 }  // namespace ctag
@@ -485,31 +349,10 @@ int ctag_camera_fit_device(ctag_handle* h, const ctag_frame_result* const* resul
                     cnt[(size_t)b * nc + a]++;
                 }
         }
-    int anchor = -1;
-    for (int a = 0; a < nc && anchor < 0; a++)
-        for (int b = 0; b < nc; b++)
-            if (cnt[(size_t)a * nc + b] >= opts.min_items) {
-                anchor = a;
-                break;
-            }
-    if (anchor < 0) return CTAG_OK;
     std::vector<ctag_camera_pose> pose(nc);  // the accepted state: X_c = R(rvec) X_anchor + tvec
     for (auto& p : pose) std::memset(&p, 0, sizeof(p));
-    std::vector<uint8_t> in_tree(nc, 0);
-    in_tree[anchor] = 1;
-    int n_placed = 1;
-    for (;;) {
-        int best = opts.min_items - 1, ba = -1, bb = -1;
-        for (int b = 0; b < nc; b++) {  // ascending b, then ascending a: the first of equal counts stays
-            if (in_tree[b]) continue;
-            for (int a = 0; a < nc; a++)
-                if (in_tree[a] && cnt[(size_t)a * nc + b] > best) {
-                    best = cnt[(size_t)a * nc + b];
-                    ba = a;
-                    bb = b;
-                }
-        }
-        if (bb < 0) break;
+    std::vector<uint8_t> in_tree;
+    const int anchor = fit::covisibility_tree(nc, cnt, opts.min_items, in_tree, [&](int ba, int bb, int best) {
         double sumR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (size_t i = 0; i < n_items; i++) {
             if (!counted(ba, i) || !counted(bb, i)) continue;
@@ -518,7 +361,7 @@ int ctag_camera_fit_device(ctag_handle* h, const ctag_frame_result* const* resul
             ctl::angle_axis_rot(rp[bb][i].rvec, Rb, nullptr);
             for (int r = 0; r < 3; r++)
                 for (int k = 0; k < 3; k++) RaT[r * 3 + k] = Ra[k * 3 + r];
-            mat_mul(Rb, RaT, Q);
+            fit::mat_mul(Rb, RaT, Q);
             for (int k = 0; k < 9; k++) sumR[k] += Q[k];
         }
         double ER[9], Et[3], sv[3], sumt[3] = {0, 0, 0};
@@ -526,31 +369,31 @@ int ctag_camera_fit_device(ctag_handle* h, const ctag_frame_result* const* resul
         for (size_t i = 0; i < n_items; i++) {
             if (!counted(ba, i) || !counted(bb, i)) continue;
             double e[3];
-            mat_vec(ER, rp[ba][i].tvec, e);
+            fit::mat_vec(ER, rp[ba][i].tvec, e);
             for (int k = 0; k < 3; k++) sumt[k] += rp[bb][i].tvec[k] - e[k];
         }
         for (int k = 0; k < 3; k++) Et[k] = sumt[k] / (double)best;
         // T_b = E o T_a
         double Ra[9], Rb[9], e[3];
         ctl::angle_axis_rot(pose[ba].rvec, Ra, nullptr);
-        mat_mul(ER, Ra, Rb);
+        fit::mat_mul(ER, Ra, Rb);
         ctl::rodrigues_from_matrix(Rb, pose[bb].rvec);
-        mat_vec(ER, pose[ba].tvec, e);
+        fit::mat_vec(ER, pose[ba].tvec, e);
         for (int k = 0; k < 3; k++) pose[bb].tvec[k] = e[k] + Et[k];
-        in_tree[bb] = 1;
-        n_placed++;
         cam_stats[bb].parent = ba;
         cam_stats[bb].n_items_with_parent = best;
-    }
+    });
+    if (anchor < 0) return CTAG_OK;
+    w.n_slots.assign(1, 0);
+    w.drop.assign(1, 0);
     std::vector<int> placed;  // slot -> camera
     for (int c = 0; c < nc; c++)
         if (in_tree[c]) {
-            if (c == anchor) w.drop = (int32_t)placed.size();
+            if (c == anchor) w.drop[0] = (int32_t)placed.size();
             placed.push_back(c);
             cam_stats[c].status = CTAG_POSE_OK;
         }
-    const int np = n_placed;
-    w.n_slots = np;
+    const int np = w.n_slots[0] = (int)placed.size();
     stat->status = CTAG_POSE_OK;
     stat->anchor = anchor;
     stat->n_placed = np;
@@ -636,9 +479,9 @@ int ctag_camera_fit_device(ctag_handle* h, const ctag_frame_result* const* resul
             double E[9], Rc[9], Rn[9], e[3];
             ctl::angle_axis_rot(d, E, nullptr);
             ctl::angle_axis_rot(pose[c].rvec, Rc, nullptr);
-            mat_mul(E, Rc, Rn);
+            fit::mat_mul(E, Rc, Rn);
             ctl::rodrigues_from_matrix(Rn, pose_t[c].rvec);
-            mat_vec(E, pose[c].tvec, e);
+            fit::mat_vec(E, pose[c].tvec, e);
             for (int i = 0; i < 3; i++) pose_t[c].tvec[i] = e[i] + d[3 + i];
             for (int i = 0; i < 3; i++) usable = usable && std::isfinite(pose_t[c].rvec[i]) && std::isfinite(pose_t[c].tvec[i]);
         }

@@ -17,8 +17,9 @@
 //   solve     k_ifit_solve: one wavefront, (S + lambda diag S) over the free rows as a 16 x 16 in LDS, fixed parameters as identity
 //             rows with a zero right-hand side, right-looking Cholesky, the two triangular solves on lane 0.
 // The host decides (accept / reject, lambda, stop: fit::Lm) between the launches and forms the float32 trial camera.  FP64 VALU like the
-// pose kernels; nothing here is MFMA-shaped.  The walk is k_rfit_record's (marker_points over member_mask, point_desc, load_state6);
-// corner_pixel (ctag_pose_dev.h) gives the raw pixel; chol6, forward6 and forward6_dot are ctag_schur6.h's, the host side of a fit
+// pose kernels; nothing here is MFMA-shaped.  The walk is the one of the rig assembly and the camera set fit (fit_member_walk,
+// ctag_pose_dev.h, as are point_desc and load_state6);
+// corner_pixel (ctag_pose_dev.h) gives the raw pixel; chol6, forward6, backward6 and forward6_dot are ctag_schur6.h's, the host side of a fit
 // (timed state, call context, systems with their pass loop, the accept / reject rule) is ctag_fit_host.h's.
 #include <hip/hip_runtime.h>
 
@@ -49,46 +50,32 @@ constexpr int kIfitGram = kIfitCols * (kIfitCols + 1) / 2; // 276: the upper tri
 constexpr int kIfitOwned = (kIfitGram + 63) / 64;          // 5 entries a lane at most
 constexpr int kIfitUpper = kIfitN * (kIfitN + 1) / 2;      // 136: the upper triangle of S_r in row order
 constexpr int kIfitDoubles = kIfitUpper + kIfitN;          // per record of a pass: S_r, then g_r
-constexpr int kIfitMaxPts = CTAG_RIG_MAX_POINTS;
 constexpr int kRecUnusable = 4;  // flags of a record beside kRecLeftOut / kRecSingular: a point of it is unusable under this state (rule 2)
 // rule 4's constants
 constexpr double kIfitMu0 = 1e-4, kIfitMuMax = 1e8, kIfitPoseTol = 1e-15;
 constexpr int kIfitPoseSteps = 40;
 
 struct IfitWalk {
-    int32_t src[kIfitMaxPts];  // point i: its descriptor (point_desc, ctag_pose_dev.h; camera 0)
-    int16_t mdl[kIfitMaxPts];  // ... and its model index
+    int32_t src[kFitMaxPts];  // point i: its descriptor (point_desc, ctag_pose_dev.h; camera 0)
+    int16_t mdl[kFitMaxPts];  // ... and its model index
 };
 
 // index of (a, b), a <= b, in the upper triangle of an n x n in row order
 __host__ __device__ constexpr int upper_index(int n, int a, int b) { return a * n - a * (a - 1) / 2 + (b - a); }
 
-// The points of rig pose record P in the builder's order (k_rfit_record's walk); false when the record does not describe its
-// detection record.  Wave-uniform.
+// The points of rig pose record P in the builder's order (fit_member_walk, ctag_pose_dev.h); false when the record does not describe
+// its detection record.  Wave-uniform.
 __device__ __forceinline__ bool ifit_walk(const ctag_frame_result* __restrict__ res, int n_frames, const ctag_rig_pose_rec& P, const PoseModelDev& model, int lane,
                                           IfitWalk& W, int& n) {
     n = 0;
     if (P.status != CTAG_POSE_OK || P.frame < 0 || P.frame >= n_frames || model.n_models > 32767) return false;
     const ctag_frame_result& FR = res[P.frame];
     if (FR.status != CTAG_OK) return false;
-    const int nm = min(max(FR.n_markers, 0), CTAG_MAX_MARKERS);
-    const ctag_feature_rec* F0 = FR.features;
-    for (int k = 0; k < nm; k++) {
-        if (!((P.member_mask[k >> 5] >> (k & 31)) & 1u)) continue;
-        const int mi = model_lookup(model, FR.markers[k].marker_id);
-        if (mi < 0) return false;
-        const int base = n;
-        int nl = 0;
-        const int st = marker_points(FR, FR.markers[k], model.model_size, kPoseMaxPts, nl, [&](const ctag_feature_rec& F, int pos, int cnt, int i0) {
-            if (lane < cnt && base + i0 + cnt <= kIfitMaxPts) {
-                W.src[base + i0 + lane] = point_desc((int)(&F - F0), lane, 0, pos);
-                W.mdl[base + i0 + lane] = (int16_t)mi;
-            }
-        });
-        if (st != CTAG_POSE_OK || base + nl > kIfitMaxPts) return false;
-        n += nl;
-    }
-    return n == P.n_points && n >= 4;
+    const bool ok = fit_member_walk(FR, P.member_mask, model, lane, 0, n, [](int, int) { return true; }, [&](int i, int32_t desc, int mi) {
+        W.src[i] = desc;
+        W.mdl[i] = (int16_t)mi;
+    });
+    return ok && n == P.n_points && n >= 4;
 }
 
 // Rule 2 at one point: the residual (q0, q1) of model point X seen at pixel uv under pose (R, dR, x) and camera c, the rows of Jp
@@ -156,17 +143,6 @@ __device__ __forceinline__ bool ifit_point(const PoseCam& c, double tie, const d
         c0[15] = 0.0, c1[15] = c.fy * r4;  // s4
     }
     return true;
-}
-
-// x <- L^-T x (back substitution with the transpose of the lower triangle of the row-major 6x6 L)
-__device__ __forceinline__ void backward6(const double* L, double* x) {
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double s = x[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) s -= L[k * 6 + i] * x[k];
-        x[i] = s / L[i * 6 + i];
-    }
 }
 
 // Rule 4 on observation records 0 .. n_obs-1 (indices into obs), in place: recs[obs[r]] gets rvec, tvec and cost; pflags[r] = 0, or
@@ -416,7 +392,8 @@ __global__ __launch_bounds__(256) void k_ifit_assemble(const double* __restrict_
 }
 
 // (S + lambda diag S) delta = -g over the rows whose bit is set in `mask`; the other rows are identity rows with a zero right-hand
-// side.  bad[0] = 1 for a pivot that is not positive (delta stays as it was).
+// side.  bad[0] = 1 for a pivot that is not positive (delta stays as it was).  Not k_fit_solve (ctag_fit_solve.h), on purpose: the
+// two triangular solves run row by row here and column by column there, which subtracts in another order per element.
 __global__ __launch_bounds__(64) void k_ifit_solve(const double* __restrict__ S, const double* __restrict__ g, const double* __restrict__ lambda,
                                                    const int32_t* __restrict__ active, uint32_t mask, double* __restrict__ delta, int32_t* __restrict__ bad) {
     __shared__ double A[kIfitN][kIfitN + 1];
@@ -510,17 +487,13 @@ struct IfitWork : fit::Systems {
         return CTAG_OK;
     }
 
-    // S and g at (cam, recs_dev); slot 2 times the record and the assemble kernel together.  Waits.
+    // S and g at (cam, recs_dev).  Waits.
     int build_system(const ctag_model* model, const ctag::PoseCam& cam, const ctag_rig_pose_rec* recs_dev) {
         const ctag::PoseModelDev md = dev_model(model);
-        return build(c, [&](int r0, int r1) {
-            if (c.mark(0) != CTAG_OK) return CTAG_ERR_HIP;
+        return build_timed(c, [&](int r0, int r1) {
             hipLaunchKernelGGL(ctag::k_ifit_record, dim3(std::min(r1 - r0, ctag::kIfitGrid)), dim3(64), 0, c.s, c.res, c.n_frames, recs_dev, d_obs.p, r0, r1, md, cam, tie,
                                d_ws.p, d_flags.p);
             hipLaunchKernelGGL(ctag::k_ifit_assemble, dim3(1), dim3(256), 0, c.s, d_ws.p, d_flags.p, r0, r1, d_S.p, d_g.p);
-            if (fit::launched() != CTAG_OK || c.mark(1) != CTAG_OK || c.reached(1) != CTAG_OK) return CTAG_ERR_HIP;
-            c.add_ms(2, 0);
-            return CTAG_OK;
         });
     }
 
@@ -591,9 +564,7 @@ bool inverse_diagonal(const double* S, uint32_t mask, double* diag) {
 int ifit_opts(const ctag_intrinsics_fit_opts* o, const ctag_camera* seed, ctag_intrinsics_fit_opts& r, uint32_t& mask, double& tie) {
     ctag_intrinsics_fit_opts_default(&r);
     if (o) r = *o;
-    if (r.max_rounds < 0 || r.min_points < 1) return CTAG_ERR_ARG;
-    for (double v : {r.lambda0, r.lambda_max, r.rel_tol})
-        if (!std::isfinite(v) || !(v > 0.0)) return CTAG_ERR_ARG;
+    if (r.max_rounds < 0 || r.min_points < 1 || !fit::lm_opts_ok(r)) return CTAG_ERR_ARG;
     const int nd = std::min(std::max(seed->n_dist, 0), 12);
     mask = r.free_mask;
     if (mask == 0u) mask = (1u << (4 + nd)) - 1u;

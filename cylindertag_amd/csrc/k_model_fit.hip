@@ -460,9 +460,7 @@ bool metric_scale(const float* corners, const uint8_t* held, int pm, double stri
 int fit_opts(const ctag_model_fit_opts* o, ctag_model_fit_opts& r) {
     ctag_model_fit_opts_default(&r);
     if (o) r = *o;
-    if (r.max_rounds < 0 || r.min_obs < 1) return CTAG_ERR_ARG;
-    for (double v : {r.lambda0, r.lambda_max, r.rel_tol})
-        if (!std::isfinite(v) || !(v > 0.0)) return CTAG_ERR_ARG;
+    if (r.max_rounds < 0 || r.min_obs < 1 || !fit::lm_opts_ok(r)) return CTAG_ERR_ARG;
     if (!std::isfinite(r.strip_height)) return CTAG_ERR_ARG;
     return CTAG_OK;
 }

@@ -69,7 +69,8 @@ __device__ __forceinline__ bool cov_add_marker(CovLds& L, const int lane, const 
     return st == CTAG_POSE_OK && n <= kCovMaxPts;
 }
 
-// the members of one frame record by a member mask, in marker order, each against the first model with its id
+// the members of one frame record by a member mask, in marker order, each against the first model with its id.  Not the fits'
+// fit_member_walk (ctag_pose_dev.h), on purpose: a mask bit at or above the frame's marker count is rejected here and ignored there
 __device__ __forceinline__ bool cov_add_members(CovLds& L, const int lane, const ctag_frame_result& FR, const uint32_t* mask, const PoseModelDev& model,
                                                 const int c, int& n) {
     if (FR.status != CTAG_OK) return false;

@@ -4,28 +4,30 @@
 // Mapping.  The reprojection problem over member transforms and per-frame rig poses separates: given the
 // transforms a frame's rig pose is the solve k_rig_pose already does, so a round is
 //   pose      ctag_rig_pose_batch_device on the call's working copy of the model (k_rig_pose.hip, untouched);
-//   record    k_rfit_record: one wavefront per observation record, grid-stride.  The member walk is the builder's (marker_points
-//             over the record's member_mask, as k_pose_cov's rig source has it), corner_point and point_residual are the pose
+//   record    k_rfit_record: one wavefront per observation record, grid-stride.  The member walk is fit_member_walk (ctag_pose_dev.h:
+//             marker_points over the record's member_mask), corner_point and point_residual are the pose
 //             kernels'.  A member's points are one contiguous run of the record, lane l takes the points l, l + 64, ... of the run.
 //             Pass 1: the 21 entries of U = sum Jp^T Jp and the 6 of sum Jp^T r over all points through wave_sum_f64, every lane
-//             factors U = L L^T.  Pass 2, member by member: the 36 + 21 + 6 sums of Jp^T Jm, Jm^T Jm and Jm^T r over the member's
-//             run through wave_sum_f64 (lanes without a point of the run add zeros: masked wave sums), then Z = L^-1 (Jp^T Jm) and
-//             g = Jm^T r - Z^T y: 63 doubles per member slot, plus the record's model-slot -> member table (int8, -1 where absent);
-//   assemble  k_rfit_assemble: for rig g one thread per entry (i <= j) of its 96 x 96 S; it walks the records in record order
-//             (other rigs' records skipped by a block-uniform branch), subtracts Z_a^T Z_b and adds Jm^T Jm on the diagonal blocks;
-//             g the same way.  The running sums live in global memory between passes of the record workspace, so the result does not
-//             depend on the pass size;
+//             factors U = L L^T.  Pass 2, member by member: the slot block (ctag_schur6.h) -- the 36 + 21 + 6 sums of Jp^T Jm, Jm^T Jm
+//             and Jm^T r over the member's run through wave_sum_f64 (lanes without a point of the run add zeros: masked wave sums),
+//             then Z = L^-1 (Jp^T Jm) and g = Jm^T r - Z^T y: 63 doubles per member slot -- plus the record's model-slot -> member
+//             table (int8, -1 where absent);
+//   assemble  k_fit_assemble<96> (ctag_fit_solve.h) with RfitSlotOf: for rig g one thread per entry (i <= j) of its 96 x 96 S; it walks
+//             the records in record order (other rigs' records skipped by a block-uniform branch), subtracts Z_a^T Z_b and adds
+//             Jm^T Jm on the diagonal blocks; g the same way.  The running sums live in global memory between passes of the record
+//             workspace, so the result does not depend on the pass size;
 //   solve     k_fit_solve<96> (ctag_fit_solve.h): one block per rig, the damped system (S + lambda diag S) as a packed lower triangle in LDS (at most
 //             96 x 97 / 2 doubles, 37 KB), right-looking Cholesky, the dropped rows (the anchor's) as identity rows with a zero
 //             right-hand side, the two triangular solves, delta and a flag for a pivot that is not positive.
 // The host decides (initial assembly, accept / reject, lambda, stop) per rig between the launches.  FP64 VALU like the pose kernels;
 // the largest system is 90 x 90, nothing here is MFMA-shaped.
 //
-// What the assembly shares with the model reconstruction (k_model_fit.hip) is not here: the pose block of a record (pass 1, a column
-// through L^-1, the point Jacobian) is ctag_schur6.h's, the point descriptor and load_state6 are ctag_pose_dev.h's, and the host side
-// of a fit -- timed state, call context, working model, systems with their pass loop and solve, the accept / reject rule --
-// is ctag_fit_host.h's.  This file keeps its kernels' own walk, tables and pass 2, the initial assembly of rules 1-4,
-// apply_rigid, report_transforms, the probe, and its round loop.
+// What the assembly shares with the other fits is not here: the pose block of a record (pass 1, a column through L^-1, the point
+// Jacobian) and the slot block are ctag_schur6.h's, the member walk, the point descriptor and load_state6 are ctag_pose_dev.h's, the
+// assemble and the solve kernel are ctag_fit_solve.h's, and the host side of a fit -- timed state, call context, working model, the
+// slot systems with their pass loop, solve and probe hand-out, the co-visibility tree of rule 2, the accept / reject rule -- is
+// ctag_fit_host.h's.  This file keeps its record kernel with its tables and its lane-to-point assignment, the counts and the edge
+// of rule 2's tree, apply_rigid, report_transforms, and its round loop.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,20 +52,18 @@ namespace ctag {
 constexpr int kRfitGrid = 256;            // wavefronts of one k_rfit_record launch at most
 constexpr int kRfitPassRecords = 512;     // observation records one pass of the workspace holds
 constexpr int kRfitSlots = CTAG_RIG_FIT_MAX_MODELS;  // member slots of a record, model slots of a rig
-constexpr int kRfitDoubles = 63;          // per member slot of a record: Z (36), Jm^T Jm (21, upper triangle in row order), g (6)
 constexpr int kRfitN = 6 * kRfitSlots;    // 96: row stride of S, delta and g
-constexpr int kRfitMaxPts = CTAG_RIG_MAX_POINTS;
 // flags of a record: kRecLeftOut (it does not describe its detection record: never for records k_rig_solve wrote) and kRecSingular
 
 struct RfitLds {
-    int32_t src[kRfitMaxPts];        // point i: its descriptor (point_desc, ctag_pose_dev.h; camera 0)
+    int32_t src[kFitMaxPts];         // point i: its descriptor (point_desc, ctag_pose_dev.h; camera 0)
     int32_t mstart[kRfitSlots + 1];  // member k owns the points mstart[k] .. mstart[k + 1] - 1
     int32_t mmodel[kRfitSlots];      // its model index
     int8_t table[kRfitSlots];        // model slot of the rig -> member, -1 where absent
 };
 
-// Observation records r0 .. r1-1 (indices into obs, which holds rig-pose record indices): workspace slot r - r0 gets the 63 doubles of
-// every member, table row r the model-slot -> member map, flags[r] the record's state.
+// Observation records r0 .. r1-1 (indices into obs, which holds rig-pose record indices): workspace slot r - r0 gets the slot block
+// (ctag_schur6.h) of every member, table row r the model-slot -> member map, flags[r] the record's state.
 __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __restrict__ res, int n_frames, const ctag_rig_pose_rec* __restrict__ recs,
                                                     const int32_t* __restrict__ obs, int r0, int r1, PoseModelDev model,
                                                     const int32_t* __restrict__ slot_of_model, PoseCam cam, double* __restrict__ ws,
@@ -77,37 +77,21 @@ __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __r
         if (lane < kRfitSlots) L.table[lane] = -1;
         wave_sync();
         int n = 0, nmem = 0;
-        bool ok = P.status == CTAG_POSE_OK && P.frame >= 0 && P.frame < n_frames;
-        if (ok) {
-            const ctag_frame_result& FR = res[P.frame];
-            ok = FR.status == CTAG_OK;
-            const int nm = ok ? min(max(FR.n_markers, 0), CTAG_MAX_MARKERS) : 0;
-            const ctag_feature_rec* F0 = FR.features;
-            for (int k = 0; k < nm && ok; k++) {  // wave-uniform
-                if (!((P.member_mask[k >> 5] >> (k & 31)) & 1u)) continue;
-                const int mi = model_lookup(model, FR.markers[k].marker_id);
-                if (mi < 0 || slot_of_model[mi] < 0 || nmem >= kRfitSlots) {
-                    ok = false;
-                    break;
-                }
-                const int base = n;
-                int nl = 0;
-                const int st = marker_points(FR, FR.markers[k], model.model_size, kPoseMaxPts, nl, [&](const ctag_feature_rec& F, int pos, int cnt, int i0) {
-                    if (lane < cnt && base + i0 + cnt <= kRfitMaxPts) L.src[base + i0 + lane] = point_desc((int)(&F - F0), lane, 0, pos);
-                });
-                if (st != CTAG_POSE_OK || base + nl > kRfitMaxPts) {
-                    ok = false;
-                    break;
-                }
-                if (lane == 0) {
-                    L.mstart[nmem] = base;
-                    L.mmodel[nmem] = mi;
-                    L.table[slot_of_model[mi]] = (int8_t)nmem;
-                }
-                nmem++;
-                n += nl;
-            }
-        }
+        bool ok = P.status == CTAG_POSE_OK && P.frame >= 0 && P.frame < n_frames && res[P.frame].status == CTAG_OK;
+        ok = ok && fit_member_walk(res[P.frame], P.member_mask, model, lane, 0, n,
+                                   // a member: its model has a slot in a system, and the record has room for it.  It is entered here, before
+                                   // its points are walked; should they turn the record down, the record is left out and the entry is never read
+                                   [&](int mi, int base) {
+                                       if (slot_of_model[mi] < 0 || nmem >= kRfitSlots) return false;
+                                       if (lane == 0) {
+                                           L.mstart[nmem] = base;
+                                           L.mmodel[nmem] = mi;
+                                           L.table[slot_of_model[mi]] = (int8_t)nmem;
+                                       }
+                                       nmem++;
+                                       return true;
+                                   },
+                                   [&](int i, int32_t desc, int) { L.src[i] = desc; });
         if (lane == 0) L.mstart[min(nmem, kRfitSlots)] = n;
         ok = ok && n == P.n_points && n >= 4 && nmem >= 2;
         double x[6];
@@ -122,6 +106,13 @@ __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __r
         const ctag_frame_result& FR = res[P.frame];
         double R[9], dR[27];
         ctl::angle_axis_rot(x, R, dR);
+        // point i of member k's run: its residual, the rows of Jp, and Y, the model point
+        auto point = [&](int k, int i, double* Y, double& q0, double& q1, double* j0, double* j1) {
+            const int s = L.src[i];
+            double xn, yn, ob[2];
+            corner_point(cam, model.corners + (size_t)L.mmodel[k] * model.model_size * 24, FR.features[desc_feature(s)], desc_pos(s), desc_q(s), xn, yn, ob, Y);
+            point_residual(R, dR, x, cam.fx, cam.fy, cam.cx, cam.cy, Y, ob, q0, q1, j0, j1, true);
+        };
         // ---- pass 1: U and sum Jp^T r over the record's points, member by member, lane l owning points l, l + 64, ... of a member's run
         double H[21], b[6];
 #pragma unroll
@@ -129,13 +120,10 @@ __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __r
 #pragma unroll
         for (int a = 0; a < 6; a++) b[a] = 0.0;
         for (int k = 0; k < nmem; k++) {
-            const float* __restrict__ corners = model.corners + (size_t)L.mmodel[k] * model.model_size * 24;
             const int i1 = L.mstart[k + 1];
             for (int i = L.mstart[k] + lane; i < i1; i += 64) {
-                const int s = L.src[i];
-                double xn, yn, ob[2], X[3], q0, q1, j0[6], j1[6];
-                corner_point(cam, corners, FR.features[desc_feature(s)], desc_pos(s), desc_q(s), xn, yn, ob, X);
-                point_residual(R, dR, x, cam.fx, cam.fy, cam.cx, cam.cy, X, ob, q0, q1, j0, j1, true);
+                double Y[3], q0, q1, j0[6], j1[6];
+                point(k, i, Y, q0, q1, j0, j1);
                 gram6_add(j0, j1, H);
                 grad6_add(j0, j1, q0, q1, b);
             }
@@ -144,10 +132,9 @@ __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __r
         const bool pd = pose_block6(H, b, Lc);  // the same in every lane; b is y from here on
         if (lane == 0) flags[r] = pd ? 0 : kRecSingular;
         if (!pd) continue;
-        // ---- pass 2: the 63 doubles of every member
-        double* W = ws + (size_t)(r - r0) * kRfitSlots * kRfitDoubles;
+        // ---- pass 2: the slot block of every member, Jm = (dr/dY) [-[Y]x | I]
+        double* W = ws + (size_t)(r - r0) * kRfitSlots * kSlotDoubles;
         for (int k = 0; k < nmem; k++) {
-            const float* __restrict__ corners = model.corners + (size_t)L.mmodel[k] * model.model_size * 24;
             const int i1 = L.mstart[k + 1];
             double Z[36], A[21], gm[6];
 #pragma unroll
@@ -156,108 +143,33 @@ __global__ __launch_bounds__(64) void k_rfit_record(const ctag_frame_result* __r
             for (int e = 0; e < 21; e++) A[e] = 0.0;
 #pragma unroll
             for (int e = 0; e < 6; e++) gm[e] = 0.0;
-            for (int i = L.mstart[k] + lane; i < i1; i += 64) {
-                const int s = L.src[i];
-                double xn, yn, ob[2], Y[3], q0, q1, j0[6], j1[6];
-                corner_point(cam, corners, FR.features[desc_feature(s)], desc_pos(s), desc_q(s), xn, yn, ob, Y);
-                point_residual(R, dR, x, cam.fx, cam.fy, cam.cx, cam.cy, Y, ob, q0, q1, j0, j1, true);
-                double x0[3], x1[3], m0[6], m1[6];
+            for (int i = L.mstart[k] + lane; i < i1; i += 64) {  // the same lanes as in pass 1: they decide the order of the wave sums
+                double Y[3], q0, q1, j0[6], j1[6], x0[3], x1[3], m0[6], m1[6];
+                point(k, i, Y, q0, q1, j0, j1);
                 point_dX(R, j0, j1, x0, x1);  // d residual / d Y
-                // Jm = (dr/dY) [-[Y]x | I]: the rotation columns are Y x (dr/dY)
-                m0[0] = Y[1] * x0[2] - Y[2] * x0[1];
-                m0[1] = Y[2] * x0[0] - Y[0] * x0[2];
-                m0[2] = Y[0] * x0[1] - Y[1] * x0[0];
-                m1[0] = Y[1] * x1[2] - Y[2] * x1[1];
-                m1[1] = Y[2] * x1[0] - Y[0] * x1[2];
-                m1[2] = Y[0] * x1[1] - Y[1] * x1[0];
-#pragma unroll
-                for (int m = 0; m < 3; m++) {
-                    m0[3 + m] = x0[m];
-                    m1[3 + m] = x1[m];
-                }
-                int e = 0;
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-#pragma unroll
-                    for (int c = 0; c < 6; c++) {
-                        Z[a * 6 + c] += j0[a] * m0[c];
-                        Z[a * 6 + c] += j1[a] * m1[c];
-                    }
-#pragma unroll
-                    for (int c = a; c < 6; c++) {
-                        A[e] += m0[a] * m0[c];
-                        A[e] += m1[a] * m1[c];
-                        e++;
-                    }
-                    gm[a] += m0[a] * q0;
-                    gm[a] += m1[a] * q1;
-                }
+                slot_rows(Y, x0, x1, m0, m1);
+                cross6_add(j0, j1, m0, m1, Z);
+                gram6_add(m0, m1, A);
+                grad6_add(m0, m1, q0, q1, gm);
             }
-#pragma unroll
-            for (int e = 0; e < 36; e++) Z[e] = wave_sum_f64(Z[e]);
-#pragma unroll
-            for (int e = 0; e < 21; e++) A[e] = wave_sum_f64(A[e]);
-#pragma unroll
-            for (int e = 0; e < 6; e++) gm[e] = wave_sum_f64(gm[e]);
-#pragma unroll
-            for (int c = 0; c < 6; c++) {  // column c of Z <- L^-1 (column c), g_c -= Z_c . y
-                double z[6];
-#pragma unroll
-                for (int a = 0; a < 6; a++) z[a] = Z[a * 6 + c];
-                gm[c] -= forward6_dot(Lc, z, b);
-#pragma unroll
-                for (int a = 0; a < 6; a++) Z[a * 6 + c] = z[a];
-            }
-            if (lane == 0) {
-                double* O = W + (size_t)k * kRfitDoubles;
-#pragma unroll
-                for (int e = 0; e < 36; e++) O[e] = Z[e];
-#pragma unroll
-                for (int e = 0; e < 21; e++) O[36 + e] = A[e];
-#pragma unroll
-                for (int e = 0; e < 6; e++) O[57 + e] = gm[e];
-            }
+            slot_finish(Z, A, gm, Lc, b, lane, W + (size_t)k * kSlotDoubles);
         }
     }
 }
 
-// Adds records r0 .. r1-1 to S and g of rig blockIdx.y.  Thread t < 96 x 96: entry (i, j) = (t / 96, t % 96) of S, the threads with
-// i <= j work and write both triangles; 96 x 96 <= t < 96 x 96 + 96: entry t - 96 x 96 of g.  S: [n_rigs][96][96], g: [n_rigs][96]; model
-// slot a of the rig owns rows 6a .. 6a + 5.
-__global__ __launch_bounds__(256) void k_rfit_assemble(const double* __restrict__ ws, const int8_t* __restrict__ table, const int32_t* __restrict__ rec_rig,
-                                                       const int32_t* __restrict__ flags, int r0, int r1, double* __restrict__ S, double* __restrict__ g) {
-    const int rig = blockIdx.y;
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    constexpr int NN = kRfitN * kRfitN;
-    const int i = t < NN ? t / kRfitN : t - NN, j = t < NN ? t - i * kRfitN : 0;
-    const bool is_s = t < NN && i <= j, is_g = t >= NN && t < NN + kRfitN;
-    if (!is_s && !is_g) return;
-    const int a = i / 6, p = i - 6 * a, bs = j / 6, q = j - 6 * bs;
-    double* dst = is_s ? S + (size_t)rig * NN + (size_t)i * kRfitN + j : g + (size_t)rig * kRfitN + i;
-    double acc = *dst;
-    int ea = 0;  // index of (p, q) in the upper triangle's row order
-    if (is_s && a == bs) ea = p * 6 - p * (p - 1) / 2 + (q - p);
-    for (int r = r0; r < r1; r++) {
-        if (rec_rig[r] != rig || flags[r] != 0) continue;  // the same for the whole block
-        const int ka = table[(size_t)r * kRfitSlots + a];
-        if (ka < 0) continue;
-        const double* za = ws + ((size_t)(r - r0) * kRfitSlots + ka) * kRfitDoubles;
-        if (is_g) {
-            acc += za[57 + p];
-            continue;
-        }
-        const int kb = table[(size_t)r * kRfitSlots + bs];
-        if (kb < 0) continue;
-        const double* zb = ws + ((size_t)(r - r0) * kRfitSlots + kb) * kRfitDoubles;
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; k++) s += za[k * 6 + p] * zb[k * 6 + q];
-        acc -= s;
-        if (a == bs) acc += za[36 + ea];
+// k_fit_assemble's SlotOf: a row of blocks per rig; the record's table row says which member holds a model slot of the rig, another
+// rig's record holds none (a block-uniform branch)
+struct RfitSlotOf {
+    const int8_t* table;
+    const int32_t* rec_rig;
+    __device__ int group() const { return blockIdx.y; }
+    __device__ bool operator()(int r, int a, int b, int& ka, int& kb) const {
+        if (rec_rig[r] != group()) return false;
+        ka = table[(size_t)r * kRfitSlots + a];
+        kb = table[(size_t)r * kRfitSlots + b];
+        return ka >= 0 && kb >= 0;
     }
-    *dst = acc;
-    if (is_s && i != j) S[(size_t)rig * NN + (size_t)j * kRfitN + i] = acc;
-}
+};
 
 }  // namespace ctag
 
@@ -272,60 +184,29 @@ struct Rigid {  // X_rig = R X_in + t
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
 };
 
-void mat_mul(const double* A, const double* B, double* C) {  // C = A B, 3x3 row-major, sums in index order
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
-}
-
-void mat_vec(const double* A, const double* v, double* o) {
-    for (int i = 0; i < 3; i++) o[i] = A[i * 3] * v[0] + A[i * 3 + 1] * v[1] + A[i * 3 + 2] * v[2];
-}
-
 // The device side of one call: the rigs' systems (a group is a rig), the record workspace, and the slots of the models in them.
-struct RfitWork : fit::Systems {
-    fit::Call c;
+struct RfitWork : fit::SlotSystems<ctag::kRfitN> {
     std::vector<int32_t> slot_of_model;  // [n_models]: the model's slot in its rig's system, -1 outside every system
-    std::vector<int32_t> n_slots, drop;  // [n_rigs]
-    ctag::DevBuf<int32_t> d_slot, d_n_slots, d_drop;
+    ctag::DevBuf<int32_t> d_slot;
     ctag::DevBuf<int8_t> d_table;
-    ctag::DevBuf<double> d_ws;
 
     int setup(int pass_records) {
-        const int n_rigs = (int)n_slots.size(), n_models = (int)slot_of_model.size();
-        if ((size_t)n_rigs * ctag::kRfitN * ctag::kRfitN * 8 > ((size_t)2 << 30)) return CTAG_ERR_LIMIT;
-        const int rc = Systems::setup(c, n_rigs, ctag::kRfitN, pass_records, ctag::kRfitPassRecords);
+        const int n_models = (int)slot_of_model.size();
+        const int rc = SlotSystems::setup(pass_records, ctag::kRfitPassRecords);
         if (rc != CTAG_OK) return rc;
         FIT_HIP(d_table.grow((size_t)std::max(R, 1) * ctag::kRfitSlots));
-        FIT_HIP(d_ws.grow((size_t)pass * ctag::kRfitSlots * ctag::kRfitDoubles));
-        FIT_HIP(d_n_slots.grow(n_rigs));
-        FIT_HIP(d_drop.grow(n_rigs));
         FIT_HIP(d_slot.grow(std::max(n_models, 1)));
         if (n_models > 0) FIT_HIP(hipMemcpyAsync(d_slot.p, slot_of_model.data(), sizeof(int32_t) * n_models, hipMemcpyHostToDevice, c.s));
-        FIT_HIP(hipMemcpyAsync(d_n_slots.p, n_slots.data(), sizeof(int32_t) * n_rigs, hipMemcpyHostToDevice, c.s));
-        FIT_HIP(hipMemcpyAsync(d_drop.p, drop.data(), sizeof(int32_t) * n_rigs, hipMemcpyHostToDevice, c.s));
         return CTAG_OK;
     }
 
-    // S and g of every rig at (model, recs_dev); slot 2 times the record and the assemble kernel together.  Waits.
+    // S and g of every rig at (model, recs_dev).  Waits.
     int build_system(const ctag_model* model, const ctag_rig_pose_rec* recs_dev) {
         const ctag::PoseModelDev md{model->n_models, model->model_size, model->d_ids.p, model->d_corners.p};
-        constexpr int kThreads = ctag::kRfitN * ctag::kRfitN + ctag::kRfitN;
-        return build(c, [&](int r0, int r1) {
-            if (c.mark(0) != CTAG_OK) return CTAG_ERR_HIP;
+        return build_timed(c, [&](int r0, int r1) {
             hipLaunchKernelGGL(ctag::k_rfit_record, dim3(std::min(r1 - r0, ctag::kRfitGrid)), dim3(64), 0, c.s, c.res, c.n_frames, recs_dev, d_obs.p, r0, r1, md,
                                d_slot.p, c.cam, d_ws.p, d_table.p, d_flags.p);
-            hipLaunchKernelGGL(ctag::k_rfit_assemble, dim3((kThreads + 255) / 256, n_groups), dim3(256), 0, c.s, d_ws.p, d_table.p, d_rec_group.p, d_flags.p, r0, r1,
-                               d_S.p, d_g.p);
-            if (fit::launched() != CTAG_OK || c.mark(1) != CTAG_OK || c.reached(1) != CTAG_OK) return CTAG_ERR_HIP;
-            c.add_ms(2, 0);
-            return CTAG_OK;
-        });
-    }
-
-    int solve(const std::vector<double>& lambda, const std::vector<int32_t>& active, int bad_flags, std::vector<double>& delta, std::vector<int32_t>& bad) {
-        return Systems::solve(c, lambda, active, bad_flags, delta, bad, [&]() {
-            hipLaunchKernelGGL(ctag::k_fit_solve<ctag::kRfitN>, dim3(n_groups), dim3(ctag::kFitSolveThreads), 0, c.s, d_S.p, d_g.p, d_n_slots.p, d_drop.p, d_lambda.p, d_active.p,
-                               d_delta.p, d_bad.p);
+            assemble(ctag::RfitSlotOf{d_table.p, d_rec_group.p}, r0, r1);
         });
     }
 };
@@ -333,10 +214,7 @@ struct RfitWork : fit::Systems {
 int rfit_opts(const ctag_rig_fit_opts* o, ctag_rig_fit_opts& r) {
     ctag_rig_fit_opts_default(&r);
     if (o) r = *o;
-    if (r.max_rounds < 0 || r.min_frames < 1) return CTAG_ERR_ARG;
-    for (double v : {r.lambda0, r.lambda_max, r.rel_tol})
-        if (!std::isfinite(v) || !(v > 0.0)) return CTAG_ERR_ARG;
-    return CTAG_OK;
+    return r.max_rounds >= 0 && r.min_frames >= 1 && fit::lm_opts_ok(r) ? CTAG_OK : CTAG_ERR_ARG;
 }
 
 struct RigsGuard {
@@ -353,15 +231,15 @@ void apply_rigid(const ctag_model* in, ctag_model* W, int m, const Rigid& T) {
         const float* p = &in->corners[((size_t)m * pm + c) * 3];
         const double X[3] = {(double)p[0], (double)p[1], (double)p[2]};
         double Y[3];
-        mat_vec(T.R, X, Y);
+        fit::mat_vec(T.R, X, Y);
         for (int k = 0; k < 3; k++) W->corners[((size_t)m * pm + c) * 3 + k] = (float)(Y[k] + T.t[k]);
     }
     const double B[3] = {(double)in->base[3 * m], (double)in->base[3 * m + 1], (double)in->base[3 * m + 2]};
     const double Ax[3] = {(double)in->axis[3 * m], (double)in->axis[3 * m + 1], (double)in->axis[3 * m + 2]};
     double Y[3];
-    mat_vec(T.R, B, Y);
+    fit::mat_vec(T.R, B, Y);
     for (int k = 0; k < 3; k++) W->base[3 * m + k] = (float)(Y[k] + T.t[k]);
-    mat_vec(T.R, Ax, Y);
+    fit::mat_vec(T.R, Ax, Y);
     for (int k = 0; k < 3; k++) W->axis[3 * m + k] = (float)Y[k];
 }
 
@@ -411,23 +289,7 @@ int rfit_probe_system(ctag_handle* h, const ctag_frame_result* results, int n_fr
     if (rc != CTAG_OK) return rc;
     rc = w.build_system(model, d_recs.p);
     if (rc != CTAG_OK) return rc;
-    std::vector<double> lam(n_rigs, lambda), d;
-    std::vector<int32_t> active(n_rigs, 0), bad;
-    active[rig] = 1;
-    rc = w.solve(lam, active, kRecSingular, d, bad);  // a caller's record may be left out; that does not make the rig bad here
-    if (rc != CTAG_OK) return rc;
-    const int N = 6 * w.n_slots[rig];
-    std::vector<double> Sf((size_t)kRfitN * kRfitN), gf(kRfitN);
-    FIT_HIP(hipMemcpy(Sf.data(), w.d_S.p + (size_t)rig * kRfitN * kRfitN, sizeof(double) * Sf.size(), hipMemcpyDeviceToHost));
-    FIT_HIP(hipMemcpy(gf.data(), w.d_g.p + (size_t)rig * kRfitN, sizeof(double) * kRfitN, hipMemcpyDeviceToHost));
-    for (int i = 0; i < N; i++) {
-        for (int j = 0; j < N; j++) S[(size_t)i * N + j] = Sf[(size_t)i * kRfitN + j];
-        g[i] = gf[i];
-        delta[i] = d[(size_t)rig * kRfitN + i];
-    }
-    *n_unknowns = N;
-    *bad_pivot = bad[rig];
-    return CTAG_OK;
+    return w.probe(rig, lambda, S, g, delta, n_unknowns, bad_pivot);
 }
 
 }  // namespace ctag
@@ -534,30 +396,8 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
                         cnt[(size_t)b * k + a]++;
                     }
             }
-        int anchor = -1;
-        for (int a = 0; a < k && anchor < 0; a++)
-            for (int b = 0; b < k; b++)
-                if (cnt[(size_t)a * k + b] >= opts.min_frames) {
-                    anchor = a;
-                    break;
-                }
-        if (anchor < 0) continue;
-        std::vector<uint8_t> in_tree(k, 0);
-        in_tree[anchor] = 1;
-        placed[M[anchor]] = 1;
-        int n_placed = 1;
-        for (;;) {
-            int best = opts.min_frames - 1, ba = -1, bb = -1;
-            for (int b = 0; b < k; b++) {  // ascending b, then ascending a: the first of equal counts stays
-                if (in_tree[b]) continue;
-                for (int a = 0; a < k; a++)
-                    if (in_tree[a] && cnt[(size_t)a * k + b] > best) {
-                        best = cnt[(size_t)a * k + b];
-                        ba = a;
-                        bb = b;
-                    }
-            }
-            if (bb < 0) break;
+        std::vector<uint8_t> in_tree;
+        const int anchor = fit::covisibility_tree(k, cnt, opts.min_frames, in_tree, [&](int ba, int bb, int best) {
             const int ma = M[ba], mb = M[bb];
             double sumR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, sumt[3] = {0, 0, 0};
             for (int f = 0; f < n_frames; f++) {
@@ -568,10 +408,10 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
                 ctl::angle_axis_rot(poses[ib].rvec, Rb, nullptr);
                 for (int i = 0; i < 3; i++)
                     for (int j = 0; j < 3; j++) RaT[i * 3 + j] = Ra[j * 3 + i];
-                mat_mul(RaT, Rb, Q);
+                fit::mat_mul(RaT, Rb, Q);
                 for (int i = 0; i < 9; i++) sumR[i] += Q[i];
                 for (int i = 0; i < 3; i++) d[i] = poses[ib].tvec[i] - poses[ia].tvec[i];
-                mat_vec(RaT, d, e);
+                fit::mat_vec(RaT, d, e);
                 for (int i = 0; i < 3; i++) sumt[i] += e[i];
             }
             Rigid E;
@@ -580,26 +420,25 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
             for (int i = 0; i < 3; i++) E.t[i] = sumt[i] / (double)best;
             Rigid& Tb = T[mb];
             const Rigid& Ta = T[ma];
-            mat_mul(Ta.R, E.R, Tb.R);
+            fit::mat_mul(Ta.R, E.R, Tb.R);
             double e[3];
-            mat_vec(Ta.R, E.t, e);
+            fit::mat_vec(Ta.R, E.t, e);
             for (int i = 0; i < 3; i++) Tb.t[i] = e[i] + Ta.t[i];
-            in_tree[bb] = 1;
-            placed[mb] = 1;
-            n_placed++;
             model_stats[mb].parent = ma;
             model_stats[mb].n_frames_with_parent = best;
-        }
-        rig_stats[g].status = CTAG_POSE_OK;
-        rig_stats[g].anchor = M[anchor];
-        rig_stats[g].n_placed = n_placed;
-        rig_stats[g].n_unplaced = k - n_placed;
+        });
+        if (anchor < 0) continue;
         for (int a = 0; a < k; a++)
             if (in_tree[a]) {
                 if (a == anchor) w.drop[g] = w.n_slots[g];
                 w.slot_of_model[M[a]] = w.n_slots[g]++;
+                placed[M[a]] = 1;
                 model_stats[M[a]].status = CTAG_POSE_OK;
             }
+        rig_stats[g].status = CTAG_POSE_OK;
+        rig_stats[g].anchor = M[anchor];
+        rig_stats[g].n_placed = w.n_slots[g];
+        rig_stats[g].n_unplaced = k - w.n_slots[g];
     }
     auto moves = [&](int m) { return placed[m] && rig_stats[rigs->rig_of_model[m]].anchor != m; };  // placed and not its rig's anchor
     auto report_transforms = [&](const std::vector<Rigid>& TT) {
@@ -699,8 +538,8 @@ int ctag_rig_fit_device(ctag_handle* h, const ctag_frame_result* results_dev, in
             }
             double E[9], e[3];
             ctl::angle_axis_rot(d, E, nullptr);
-            mat_mul(E, T[m].R, Tt[m].R);
-            mat_vec(E, T[m].t, e);
+            fit::mat_mul(E, T[m].R, Tt[m].R);
+            fit::mat_vec(E, T[m].t, e);
             for (int i = 0; i < 3; i++) Tt[m].t[i] = e[i] + d[3 + i];
             apply_rigid(in, W, m, Tt[m]);
             any_trial = true;

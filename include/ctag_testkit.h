@@ -150,7 +150,7 @@ int ctag_testkit_model_fit_system(ctag_handle* h, const ctag_frame_result* resul
 int ctag_testkit_model_fit_limits(int32_t* out, int capacity);
 
 /* ---- the reduced system of the rig assembly (cylindertag_amd/csrc/k_rig_fit.hip; include/ctag_pose.h, rig assembly) ---------------------------
- * k_rfit_record, k_rfit_assemble and k_rfit_solve at a caller-given state instead of inside the assembly's loop.  results: n_frames HOST
+ * k_rfit_record, k_fit_assemble<96> and k_fit_solve<96> at a caller-given state instead of inside the assembly's loop.  results: n_frames HOST
  * detection records; rig_poses: the n_frames x n_rigs HOST records ctag_rig_pose_batch_device gives over them on `model` with `rigs` -- the
  * CTAG_POSE_OK ones with n_members >= 2 are the observation records (rule 4) and their rvec / tvec the state; model: the corner lists, already
  * in the rig's frame; lambda: the damping (any finite value: a negative one makes the system indefinite).  For rig `rig`, whose M models (2 ..
@@ -166,7 +166,7 @@ int ctag_testkit_rig_fit_system(ctag_handle* h, const ctag_frame_result* results
 int ctag_testkit_rig_fit_limits(int32_t* out, int capacity);
 
 /* ---- the reduced system of the camera set fit (cylindertag_amd/csrc/k_cam_fit.hip; include/ctag_pose.h, camera set fit) -------------------
- * k_cfit_record, k_cfit_assemble and k_fit_solve<48> at a caller-given state instead of inside the fit's loop.  results: n_cameras x n_frames
+ * k_cfit_record, k_fit_assemble<48> and k_fit_solve<48> at a caller-given state instead of inside the fit's loop.  results: n_cameras x n_frames
  * HOST detection records, camera-major (n_cameras is the set's); mv_poses: the n_frames x n_rigs HOST records
  * ctag_mv_rig_pose_batch_device gives over them under `cams` -- the CTAG_POSE_OK ones with n_cameras >= 2 are the observation records
  * (rule 3) and their rvec / tvec the state; lambda: the damping (any finite value: a negative one makes the system indefinite).  Camera c of

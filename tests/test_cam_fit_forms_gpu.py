@@ -1,4 +1,4 @@
-"""GPU tests of the camera set fit's kernels through the probe ctag_testkit_camera_fit_system (k_cfit_record, k_cfit_assemble,
+"""GPU tests of the camera set fit's kernels through the probe ctag_testkit_camera_fit_system (k_cfit_record, k_fit_assemble<48>,
 k_fit_solve<48> at a given state): S, g and delta of every case of tests/cam_fit_shapes.py against the independent statement at the
 rule-2 start, with the anchor in its own slot and (case c) in the last one, the pass-size independence of rule 5, a pivot that is not
 positive, and the limits."""

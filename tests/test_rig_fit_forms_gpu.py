@@ -1,5 +1,5 @@
-"""GPU tests of the rig assembly's kernels through the probe ctag_testkit_rig_fit_system (k_rfit_record, k_rfit_assemble, k_rfit_solve
-at a given state): S, g and delta of every rig of every batch of tests/rig_fit_shapes.py against the independent statement at the
+"""GPU tests of the rig assembly's kernels through the probe ctag_testkit_rig_fit_system (k_rfit_record, k_fit_assemble<96>,
+k_fit_solve<96> at a given state): S, g and delta of every rig of every batch of tests/rig_fit_shapes.py against the independent statement at the
 rule-2 start and at one perturbed state, the pass-size independence of rule 6, a pivot that is not positive, and the limits."""
 import numpy as np
 import pytest
