@@ -349,6 +349,9 @@ static size_t carve_workspace(Workspace& W, size_t frames, char* base) {
     put(W.npacks, F * 8);
     put(W.packs, F * CC * 4);
     put(W.pack_order, F * CC * 4);
+    put(W.npacks2, F * 8);
+    put(W.packs2, F * CC * 4);
+    put(W.pack_order2, F * CC * 4);
     put(W.welsch_rs, std::min<size_t>(F, kLatencyFrames) * kLatLines * 20 * 6 * 4);
     put(W.quad_derived, F * kQuadStride * 48);
     put(W.quad_index, F * kQuadStride * 4);

@@ -227,6 +227,9 @@ struct Workspace {
     int32_t* npacks = nullptr;      // [F][2]          packs, oversize components
     uint32_t* packs = nullptr;      // [F][cand_cap]
     uint32_t* pack_order = nullptr; // [F][cand_cap]
+    int32_t* npacks2 = nullptr;     // [F][2]          the second packed kernel's packs (k_repack), components in them
+    uint32_t* packs2 = nullptr;     // [F][cand_cap]
+    uint32_t* pack_order2 = nullptr;// [F][cand_cap]
     float* welsch_rs = nullptr;     // [min(F, kLatencyFrames)][kLatLines][20][6]: line + err (as a double) of every restart, few-frame calls only
     const uint8_t* pick_table = nullptr;  // [kPickN][20][10], owned by the handle
     const uint16_t* pick_table16 = nullptr;  // [kPickN2 - kPickN][20][10]

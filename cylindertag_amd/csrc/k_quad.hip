@@ -46,6 +46,9 @@ struct QuadPtrs {
     int32_t* npacks;       // [F][2] packs, oversize components
     uint32_t* packs;       // [F][cand_cap] first entry of pack_order | count << 24, longest first
     uint32_t* pack_order;  // [F][cand_cap] candidate indices by descending boundary capacity
+    int32_t* npacks2;      // [F][2] the second packed kernel's own packs (k_repack), the components in them
+    uint32_t* packs2;      // [F][cand_cap] first entry of pack_order2 | count << 24, longest first
+    uint32_t* pack_order2; // [F][cand_cap] the packed components the first kernel left a boundary of, by descending boundary length
     unsigned long long* stamps;  // developer aid (CTAG_QUAD_STAMPS=1): cycles per phase of k_quad_edges, else null
     // tunables (include/ctag.h: ctag_params; the reference's values in brackets)
     float thr_line, thr_expand, rac;  // threshold_line [1.8], threshold_expand [1.2], threshold_RAC [0.3]
@@ -64,6 +67,7 @@ static QuadPtrs quad_ptrs(const ChunkPlan& pl, const Workspace& ws, unsigned lon
     P.line_fit = ws.line_fit, P.cand_aux = ws.cand_aux, P.pick_table = ws.pick_table, P.pick_table16 = ws.pick_table16;
     P.pool_tile = ws.pool_tile, P.member_head = ws.member_head, P.member_next = ws.member_next;
     P.npacks = ws.npacks, P.packs = ws.packs, P.pack_order = ws.pack_order, P.stamps = stamps;
+    P.npacks2 = ws.npacks2, P.packs2 = ws.packs2, P.pack_order2 = ws.pack_order2;
     P.thr_line = ws.kp.thr_line, P.thr_expand = ws.kp.thr_expand, P.rac = ws.kp.rac, P.c2_far = ws.kp.c2_far, P.c2_near = ws.kp.c2_near, P.expand_eps = ws.kp.expand_eps;
     P.cand_cap = ws.cand_cap, P.line_cap = ws.line_cap, P.cl_cap = ws.cl_cap;
     P.mask = pl.fused ? reinterpret_cast<const uint64_t*>(ws.half) : nullptr, P.mask_words = ws.g.hcols >> 6;  // the fused sweep's threshold mask
@@ -356,7 +360,7 @@ __device__ __forceinline__ void welsch_restart(const Pts pts, int n, const Picks
 #endif
 constexpr int kPackWords = CTAG_PACK_WORDS;  // LDS words shared by the up to 8 components of a wave (large configuration)
 // Two builds of the packed kernel.  The kernel is bound by dependent LDS round trips (24 % of the issue roof at 2 waves per
-// SIMD), so for frames of 1080p class -- boundaries of ~150 points, a pack of 5 components in 10 KB -- the small configuration
+// SIMD), so for frames of 1080p class -- boundaries of ~150 points, a pack of 5 components in 10 KB (the first kernel's packs, sized by box capacity; the second kernel's are k_repack's, sized by traced length) -- the small configuration
 // runs 4 waves per SIMD (128 VGPRs, 61 of them spilled to scratch: still 6.8 -> 6.2 ms per 4096 frames); 4K frames have
 // components four times the size and keep the large one (same-box A/B: 8.4 vs 7.9 ms per 1024 frames with the small one).
 #ifndef CTAG_PACK_WAVES_P2
@@ -372,6 +376,12 @@ __host__ __device__ __forceinline__ int pack_need(int w, int h) {
     const int C = pack_points(w, h);
     return ((w + 1) & ~1) + 2 * h + 2 * C + 4;
 }
+// LDS words a component of n boundary points needs in the packed builds' SECOND kernel (PHASE 2: extended RDP + expand_line), which holds the two
+// ping-pong lists W / Wn and nothing else.  Every LDS index it forms is one of: W[init], W[end], W[it] with init < it < end <= n - 1; W[(a + k) % n]
+// (tri2); sg_expand_line's W[k], init <= k <= end, and W[idxL / idxR], which wrap into [0, n) (n >= 3 there: at most three wraps of at most 8 steps);
+// the cluster copy's W[idx], idx in [0, n); the erase's W[src] with src = k - keep + m < new_n - keep + m = n and W[b + 1 + k] < a < n; Wn[k], k < new_n < n.
+// So n words each; each list starts on an even word.  n <= pack_points(w, h), hence need2(n) <= pack_need(w, h): whatever k_pack packed fits alone.
+__host__ __device__ __forceinline__ int need2(int n) { return 2 * ((n + 1) & ~1); }
 // the packed kernel takes every component whose working set fits the wave's LDS budget (the silhouette scan walks a wide
 // box in passes of 128 columns); the rest are "big" and get a wave of their own (k_quad_edges_packed<64, ...>)
 // big_points: in latency mode (a few frames per call) components with a long boundary also go there -- a whole wave per
@@ -402,8 +412,81 @@ struct CornerPre {
 // anywhere and were the kernel's tail: a 150-point boundary is ~0.3 ms of dependent LDS round trips).
 // One block per frame; rank sort in LDS like k_candidates.  Oversize components are skipped; the whole-wave builds take them.
 // =====================================================================================================
-// Block size: 64 for batches; 1024 for calls of a few frames (the rank sort is nc / threads trips of nc comparisons).  The pack builder -- a
-// sequential scan of the ordered list -- runs on wave 0 with the list in registers, 64 entries at a time, read back with v_readlane.
+// ---- what k_pack and k_repack share: an order of a frame's items by descending key (negative keys last), and the pack builder over that order ----
+// Rank sort in LDS, n <= kLdsCand items: s_ord[rank] = item; ties in item order.  Returns how many of this thread's items have a negative key.
+__device__ __forceinline__ int pack_rank_sort(const int* s_key, uint16_t* s_ord, int n, int tid, int nt) {
+    int neg = 0;
+    for (int i = tid; i < n; i += nt) {
+        const int ki = s_key[i];
+        int rank = 0;
+        for (int j = 0; j < n; j++) {
+            const int kj = s_key[j];
+            rank += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
+        }
+        s_ord[rank] = (uint16_t)i;
+        neg += ki < 0 ? 1 : 0;
+    }
+    return neg;
+}
+// A frame of thousands of blobs (more items than the LDS arrays hold).  The order is scheduling only -- results do not depend on it beyond
+// "negative keys last" -- so a counting sort (descending, keys of kLdsCand - 1 and more in one bucket, ties in arrival order) replaces the
+// rank sort: out[position] = val_of(item).  s_cnt: kLdsCand + 2 counters.  Every thread of the block calls it; returns the number of items
+// with a key >= 0 (they are entries [0, that) of `out`, which the block may read after its next barrier).
+template <class KeyOf, class ValOf>
+__device__ __forceinline__ int pack_counting_sort(int* s_cnt, uint32_t* out, int n, int tid, int nt, KeyOf key_of, ValOf val_of) {
+    constexpr int kB = kLdsCand;  // buckets 0..kB-1: key kB-1-b (longest first); bucket kB: negative keys
+    auto bucket_of = [&](int key) { return key < 0 ? kB : kB - 1 - min(key, kB - 1); };
+    for (int b = tid; b <= kB; b += nt) s_cnt[b] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += nt) atomicAdd(&s_cnt[bucket_of(key_of(i))], 1);
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int b = 0; b <= kB; b++) {
+            const int v = s_cnt[b];
+            s_cnt[b] = run;
+            run += v;
+        }
+        s_cnt[kB + 1] = run;
+    }
+    __syncthreads();
+    const int first_neg = s_cnt[kB];
+    __syncthreads();
+    for (int i = tid; i < n; i += nt) out[atomicAdd(&s_cnt[bucket_of(key_of(i))], 1)] = val_of(i);
+    __syncthreads();
+    return first_neg;
+}
+// The pack builder (wave 0; tid = lane): a pack = consecutive entries of the order's first `npacked`, at most max_per_pack of them, whose needs
+// sum to at most pack_words; need_of(r) = LDS words of entry r.  A sequential scan with the list in registers, 64 entries at a time, read back
+// with v_readlane.  Returns the number of packs.
+template <class NeedOf>
+__device__ __forceinline__ int build_packs(uint32_t* packs, int npacked, int max_per_pack, int pack_words, int tid, NeedOf need_of) {
+    int np = 0, first = -1, cnt = 0, words = 0;  // uniform across the wave
+    for (int r0 = 0; r0 < npacked; r0 += 64) {
+        const int r = r0 + tid;
+        const int need = r < npacked ? need_of(r) : 0;
+        const int m = min(64, npacked - r0);
+        for (int k = 0; k < m; k++) {
+            const int nk = __builtin_amdgcn_readlane(need, k);
+            if (cnt > 0 && (cnt == max_per_pack || words + nk > pack_words)) {
+                if (tid == 0) packs[np] = (uint32_t)first | ((uint32_t)cnt << 24);
+                np++;
+                cnt = 0;
+                words = 0;
+            }
+            if (cnt == 0) first = r0 + k;
+            cnt++;
+            words += nk;
+        }
+    }
+    if (cnt > 0) {
+        if (tid == 0) packs[np] = (uint32_t)first | ((uint32_t)cnt << 24);
+        np++;
+    }
+    return np;
+}
+
+// Block size: 64 for batches; 1024 for calls of a few frames (the rank sort is nc / threads trips of nc comparisons).  The pack builder runs on wave 0.
 __global__ __launch_bounds__(1024) void k_pack(QuadPtrs P, int nframes, int max_per_pack, int big_points, int pack_words, int scan_words) {
     __shared__ int s_key[kLdsCand + 2];
     __shared__ int s_need[kLdsCand];
@@ -418,32 +501,6 @@ __global__ __launch_bounds__(1024) void k_pack(QuadPtrs P, int nframes, int max_
     auto key_of = [&](const Candidate& c) {
         const int w = c.x_max - c.x_min + 1, h = c.y_max - c.y_min + 1;
         return pack_big(c.x_min, w, h, big_points, pack_words, scan_words) ? -1 : pack_points(w, h);  // -1: not packed, sorts last
-    };
-    // the pack builder (wave 0): a pack = consecutive entries [0, npacked) of `order`; need_of(r) = LDS words of entry r
-    auto build_packs = [&](int npacked, auto need_of) {
-        int np = 0, first = -1, cnt = 0, words = 0;  // uniform across the wave
-        for (int r0 = 0; r0 < npacked; r0 += 64) {
-            const int r = r0 + tid;
-            const int need = r < npacked ? need_of(r) : 0;
-            const int m = min(64, npacked - r0);
-            for (int k = 0; k < m; k++) {
-                const int nk = __builtin_amdgcn_readlane(need, k);
-                if (cnt > 0 && (cnt == max_per_pack || words + nk > pack_words)) {
-                    if (tid == 0) packs[np] = (uint32_t)first | ((uint32_t)cnt << 24);
-                    np++;
-                    cnt = 0;
-                    words = 0;
-                }
-                if (cnt == 0) first = r0 + k;
-                cnt++;
-                words += nk;
-            }
-        }
-        if (cnt > 0) {
-            if (tid == 0) packs[np] = (uint32_t)first | ((uint32_t)cnt << 24);
-            np++;
-        }
-        return np;
     };
     // scan_words < 0 (the silhouettes come from k_silhouette_mask): the packed components' cluster-pool slots are handed out HERE, in pack order -- an exclusive prefix
     // sum of their C + 64 words (wave 0) -- instead of by one returning atomic per component in the scan kernel, whose chain of dependent loads it would lengthen
@@ -469,32 +526,10 @@ __global__ __launch_bounds__(1024) void k_pack(QuadPtrs P, int nframes, int max_
         if (tid == 0) P.clp_used[frame] = base;  // (the chain's first kernel that reserves cluster space: nothing has been added yet)
     };
     if (nc > kLdsCand) {
-        // A frame of thousands of blobs (more candidates than the LDS arrays hold).  The order is scheduling only -- results do not
-        // depend on it beyond "oversize components last" -- so a counting sort by boundary capacity (descending, capacities of 2047
-        // and more in one bucket, ties in arrival order) replaces the rank sort, and the pack builder reads the ordered
-        // candidates 64 at a time instead of from LDS.
-        constexpr int kB = kLdsCand;  // buckets 0..kB-1: capacity kB-1-b (longest first); bucket kB: oversize
-        auto bucket_of = [&](int key) { return key < 0 ? kB : kB - 1 - min(key, kB - 1); };
-        for (int b = tid; b <= kB; b += nt) s_key[b] = 0;
-        __syncthreads();
-        for (int i = tid; i < nc; i += nt) atomicAdd(&s_key[bucket_of(key_of(cand[i]))], 1);
-        __syncthreads();
-        if (tid == 0) {
-            int run = 0;
-            for (int b = 0; b <= kB; b++) {
-                const int v = s_key[b];
-                s_key[b] = run;
-                run += v;
-            }
-            s_key[kB + 1] = run;
-        }
-        __syncthreads();
-        const int first_big = s_key[kB];  // oversize components: entries [first_big, nc) of `order`
-        __syncthreads();
-        for (int i = tid; i < nc; i += nt) order[atomicAdd(&s_key[bucket_of(key_of(cand[i]))], 1)] = (uint32_t)i;
-        __syncthreads();
+        // the counting sort by boundary capacity; the pack builder reads the ordered candidates 64 at a time instead of from LDS
+        const int first_big = pack_counting_sort(s_key, order, nc, tid, nt, [&](int i) { return key_of(cand[i]); }, [&](int i) { return (uint32_t)i; });  // oversize components: entries [first_big, nc) of `order`
         if (tid >= 64) return;
-        const int np = build_packs(first_big, [&](int r) {
+        const int np = build_packs(packs, first_big, max_per_pack, pack_words, tid, [&](int r) {
             const Candidate c = cand[order[r]];
             return pack_need(c.x_max - c.x_min + 1, c.y_max - c.y_min + 1);
         });
@@ -513,26 +548,61 @@ __global__ __launch_bounds__(1024) void k_pack(QuadPtrs P, int nframes, int max_
     }
     if (tid == 0) s_key[kLdsCand] = 0;  // number of oversize components
     __syncthreads();
-    for (int i = tid; i < nc; i += nt) {
-        const int ki = s_key[i];
-        int rank = 0;
-        for (int j = 0; j < nc; j++) {
-            const int kj = s_key[j];
-            rank += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
-        }
-        s_ord[rank] = (uint16_t)i;
-        if (ki < 0) atomicAdd(&s_key[kLdsCand], 1);
-    }
+    if (const int neg = pack_rank_sort(s_key, s_ord, nc, tid, nt)) atomicAdd(&s_key[kLdsCand], neg);
     __syncthreads();
     for (int i = tid; i < nc; i += nt) order[i] = s_ord[i];
     if (tid >= 64) return;
     const int nbig = s_key[kLdsCand];  // the oversize components sort last: entries [nc - nbig, nc) of `order`, the whole-wave builds walk only those
-    const int np = build_packs(nc - nbig, [&](int r) { return s_need[s_ord[r]]; });
+    const int np = build_packs(packs, nc - nbig, max_per_pack, pack_words, tid, [&](int r) { return s_need[s_ord[r]]; });
     if (tid == 0) {
         P.npacks[2 * frame] = np;
         P.npacks[2 * frame + 1] = nbig;
     }
     if (scan_words < 0) slot_prefix(nc - nbig, [&](int r) { return (int)s_ord[r]; });
+}
+
+// =====================================================================================================
+// K6r: the packs of the packed builds' SECOND kernel (PHASE 2).  k_pack sizes a component by the CAPACITY of its box -- silhouette arrays,
+// a boundary list and a stack of pack_points(w, h) words each -- which is what the first kernel holds in LDS.  The second kernel holds two lists of
+// the boundary the first one traced (need2(n_boundary) words), and skips the components the first one finalised (no boundary, no pool space).  Both
+// are known when the first kernel ends, so the packed components [0, nc - oversize) of k_pack's order are ranked again, by traced length, longest
+// first (scheduling only, as in k_pack), and packed by need2: more sub-groups of a wave filled, fewer packs for the lockstep kernel to walk.
+// One block of 64 threads per frame (batches only: few-frame calls have no packs).
+// =====================================================================================================
+__global__ __launch_bounds__(64) void k_repack(QuadPtrs P, int nframes, int max_per_pack, int pack_words) {
+    __shared__ int s_key[kLdsCand + 2];
+    __shared__ uint16_t s_ord[kLdsCand];
+    const int frame = blockIdx.x;
+    if (frame >= nframes) return;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int nc = min(P.ncand[frame], P.cand_cap);
+    const int npk = max(nc - P.npacks[2 * frame + 1], 0);
+    const CandAux* aux = P.cand_aux + (size_t)frame * P.cand_cap;
+    const uint32_t* order = P.pack_order + (size_t)frame * P.cand_cap;
+    uint32_t* order2 = P.pack_order2 + (size_t)frame * P.cand_cap;
+    uint32_t* packs2 = P.packs2 + (size_t)frame * P.cand_cap;
+    auto key_of = [&](int r) {  // the traced length; -1: finalised by the first kernel, in no pack
+        const CandAux a = aux[order[r]];
+        return (a.line0 >= 0 && a.n_boundary > 0) ? a.n_boundary : -1;
+    };
+    int nel, np;
+    if (npk > kLdsCand) {
+        nel = pack_counting_sort(s_key, order2, npk, tid, nt, key_of, [&](int r) { return order[r]; });
+        np = build_packs(packs2, nel, max_per_pack, pack_words, tid, [&](int r) { return need2(aux[order2[r]].n_boundary); });
+    } else {
+        for (int r = tid; r < npk; r += nt) s_key[r] = key_of(r);
+        if (tid == 0) s_key[kLdsCand] = 0;  // number of finalised components
+        __syncthreads();
+        if (const int neg = pack_rank_sort(s_key, s_ord, npk, tid, nt)) atomicAdd(&s_key[kLdsCand], neg);
+        __syncthreads();
+        nel = npk - s_key[kLdsCand];
+        for (int i = tid; i < nel; i += nt) order2[i] = order[s_ord[i]];
+        np = build_packs(packs2, nel, max_per_pack, pack_words, tid, [&](int r) { return need2(s_key[s_ord[r]]); });
+    }
+    if (tid == 0) {
+        P.npacks2[2 * frame] = np;
+        P.npacks2[2 * frame + 1] = nel;
+    }
 }
 
 // (the 8-lane sub-groups of a wave run in lockstep: their ordering point is wave_fence, ctag_wave.h -- no barrier)
@@ -1035,7 +1105,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     // SG == 8: the frame's packs; SG == 64: the oversize tail of k_pack's order, one component per wave
     const int nc = min(P.ncand[frame], P.cand_cap);
     const int npk = PHASE == 3 ? nc - P.npacks[2 * frame + 1]  // every packed component: entries [0, nc - oversize) of k_pack's order
+                  : PHASE == 2 ? P.npacks2[2 * frame]          // the second kernel walks k_repack's packs: sized by traced length, not by capacity
                                : P.npacks[2 * frame + (SG == 8 ? 0 : 1)];
+    static_assert(PHASE != 2 || SG == 8, "the second kernel is a packed build");
+    const uint32_t* __restrict__ pack_list = (PHASE == 2 ? P.packs2 : P.packs) + (size_t)frame * P.cand_cap;
+    const uint32_t* __restrict__ pack_ord = (PHASE == 2 ? P.pack_order2 : P.pack_order) + (size_t)frame * P.cand_cap;
     const uint16_t* __restrict__ limg = P.labels + ((size_t)frame * g.hrows) * g.lp;
     const int32_t* __restrict__ tbase = P.tile_base + (size_t)frame * g.tiles_x * g.tiles_y;
     const int32_t* __restrict__ rootof = P.root_of + (size_t)frame * g.pool_cap;
@@ -1054,7 +1128,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
         stamp(-1);
         int first, cnt;
         if constexpr (SG == 8) {
-            const uint32_t pw = P.packs[(size_t)frame * P.cand_cap + pk];
+            const uint32_t pw = pack_list[pk];
             first = (int)(pw & 0xffffffu);
             cnt = (int)(pw >> 24);
         } else if constexpr (PHASE == 3) {
@@ -1065,12 +1139,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             cnt = 1;
         }
         const bool act = sub < cnt;
-        const int ci = (int)P.pack_order[(size_t)frame * P.cand_cap + first + (act ? sub : 0)];
+        const int ci = (int)pack_ord[first + (act ? sub : 0)];
         const Candidate cd = P.cand[(size_t)frame * P.cand_cap + ci];
+        CandAux* aux = P.cand_aux + (size_t)frame * P.cand_cap + ci;
         const int x_min = cd.x_min, y_min = cd.y_min;
         const int w = cd.x_max - cd.x_min + 1, h = cd.y_max - cd.y_min + 1;
         const int C = pack_points(w, h);
-        const int need = act ? (PHASE == 3 ? scan_need(w, h) : pack_need(w, h)) : 0;
+        int nb2 = 0;  // PHASE 2: the length the first kernel traced (> 0: k_repack packs no other component)
+        if constexpr (PHASE == 2) nb2 = aux->n_boundary;
+        const int need = act ? (PHASE == 3 ? scan_need(w, h) : PHASE == 2 ? need2(nb2) : pack_need(w, h)) : 0;
         int off = 0;
 #pragma unroll
         for (int k = 0; k < 64 / SG; k++) {
@@ -1078,7 +1155,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             if (k < sub) off += v;
         }
         if (!act) continue;
-        CandAux* aux = P.cand_aux + (size_t)frame * P.cand_cap + ci;
         if constexpr (SG == 64 && PHASE != 3) {
             // two builds share the oversize components by working-set size: (tier_lo, WORDS] is this one's
             if (need <= tier_lo) continue;
@@ -1099,8 +1175,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
         // traversal needs no bounds checks.
         uint32_t* tb = mem;               // w + 2 words
         uint32_t* lr = tb + w + 2;        // h + 2 words
-        uint32_t* bufA = lr + h + 2;      // C words
-        uint32_t* bufB = bufA + (PHASE == 3 ? h : C);  // C + 1 words (scan only: the row extents, h words each)
+        // (PHASE 2 holds the two ping-pong lists alone, need2(n_boundary) / 2 words each: bufB = W first, bufA = Wn)
+        uint32_t* bufA = PHASE == 2 ? mem + (need >> 1) : lr + h + 2;      // C words
+        uint32_t* bufB = PHASE == 2 ? mem : bufA + (PHASE == 3 ? h : C);  // C + 1 words (scan only: the row extents, h words each)
         uint32_t* lef = bufA;             // P1 only: row extents by atomics (h <= C words each)
         uint32_t* rig = bufB;
         const int sgshift = sub * SG;
@@ -1920,9 +1997,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
         if constexpr (PHASE == 2) {
             p0 = aux->line0;  // the first kernel left the slot here (-1: it gave up on the component, flags and aux are final)
             if (p0 < 0) continue;
-            n = n_boundary = aux->n_boundary;
-            acx = aux->acx;
-            acy = aux->acy;
+            n = nb2;  // (the centroid and the length stay where the first kernel left them, in aux: three registers fewer across the loops below)
             const uint32_t* slot = P.cl_pool + (size_t)frame * P.cl_cap + p0;
             for (int k = sl; k < n; k += SG) bufB[k] = slot[k];
             wave_fence();
@@ -2076,9 +2151,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
         }
         if (sl == 0) {
             aux->line0 = ok ? l0 : -1;
-            aux->acx = ok ? acx : 0.f;
-            aux->acy = ok ? acy : 0.f;
-            aux->n_boundary = n_boundary;
+            if constexpr (PHASE == 2) {
+                if (!ok) aux->acx = 0.f, aux->acy = 0.f;
+            } else {
+                aux->acx = ok ? acx : 0.f;
+                aux->acy = ok ? acy : 0.f;
+                aux->n_boundary = n_boundary;
+            }
         }
         stamp(4);
     }
@@ -2852,12 +2931,14 @@ static void launch_quad_edges(const ChunkPlan& pl, const QuadPtrs& P, const Fram
             hipLaunchKernelGGL((k_quad_edges_packed<64, kScanWords, CTAG_SCAN_WAVES, false, true, 3>), dim3(nframes, pl.scan_gx), dim3(64), 0, s, P, g, nframes, 0);
         if (pl.small_cfg) {
             hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmall, false, REF, 1, true>), grid, dim3(64), 0, s, P, g, nframes, 0);
+            hipLaunchKernelGGL(k_repack, dim3(nframes), dim3(64), 0, s, P, nframes, pl.pack_max, kPackWordsSmall);
             hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmallP2, false, REF, 2>), grid, dim3(64), 0, s, P, g, nframes, 0);
         } else {
             hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWords, CTAG_PACK_WAVES, false, REF, 0, true>), grid, dim3(64), 0, s, P, g, nframes, 0);
         }
     } else if (pl.small_cfg) {
         hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmall, false, REF, 1>), grid, dim3(64), 0, s, P, g, nframes, 0);
+        hipLaunchKernelGGL(k_repack, dim3(nframes), dim3(64), 0, s, P, nframes, pl.pack_max, kPackWordsSmall);
         hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmallP2, false, REF, 2>), grid, dim3(64), 0, s, P, g, nframes, 0);
     } else {
         hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWords, CTAG_PACK_WAVES, false, REF>), grid, dim3(64), 0, s, P, g, nframes, 0);

@@ -36,6 +36,10 @@ extern "C" {
 #define CTAG_DBG_LINES 10     /* int32  [nlines]        point count of every edge cluster handed to the Welsch fit (a4) */
 #define CTAG_DBG_LINE_POINTS 12 /* int32 [sum n][2]       x, y of those clusters' points, cluster after cluster in the order of CTAG_DBG_LINES */
 #define CTAG_DBG_LINE_FITS 13   /* float [nlines][4]      vx, vy, x0, y0 the Welsch fit gave every one of them */
+#define CTAG_DBG_PACKS 14       /* int32 [5 + np1 + np2 + nc + nel + nc]  the packed boundary kernels' work lists of a frame of a batch: nc candidates, np1 packs of the first
+                                 * kernel, oversize components, np2 packs of the second kernel, nel components in those; then the np1 and the np2 pack words
+                                 * (first entry of the order | count << 24), the first kernel's order (nc candidate indices, oversize last), the second
+                                 * kernel's order (nel indices) and every candidate's traced boundary length */
 /* returns the number of ELEMENTS available (copies min(available, capacity) elements), < 0 on error */
 long ctag_debug_fetch(ctag_handle* h, int frame, int what, void* dst, size_t capacity_elems);
 

@@ -405,6 +405,32 @@ long ctag_debug_fetch(ctag_handle* h, int frame, int what, void* dst, size_t cap
             }
             return (long)(total * 2);
         }
+        case CTAG_DBG_PACKS: {
+            int32_t hd[5] = {0, 0, 0, 0, 0};  // nc, np1, nbig, np2, nel
+            if (!d2h(&hd[0], W.ncand + frame, 4) || !d2h(&hd[1], W.npacks + 2 * frame, 8) || !d2h(&hd[3], W.npacks2 + 2 * frame, 8)) return -2;
+            hd[0] = std::min(hd[0], W.cand_cap);
+            const size_t nc = (size_t)hd[0], np1 = (size_t)hd[1], np2 = (size_t)hd[3], nel = (size_t)hd[4];
+            if (hd[1] < 0 || hd[3] < 0 || hd[4] < 0 || np1 > nc || np2 > nc || nel > nc) return -2;
+            const size_t total = 5 + np1 + np2 + nc + nel + nc;
+            if (dst && cap >= total) {
+                int32_t* o = static_cast<int32_t*>(dst);
+                std::memcpy(o, hd, sizeof(hd));
+                o += 5;
+                const size_t fo = (size_t)frame * W.cand_cap;
+                if (np1 && !d2h(o, W.packs + fo, np1 * 4)) return -2;
+                o += np1;
+                if (np2 && !d2h(o, W.packs2 + fo, np2 * 4)) return -2;
+                o += np2;
+                if (nc && !d2h(o, W.pack_order + fo, nc * 4)) return -2;
+                o += nc;
+                if (nel && !d2h(o, W.pack_order2 + fo, nel * 4)) return -2;
+                o += nel;
+                std::vector<CandAux> a(std::max<size_t>(nc, 1));
+                if (nc && !d2h(a.data(), W.cand_aux + fo, nc * sizeof(CandAux))) return -2;
+                for (size_t i = 0; i < nc; i++) o[i] = a[i].n_boundary;
+            }
+            return (long)total;
+        }
         case CTAG_DBG_PREMARKERS: {
             if (!v.keep_pre) return -1;
             if (dst && cap >= 1) {
