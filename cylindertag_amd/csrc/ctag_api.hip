@@ -193,6 +193,7 @@ void handle_view(const ctag_handle* h, HandleView* out) {
     out->dict_rows = h->dict_rows;
     out->dict_cols = h->dict_cols;
     out->fused = h->last_plan.fused;
+    out->packs1 = !h->last_plan.all_wave && h->last_plan.prescan && h->last_plan.small_cfg;  // (launch_quad_edges' two branches with k_prepack)
     out->frames = h->last_frames;
     out->row_stride = h->last_row_stride;
     out->frame_stride = h->last_frame_stride;
@@ -352,6 +353,10 @@ static size_t carve_workspace(Workspace& W, size_t frames, char* base) {
     put(W.npacks2, F * 8);
     put(W.packs2, F * CC * 4);
     put(W.pack_order2, F * CC * 4);
+    put(W.npacks1, F * 8);
+    put(W.packs1, F * CC * 4);
+    put(W.pack_order1, F * CC * 4);
+    put(W.ntotal1, F * CC * 4);
     put(W.welsch_rs, std::min<size_t>(F, kLatencyFrames) * kLatLines * 20 * 6 * 4);
     put(W.quad_derived, F * kQuadStride * 48);
     put(W.quad_index, F * kQuadStride * 4);

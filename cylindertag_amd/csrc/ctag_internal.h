@@ -230,6 +230,10 @@ struct Workspace {
     int32_t* npacks2 = nullptr;     // [F][2]          the second packed kernel's packs (k_repack), components in them
     uint32_t* packs2 = nullptr;     // [F][cand_cap]
     uint32_t* pack_order2 = nullptr;// [F][cand_cap]
+    int32_t* npacks1 = nullptr;     // [F][2]          the first packed kernel's own packs behind a silhouette scan (k_prepack), components in them
+    uint32_t* packs1 = nullptr;     // [F][cand_cap]
+    uint32_t* pack_order1 = nullptr;// [F][cand_cap]
+    int32_t* ntotal1 = nullptr;     // [F][cand_cap]   distinct silhouette pixels of the components in them, by candidate index
     float* welsch_rs = nullptr;     // [min(F, kLatencyFrames)][kLatLines][20][6]: line + err (as a double) of every restart, few-frame calls only
     const uint8_t* pick_table = nullptr;  // [kPickN][20][10], owned by the handle
     const uint16_t* pick_table16 = nullptr;  // [kPickN2 - kPickN][20][10]
@@ -409,6 +413,7 @@ struct HandleView {
     const int32_t* dict;            // host copy of the dictionary
     int dict_rows, dict_cols;
     bool fused;                     // the last chunk took the fused sweep: ws->half holds the threshold mask (1 bit per pixel), not the half-size image
+    bool packs1;                    // the last chunk's branch of the boundary stage built the first packed kernel's own packs (k_prepack: ws->packs1 ...)
     const uint8_t* frames;          // the frames the last chunk read (device memory) and their strides
     ptrdiff_t row_stride, frame_stride;
     hipStream_t stream;

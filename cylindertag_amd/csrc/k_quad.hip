@@ -49,6 +49,10 @@ struct QuadPtrs {
     int32_t* npacks2;      // [F][2] the second packed kernel's own packs (k_repack), the components in them
     uint32_t* packs2;      // [F][cand_cap] first entry of pack_order2 | count << 24, longest first
     uint32_t* pack_order2; // [F][cand_cap] the packed components the first kernel left a boundary of, by descending boundary length
+    int32_t* npacks1;      // [F][2] the small configuration's first packed kernel's own packs behind a silhouette scan (k_prepack), the components in them
+    uint32_t* packs1;      // [F][cand_cap] first entry of pack_order1 | count << 24, longest first
+    uint32_t* pack_order1; // [F][cand_cap] the packed components that have a cluster-pool slot, by descending number of distinct silhouette pixels
+    int32_t* ntotal1;      // [F][cand_cap] that number, by candidate index (-1: no slot); written by k_prepack for the packed components only
     unsigned long long* stamps;  // developer aid (CTAG_QUAD_STAMPS=1): cycles per phase of k_quad_edges, else null
     // tunables (include/ctag.h: ctag_params; the reference's values in brackets)
     float thr_line, thr_expand, rac;  // threshold_line [1.8], threshold_expand [1.2], threshold_RAC [0.3]
@@ -68,6 +72,7 @@ static QuadPtrs quad_ptrs(const ChunkPlan& pl, const Workspace& ws, unsigned lon
     P.pool_tile = ws.pool_tile, P.member_head = ws.member_head, P.member_next = ws.member_next;
     P.npacks = ws.npacks, P.packs = ws.packs, P.pack_order = ws.pack_order, P.stamps = stamps;
     P.npacks2 = ws.npacks2, P.packs2 = ws.packs2, P.pack_order2 = ws.pack_order2;
+    P.npacks1 = ws.npacks1, P.packs1 = ws.packs1, P.pack_order1 = ws.pack_order1, P.ntotal1 = ws.ntotal1;
     P.thr_line = ws.kp.thr_line, P.thr_expand = ws.kp.thr_expand, P.rac = ws.kp.rac, P.c2_far = ws.kp.c2_far, P.c2_near = ws.kp.c2_near, P.expand_eps = ws.kp.expand_eps;
     P.cand_cap = ws.cand_cap, P.line_cap = ws.line_cap, P.cl_cap = ws.cl_cap;
     P.mask = pl.fused ? reinterpret_cast<const uint64_t*>(ws.half) : nullptr, P.mask_words = ws.g.hcols >> 6;  // the fused sweep's threshold mask
@@ -360,7 +365,7 @@ __device__ __forceinline__ void welsch_restart(const Pts pts, int n, const Picks
 #endif
 constexpr int kPackWords = CTAG_PACK_WORDS;  // LDS words shared by the up to 8 components of a wave (large configuration)
 // Two builds of the packed kernel.  The kernel is bound by dependent LDS round trips (24 % of the issue roof at 2 waves per
-// SIMD), so for frames of 1080p class -- boundaries of ~150 points, a pack of 5 components in 10 KB (the first kernel's packs, sized by box capacity; the second kernel's are k_repack's, sized by traced length) -- the small configuration
+// SIMD), so for frames of 1080p class -- boundaries of ~150 points, a pack of 5 components in 10 KB (the first kernel's packs, sized by box capacity -- behind a silhouette scan they are k_prepack's, sized by the silhouette's pixel count; the second kernel's are k_repack's, sized by traced length) -- the small configuration
 // runs 4 waves per SIMD (128 VGPRs, 61 of them spilled to scratch: still 6.8 -> 6.2 ms per 4096 frames); 4K frames have
 // components four times the size and keep the large one (same-box A/B: 8.4 vs 7.9 ms per 1024 frames with the small one).
 #ifndef CTAG_PACK_WAVES_P2
@@ -382,6 +387,16 @@ __host__ __device__ __forceinline__ int pack_need(int w, int h) {
 // the cluster copy's W[idx], idx in [0, n); the erase's W[src] with src = k - keep + m < new_n - keep + m = n and W[b + 1 + k] < a < n; Wn[k], k < new_n < n.
 // So n words each; each list starts on an even word.  n <= pack_points(w, h), hence need2(n) <= pack_need(w, h): whatever k_pack packed fits alone.
 __host__ __device__ __forceinline__ int need2(int n) { return 2 * ((n + 1) & ~1); }
+// LDS words a component needs in the small packed configuration's FIRST kernel when its silhouette was scanned beforehand (PHASE 1, PRESCAN) and its
+// distinct silhouette pixels counted (nt = silhouette_points, k_prepack).  The traversal stops at n == nt, so the kernel lays out tb (w + 2 words),
+// lr (h + 2), the boundary list bufA (nt) and the stack / rotated list bufB (nt + 1), and every LDS index it forms is one of: tb[x], x <= w + 1 and
+// lr[y], y <= h + 1 (the slot's copy; tb[nx + 1], lr[ny + 1] with -1 <= nx <= w, -1 <= ny <= h: a neighbour of a pixel of the box); bufA[0] with nt >= 1
+// (tb[1] != 0 counts); bufA[n], n < nt (the loop condition, and the guard n < cap); the push bufB[sp], sp <= n - 1 <= nt - 2 (a frame per appended point
+// at most; the guard allows sp <= cap = nt, the last of the nt + 1 words); the pop's bufB[sp], lower; the centroid's bufA[k] and the rotation's bufA[src],
+// bufB[k], k, src < n <= nt.  No lef / rig: the label scan is not in this build.  Rounded up to an even word, so every component's tb starts on one, as
+// with pack_need.  nt <= min(2 (w + h), w h) = C - 1 (two pixels per column and per row at most, and no more than the box has), so
+// need1 <= w + h + 2 C + 4 <= pack_need(w, h): whatever k_pack packed fits alone.
+__host__ __device__ __forceinline__ int need1(int w, int h, int nt) { return (w + h + 2 * nt + 6) & ~1; }
 // the packed kernel takes every component whose working set fits the wave's LDS budget (the silhouette scan walks a wide
 // box in passes of 128 columns); the rest are "big" and get a wave of their own (k_quad_edges_packed<64, ...>)
 // big_points: in latency mode (a few frames per call) components with a long boundary also go there -- a whole wave per
@@ -602,6 +617,111 @@ __global__ __launch_bounds__(64) void k_repack(QuadPtrs P, int nframes, int max_
     if (tid == 0) {
         P.npacks2[2 * frame] = np;
         P.npacks2[2 * frame + 1] = nel;
+    }
+}
+
+// A component's distinct silhouette pixels from its two sentinel-padded arrays (tb[x + 1] = (top + 2) | (bottom + 2) << 16 per column, lr[y + 1] likewise per
+// row, 0 = none; in LDS or in the component's cluster-pool slot): two per column (one where top == bottom) plus the row ends that head no column list.  The
+// ordered traversal visits every listed pixel at most once, so once it has appended this many points nothing is left to find and the rest of its work --
+// unwinding a stack as deep as the boundary is long, a full neighbour test per frame -- changes nothing: it stops there.  Lane sl of the SG lanes of the
+// component's sub-group, all of them calling; every lane gets the sum.
+// U: columns / rows a lane requests before it looks at any of them (from global memory every trip of these loops is a round trip: k_prepack takes four at once).
+template <int SG, int U = 1>
+__device__ __forceinline__ int silhouette_points(const uint32_t* tb, const uint32_t* lr, int w, int h, int sl) {
+    int nt = 0;
+    for (int x0 = sl; x0 < w; x0 += SG * U) {
+        uint32_t t[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) t[u] = x0 + SG * u < w ? tb[x0 + SG * u + 1] : 0u;
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (t[u]) nt += 1 + ((t[u] & 0xffffu) != (t[u] >> 16) ? 1 : 0);
+    }
+    for (int y0 = sl; y0 < h; y0 += SG * U) {
+        uint32_t v[U], tl[U], tr[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) v[u] = y0 + SG * u < h ? lr[y0 + SG * u + 1] : 0u;
+#pragma unroll
+        for (int u = 0; u < U; u++) {  // (a row's ends lie in the box: the clamps are for a slot that holds something else)
+            tl[u] = v[u] ? tb[min((v[u] & 0xffffu) - 2u, (uint32_t)(w - 1)) + 1] : 0u;
+            tr[u] = v[u] ? tb[min((v[u] >> 16) - 2u, (uint32_t)(w - 1)) + 1] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (v[u]) {
+                const uint32_t ky = (uint32_t)(y0 + SG * u + 2);
+                if ((tl[u] & 0xffffu) != ky && (tl[u] >> 16) != ky) nt++;
+                if ((v[u] >> 16) != (v[u] & 0xffffu) && (tr[u] & 0xffffu) != ky && (tr[u] >> 16) != ky) nt++;
+            }
+    }
+    return sg_sum<SG>(nt);
+}
+
+// =====================================================================================================
+// K6q: the packs of the small packed configuration's FIRST kernel (PHASE 1) where the silhouettes were scanned beforehand (k_silhouette_mask or the PHASE 3
+// build).  k_pack sizes a component by the capacity of its box before anything of it is known; behind the scan its tb / lr lie in its cluster-pool slot, and
+// the number of distinct silhouette pixels -- where the first kernel's traversal stops, hence all its boundary list and its stack ever hold -- is a count over
+// them.  So the packed components [0, nc - oversize) of k_pack's order that have a slot are counted (8 lanes per component, silhouette_points), ranked by that
+// count, longest first, and packed by need1(w, h, count): more sub-groups of a wave filled, fewer packs for the lockstep kernel to walk, and components of
+// similar traversal length side by side.  The counts go to ntotal1, where the first kernel reads them instead of counting again.  A component without a slot
+// (pool exhausted: cand_aux already final) is in no pack.  One block of kPrepackThreads per frame (batches only: few-frame calls have no packs).
+// =====================================================================================================
+constexpr int kPrepackThreads = 256;
+__global__ __launch_bounds__(kPrepackThreads) void k_prepack(QuadPtrs P, int nframes, int max_per_pack, int pack_words) {
+    __shared__ int s_key[kLdsCand + 2];
+    __shared__ int s_need[kLdsCand];
+    __shared__ uint16_t s_ord[kLdsCand];
+    const int frame = blockIdx.x;
+    if (frame >= nframes) return;
+    const int tid = threadIdx.x, nt = blockDim.x, sub = tid >> 3, sl = tid & 7;
+    const int nc = min(P.ncand[frame], P.cand_cap);
+    const int npk = max(nc - P.npacks[2 * frame + 1], 0);
+    const Candidate* cand = P.cand + (size_t)frame * P.cand_cap;
+    const CandAux* aux = P.cand_aux + (size_t)frame * P.cand_cap;
+    const uint32_t* order = P.pack_order + (size_t)frame * P.cand_cap;
+    uint32_t* order1 = P.pack_order1 + (size_t)frame * P.cand_cap;
+    uint32_t* packs1 = P.packs1 + (size_t)frame * P.cand_cap;
+    int32_t* ntot = P.ntotal1 + (size_t)frame * P.cand_cap;
+    const bool in_lds = npk <= kLdsCand;
+    // the counts: a sub-group of 8 lanes per component (every lane of the block makes the same number of trips: the sum is a cross-lane operation)
+    for (int r0 = 0; r0 < npk; r0 += nt >> 3) {
+        const int r = r0 + sub;
+        const bool act = r < npk;
+        const int ci = (int)order[act ? r : 0];
+        const Candidate c = cand[ci];
+        const int p0 = aux[ci].line0;  // the component's slot (-1: none)
+        const bool has = act && p0 >= 0;
+        const int w = has ? c.x_max - c.x_min + 1 : 0, h = has ? c.y_max - c.y_min + 1 : 0;
+        const uint32_t* slot = P.cl_pool + (size_t)frame * P.cl_cap + (has ? p0 : 0);  // tb: [0, w + 2), lr: [w + 2, w + h + 4)
+        const int cnt = silhouette_points<8, 4>(slot, slot + w + 2, w, h, sl);
+        if (act && sl == 0) {
+            ntot[ci] = has ? cnt : -1;
+            if (in_lds) s_key[r] = has ? cnt : -1, s_need[r] = need1(w, h, cnt);
+        }
+    }
+    __syncthreads();  // (the block's own stores to ntotal1 are visible to it behind the barrier)
+    auto need_of_cand = [&](int ci) {
+        const Candidate c = cand[ci];
+        return need1(c.x_max - c.x_min + 1, c.y_max - c.y_min + 1, ntot[ci]);
+    };
+    int nel, np;
+    if (!in_lds) {
+        nel = pack_counting_sort(s_key, order1, npk, tid, nt, [&](int r) { return (int)ntot[order[r]]; }, [&](int r) { return order[r]; });
+        if (tid >= 64) return;
+        np = build_packs(packs1, nel, max_per_pack, pack_words, tid, [&](int r) { return need_of_cand((int)order1[r]); });
+    } else {
+        if (tid == 0) s_key[kLdsCand] = 0;  // number of components without a slot
+        __syncthreads();
+        if (const int neg = pack_rank_sort(s_key, s_ord, npk, tid, nt)) atomicAdd(&s_key[kLdsCand], neg);
+        __syncthreads();
+        nel = npk - s_key[kLdsCand];
+        for (int i = tid; i < nel; i += nt) order1[i] = order[s_ord[i]];
+        if (tid >= 64) return;
+        np = build_packs(packs1, nel, max_per_pack, pack_words, tid, [&](int r) { return s_need[s_ord[r]]; });
+    }
+    if (tid == 0) {
+        P.npacks1[2 * frame] = np;
+        P.npacks1[2 * frame + 1] = nel;
     }
 }
 
@@ -1104,12 +1224,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     const int lane = threadIdx.x, sub = lane / SG, sl = lane % SG, lane0 = lane - sl;
     // SG == 8: the frame's packs; SG == 64: the oversize tail of k_pack's order, one component per wave
     const int nc = min(P.ncand[frame], P.cand_cap);
+    constexpr bool PACKS1 = PRESCAN && PHASE == 1;  // the first kernel behind a silhouette scan walks k_prepack's packs: sized by the silhouette's pixel count, not by capacity
     const int npk = PHASE == 3 ? nc - P.npacks[2 * frame + 1]  // every packed component: entries [0, nc - oversize) of k_pack's order
                   : PHASE == 2 ? P.npacks2[2 * frame]          // the second kernel walks k_repack's packs: sized by traced length, not by capacity
-                               : P.npacks[2 * frame + (SG == 8 ? 0 : 1)];
+                  : PACKS1 ? P.npacks1[2 * frame]
+                           : P.npacks[2 * frame + (SG == 8 ? 0 : 1)];
     static_assert(PHASE != 2 || SG == 8, "the second kernel is a packed build");
-    const uint32_t* __restrict__ pack_list = (PHASE == 2 ? P.packs2 : P.packs) + (size_t)frame * P.cand_cap;
-    const uint32_t* __restrict__ pack_ord = (PHASE == 2 ? P.pack_order2 : P.pack_order) + (size_t)frame * P.cand_cap;
+    const uint32_t* __restrict__ pack_list = (PHASE == 2 ? P.packs2 : PACKS1 ? P.packs1 : P.packs) + (size_t)frame * P.cand_cap;
+    const uint32_t* __restrict__ pack_ord = (PHASE == 2 ? P.pack_order2 : PACKS1 ? P.pack_order1 : P.pack_order) + (size_t)frame * P.cand_cap;
     const uint16_t* __restrict__ limg = P.labels + ((size_t)frame * g.hrows) * g.lp;
     const int32_t* __restrict__ tbase = P.tile_base + (size_t)frame * g.tiles_x * g.tiles_y;
     const int32_t* __restrict__ rootof = P.root_of + (size_t)frame * g.pool_cap;
@@ -1147,7 +1269,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
         const int C = pack_points(w, h);
         int nb2 = 0;  // PHASE 2: the length the first kernel traced (> 0: k_repack packs no other component)
         if constexpr (PHASE == 2) nb2 = aux->n_boundary;
-        const int need = act ? (PHASE == 3 ? scan_need(w, h) : PHASE == 2 ? need2(nb2) : pack_need(w, h)) : 0;
+        int nt1 = 0;  // PACKS1: the component's distinct silhouette pixels as k_prepack counted them (>= 0: it packs no component without a slot)
+        if constexpr (PACKS1) nt1 = P.ntotal1[(size_t)frame * P.cand_cap + ci];
+        const int need = act ? (PHASE == 3 ? scan_need(w, h) : PHASE == 2 ? need2(nb2) : PACKS1 ? need1(w, h, nt1) : pack_need(w, h)) : 0;
         int off = 0;
 #pragma unroll
         for (int k = 0; k < 64 / SG; k++) {
@@ -1176,8 +1300,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
         uint32_t* tb = mem;               // w + 2 words
         uint32_t* lr = tb + w + 2;        // h + 2 words
         // (PHASE 2 holds the two ping-pong lists alone, need2(n_boundary) / 2 words each: bufB = W first, bufA = Wn)
-        uint32_t* bufA = PHASE == 2 ? mem + (need >> 1) : lr + h + 2;      // C words
-        uint32_t* bufB = PHASE == 2 ? mem : bufA + (PHASE == 3 ? h : C);  // C + 1 words (scan only: the row extents, h words each)
+        // (PACKS1 lays the list and the stack out with the capacity the traversal can reach, cap = the silhouette's pixel count: need1)
+        const int cap = PACKS1 ? nt1 : C;  // words of the boundary list; the stack / rotated list has one more
+        uint32_t* bufA = PHASE == 2 ? mem + (need >> 1) : lr + h + 2;      // cap words
+        uint32_t* bufB = PHASE == 2 ? mem : bufA + (PHASE == 3 ? h : cap);  // cap + 1 words (scan only: the row extents, h words each)
         uint32_t* lef = bufA;             // P1 only: row extents by atomics (h <= C words each)
         uint32_t* rig = bufB;
         const int sgshift = sub * SG;
@@ -1758,25 +1884,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             for (int y = sl; y < h + 2; y += SG) lr[y] = slot[w + 2 + y];
             wave_fence();
         }
-        // distinct silhouette pixels: two per column (one where top == bottom) plus the row ends that head no column list.  The
-        // traversal below visits every listed pixel at most once, so once it has appended this many points nothing is left to
-        // find and the rest of its work -- unwinding a stack as deep as the boundary is long, a full neighbour test per frame --
-        // changes nothing: it stops there.
-        int ntotal = 0;
-        for (int x = sl; x < w; x += SG) {
-            const uint32_t t = tb[x + 1];
-            if (t) ntotal += 1 + ((t & 0xffffu) != (t >> 16) ? 1 : 0);
-        }
-        for (int y = sl; y < h; y += SG) {
-            const uint32_t v = lr[y + 1];
-            if (v) {
-                const uint32_t ky = (uint32_t)(y + 2), xl = (v & 0xffffu) - 2u, xr = (v >> 16) - 2u;
-                const uint32_t tl = tb[xl + 1], tr = tb[xr + 1];
-                if ((tl & 0xffffu) != ky && (tl >> 16) != ky) ntotal++;
-                if (xr != xl && (tr & 0xffffu) != ky && (tr >> 16) != ky) ntotal++;
-            }
-        }
-        ntotal = sg_sum<SG>(ntotal);
+        // distinct silhouette pixels (silhouette_points): where the traversal below stops.  PACKS1: k_prepack counted them, on these words, for its packs
+        const int ntotal = PACKS1 ? nt1 : silhouette_points<SG>(tb, lr, w, h, sl);
         stamp(0);
         // ---- P2: ordered traversal (corner_detector.cpp:235-247, :407-418): lanes 0..7 of the sub-group test the
         // 8 neighbours (N,NE,E,SE,S,SW,W,NW); the first hit at or after the frame's resume index wins (B7)
@@ -1899,7 +2008,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                     const int j = __ffs(m) - 1;
                     const int hx = fx + ((int)((0x01A9u >> (2 * j)) & 3u) - 1), hy = fy + ((int)((0x1A90u >> (2 * j)) & 3u) - 1);
                     if (sl == j) {  // the hit lane holds the list words of (hx, hy): it appends the point and clears them
-                        if (n < C) bufA[n] = pack_xy(hx + x_min, hy + y_min);
+                        if (n < cap) bufA[n] = pack_xy(hx + x_min, hy + y_min);
                         uint32_t c2 = c, r2 = r;
                         if ((c2 & 0xffffu) == ky) c2 &= 0xffff0000u;
                         if ((c2 >> 16) == ky) c2 &= 0xffffu;
@@ -1908,13 +2017,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                         tb[nx + 1] = c2;
                         lr[ny + 1] = r2;
                         // the current frame moves to the hit pixel and resumes at j+1 (B7); it becomes the frame below the top
-                        if (sp <= C) bufB[sp] = (uint32_t)hx | ((uint32_t)hy << 14) | ((uint32_t)(j + 1) << 28);
+                        if (sp <= cap) bufB[sp] = (uint32_t)hx | ((uint32_t)hy << 14) | ((uint32_t)(j + 1) << 28);
                     }
                     wave_fence();
                     n++;
                     fx = hx;
                     fy = hy;
-                    if (sp + 1 <= C) {  // (always: kept because this build's register allocation is better with it -- 5.19 vs 5.55 ms)
+                    if (sp + 1 <= cap) {  // (always: kept because this build's register allocation is better with it -- 5.19 vs 5.55 ms)
                         sp++;
                         j0 = 0;
                     } else {
@@ -1922,7 +2031,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                     }
                 }
             }
-            n = min(n, C);
+            n = min(n, cap);
         }
         n_boundary = n;
         if (n == 0) {
@@ -2930,6 +3039,7 @@ static void launch_quad_edges(const ChunkPlan& pl, const QuadPtrs& P, const Fram
         else
             hipLaunchKernelGGL((k_quad_edges_packed<64, kScanWords, CTAG_SCAN_WAVES, false, true, 3>), dim3(nframes, pl.scan_gx), dim3(64), 0, s, P, g, nframes, 0);
         if (pl.small_cfg) {
+            hipLaunchKernelGGL(k_prepack, dim3(nframes), dim3(kPrepackThreads), 0, s, P, nframes, pl.pack_max, kPackWordsSmall);
             hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmall, false, REF, 1, true>), grid, dim3(64), 0, s, P, g, nframes, 0);
             hipLaunchKernelGGL(k_repack, dim3(nframes), dim3(64), 0, s, P, nframes, pl.pack_max, kPackWordsSmall);
             hipLaunchKernelGGL((k_quad_edges_packed<8, kPackWordsSmall, kPackWavesSmallP2, false, REF, 2>), grid, dim3(64), 0, s, P, g, nframes, 0);

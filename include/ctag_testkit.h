@@ -40,6 +40,10 @@ extern "C" {
                                  * kernel, oversize components, np2 packs of the second kernel, nel components in those; then the np1 and the np2 pack words
                                  * (first entry of the order | count << 24), the first kernel's order (nc candidate indices, oversize last), the second
                                  * kernel's order (nel indices) and every candidate's traced boundary length */
+#define CTAG_DBG_PACKS1 15      /* int32 [4 + np + nel + nc]  the work lists the first packed boundary kernel walks behind a silhouette scan (k_prepack), of a frame of a batch: nc candidates,
+                                 * built (1, or 0: the last chunk's branch of the boundary stage built no such lists -- the four header words are all there is), np packs, nel
+                                 * components in them; then the np pack words (first entry of the order | count << 24), the order (nel candidate indices) and, per
+                                 * candidate, the number of distinct silhouette pixels the packs were built from (-1: in no pack) */
 /* returns the number of ELEMENTS available (copies min(available, capacity) elements), < 0 on error */
 long ctag_debug_fetch(ctag_handle* h, int frame, int what, void* dst, size_t capacity_elems);
 

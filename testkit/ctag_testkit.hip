@@ -431,6 +431,34 @@ long ctag_debug_fetch(ctag_handle* h, int frame, int what, void* dst, size_t cap
             }
             return (long)total;
         }
+        case CTAG_DBG_PACKS1: {
+            int32_t hd[4] = {0, v.packs1 ? 1 : 0, 0, 0};  // nc, built, np, nel
+            if (!d2h(&hd[0], W.ncand + frame, 4)) return -2;
+            hd[0] = std::min(hd[0], W.cand_cap);
+            if (v.packs1 && !d2h(&hd[2], W.npacks1 + 2 * frame, 8)) return -2;
+            const size_t nc = (size_t)hd[0], np = (size_t)hd[2], nel = (size_t)hd[3];
+            if (hd[2] < 0 || hd[3] < 0 || np > nc || nel > nc) return -2;
+            if (!v.packs1) {  // the last chunk's branch built no such lists: the header says so, nothing follows it
+                if (dst && cap >= 4) std::memcpy(dst, hd, sizeof(hd));
+                return 4;
+            }
+            const size_t total = 4 + np + nel + nc;
+            if (dst && cap >= total) {
+                int32_t* o = static_cast<int32_t*>(dst);
+                std::memcpy(o, hd, sizeof(hd));
+                o += 4;
+                const size_t fo = (size_t)frame * W.cand_cap;
+                if (np && !d2h(o, W.packs1 + fo, np * 4)) return -2;
+                o += np;
+                if (nel && !d2h(o, W.pack_order1 + fo, nel * 4)) return -2;
+                std::vector<int32_t> nt(std::max<size_t>(nc, 1));
+                if (nc && !d2h(nt.data(), W.ntotal1 + fo, nc * 4)) return -2;
+                for (size_t i = 0; i < nc; i++) o[nel + i] = -1;  // (k_prepack writes the packed components' entries only: the rest are whatever an earlier chunk left)
+                for (size_t i = 0; i < nel; i++)
+                    if (o[i] >= 0 && (size_t)o[i] < nc) o[nel + o[i]] = nt[o[i]];
+            }
+            return (long)total;
+        }
         case CTAG_DBG_PREMARKERS: {
             if (!v.keep_pre) return -1;
             if (dst && cap >= 1) {
