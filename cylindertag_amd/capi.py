@@ -32,6 +32,8 @@ POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag
                 "ctag_camera_set_create", "ctag_camera_set_free", "ctag_mv_rig_pose_batch_device", "ctag_estimate_mv_rig_pose",
                 "ctag_cov_opts_default", "ctag_pose_cov_batch_device", "ctag_rig_pose_cov_batch_device", "ctag_mv_rig_pose_cov_batch_device",
                 "ctag_estimate_pose_cov", "ctag_estimate_rig_pose_cov", "ctag_estimate_mv_rig_pose_cov",
+                "ctag_robust_opts_default", "ctag_pose_robust_batch_device", "ctag_rig_pose_robust_batch_device", "ctag_mv_rig_pose_robust_batch_device",
+                "ctag_estimate_pose_robust", "ctag_estimate_rig_pose_robust", "ctag_estimate_mv_rig_pose_robust",
                 "ctag_model_fit_opts_default", "ctag_model_fit_device", "ctag_model_fit", "ctag_model_save", "ctag_model_fit_last_ms",
                 "ctag_rig_fit_opts_default", "ctag_rig_fit_device", "ctag_rig_fit", "ctag_rig_fit_last_ms",
                 "ctag_camera_fit_opts_default", "ctag_camera_fit_device", "ctag_camera_fit", "ctag_camera_fit_last_ms", "ctag_camera_set_get",
@@ -69,6 +71,13 @@ POSE_COV_DT = np.dtype([("status", "<i4"), ("n_points", "<i4"), ("dof", "<i4"), 
 assert POSE_COV_DT.itemsize == 352
 COV_OK, COV_NO_POSE, COV_BAD_RECORD, COV_SINGULAR = range(4)
 COV_PARAM_TANGENT, COV_PARAM_RVEC = 0, 1
+# ctag_robust_pose_rec: one pose record of any kind minimised again under a loss (include/ctag_pose.h, robust refit)
+ROBUST_POSE_DT = np.dtype([("status", "<i4"), ("n_points", "<i4"), ("n_inliers", "<i4"), ("iterations", "<i4"), ("loss", "<i4"), ("worst_point", "<i4"),
+                           ("inlier_mask", "<u4", (25,)), ("reserved", "<i4"), ("scale_px", "<f8"), ("sigma_hat", "<f8"), ("cost_ls0", "<f8"),
+                           ("cost_ls", "<f8"), ("cost0", "<f8"), ("cost", "<f8"), ("max_residual_px", "<f8"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
+assert ROBUST_POSE_DT.itemsize == 232
+ROBUST_OK, ROBUST_NO_POSE, ROBUST_BAD_RECORD, ROBUST_DEGENERATE = range(4)
+LOSS_HUBER, LOSS_CAUCHY = 0, 1
 # ctag_model_fit_stat: one record per model of a model reconstruction (include/ctag_pose.h)
 MODEL_FIT_STAT_DT = np.dtype([("status", "<i4"), ("n_records", "<i4"), ("n_points_fitted", "<i4"), ("n_points_held", "<i4"), ("rounds", "<i4"),
                               ("reserved", "<i4"), ("cost0", "<f8"), ("cost", "<f8"), ("lambda", "<f8"), ("rms_px", "<f8")])
@@ -143,6 +152,38 @@ def cov_opts(param=None, sigma_px=None, outlier_k=None):
     if outlier_k is not None:
         o.outlier_k = float(outlier_k)
     return o
+
+
+class RobustOptsC(C.Structure):  # ctag_robust_opts
+    _fields_ = [("struct_size", C.c_uint32), ("loss", C.c_int32), ("max_iterations", C.c_int32), ("reserved", C.c_int32), ("scale_px", C.c_double),
+                ("auto_k", C.c_double), ("min_scale_px", C.c_double)]
+
+
+def robust_opts(loss=None, max_iterations=None, scale_px=None, auto_k=None, min_scale_px=None):
+    """ctag_robust_opts_default, then the given fields."""
+    o = RobustOptsC()
+    load_library().ctag_robust_opts_default(C.byref(o))
+    if loss is not None:
+        o.loss = int(loss)
+    if max_iterations is not None:
+        o.max_iterations = int(max_iterations)
+    for k, v in (("scale_px", scale_px), ("auto_k", auto_k), ("min_scale_px", min_scale_px)):
+        if v is not None:
+            setattr(o, k, float(v))
+    return o
+
+
+def apply_robust(pose_records, robust_records):
+    """A copy of the pose records (POSE_DT, RIG_POSE_DT or MV_POSE_DT) with rvec, tvec replaced by the refit's where the robust record's
+    status is ROBUST_OK: what the covariance and overlay calls take in place of the least-squares poses."""
+    poses = np.array(pose_records, copy=True)
+    rob = np.asarray(robust_records)
+    if rob.dtype != ROBUST_POSE_DT or rob.shape != poses.shape or "rvec" not in (poses.dtype.names or ()):
+        raise ValueError("apply_robust: one ROBUST_POSE_DT record per pose record")
+    ok = rob["status"] == ROBUST_OK
+    poses["rvec"][ok] = rob["rvec"][ok]
+    poses["tvec"][ok] = rob["tvec"][ok]
+    return poses
 
 
 class ModelFitOptsC(C.Structure):  # ctag_model_fit_opts
@@ -346,6 +387,21 @@ def load_library():
     L.ctag_estimate_rig_pose_cov.argtypes = [vp, vp, vp, vp, C.POINTER(CameraC), vp, optp, vp]
     L.ctag_estimate_mv_rig_pose_cov.restype = C.c_int
     L.ctag_estimate_mv_rig_pose_cov.argtypes = [vp, vp, vp, vp, vp, vp, optp, vp]
+    optp = C.POINTER(RobustOptsC)
+    L.ctag_robust_opts_default.restype = None
+    L.ctag_robust_opts_default.argtypes = [optp]
+    L.ctag_pose_robust_batch_device.restype = C.c_int
+    L.ctag_pose_robust_batch_device.argtypes = [vp, vp, C.c_int, vp, C.POINTER(CameraC), vp, vp, C.c_int, optp, vp]
+    L.ctag_rig_pose_robust_batch_device.restype = C.c_int
+    L.ctag_rig_pose_robust_batch_device.argtypes = [vp, vp, C.c_int, vp, vp, C.POINTER(CameraC), vp, optp, vp]
+    L.ctag_mv_rig_pose_robust_batch_device.restype = C.c_int
+    L.ctag_mv_rig_pose_robust_batch_device.argtypes = [vp, C.POINTER(vp), C.c_int, vp, vp, vp, vp, optp, vp]
+    L.ctag_estimate_pose_robust.restype = C.c_int
+    L.ctag_estimate_pose_robust.argtypes = [vp, vp, vp, C.POINTER(CameraC), vp, optp, vp]
+    L.ctag_estimate_rig_pose_robust.restype = C.c_int
+    L.ctag_estimate_rig_pose_robust.argtypes = [vp, vp, vp, vp, C.POINTER(CameraC), vp, optp, vp]
+    L.ctag_estimate_mv_rig_pose_robust.restype = C.c_int
+    L.ctag_estimate_mv_rig_pose_robust.argtypes = [vp, vp, vp, vp, vp, vp, optp, vp]
     fitp = C.POINTER(ModelFitOptsC)
     L.ctag_model_fit_opts_default.restype = None
     L.ctag_model_fit_opts_default.argtypes = [fitp]
@@ -1109,6 +1165,77 @@ class Detector:
         st = self.L.ctag_mv_rig_pose_cov_batch_device(self.h, arr, n_frames, model.m, rigs.r, cams.s, mv_poses_ptr, self._optp(opts), out_ptr)
         if st != 0:
             raise CtagError(st, "ctag_mv_rig_pose_cov_batch_device")
+
+    # ---- robust refit (include/ctag_pose.h): opts is a RobustOptsC (robust_opts(...)) or None for the defaults; apply_robust() puts the
+    # refitted poses into the pose records for the covariance and overlay calls
+    def robust_pose(self, result, poses, model, camera, opts=None):
+        """One frame: its host ctag_frame_result record and the POSE_DT records of estimate_pose -> one ROBUST_POSE_DT record per marker."""
+        res = np.ascontiguousarray(result).reshape(1)
+        assert res.dtype == RESULT_DT
+        n = int(res[0]["n_markers"]) if res[0]["status"] == 0 else 0
+        poses = np.ascontiguousarray(poses, POSE_DT).reshape(-1)
+        if len(poses) != n:
+            raise ValueError("%d pose records for %d markers" % (len(poses), n))
+        out = np.zeros(max(n, 1), ROBUST_POSE_DT)
+        st = self.L.ctag_estimate_pose_robust(self.h, res.ctypes.data, model.m, C.byref(camera), poses.ctypes.data if n else None,
+                                           self._optp(opts), out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_estimate_pose_robust")
+        return out[:n]
+
+    def robust_pose_batch_device(self, results_ptr, n_frames, model, camera, offsets_ptr, poses_ptr, capacity, out_ptr, opts=None):
+        """Device pointers as pose_batch_device left them -> ROBUST_POSE_DT record w for pose record w at out_ptr; enqueued, does not wait."""
+        st = self.L.ctag_pose_robust_batch_device(self.h, results_ptr, n_frames, model.m, C.byref(camera), offsets_ptr, poses_ptr, capacity,
+                                               self._optp(opts), out_ptr)
+        if st != 0:
+            raise CtagError(st, "ctag_pose_robust_batch_device")
+
+    def robust_rig_pose(self, result, rig_poses, model, rigs, camera, opts=None):
+        """One frame: its host record and the RIG_POSE_DT records of estimate_rig_pose -> rigs.n_rigs ROBUST_POSE_DT records."""
+        res = np.ascontiguousarray(result).reshape(1)
+        assert res.dtype == RESULT_DT
+        rig_poses = np.ascontiguousarray(rig_poses, RIG_POSE_DT).reshape(-1)
+        if len(rig_poses) != rigs.n_rigs:
+            raise ValueError("%d rig pose records for %d rigs" % (len(rig_poses), rigs.n_rigs))
+        out = np.zeros(rigs.n_rigs, ROBUST_POSE_DT)
+        st = self.L.ctag_estimate_rig_pose_robust(self.h, res.ctypes.data, model.m, rigs.r, C.byref(camera), rig_poses.ctypes.data,
+                                               self._optp(opts), out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_estimate_rig_pose_robust")
+        return out
+
+    def robust_rig_pose_batch_device(self, results_ptr, n_frames, model, rigs, camera, rig_poses_ptr, out_ptr, opts=None):
+        """n_frames * rigs.n_rigs device RIG_POSE_DT records -> as many device ROBUST_POSE_DT records at out_ptr; enqueued."""
+        st = self.L.ctag_rig_pose_robust_batch_device(self.h, results_ptr, n_frames, model.m, rigs.r, C.byref(camera), rig_poses_ptr,
+                                                   self._optp(opts), out_ptr)
+        if st != 0:
+            raise CtagError(st, "ctag_rig_pose_robust_batch_device")
+
+    def robust_mv_rig_pose(self, results, mv_poses, model, rigs, cams, opts=None):
+        """One instant: cams.n host records and the MV_POSE_DT records of estimate_mv_rig_pose -> rigs.n_rigs ROBUST_POSE_DT records."""
+        res = np.ascontiguousarray(results).reshape(-1)
+        assert res.dtype == RESULT_DT
+        if len(res) != cams.n:
+            raise ValueError("%d records for %d cameras" % (len(res), cams.n))
+        mv_poses = np.ascontiguousarray(mv_poses, MV_POSE_DT).reshape(-1)
+        if len(mv_poses) != rigs.n_rigs:
+            raise ValueError("%d pose records for %d rigs" % (len(mv_poses), rigs.n_rigs))
+        out = np.zeros(rigs.n_rigs, ROBUST_POSE_DT)
+        st = self.L.ctag_estimate_mv_rig_pose_robust(self.h, res.ctypes.data, model.m, rigs.r, cams.s, mv_poses.ctypes.data, self._optp(opts),
+                                                  out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_estimate_mv_rig_pose_robust")
+        return out
+
+    def robust_mv_rig_pose_batch_device(self, results_ptrs, n_frames, model, rigs, cams, mv_poses_ptr, out_ptr, opts=None):
+        """results_ptrs: one device pointer per camera; n_frames * rigs.n_rigs device MV_POSE_DT records -> as many ROBUST_POSE_DT records."""
+        ptrs = list(results_ptrs)
+        if len(ptrs) != cams.n:
+            raise ValueError("%d pointers for %d cameras" % (len(ptrs), cams.n))
+        arr = (C.c_void_p * max(len(ptrs), 1))(*[C.c_void_p(int(p) if p else None) for p in ptrs])
+        st = self.L.ctag_mv_rig_pose_robust_batch_device(self.h, arr, n_frames, model.m, rigs.r, cams.s, mv_poses_ptr, self._optp(opts), out_ptr)
+        if st != 0:
+            raise CtagError(st, "ctag_mv_rig_pose_robust_batch_device")
 
     # ---- overlay (CylinderTag::drawAxis)
     def draw_axis(self, gray, result, poses, model, camera, axis_length=5, out=None):

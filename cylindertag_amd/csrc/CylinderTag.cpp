@@ -531,6 +531,65 @@ void CylinderTag::estimatePoseCovariance(std::vector<MarkerInfo> markers, std::v
     }
 }
 
+void CylinderTag::estimatePoseRobust(std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, CamInfo camera,
+                                     std::vector<RobustPoseInfo>& robust, bool cauchy, double scalePx, int maxIterations) {
+    robust.clear();
+    if (markers.empty()) return;
+    for (const MarkerInfo& mi : markers)
+        if (mi.cornerLists.size() > (size_t)CTAG_MAX_FEATURES) throw std::string("estimatePoseRobust, a marker with more than 100 features\n");
+    ctag_model* model = make_model(reconstruct_model, __FUNCTION__);
+    const ctag_camera cam = make_camera(camera);
+    ctag_robust_opts opts;
+    ctag_robust_opts_default(&opts);
+    opts.loss = cauchy ? CTAG_LOSS_CAUCHY : CTAG_LOSS_HUBER;
+    opts.scale_px = scalePx;
+    opts.max_iterations = maxIterations;
+    std::vector<ctag_pose_rec> rec;
+    std::vector<ctag_robust_pose_rec> rob;
+    for (size_t first = 0; first < markers.size();) {  // one record (<= 100 markers / features) at a time, as estimatePose
+        ctag_frame_result res;
+        const size_t next = flatten(markers, first, res);
+        const size_t at = rec.size();
+        rec.resize(at + (size_t)res.n_markers);
+        rob.resize(at + (size_t)res.n_markers);
+        int st = ctag_estimate_pose(h_, &res, model, &cam, rec.data() + at);
+        if (st == CTAG_OK) st = ctag_estimate_pose_robust(h_, &res, model, &cam, rec.data() + at, &opts, rob.data() + at);
+        if (st != CTAG_OK) {
+            ctag_model_free(model);
+            throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+        }
+        first = next;
+    }
+    ctag_model_free(model);
+    for (size_t i = 0; i < rec.size(); i++) {
+        if (rec[i].status == CTAG_POSE_NO_MODEL) continue;  // erased, as in estimatePose
+        if (rec[i].status != CTAG_POSE_OK) throw __FUNCTION__ + std::string(", ") + "marker without a usable point set\n";
+        const ctag_robust_pose_rec& r = rob[i];
+        RobustPoseInfo ri;
+        ri.markerID = rec[i].model_index;
+        ri.status = r.status;
+        ri.nPoints = r.n_points;
+        ri.nInliers = r.n_inliers;
+        ri.iterations = r.iterations;
+        ri.loss = r.loss;
+        ri.worstPoint = r.worst_point;
+        ri.inlier.resize((size_t)r.n_points);
+        for (int k = 0; k < r.n_points; k++) ri.inlier[(size_t)k] = ((r.inlier_mask[k >> 5] >> (k & 31)) & 1u) != 0;
+        ri.scalePx = r.scale_px;
+        ri.sigmaHat = r.sigma_hat;
+        ri.costLs0 = r.cost_ls0;
+        ri.costLs = r.cost_ls;
+        ri.cost0 = r.cost0;
+        ri.cost = r.cost;
+        ri.maxResidualPx = r.max_residual_px;
+        for (int k = 0; k < 3; k++) {
+            ri.rvec[k] = r.rvec[k];
+            ri.tvec[k] = r.tvec[k];
+        }
+        robust.push_back(ri);
+    }
+}
+
 void CylinderTag::estimateRigPose(std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, const std::vector<int>& rigOfModel,
                                   CamInfo camera, std::vector<RigPoseInfo>& pose) {
     pose.clear();

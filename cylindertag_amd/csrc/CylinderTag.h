@@ -126,6 +126,16 @@ struct PoseCovInfo {
     double cost = 0, sigma2Hat = 0, sigma2Used = 0, maxResidualPx = 0, minPivot = 0;
     double cov[36] = {0};  // row-major 6x6: rows / columns 0-2 rotation (rad), 3-5 translation (model units)
 };
+// one per-marker pose minimised again under a loss (new): the fields of ctag_robust_pose_rec (include/ctag_pose.h, robust refit) for the
+// PoseInfo with the same markerID at the same place of estimatePose's list
+struct RobustPoseInfo {
+    int markerID = -1;
+    int status = 0;  // CTAG_ROBUST_*; every other field is 0 unless it is CTAG_ROBUST_OK
+    int nPoints = 0, nInliers = 0, iterations = 0, loss = 0, worstPoint = 0;
+    std::vector<bool> inlier;  // nPoints entries, in the correspondence builder's point order
+    double scalePx = 0, sigmaHat = 0, costLs0 = 0, costLs = 0, cost0 = 0, cost = 0, maxResidualPx = 0;
+    double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};  // the refitted pose
+};
 // the annotated frame of drawAxis: rows x cols pixels of 3 bytes, channel c = Scalar component c (imgMark in the reference)
 struct AxisImage {
     int rows = 0, cols = 0;
@@ -217,6 +227,13 @@ class CylinderTag {
     // the pixel noise to assume, else the residuals' own estimate; outlierK as ctag_cov_opts::outlier_k.
     void estimatePoseCovariance(std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, CamInfo camera,
                                 std::vector<PoseCovInfo>& covariance, bool tangent = true, double sigmaPx = 0.0, double outlierK = 3.0);
+
+    // estimatePose's poses minimised again under a loss (new; ctag_estimate_pose_robust): the poses are estimated again from `markers`,
+    // and robust[i] refits the pose estimatePose returns at place i (markers without a model are erased in both).  cauchy: Ceres'
+    // CauchyLoss, else HuberLoss, per point; scalePx > 0: the loss's scale, else 2.5 x the residuals' own median-based sigma, at least
+    // 0.05 px; maxIterations 0 .. 50 (0: evaluate the source pose only).
+    void estimatePoseRobust(std::vector<MarkerInfo> markers, std::vector<ModelInfo> reconstruct_model, CamInfo camera,
+                            std::vector<RobustPoseInfo>& robust, bool cauchy = true, double scalePx = 0.0, int maxIterations = 50);
 
     // One pose per rig of markers (new; include/ctag_pose.h, ctag_estimate_rig_pose): rigOfModel[i] is the rig of model i (-1: none,
     // rigs 0 .. max), the models of one rig share one frame.  The pose of a rig is EPnP + PoseBA over the union of its member

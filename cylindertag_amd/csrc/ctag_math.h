@@ -209,6 +209,44 @@ CTM_HD double exp64(double x) {
     return (T[j] * e) * scale;
 }
 
+// log(x), the natural logarithm (the Cauchy loss of k_pose_robust.hip): fdlibm's scheme, x = 2^k (1 + f) with sqrt(2)/2 < 1 + f < sqrt(2),
+// s = f / (2 + f), log(1 + f) = f - f^2/2 + s (f^2/2 + R(s^2)), R a minimax polynomial of degree 14 in s; error < 1 ulp.  Zero gives -inf,
+// a negative argument NaN, inf and NaN themselves.
+CTM_HD double log64(double x) {
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
+    const double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
+                 Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
+                 Lg7 = 1.479819860511658591e-01;
+    uint64_t u = f64_to_bits(x);
+    uint32_t hx = (uint32_t)(u >> 32);
+    int k = 0;
+    if (hx < 0x00100000u || (hx >> 31)) {
+        if ((u << 1) == 0) return -bits_to_f64(0x7ff0000000000000ULL);
+        if (hx >> 31) return bits_to_f64(0x7ff8000000000000ULL);
+        k -= 54;  // subnormal: scale up
+        x = x * 18014398509481984.0;
+        u = f64_to_bits(x);
+        hx = (uint32_t)(u >> 32);
+    } else if (hx >= 0x7ff00000u) {
+        return x;
+    } else if (u == 0x3ff0000000000000ULL) {
+        return 0.0;
+    }
+    hx += 0x3ff00000u - 0x3fe6a09eu;  // reduce to [sqrt(2)/2, sqrt(2)]
+    k += (int)(hx >> 20) - 0x3ff;
+    hx = (hx & 0x000fffffu) + 0x3fe6a09eu;
+    const double f = bits_to_f64(((uint64_t)hx << 32) | (u & 0xffffffffULL)) - 1.0;
+    const double hfsq = 0.5 * f * f;
+    const double s = f / (2.0 + f);
+    const double z = s * s;
+    const double w = z * z;
+    const double t1 = w * (Lg2 + w * (Lg4 + w * Lg6));
+    const double t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
+    const double R = t2 + t1;
+    const double dk = (double)k;
+    return s * (hfsq + R) + dk * ln2_lo - hfsq + f + dk * ln2_hi;
+}
+
 // acos via atan2; exact subtraction 1-t for the float-valued t the path feeds it
 CTM_HD double acos64(double t) {
     if (t >= 1.0) return 0.0;

@@ -5,7 +5,7 @@
 // Mapping: one kernel body, k_pose_cov<Src>, for the three record kinds and both parametrisations; Src
 // says where a record's frames and members are.  One wavefront per source record for every size (4 .. 800 points), grid-stride
 // over the records.
-//   walk      the whole wave walks the record's members with the builder of ctag_pose_dev.h (marker_points) and leaves one
+//   walk      the whole wave walks the record's members (ctag_cov_src.h, shared with k_pose_robust.hip) with the builder of ctag_pose_dev.h (marker_points) and leaves one
 //             8-byte descriptor per point in LDS (which feature, corner, camera, model position) -- there is no LDS image of the
 //             problem itself;
 //   points    lane l takes points l, l+64, ... in order: corner_point (load + undistort), the residual of the pose kernels with
@@ -21,6 +21,7 @@
 #include <new>
 
 #include "../../include/ctag_pose.h"
+#include "ctag_cov_src.h"
 #include "ctag_internal.h"
 #include "ctag_pose_dev.h"
 #include "ctag_schur6.h"
@@ -31,7 +32,6 @@ static_assert(sizeof(ctag_cov_opts) == 24, "ctag_cov_opts layout");
 
 namespace ctag {
 
-constexpr int kCovMaxPts = CTAG_RIG_MAX_POINTS;  // 800
 constexpr int kCovGrid = 256 * 16;               // wavefronts of one launch at most
 constexpr double kCovMinPivot = 1e-12;
 
@@ -48,106 +48,6 @@ struct CovLds {
     int32_t src[kCovMaxPts];
     int32_t model[kCovMaxPts];
     double norm[kCovMaxPts];  // residual norm of point i, written and read by its owner lane
-};
-
-// Member k of frame record FR against model mi, seen by camera c: its points' descriptors from index n on.  False when the
-// marker or the model lies outside its array, the builder rejects the marker or the total passes kCovMaxPts.
-__device__ __forceinline__ bool cov_add_marker(CovLds& L, const int lane, const ctag_frame_result& FR, const int k, const PoseModelDev& model,
-                                               const int mi, const int c, int& n) {
-    if (k < 0 || k >= min(max(FR.n_markers, 0), CTAG_MAX_MARKERS) || mi < 0 || mi >= model.n_models) return false;
-    const ctag_marker_rec& M = FR.markers[k];
-    const ctag_feature_rec* F0 = FR.features;
-    const int base = n;
-    int nl = 0;
-    const int st = marker_points(FR, M, model.model_size, kPoseMaxPts, nl, [&](const ctag_feature_rec& F, int pos, int cnt, int i0) {
-        if (lane < cnt && base + i0 + cnt <= kCovMaxPts) {
-            L.src[base + i0 + lane] = point_desc((int)(&F - F0), lane, c, pos);
-            L.model[base + i0 + lane] = mi;
-        }
-    });
-    n += nl;
-    return st == CTAG_POSE_OK && n <= kCovMaxPts;
-}
-
-// the members of one frame record by a member mask, in marker order, each against the first model with its id.  Not the fits'
-// fit_member_walk (ctag_pose_dev.h), on purpose: a mask bit at or above the frame's marker count is rejected here and ignored there
-__device__ __forceinline__ bool cov_add_members(CovLds& L, const int lane, const ctag_frame_result& FR, const uint32_t* mask, const PoseModelDev& model,
-                                                const int c, int& n) {
-    if (FR.status != CTAG_OK) return false;
-    for (int k = 0; k < 128; k++) {
-        if (!((mask[k >> 5] >> (k & 31)) & 1u)) continue;
-        if (k >= min(max(FR.n_markers, 0), CTAG_MAX_MARKERS)) return false;
-        if (!cov_add_marker(L, lane, FR, k, model, model_lookup(model, FR.markers[k].marker_id), c, n)) return false;
-    }
-    return true;
-}
-
-// ---- the three kinds of source record: count() records; build() leaves the descriptors of record P's points in L (false: rule
-// 2's CTAG_COV_BAD_RECORD); frame(P, c) is the detection record camera c's points of P come from
-struct CovMarkerSrc {
-    using Rec = ctag_pose_rec;
-    static constexpr bool kMultiView = false;
-    const ctag_frame_result* res;
-    int n_frames;
-    const int32_t* offsets;
-    const Rec* recs;
-    int capacity;
-    PoseCam cam;
-    __device__ int count() const { return min(offsets[n_frames], capacity); }
-    __device__ void stage(CovLds& L, int lane) const {
-        if (lane == 0) L.cam[0] = cam;
-    }
-    __device__ const ctag_frame_result& frame(const Rec& P, int) const { return res[P.frame]; }
-    __device__ bool build(const Rec& P, const PoseModelDev& model, CovLds& L, int lane, int& n) const {
-        if (P.frame < 0 || P.frame >= n_frames || res[P.frame].status != CTAG_OK) return false;
-        return cov_add_marker(L, lane, res[P.frame], P.marker, model, P.model_index, 0, n);
-    }
-};
-
-struct CovRigSrc {
-    using Rec = ctag_rig_pose_rec;
-    static constexpr bool kMultiView = false;
-    const ctag_frame_result* res;
-    int n_frames, n_records;
-    const Rec* recs;
-    PoseCam cam;
-    __device__ int count() const { return n_records; }
-    __device__ void stage(CovLds& L, int lane) const {
-        if (lane == 0) L.cam[0] = cam;
-    }
-    __device__ const ctag_frame_result& frame(const Rec& P, int) const { return res[P.frame]; }
-    __device__ bool build(const Rec& P, const PoseModelDev& model, CovLds& L, int lane, int& n) const {
-        if (P.frame < 0 || P.frame >= n_frames) return false;
-        return cov_add_members(L, lane, res[P.frame], P.member_mask, model, 0, n);
-    }
-};
-
-struct CovMvSrc {
-    using Rec = ctag_mv_pose_rec;
-    static constexpr bool kMultiView = true;
-    MvResults res;
-    int n_frames, n_records;
-    const Rec* recs;
-    MvCams cams;
-    __device__ int count() const { return n_records; }
-    __device__ void stage(CovLds& L, int lane) const {
-        for (int c = lane; c < kMvCams; c += 64) {
-            L.cam[c] = cams.cam[c];
-            for (int i = 0; i < 9; i++) L.R[c][i] = cams.R[c][i];
-            for (int i = 0; i < 3; i++) L.t[c][i] = cams.t[c][i];
-        }
-    }
-    __device__ const ctag_frame_result& frame(const Rec& P, int c) const { return res.p[c][P.frame]; }
-    __device__ bool build(const Rec& P, const PoseModelDev& model, CovLds& L, int lane, int& n) const {
-        if (P.frame < 0 || P.frame >= n_frames) return false;
-        for (int c = 0; c < kMvCams; c++) {
-            const uint32_t* mask = P.member_mask[c];
-            if ((mask[0] | mask[1] | mask[2] | mask[3]) == 0u) continue;
-            if (c >= cams.n) return false;
-            if (!cov_add_members(L, lane, res.p[c][P.frame], mask, model, c, n)) return false;
-        }
-        return true;
-    }
 };
 
 // Inverse of a symmetric 6x6 C (row-major, the lower triangle is read) by Cholesky, C = L L^T: inv = L^-T L^-1, exactly
@@ -371,19 +271,6 @@ int cov_opts(const ctag_cov_opts* o, ctag::CovOpts& r) {
     return CTAG_OK;
 }
 
-// what every batch call does before it launches: the device, the model's device copy, the frames that wait for the any-frame pass
-int cov_prepare(ctag_handle* h, const ctag_model* model_c, ctag::PoseModelDev& md, hipStream_t& s) {
-    ctag_model* model = const_cast<ctag_model*>(model_c);
-    const int dev = ctag::handle_device(h);
-    if (hipSetDevice(dev) != hipSuccess) return CTAG_ERR_HIP;
-    if (ctag::model_to_device(model, dev) != CTAG_OK) return CTAG_ERR_HIP;
-    const int fr = ctag::handle_finish_pending(h);
-    if (fr != CTAG_OK) return fr;
-    md = ctag::PoseModelDev{model->n_models, model->model_size, model->d_ids.p, model->d_corners.p};
-    s = static_cast<hipStream_t>(ctag_stream(h));
-    return CTAG_OK;
-}
-
 template <class Src>
 int cov_launch(const Src& src, int n_records, const ctag::PoseModelDev& md, const ctag::CovOpts& opts, ctag_pose_cov_rec* out_dev, hipStream_t s) {
     hipLaunchKernelGGL(ctag::k_pose_cov<Src>, dim3(std::min(n_records, ctag::kCovGrid)), dim3(64), 0, s, src, md, opts, out_dev);
@@ -432,7 +319,7 @@ int ctag_pose_cov_batch_device(ctag_handle* h, const ctag_frame_result* results_
     if (n_frames == 0 || capacity == 0) return CTAG_OK;
     ctag::PoseModelDev md;
     hipStream_t s;
-    const int rc = cov_prepare(h, model, md, s);
+    const int rc = ctag::cov_prepare(h, model, md, s);
     if (rc != CTAG_OK) return rc;
     const ctag::CovMarkerSrc src{results_dev, n_frames, offsets_dev, poses_dev, capacity, ctag::make_pose_cam(camera)};
     return cov_launch(src, capacity, md, o, out_dev, s);
@@ -451,7 +338,7 @@ int ctag_rig_pose_cov_batch_device(ctag_handle* h, const ctag_frame_result* resu
     if (n_items == 0) return CTAG_OK;
     ctag::PoseModelDev md;
     hipStream_t s;
-    const int rc = cov_prepare(h, model, md, s);
+    const int rc = ctag::cov_prepare(h, model, md, s);
     if (rc != CTAG_OK) return rc;
     const ctag::CovRigSrc src{results_dev, n_frames, (int)n_items, rig_poses_dev, ctag::make_pose_cam(camera)};
     return cov_launch(src, (int)n_items, md, o, out_dev, s);
@@ -474,7 +361,7 @@ int ctag_mv_rig_pose_cov_batch_device(ctag_handle* h, const ctag_frame_result* c
     if (n_items == 0) return CTAG_OK;
     ctag::PoseModelDev md;
     hipStream_t s;
-    const int rc = cov_prepare(h, model, md, s);
+    const int rc = ctag::cov_prepare(h, model, md, s);
     if (rc != CTAG_OK) return rc;
     src.n_frames = n_frames;
     src.n_records = (int)n_items;

@@ -102,6 +102,29 @@ int main(int argc, char** argv) {
             }
             return 0;
         }
+        if (mode == "robust") {  // estimatePoseRobust on the image's markers, every double as a hexadecimal float, the inlier flags as 0 / 1
+            if (argc < 9) return 2;
+            CylinderTag t(argv[2]);
+            const ctag_host::GrayImage g = ctag_host::read_bmp_gray(argv[3]);
+            std::vector<MarkerInfo> m;
+            t.detect(ctag_host::Mat(g.rows, g.cols, g.px.data()), m, 5, true, 5);
+            std::vector<ModelInfo> model;
+            CamInfo cam;
+            t.loadModel(argv[4], model);
+            t.loadCamera(argv[5], cam);
+            std::vector<RobustPoseInfo> rob;
+            t.estimatePoseRobust(m, model, cam, rob, std::atoi(argv[6]) != 0, std::atof(argv[7]), std::atoi(argv[8]));
+            for (const RobustPoseInfo& r : rob) {
+                std::printf("robust %d %d %d %d %d %d %d %a %a %a %a %a %a %a", r.markerID, r.status, r.nPoints, r.nInliers, r.iterations, r.loss, r.worstPoint,
+                            r.scalePx, r.sigmaHat, r.costLs0, r.costLs, r.cost0, r.cost, r.maxResidualPx);
+                for (int k = 0; k < 3; k++) std::printf(" %a", r.rvec[k]);
+                for (int k = 0; k < 3; k++) std::printf(" %a", r.tvec[k]);
+                std::printf(" ");
+                for (bool b : r.inlier) std::printf("%d", b ? 1 : 0);
+                std::printf("\n");
+            }
+            return 0;
+        }
         int fs = 0;
         const ctag_host::Mat1i dict = read_dictionary(argv[2], fs);
         CylinderTag marker(dict, fs);  // CylinderTag(const Mat1i&) (header/CylinderTag.h:18)

@@ -39,7 +39,7 @@ WELSCH_LIMITS = ("kWShort", "kWCap", "kWRes", "kWPts", "kWPtsU", "kPickN", "kPic
                  "kLatencyFrames", "kLatRankBlocks", "kLineSortBuckets")
 REFINE_FORMS = ("none", "one", "split_large", "split_looping", "split")                     # ChunkPlan::refine
 # op codes of Detector.math (ctag_math_probe; oracle/ctag_oracle.h lists 0..16) that tests name
-MATH_EXP32_NONPOS, MATH_EXP32_NONPOS_K0 = 15, 17
+MATH_EXP32_NONPOS, MATH_EXP32_NONPOS_K0, MATH_LOG64 = 15, 17, 18
 
 
 def lib_path():

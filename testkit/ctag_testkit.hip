@@ -45,6 +45,7 @@ __global__ void k_math_probe(int op, int n, const double* a, const double* b, do
         case 15: r = ctm::exp32_nonpos((float)x); break;  // x <= 0, not NaN
         case 16: r = ctm::div64(x, ctm::recip64(y)); break;  // x / y through the shared-reciprocal form (device) or `/` (host)
         case 17: r = ctm::exp32_nonpos_k0((float)x); break;  // x <= 0 with ctm::exp32_k_is_zero(x)
+        case 18: r = ctm::log64(x); break;
         default: break;
     }
     out[i] = r;
