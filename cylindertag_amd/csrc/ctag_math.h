@@ -6,10 +6,20 @@
 // function below is built only from IEEE-754 +,-,*,/ and sqrt in a fixed evaluation order, so the same
 // source gives the same bits under gcc (x86-64, -ffp-contract=off) and hipcc (gfx950, -ffp-contract=off).
 //
-// Accuracy: the double kernels follow the classic fdlibm argument-reduction + minimax-polynomial schemes
-// (error < 1 ulp in double).  The float entry points evaluate in double and round once, which is the
-// correctly rounded float result except in ~2^-29 of cases.  tests/test_math.py pins all of this against
-// glibc on the CPU and against the gfx950 build on the GPU.
+// Accuracy: the double kernels follow the classic fdlibm argument-reduction + minimax-polynomial schemes, with shorter reductions (one Cody-Waite
+// step for sin / cos, a table and a Taylor series for exp, acos through atan2) that cost a little of fdlibm's "< 1 ulp".  Worst errors against the
+// true value (mpmath, 240 bits) over the fixed argument sets of tests/math_shapes.py, in ulp of the true value, each rounded up to the next tenth
+// ("Accuracy of the shared math", has the table per set):
+//   sin64  1.4   cos64  1.3   over |x| <= 1e5, the doubles next to k pi/2 included (0.5 there)      atan2_64  1.2   over 2^+-430, at the 2^+-60 shortcut
+//   exp64  1.8   over [-708, 709]                 log64  0.7   over every positive double            acos64    2.1   on float-valued arguments
+//   exp32  1.0 float ulp over [-87, 88]
+// Nothing downstream needs less: the float entry points evaluate in double and round once, which is the correctly rounded float result except where the
+// double lands within its own error of a float rounding boundary (never more than 1 float ulp off, correctly rounded in > 99.9 % of cases), and the
+// knife-edge constants (kAcosBelowTenMilli) are pinned to these functions themselves.  Special values are C's, with three documented exceptions: exp64
+// is inf above 709 and 0 below -708, exp32 is 0 below -87 and inf above 88, and sin64 / sin32 do not keep the sign of a zero (sin64(-0.0) is +0.0).
+// Tests: tests/test_math_statement_cpu.py holds the host build to the figures above and to the special values (tests/test_oracle_cpu.py has the older,
+// looser checks against numpy and the knife-edge constants); tests/test_math_device_gpu.py and tests/test_gpu_parity.py require the gfx950 build to give
+// the host's bits, on the edge sets and on broad random ones.
 #pragma once
 #include <stdint.h>
 
@@ -93,7 +103,10 @@ CTM_HD double atan2_64(double y, double x) {
     const int k = ey - ex;
     double z;
     if (k > 60) {
-        z = pi_o_2 + 0.5 * pi_lo;
+        // |y / x| > 2^60: the angle is pi/2 -+ |x / y| with |x / y| < 2^-60, and pi/2 lies 0.28 ulp above pi_o_2 -- the nearest double is pi_o_2 on
+        // either side of the y axis.  (fdlibm's z = pi_o_2 + 0.5 pi_lo is pi_o_2 too; sent through pi - (z - pi_lo) for x < 0 it came out one ulp
+        // above, where C's atan2 gives pi_o_2: tests/test_math_statement_cpu.py, the pairs of a finite y with the smallest negative subnormal x.)
+        return sy ? -pi_o_2 : pi_o_2;
     } else if (sx && k < -60) {
         z = 0.0;
     } else {
@@ -210,7 +223,7 @@ CTM_HD double exp64(double x) {
 }
 
 // log(x), the natural logarithm (the Cauchy loss of k_pose_robust.hip): fdlibm's scheme, x = 2^k (1 + f) with sqrt(2)/2 < 1 + f < sqrt(2),
-// s = f / (2 + f), log(1 + f) = f - f^2/2 + s (f^2/2 + R(s^2)), R a minimax polynomial of degree 14 in s; error < 1 ulp.  Zero gives -inf,
+// s = f / (2 + f), log(1 + f) = f - f^2/2 + s (f^2/2 + R(s^2)), R a minimax polynomial of degree 14 in s; error 0.7 ulp at worst (see the top).  Zero gives -inf,
 // a negative argument NaN, inf and NaN themselves.
 CTM_HD double log64(double x) {
     const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
@@ -329,8 +342,11 @@ CTM_HD float exp32_nonpos_k0(float x) {
 // on the host; on the device the compiler's own expansion of a double division -- v_rcp_f64, two Newton steps on the reciprocal, then
 // per numerator q = a r, e = a - d q, q + e r (correctly rounded: it is the sequence v_div_fmas / v_div_fixup finish) -- with the
 // reciprocal's part done once instead of once per quotient.  The expansion's v_div_scale / v_div_fixup guard exponents near the ends of
-// the range; left out, so: d and every a / d normal and far from overflow (|d| in [2^-500, 2^500], |a| <= 2^500 |d|, a / d >= 2^-500
-// or zero), which sums of at most a few thousand pixel coordinates times weights in (0, 1] are.  tests: math probe 16 against `/`.
+// the range; left out, so: d and every a / d normal and far from overflow (|d| in [2^-500, 2^500], |a| <= 2^500 |d|, |a / d| >= 2^-500
+// or a = +0.0), which sums of at most a few thousand pixel coordinates times weights in (0, 1] are.  A zero numerator is +0.0, never -0.0: for
+// a = -0.0 and d > 0 the device form returns +0.0 (a - d q is +0, and +0 r + -0 is +0) where `/` gives -0.0.  Every caller divides sums that start at +0.0
+// and add products of non-negative coordinates, weights and counts (moments_to_line in k_quad.hip, refine_line in k_feature.hip): such a sum is never -0.0.  tests: math probe 16 against `/`, on broad ranges
+// (tests/test_gpu_parity.py) and at the corners of this domain (tests/test_math_device_gpu.py).
 struct Recip64 {
     double d, r;
 };

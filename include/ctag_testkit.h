@@ -5,6 +5,7 @@
  * bench.py and the developer tools need around the product:
  *   - parity probes: the intermediates of a frame of the last chunk (stages a1..a8 of SURVEY.md 8(a)),
  *   - the shared deterministic math (cylindertag_amd/csrc/ctag_math.h) evaluated on the device,
+ *   - one wave primitive of cylindertag_amd/csrc/ctag_wave.h at a time, under caller-given lane masks,
  *   - the synthetic frame generators,
  *   - the unpack half of ctag_gather_end on a caller-built gathered buffer (the multi-rank device path on one GPU).
  * libctag_testkit.so links against libctag_hip.so and reaches into a handle only through the private accessors of
@@ -50,6 +51,55 @@ long ctag_debug_fetch(ctag_handle* h, int frame, int what, void* dst, size_t cap
 /* evaluates the shared deterministic math on the device; op codes as oracle/ctag_oracle.h:ctago_math_probe.
  * Host arrays in/out. */
 int ctag_math_probe(ctag_handle* h, int op, int n, const double* a, const double* b, double* out);
+
+/* ---- one primitive of cylindertag_amd/csrc/ctag_wave.h by itself ---------------------------------------------------------------------------
+ * n_waves waves of 64 lanes; lane l of wave w is element 64 w + l of a, ia, out and iout (host arrays) and bit l of active[w].  Every lane's out / iout
+ * first get the sentinels; the lanes whose bit is set then call the primitive inside a branch, so the other lanes are off where it runs and keep the
+ * sentinels.  block_threads is 64 or 256 (four waves a block).  Operands and results:
+ *   lane moves, scan and sums on int          low word of ia -> iout, zero-extended (SHR1_F32: the float's bits)
+ *   lane moves and sums on long long          ia -> iout
+ *   SHR1_F64, SUM_F64                         a -> out
+ *   SG_BEST* (d = (float)a, index = ia), MAX_F64 (d = a, index = ia)   -> out (the best d), iout (its index); NEAREST: the smallest d, ties to the lowest
+ *                                             index; FARTHEST: the largest d, ties to the highest index (the two orders of k_quad.hip)
+ *   ALL                                       predicate ia != 0 -> iout 0 / 1
+ *   PK_MIN_U16 / PK_MAX_U16                   the low and the high word of ia -> iout
+ * CTAG_ERR_ARG where the mask breaks the primitive's contract (ctag_wave.h), so that no result is an undefined value: the whole-wave forms (SG_SUM64*,
+ * SG_BEST64*, SUM_F64, MAX_F64, INCL_SCAN) take all-ones masks only, the 8-lane forms (SG_SUM8*, SG_BEST8*) masks whose sub-groups are on or off as a
+ * whole.  Runs on the handle's device and stream and waits. */
+#define CTAG_WAVE_FROM_PREV 0
+#define CTAG_WAVE_FROM_NEXT 1
+#define CTAG_WAVE_SHR1_I32 2
+#define CTAG_WAVE_SHR2_I32 3
+#define CTAG_WAVE_SHR4_I32 4
+#define CTAG_WAVE_SHR1_F32 5
+#define CTAG_WAVE_SHR1_F64 6
+#define CTAG_WAVE_XOR1_I32 7
+#define CTAG_WAVE_XOR2_I32 8
+#define CTAG_WAVE_HALF_MIRROR_I32 9
+#define CTAG_WAVE_ROW_MIRROR_I32 10
+#define CTAG_WAVE_XOR1_I64 11
+#define CTAG_WAVE_XOR2_I64 12
+#define CTAG_WAVE_HALF_MIRROR_I64 13
+#define CTAG_WAVE_ROW_MIRROR_I64 14
+#define CTAG_WAVE_INCL_SCAN 15
+#define CTAG_WAVE_SG_SUM8_I32 16
+#define CTAG_WAVE_SG_SUM64_I32 17
+#define CTAG_WAVE_SG_SUM8_I64 18
+#define CTAG_WAVE_SG_SUM64_I64 19
+#define CTAG_WAVE_SG_BEST8_NEAREST 20
+#define CTAG_WAVE_SG_BEST8_FARTHEST 21
+#define CTAG_WAVE_SG_BEST64_NEAREST 22
+#define CTAG_WAVE_SG_BEST64_FARTHEST 23
+#define CTAG_WAVE_SUM_F64 24
+#define CTAG_WAVE_MAX_F64 25
+#define CTAG_WAVE_ALL 26
+#define CTAG_WAVE_PK_MIN_U16 27
+#define CTAG_WAVE_PK_MAX_U16 28
+#define CTAG_WAVE_OPS 29
+#define CTAG_WAVE_SENTINEL_F64 (-12345.6789)
+#define CTAG_WAVE_SENTINEL_I64 (-0x5a5a5a5a5a5a5a5aLL)
+int ctag_testkit_wave_probe(ctag_handle* h, int op, int block_threads, int n_waves, const uint64_t* active, const double* a, const int64_t* ia, double* out,
+                            int64_t* iout);
 
 /* exp32_nonpos_k0 and exp32_k_is_zero (cylindertag_amd/csrc/ctag_math.h) against exp32_nonpos on the HOST, over the floats of bit patterns first_bits,
  * first_bits + step, ... up to last_bits (all of them <= 0 and not NaN, else CTAG_ERR_ARG; among negative floats a larger pattern lies further from zero).

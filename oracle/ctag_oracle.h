@@ -91,7 +91,8 @@ void ctago_fitline_welsch(const int32_t* xy, int n, float* line4);
 void ctago_set_variants(int welsch_minerr_in_loop, int resize_simd_lanes);
 void ctago_fitline_welsch_variant(const int32_t* xy, int n, int variant, float* line4);
 /* op: 0 atan2_64(a,b) 1 sin64(a) 2 cos64(a) 3 exp64(a) 4 acos64(a) 5 atan2_32 6 sin32 7 cos32 8 exp32
- *     9 fast_atan2_deg(a,b) 10 a/b (f64) 11 sqrt(a) (f64) 12 a/b (f32) 13 sqrtf(a) 14 round32(a) */
+ *     9 fast_atan2_deg(a,b) 10 a/b (f64) 11 sqrt(a) (f64) 12 a/b (f32) 13 sqrtf(a) 14 round32(a)
+ *     15 exp32_nonpos(a) 16 div64(a, recip64(b)) 17 exp32_nonpos_k0(a) 18 log64(a) */
 void ctago_math_probe(int op, int n, const double* a, const double* b, double* out);
 /* 1 when built with -DCTAG_ORACLE_LIBM (glibc libm instead of ctag_math.h) */
 int ctago_uses_libm(void);

@@ -22,7 +22,7 @@ DBG_HALF, DBG_LABELS, DBG_CANDIDATES, DBG_CAND_QUADS, DBG_FEATURES0, DBG_FEATURE
 SYNTH_SEED = 0x4354616753594E00  # "CTagSYN\0", SURVEY.md 8(d)
 
 # every symbol include/ctag_testkit.h declares (tests check the library exports all of them)
-EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_exp32_k0_sweep", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
+EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_wave_probe", "ctag_testkit_exp32_k0_sweep", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
            "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model",
            "ctag_testkit_dense_edge_probe", "ctag_testkit_plan", "ctag_testkit_welsch_fit", "ctag_testkit_welsch_limits",
            "ctag_testkit_model_fit_system", "ctag_testkit_model_fit_limits", "ctag_testkit_rig_fit_system", "ctag_testkit_rig_fit_limits",
@@ -38,8 +38,15 @@ CCL_FORMS = ("mask", "tw5", "any")                                              
 WELSCH_LIMITS = ("kWShort", "kWCap", "kWRes", "kWPts", "kWPtsU", "kPickN", "kPickN2", "kWE", "kWT", "kLatLines", "kLatPoints", "kLatChunk", "kLdsLines",
                  "kLatencyFrames", "kLatRankBlocks", "kLineSortBuckets")
 REFINE_FORMS = ("none", "one", "split_large", "split_looping", "split")                     # ChunkPlan::refine
-# op codes of Detector.math (ctag_math_probe; oracle/ctag_oracle.h lists 0..16) that tests name
+# op codes of Detector.math (ctag_math_probe; oracle/ctag_oracle.h lists them) that tests name
 MATH_EXP32_NONPOS, MATH_EXP32_NONPOS_K0, MATH_LOG64 = 15, 17, 18
+# op codes of Detector.wave (ctag_testkit_wave_probe; include/ctag_testkit.h: CTAG_WAVE_*), in the header's order
+WAVE_OPS = ("FROM_PREV", "FROM_NEXT", "SHR1_I32", "SHR2_I32", "SHR4_I32", "SHR1_F32", "SHR1_F64", "XOR1_I32", "XOR2_I32", "HALF_MIRROR_I32", "ROW_MIRROR_I32",
+            "XOR1_I64", "XOR2_I64", "HALF_MIRROR_I64", "ROW_MIRROR_I64", "INCL_SCAN", "SG_SUM8_I32", "SG_SUM64_I32", "SG_SUM8_I64", "SG_SUM64_I64",
+            "SG_BEST8_NEAREST", "SG_BEST8_FARTHEST", "SG_BEST64_NEAREST", "SG_BEST64_FARTHEST", "SUM_F64", "MAX_F64", "ALL", "PK_MIN_U16", "PK_MAX_U16")
+for _i, _n in enumerate(WAVE_OPS):
+    globals()["WAVE_" + _n] = _i
+WAVE_SENTINEL_F64, WAVE_SENTINEL_I64 = -12345.6789, -0x5a5a5a5a5a5a5a5a  # what a lane that was off keeps (CTAG_WAVE_SENTINEL_*)
 
 
 def lib_path():
@@ -68,6 +75,8 @@ def load_library():
     L.ctag_debug_fetch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L.ctag_math_probe.restype = C.c_int
     L.ctag_math_probe.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    L.ctag_testkit_wave_probe.restype = C.c_int
+    L.ctag_testkit_wave_probe.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.ctag_testkit_exp32_k0_sweep.restype = C.c_int
     L.ctag_testkit_exp32_k0_sweep.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.ctag_testkit_unpack_gathered.restype = C.c_int
@@ -436,3 +445,18 @@ class Detector(ca.Detector):
         if st != 0:
             raise CtagError(st, "ctag_math_probe")
         return out
+
+    def wave(self, op, active, a=None, ia=None, block_threads=64):
+        """One primitive of ctag_wave.h by itself (ctag_testkit_wave_probe): active uint64 [n_waves], a float64 / ia int64 [n_waves, 64] (zeros when
+        left out) -> (out float64, iout int64), both [n_waves, 64]; a lane that was off keeps WAVE_SENTINEL_*.  Raises CtagError where the mask breaks
+        the primitive's contract."""
+        active = np.ascontiguousarray(active, np.uint64).reshape(-1)
+        n = active.size
+        a = np.ascontiguousarray(a if a is not None else np.zeros((n, 64)), np.float64).reshape(n, 64)
+        ia = np.ascontiguousarray(ia if ia is not None else np.zeros((n, 64), np.int64), np.int64).reshape(n, 64)
+        out, iout = np.zeros((n, 64), np.float64), np.zeros((n, 64), np.int64)
+        st = self.T.ctag_testkit_wave_probe(self.h, int(op), int(block_threads), n, active.ctypes.data, a.ctypes.data, ia.ctypes.data, out.ctypes.data,
+                                            iout.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_testkit_wave_probe")
+        return out, iout

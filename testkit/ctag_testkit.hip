@@ -10,6 +10,7 @@
 #include "../include/ctag_testkit.h"
 #include "../cylindertag_amd/csrc/ctag_internal.h"
 #include "../cylindertag_amd/csrc/ctag_math.h"
+#include "../cylindertag_amd/csrc/ctag_wave.h"
 #include "ctag_synth.h"
 
 using namespace ctag;
@@ -49,6 +50,75 @@ __global__ void k_math_probe(int op, int n, const double* a, const double* b, do
         default: break;
     }
     out[i] = r;
+}
+
+// One primitive of ctag_wave.h per launch, one wave per 64 consecutive threads.  Every lane first writes the sentinel; the lanes of the wave's `active` mask
+// then call the primitive inside the branch, so the other lanes are off in EXEC where it runs.  `op` is uniform: the switch is a scalar branch.
+__global__ void k_wave_probe(int op, const unsigned long long* active, const double* a, const long long* ia, double* out, long long* iout) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    out[i] = CTAG_WAVE_SENTINEL_F64;
+    iout[i] = CTAG_WAVE_SENTINEL_I64;
+    const double x = a[i];
+    const long long w = ia[i];
+    const int w32 = (int)(unsigned)((unsigned long long)w & 0xffffffffull);
+    const uint32_t whi = (uint32_t)((unsigned long long)w >> 32);
+    if (!((active[i >> 6] >> (i & 63)) & 1ull)) return;
+    double r = 0.0;
+    long long ir = 0;
+    auto u32 = [](int v) { return (long long)(unsigned long long)(uint32_t)v; };
+    auto nearest = [](float od, int oi, float d, int k) { return od < d || (od == d && oi < k); };   // k_quad.hip: the nearest, ties: the first
+    auto farthest = [](float od, int oi, float d, int k) { return od > d || (od == d && oi > k); };  // k_quad.hip: the farthest, ties: the last
+    switch (op) {
+        case CTAG_WAVE_FROM_PREV: ir = (long long)wave_from_prev((uint32_t)w32); break;
+        case CTAG_WAVE_FROM_NEXT: ir = (long long)wave_from_next((uint32_t)w32); break;
+        case CTAG_WAVE_SHR1_I32: ir = u32(dpp_shr<1>(w32)); break;
+        case CTAG_WAVE_SHR2_I32: ir = u32(dpp_shr<2>(w32)); break;
+        case CTAG_WAVE_SHR4_I32: ir = u32(dpp_shr<4>(w32)); break;
+        case CTAG_WAVE_SHR1_F32: ir = u32(__float_as_int(dpp_shr<1>(__int_as_float(w32)))); break;
+        case CTAG_WAVE_SHR1_F64: r = dpp_shr<1>(x); break;
+        case CTAG_WAVE_XOR1_I32: ir = u32(dpp_mov<kDppXor1>(w32)); break;
+        case CTAG_WAVE_XOR2_I32: ir = u32(dpp_mov<kDppXor2>(w32)); break;
+        case CTAG_WAVE_HALF_MIRROR_I32: ir = u32(dpp_mov<kDppHalfMirror>(w32)); break;
+        case CTAG_WAVE_ROW_MIRROR_I32: ir = u32(dpp_mov<kDppRowMirror>(w32)); break;
+        case CTAG_WAVE_XOR1_I64: ir = dpp_mov<kDppXor1>(w); break;
+        case CTAG_WAVE_XOR2_I64: ir = dpp_mov<kDppXor2>(w); break;
+        case CTAG_WAVE_HALF_MIRROR_I64: ir = dpp_mov<kDppHalfMirror>(w); break;
+        case CTAG_WAVE_ROW_MIRROR_I64: ir = dpp_mov<kDppRowMirror>(w); break;
+        case CTAG_WAVE_INCL_SCAN: ir = u32(wave_incl_scan(w32)); break;
+        case CTAG_WAVE_SG_SUM8_I32: ir = u32(sg_sum<8>(w32)); break;
+        case CTAG_WAVE_SG_SUM64_I32: ir = u32(sg_sum<64>(w32)); break;
+        case CTAG_WAVE_SG_SUM8_I64: ir = sg_sum<8>(w); break;
+        case CTAG_WAVE_SG_SUM64_I64: ir = sg_sum<64>(w); break;
+        case CTAG_WAVE_SG_BEST8_NEAREST:
+        case CTAG_WAVE_SG_BEST8_FARTHEST:
+        case CTAG_WAVE_SG_BEST64_NEAREST:
+        case CTAG_WAVE_SG_BEST64_FARTHEST: {
+            float bd = (float)x;  // -0, +-inf and every float-valued double pass unchanged
+            int bi = w32;
+            if (op == CTAG_WAVE_SG_BEST8_NEAREST) sg_best<8>(bd, bi, nearest);
+            else if (op == CTAG_WAVE_SG_BEST8_FARTHEST) sg_best<8>(bd, bi, farthest);
+            else if (op == CTAG_WAVE_SG_BEST64_NEAREST) sg_best<64>(bd, bi, nearest);
+            else sg_best<64>(bd, bi, farthest);
+            r = (double)bd;
+            ir = (long long)bi;
+            break;
+        }
+        case CTAG_WAVE_SUM_F64: r = wave_sum_f64(x); break;
+        case CTAG_WAVE_MAX_F64: {
+            double bd = x;
+            int bi = w32;
+            wave_max_f64(bd, bi);
+            r = bd;
+            ir = (long long)bi;
+            break;
+        }
+        case CTAG_WAVE_ALL: ir = wave_all(w != 0) ? 1 : 0; break;
+        case CTAG_WAVE_PK_MIN_U16: ir = (long long)pk_min_u16((uint32_t)w32, whi); break;
+        case CTAG_WAVE_PK_MAX_U16: ir = (long long)pk_max_u16((uint32_t)w32, whi); break;
+        default: break;
+    }
+    out[i] = r;
+    iout[i] = ir;
 }
 
 __global__ void k_label_roots(const uint16_t* labels, const int32_t* tile_base, const int32_t* root_of, int32_t* out, FrameGeom g) {
@@ -493,6 +563,55 @@ int ctag_math_probe(ctag_handle* h, int op, int n, const double* a, const double
     (void)hipFree(da);
     (void)hipFree(db);
     (void)hipFree(dout);
+    return rc;
+}
+
+int ctag_testkit_wave_probe(ctag_handle* h, int op, int block_threads, int n_waves, const uint64_t* active, const double* a, const int64_t* ia, double* out,
+                            int64_t* iout) {
+    if (!h || op < 0 || op >= CTAG_WAVE_OPS || (block_threads != 64 && block_threads != 256) || n_waves < 0 || n_waves > 65536 || !active || !a || !ia || !out ||
+        !iout)
+        return CTAG_ERR_ARG;
+    const bool whole = op == CTAG_WAVE_SG_SUM64_I32 || op == CTAG_WAVE_SG_SUM64_I64 || op == CTAG_WAVE_SG_BEST64_NEAREST || op == CTAG_WAVE_SG_BEST64_FARTHEST ||
+                       op == CTAG_WAVE_SUM_F64 || op == CTAG_WAVE_MAX_F64 || op == CTAG_WAVE_INCL_SCAN;
+    const bool sub8 = op == CTAG_WAVE_SG_SUM8_I32 || op == CTAG_WAVE_SG_SUM8_I64 || op == CTAG_WAVE_SG_BEST8_NEAREST || op == CTAG_WAVE_SG_BEST8_FARTHEST;
+    for (int w = 0; w < n_waves; w++) {
+        if (whole && active[w] != ~0ull) return CTAG_ERR_ARG;  // all 64 lanes are the caller's duty: a v_readlane would read a masked-off lane's stale register
+        if (sub8)
+            for (int g = 0; g < 8; g++) {
+                const uint64_t m = (active[w] >> (8 * g)) & 0xffull;
+                if (m != 0 && m != 0xffull) return CTAG_ERR_ARG;  // a sub-group is on or off as a whole (ctag_wave.h)
+            }
+    }
+    if (n_waves == 0) return CTAG_OK;
+    HandleView v{};
+    handle_view(h, &v);
+    TK_TRY(hipSetDevice(v.device));
+    hipStream_t s = static_cast<hipStream_t>(ctag_stream(h));
+    const int wpb = block_threads / 64, blocks = (n_waves + wpb - 1) / wpb;
+    const size_t nw = (size_t)blocks * wpb, nl = nw * 64, n = (size_t)n_waves * 64;  // whole blocks: the waves past n_waves have no active lane
+    unsigned long long* dact = nullptr;
+    double *da = nullptr, *dout = nullptr;
+    long long *dia = nullptr, *diout = nullptr;
+    int rc = CTAG_OK;
+    if (hipMalloc(reinterpret_cast<void**>(&dact), nw * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&da), nl * 8) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&dia), nl * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&dout), nl * 8) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&diout), nl * 8) != hipSuccess)
+        rc = CTAG_ERR_HIP;
+    if (rc == CTAG_OK && (hipMemset(dact, 0, nw * 8) != hipSuccess || hipMemset(da, 0, nl * 8) != hipSuccess || hipMemset(dia, 0, nl * 8) != hipSuccess)) rc = CTAG_ERR_HIP;
+    if (rc == CTAG_OK && (hipMemcpy(dact, active, (size_t)n_waves * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(da, a, n * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(dia, ia, n * 8, hipMemcpyHostToDevice) != hipSuccess))
+        rc = CTAG_ERR_HIP;
+    if (rc == CTAG_OK) {
+        hipLaunchKernelGGL(k_wave_probe, dim3(blocks), dim3(block_threads), 0, s, op, dact, da, dia, dout, diout);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess || hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(iout, diout, n * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = CTAG_ERR_HIP;
+    }
+    (void)hipFree(dact);
+    (void)hipFree(da);
+    (void)hipFree(dia);
+    (void)hipFree(dout);
+    (void)hipFree(diout);
     return rc;
 }
 
