@@ -338,6 +338,14 @@ CTM_HD float exp32_nonpos_k0(float x) {
     p = p * r + 0.5f;
     return (p * (r * r) + r) + 1.0f;
 }
+// exp32_k_is_zero of the Welsch weight's argument, asked of the distance itself.  k_welsch forms the argument as a = -r * r * c * c with c = 1 / 2.9846f
+// (left to right: three float products) and |r| the point's distance from the line.  Every step of that chain, and the product a * log2e the predicate
+// rounds, is monotone in |r| (rounding is monotone, the factors are positive), so exp32_k_is_zero(a) is a threshold on |r|: kWelschK0MaxDist is the
+// largest float |r| for which it holds (0x3fe0e6fb = 1.75704896450042724609375; the next float up gives k = -1).  NaN fails both.
+// tests/test_welsch_rzero_cpu.py finds the constant again by bisection and holds the two predicates together over every float of the binades around it
+// and every 64th elsewhere up to 2^12.
+constexpr float kWelschK0MaxDist = 1.75704896450042724609375f;
+CTM_HD bool welsch_k_is_zero(float abs_r) { return abs_r <= kWelschK0MaxDist; }
 // Several quotients with ONE denominator (the five moments over their weight in fitLine and in edgeRefine): IEEE division, so a / d
 // on the host; on the device the compiler's own expansion of a double division -- v_rcp_f64, two Newton steps on the reciprocal, then
 // per numerator q = a r, e = a - d q, q + e r (correctly rounded: it is the sequence v_div_fmas / v_div_fixup finish) -- with the

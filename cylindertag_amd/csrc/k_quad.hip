@@ -116,11 +116,6 @@ struct CvRng {
 #ifndef CTAG_WCAP
 #define CTAG_WCAP 16
 #endif
-#ifndef CTAG_WUNROLL
-#define CTAG_WUNROLL 2
-#endif
-#define CTAG_PRAGMA_(x) _Pragma(#x)
-#define CTAG_PRAGMA(x) CTAG_PRAGMA_(x)
 constexpr int kWCap = CTAG_WCAP;  // Welsch weights of the first kWCap points are kept in LDS between the two passes
 // Point sources of a restart: the cluster in global memory as packed (x | y << 16) words, or -- for a wave's three edges of at most
 // kWPts points -- the same points converted to float pairs once per block in LDS (the 20 restarts of an edge read the same
@@ -195,9 +190,12 @@ __device__ __forceinline__ void welsch_first_fit(const Pts pts, const Picks pick
 struct WeightTrips {
     unsigned fast = 0, general = 0;
 };
+// The vote is taken on the distance r (not negative) itself: ctm::welsch_k_is_zero(r) is exp32_k_is_zero(a) for a = -r * r * c * c, without the product by log2e.
+constexpr float kWelschC = 1 / 2.9846f;
 template <bool COUNT>
-__device__ __forceinline__ float welsch_weight(float a, WeightTrips& trips) {
-    const bool fast = wave_all(ctm::exp32_k_is_zero(a));
+__device__ __forceinline__ float welsch_weight(float r, WeightTrips& trips) {
+    const float a = -r * r * kWelschC * kWelschC;
+    const bool fast = wave_all(ctm::welsch_k_is_zero(r));
     if constexpr (COUNT) {
         const bool first = (int)__lane_id() == __ffsll((unsigned long long)__ballot(1)) - 1;
         trips.fast += first && fast ? 1u : 0u;
@@ -206,15 +204,101 @@ __device__ __forceinline__ float welsch_weight(float a, WeightTrips& trips) {
     if (fast) return ctm::exp32_nonpos_k0(a);
     return ctm::exp32_nonpos(a);
 }
+
+// (double)|d| as ONE instruction: the |.| is the conversion's source modifier.  (Written as (double)fabsf(d) the compiler sinks the addition to `err` below the
+// vote's branch and then clears the sign bit with a v_and_b32 of its own per point.)
+__device__ __forceinline__ double welsch_abs_f64(float d) {
+    double r;
+    asm("v_cvt_f64_f32_e64 %0, |%1|" : "=v"(r) : "v"(d));
+    return r;
+}
+
+// ---- wave-uniform point loops.  A lane walks the points 0 .. n - 1 of its edge, and n differs between the lanes of a wave (restarts of several edges), so a
+// loop `for (j = 0; j < n; j++)` is an exec-mask loop with a counter, a compare and the addresses in vector registers.  But the lanes on at trip j are "the
+// lanes with n > j" and n never changes: between two consecutive values of n in the wave -- the STOPS -- the set of lanes is fixed.  welsch_walk runs a loop
+// as segments [j0, stop): inside a segment j and the bound are scalar, exec does not change, the body is unrolled by four with a scalar single-step
+// remainder, the addresses are one base plus immediate offsets and the point requested one trip ahead is a renamed register.  At a stop the lanes with
+// n == stop leave.  A lane's trips, their order and the lanes beside it at each trip are those of the per-lane loop.
+// The stops are the distinct n of the lanes on at the start of welsch_rounds, kept in kWStops scalars (unsorted: the next stop is the smallest one above
+// j0).  Lanes that end their restart later only make a stop a boundary at which nobody leaves.  kWStops = 8: a wave of k_welsch's first phase holds
+// restarts of at most 4 edges and always fits; after the regroup (up to 16 edges) and in welsch_short (up to 9 lengths) a wave can hold more distinct n,
+// and then finds each next stop on the spot (welsch_next_stop: a few scalar instructions per distinct length and segment) -- the same segments, so one
+// form of every loop serves any distribution of n.  (A second, per-lane form of the five loops beside this one cost k_welsch scratch: 52 bytes per lane.)
+constexpr int kWStops = 8;
+struct WelschStops {
+    int s[kWStops];
+    bool ok;  // every lane's n is among s[]; wave-uniform
+    __device__ __forceinline__ int next_after(int j0) const {  // the smallest stop above j0, INT_MAX if none; scalar
+        int m = 0x7fffffff;
+#pragma unroll
+        for (int q = 0; q < kWStops; q++) m = s[q] > j0 && s[q] < m ? s[q] : m;
+        return m;
+    }
+};
+__device__ __forceinline__ WelschStops welsch_stops(int n) {
+    WelschStops st;
+    unsigned long long todo = __ballot(1);
+#pragma unroll
+    for (int q = 0; q < kWStops; q++) {
+        int v = 0;  // (0 is never above j0: an unused slot)
+        if (todo != 0ull) {
+            v = __builtin_amdgcn_readlane(n, __ffsll(todo) - 1);
+            todo &= ~__ballot(n == v);
+        }
+        st.s[q] = v;
+    }
+    st.ok = todo == 0ull;
+    return st;
+}
+// the smallest n above j0 among the lanes that are on, found on the spot (a wave with more lengths than stops); some lane has n > j0
+__device__ __forceinline__ int welsch_next_stop(int n, int j0) {
+    int m = 0x7fffffff;
+    for (unsigned long long todo = __ballot(n > j0); todo != 0ull;) {
+        const int v = __builtin_amdgcn_readlane(n, __ffsll(todo) - 1);
+        m = min(m, v);
+        todo &= ~__ballot(n == v);
+    }
+    return m;
+}
+// body(j, p) for j = lo .. min(n, cap) - 1 on every lane that is on, p = pts(j); lo and cap are wave-uniform.  The point after the last is requested and never used, as in
+// the per-lane loops (padded rows, padded pool).
+template <class Pts, class Body>
+__device__ __forceinline__ void welsch_walk(const WelschStops& st, const Pts pts, int n, int lo, int cap, Body body) {
+    float2 pn = make_float2(0.f, 0.f);  // next point, loaded one trip ahead
+    if (n > lo) pn = pts(lo);
+    int j0 = lo;
+    while (j0 < cap && __ballot(n > j0) != 0ull) {
+        const int stop = min(st.ok ? st.next_after(j0) : welsch_next_stop(n, j0), cap);  // (a lane with n > j0 is on: its n is a stop above j0)
+        if (n > j0) {
+            int j = j0;
+            for (; j + 4 <= stop; j += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const float2 p = pn;
+                    pn = pts(j + u + 1);
+                    body(j + u, p);
+                }
+            }
+            for (; j < stop; j++) {
+                const float2 p = pn;
+                pn = pts(j + 1);
+                body(j, p);
+            }
+        }
+        j0 = stop;
+    }
+}
 // IRLS iterations it0, it0 + 1, ... of one restart from `line` (the body of fitLine2D's inner loop).  Returns true when the restart has ENDED -- converged,
 // err < EPS, or 30 iterations -- with (line, err) as the reference leaves them; returns false at iteration it_stop, AFTER that iteration's convergence test
 // has failed: the caller goes on later (on any lane) with welsch_rounds(.., it0 = it_stop, resume = true), which skips the test it already knows the
 // outcome of -- so neither the previous line nor err has to travel.  it_stop = 30: to the end.
-// wc: this lane's column of a [rows][WS] float array in LDS (element j at wc[j * WS]) for the weights of the first `ncache` points between the two passes.
+// wc: this lane's column of a [rows][WS] float array in LDS (element j at wc[j * WS]) for the weights of the first min(n, wcap) points between the two
+// passes; wcap is wave-uniform.
 template <int WS, bool COUNT, class Pts>
-__device__ __forceinline__ bool welsch_rounds(const Pts pts, int n, double EPS, float* line, double& err, int it0, int it_stop, bool resume, float* wc, int ncache, WeightTrips& trips) {
+__device__ __forceinline__ bool welsch_rounds(const Pts pts, int n, double EPS, float* line, double& err, int it0, int it_stop, bool resume, float* wc, int wcap, WeightTrips& trips) {
     float prev[4] = {0.f, 0.f, 0.f, 0.f};
-    const float c = 1 / 2.9846f;
+    const WelschStops st = welsch_stops(n);
+    constexpr int kNoCap = 0x7fffffff;
 #ifdef CTAG_WELSCH_MINERR_IN_LOOP
     // The other placement of fitLine2D's `if (err < min_err)` (oracle: OracleVariants::welsch_minerr_in_loop): the pair is taken right after calcDist2D, so a restart
     // hands on the FIRST SMALLEST (err, line) of its iterations instead of (last err, last refit).  The restart ends early on an error below EPS only when that error
@@ -252,28 +336,23 @@ __device__ __forceinline__ bool welsch_rounds(const Pts pts, int n, double EPS, 
         err = 0;
         // (the point after the last is requested too and never used: the staged rows and the cluster pool are padded by one element, which
         // spares every trip the clamp of its index -- v_min_i32, sign extension and a 64-bit address per point and pass)
-        float2 pn0 = pts(min(0, n - 1));  // next point, loaded one trip ahead
-        // (the three loops that vote are not unrolled: a loop with a wave vote in it cannot be given a remainder loop, and the kernel's time was flat in
-        // CTAG_WUNROLL)
-        for (int j = 0; j < ncache; j++) {
-            const float2 p = pn0;
-            pn0 = pts(j + 1);
+        // The five point loops run as wave-uniform segments (welsch_walk): unrolled by four with a single-step remainder, votes included.  (As per-lane
+        // loops the three that vote could not be unrolled: the compiler will not give a loop with a wave vote in it a remainder loop -- the vote's lanes
+        // would change.  In a segment the lanes are fixed, and every trip votes with the lanes the rolled loop's trip had.)
+        welsch_walk(st, pts, n, 0, wcap, [&](int j, float2 p) __attribute__((always_inline)) {
             const float x = p.x - lx, y = p.y - ly;
-            const float r = ctm::fabs32(nx * x + ny * y);
-            err += r;
-            const float wj = welsch_weight<COUNT>(-r * r * c * c, trips);
+            const float d = nx * x + ny * y, r = __builtin_fabsf(d);
+            err += welsch_abs_f64(d);  // (double)r
+            const float wj = welsch_weight<COUNT>(r, trips);
             wc[j * WS] = wj;
             sum_w += wj;
-        }
-        float2 pn1 = pts(min(ncache, n - 1));  // next point, loaded one trip ahead
-        for (int j = ncache; j < n; j++) {
-            const float2 p = pn1;
-            pn1 = pts(j + 1);
+        });
+        welsch_walk(st, pts, n, wcap, kNoCap, [&](int j, float2 p) __attribute__((always_inline)) {
             const float x = p.x - lx, y = p.y - ly;
-            const float r = ctm::fabs32(nx * x + ny * y);
-            err += r;
-            sum_w += welsch_weight<COUNT>(-r * r * c * c, trips);
-        }
+            const float d = nx * x + ny * y, r = __builtin_fabsf(d);
+            err += welsch_abs_f64(d);  // (double)r
+            sum_w += welsch_weight<COUNT>(r, trips);
+        });
 #ifdef CTAG_WELSCH_MINERR_IN_LOOP
         if (err < berr) {
             berr = err;
@@ -286,11 +365,7 @@ __device__ __forceinline__ bool welsch_rounds(const Pts pts, int n, double EPS, 
         double x = 0, y = 0, x2 = 0, y2 = 0, xy = 0, w = 0;
         if (ctm::fabs64(sum_w) > 1.1920928955078125e-07) {
             const double inv = 1. / sum_w;
-            float2 pn2 = pts(min(0, n - 1));  // next point, loaded one trip ahead
-            CTAG_PRAGMA(unroll CTAG_WUNROLL)
-            for (int j = 0; j < ncache; j++) {
-                const float2 p = pn2;
-                pn2 = pts(j + 1);
+            welsch_walk(st, pts, n, 0, wcap, [&](int j, float2 p) __attribute__((always_inline)) {
                 const float px = p.x, py = p.y;
                 const float wj = (float)(wc[j * WS] * inv);
                 x += wj * px;
@@ -299,26 +374,22 @@ __device__ __forceinline__ bool welsch_rounds(const Pts pts, int n, double EPS, 
                 y2 += wj * py * py;
                 xy += wj * px * py;
                 w += wj;
-            }
-            float2 pn3 = pts(min(ncache, n - 1));  // next point, loaded one trip ahead
-            for (int j = ncache; j < n; j++) {
-                const float2 p = pn3;
-                pn3 = pts(j + 1);
+            });
+            // (the weights the first pass did not keep are evaluated again, vote included: a vote-free copy of this loop for the iterations whose first
+            // pass had voted fast at every trip was measured and cost the kernel 0.1 ms -- docs/history.md)
+            welsch_walk(st, pts, n, wcap, kNoCap, [&](int j, float2 p) __attribute__((always_inline)) {
                 const float px = p.x, py = p.y;
-                const float r = ctm::fabs32(nx * (px - lx) + ny * (py - ly));
-                const float wj = (float)(welsch_weight<COUNT>(-r * r * c * c, trips) * inv);
+                const float r = __builtin_fabsf(nx * (px - lx) + ny * (py - ly));
+                const float wj = (float)(welsch_weight<COUNT>(r, trips) * inv);
                 x += wj * px;
                 y += wj * py;
                 x2 += wj * px * px;
                 y2 += wj * py * py;
                 xy += wj * px * py;
                 w += wj;
-            }
+            });
         } else {
-            float2 pn4 = pts(min(0, n - 1));  // next point, loaded one trip ahead
-            for (int j = 0; j < n; j++) {
-                const float2 p = pn4;
-                pn4 = pts(j + 1);
+            welsch_walk(st, pts, n, 0, kNoCap, [&](int j, float2 p) __attribute__((always_inline)) {
                 const float px = p.x, py = p.y;
                 x += px;
                 y += py;
@@ -326,7 +397,7 @@ __device__ __forceinline__ bool welsch_rounds(const Pts pts, int n, double EPS, 
                 y2 += py * py;
                 xy += px * py;
                 w += 1.f;
-            }
+            });
         }
         prev[0] = line[0];
         prev[1] = line[1];
@@ -352,7 +423,7 @@ __device__ __forceinline__ void welsch_restart(const Pts pts, int n, const Picks
     float line[4];
     double err = 0;
     welsch_first_fit(pts, picks, npick, line);
-    (void)welsch_rounds<WS, COUNT>(pts, n, EPS, line, err, 0, 30, false, wc, min(n, kWCap), trips);
+    (void)welsch_rounds<WS, COUNT>(pts, n, EPS, line, err, 0, 30, false, wc, kWCap, trips);
     restart_store(res, rstride, line, err);
 }
 
@@ -2513,7 +2584,7 @@ __device__ __forceinline__ void welsch_block_run(const QuadPtrs& P, WelschLds& S
                     welsch_first_fit(pts, ListPicks{pk}, 10, line);
                 }
             }
-            fin = welsch_rounds<kWT, COUNT>(pts, n, EPS, line, err, phase == 0 ? 0 : kWRegroupAt, phase == 0 ? kWRegroupAt : 30, phase != 0, S.wc + tid, min(n, phase == 0 ? kWCap : kWRes), trips);
+            fin = welsch_rounds<kWT, COUNT>(pts, n, EPS, line, err, phase == 0 ? 0 : kWRegroupAt, phase == 0 ? kWRegroupAt : 30, phase != 0, S.wc + tid, phase == 0 ? kWCap : kWRes, trips);
             if (fin) restart_store(S.wc + kWRes * kWT + item, kWT, line, err);
         } else {
             fin = true;
@@ -2532,7 +2603,9 @@ __device__ __forceinline__ void welsch_block(const QuadPtrs& P, WelschLds& S, in
         int n = 0, lid = 0;
         const uint32_t* p = nullptr;
         if (first + tid < L) {
-            lid = P.line_sorted[(size_t)frame * P.line_cap + first + tid];
+            int rank = first + tid;
+            asm volatile("" : "+v"(rank));  // (keeps this address, formed once per block, from being hoisted out of k_welsch's loop over the blocks: a register pair held -- and spilled -- across every point loop)
+            lid = P.line_sorted[(size_t)frame * P.line_cap + rank];
             const LineDesc d = P.line_desc[(size_t)frame * P.line_cap + lid];
             n = d.n;
             p = P.cl_pool + (size_t)frame * P.cl_cap + d.off;
