@@ -34,6 +34,8 @@ POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag
                 "ctag_estimate_pose_cov", "ctag_estimate_rig_pose_cov", "ctag_estimate_mv_rig_pose_cov",
                 "ctag_robust_opts_default", "ctag_pose_robust_batch_device", "ctag_rig_pose_robust_batch_device", "ctag_mv_rig_pose_robust_batch_device",
                 "ctag_estimate_pose_robust", "ctag_estimate_rig_pose_robust", "ctag_estimate_mv_rig_pose_robust",
+                "ctag_track_opts_default", "ctag_rig_track_smooth_device", "ctag_mv_rig_track_smooth_device", "ctag_rig_track_smooth",
+                "ctag_mv_rig_track_smooth", "ctag_track_last_ms",
                 "ctag_model_fit_opts_default", "ctag_model_fit_device", "ctag_model_fit", "ctag_model_save", "ctag_model_fit_last_ms",
                 "ctag_rig_fit_opts_default", "ctag_rig_fit_device", "ctag_rig_fit", "ctag_rig_fit_last_ms",
                 "ctag_camera_fit_opts_default", "ctag_camera_fit_device", "ctag_camera_fit", "ctag_camera_fit_last_ms", "ctag_camera_set_get",
@@ -78,6 +80,18 @@ ROBUST_POSE_DT = np.dtype([("status", "<i4"), ("n_points", "<i4"), ("n_inliers",
 assert ROBUST_POSE_DT.itemsize == 232
 ROBUST_OK, ROBUST_NO_POSE, ROBUST_BAD_RECORD, ROBUST_DEGENERATE = range(4)
 LOSS_HUBER, LOSS_CAUCHY = 0, 1
+# ctag_track_rec / ctag_track_stat: one record per (frame, rig) / per rig of a track smoothing (include/ctag_pose.h)
+TRACK_DT = np.dtype([("status", "<i4"), ("rig", "<i4"), ("frame", "<i4"), ("flags", "<u4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)),
+                     ("w", "<f8", (3,)), ("v", "<f8", (3,)), ("cov", "<f8", (6, 6)), ("vel_sigma", "<f8", (6,)), ("mahalanobis2", "<f8"),
+                     ("weight", "<f8")])
+assert TRACK_DT.itemsize == 464
+TRACK_STAT_DT = np.dtype([("status", "<i4"), ("n_measured", "<i4"), ("n_pieces", "<i4"), ("n_tracked", "<i4"), ("longest_piece", "<i4"),
+                          ("rounds", "<i4"), ("cost0", "<f8"), ("cost", "<f8")])
+assert TRACK_STAT_DT.itemsize == 40
+TRACK_OK, TRACK_NOT_TRACKED, TRACK_BAD_INPUT, TRACK_SINGULAR = range(4)
+TRACK_LOSS_NONE = 2
+TRACK_MAX_ITEMS = 65536
+TRACK_FLAG_MEASURED, TRACK_FLAG_DOWNWEIGHTED = 1, 2
 # ctag_model_fit_stat: one record per model of a model reconstruction (include/ctag_pose.h)
 MODEL_FIT_STAT_DT = np.dtype([("status", "<i4"), ("n_records", "<i4"), ("n_points_fitted", "<i4"), ("n_points_held", "<i4"), ("rounds", "<i4"),
                               ("reserved", "<i4"), ("cost0", "<f8"), ("cost", "<f8"), ("lambda", "<f8"), ("rms_px", "<f8")])
@@ -170,6 +184,26 @@ def robust_opts(loss=None, max_iterations=None, scale_px=None, auto_k=None, min_
     for k, v in (("scale_px", scale_px), ("auto_k", auto_k), ("min_scale_px", min_scale_px)):
         if v is not None:
             setattr(o, k, float(v))
+    return o
+
+
+class TrackOptsC(C.Structure):  # ctag_track_opts
+    _fields_ = [("struct_size", C.c_uint32), ("loss", C.c_int32), ("max_iterations", C.c_int32), ("max_gap", C.c_int32), ("segment_frames", C.c_int32),
+                ("reserved", C.c_int32), ("dt", C.c_double), ("q_rot", C.c_double), ("q_trans", C.c_double), ("vel0_sigma_rot", C.c_double),
+                ("vel0_sigma_trans", C.c_double), ("loss_scale", C.c_double), ("lambda0", C.c_double)]
+
+
+def track_opts(**fields):
+    """ctag_track_opts_default, then the given fields."""
+    o = TrackOptsC()
+    load_library().ctag_track_opts_default(C.byref(o))
+    for k, v in fields.items():
+        if k in ("loss", "max_iterations", "max_gap", "segment_frames", "struct_size"):
+            setattr(o, k, int(v))
+        elif k in ("dt", "q_rot", "q_trans", "vel0_sigma_rot", "vel0_sigma_trans", "loss_scale", "lambda0"):
+            setattr(o, k, float(v))
+        else:
+            raise TypeError("ctag_track_opts has no field %r" % k)
     return o
 
 
@@ -402,6 +436,14 @@ def load_library():
     L.ctag_estimate_rig_pose_robust.argtypes = [vp, vp, vp, vp, C.POINTER(CameraC), vp, optp, vp]
     L.ctag_estimate_mv_rig_pose_robust.restype = C.c_int
     L.ctag_estimate_mv_rig_pose_robust.argtypes = [vp, vp, vp, vp, vp, vp, optp, vp]
+    trkp = C.POINTER(TrackOptsC)
+    L.ctag_track_opts_default.restype = None
+    L.ctag_track_opts_default.argtypes = [trkp]
+    for fn in (L.ctag_rig_track_smooth_device, L.ctag_mv_rig_track_smooth_device, L.ctag_rig_track_smooth, L.ctag_mv_rig_track_smooth):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, vp, vp, C.c_int, vp, trkp, vp, vp]
+    L.ctag_track_last_ms.restype = C.c_int
+    L.ctag_track_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     fitp = C.POINTER(ModelFitOptsC)
     L.ctag_model_fit_opts_default.restype = None
     L.ctag_model_fit_opts_default.argtypes = [fitp]
@@ -1091,6 +1133,54 @@ class Detector:
         out = (C.c_float * 4)()
         self.L.ctag_intrinsics_fit_last_ms(self.h, out)
         return dict(zip(("rig_pose", "view_pose", "record", "solve"), (float(v) for v in out)))
+
+    # ---- track smoothing (include/ctag_pose.h): opts is a TrackOptsC (track_opts(...)) or None for the defaults
+    def _smooth(self, fn, name, rec_dt, rigs, poses, cov, n_frames, times, opts):
+        n = n_frames * rigs.n_rigs
+        poses = np.ascontiguousarray(poses, rec_dt).reshape(-1)
+        cov = np.ascontiguousarray(cov, POSE_COV_DT).reshape(-1)
+        if len(poses) != n or len(cov) != n:
+            raise ValueError("%s: %d pose and %d covariance records for %d frames x %d rigs" % (name, len(poses), len(cov), n_frames, rigs.n_rigs))
+        t = None if times is None else np.ascontiguousarray(times, np.float64).reshape(-1)
+        if t is not None and len(t) != n_frames:
+            raise ValueError("%s: %d times for %d frames" % (name, len(t), n_frames))
+        out, stat = np.zeros(max(n, 1), TRACK_DT), np.zeros(rigs.n_rigs, TRACK_STAT_DT)
+        st = fn(self.h, rigs.r, poses.ctypes.data, cov.ctypes.data, n_frames, None if t is None else t.ctypes.data, self._optp(opts),
+                out.ctypes.data, stat.ctypes.data)
+        if st != 0:
+            raise CtagError(st, name)
+        return out[:n].reshape(n_frames, rigs.n_rigs), stat
+
+    def smooth_rig_track(self, rigs, rig_poses, cov, n_frames, times=None, opts=None):
+        """n_frames x rigs.n_rigs host RIG_POSE_DT records with their POSE_COV_DT records -> (TRACK_DT [n_frames, n_rigs], TRACK_STAT_DT [n_rigs]).
+        Waits."""
+        return self._smooth(self.L.ctag_rig_track_smooth, "ctag_rig_track_smooth", RIG_POSE_DT, rigs, rig_poses, cov, n_frames, times, opts)
+
+    def smooth_mv_rig_track(self, rigs, mv_poses, cov, n_frames, times=None, opts=None):
+        """The same from MV_POSE_DT records (poses in the reference frame)."""
+        return self._smooth(self.L.ctag_mv_rig_track_smooth, "ctag_mv_rig_track_smooth", MV_POSE_DT, rigs, mv_poses, cov, n_frames, times, opts)
+
+    def _smooth_device(self, fn, name, rigs, poses_ptr, cov_ptr, n_frames, times, opts, out_ptr, stat_ptr):
+        t = None if times is None else np.ascontiguousarray(times, np.float64).reshape(-1)
+        if t is not None and len(t) != n_frames:
+            raise ValueError("%s: %d times for %d frames" % (name, len(t), n_frames))
+        st = fn(self.h, rigs.r, poses_ptr, cov_ptr, n_frames, None if t is None else t.ctypes.data, self._optp(opts), out_ptr, stat_ptr)
+        if st != 0:
+            raise CtagError(st, name)
+
+    def smooth_rig_track_device(self, rigs, rig_poses_ptr, cov_ptr, n_frames, out_ptr, stat_ptr, times=None, opts=None):
+        """Device RIG_POSE_DT / POSE_COV_DT records -> n_frames * n_rigs device TRACK_DT records at out_ptr, n_rigs TRACK_STAT_DT at stat_ptr; enqueued."""
+        self._smooth_device(self.L.ctag_rig_track_smooth_device, "ctag_rig_track_smooth_device", rigs, rig_poses_ptr, cov_ptr, n_frames, times, opts, out_ptr, stat_ptr)
+
+    def smooth_mv_rig_track_device(self, rigs, mv_poses_ptr, cov_ptr, n_frames, out_ptr, stat_ptr, times=None, opts=None):
+        """The same from device MV_POSE_DT records."""
+        self._smooth_device(self.L.ctag_mv_rig_track_smooth_device, "ctag_mv_rig_track_smooth_device", rigs, mv_poses_ptr, cov_ptr, n_frames, times, opts, out_ptr, stat_ptr)
+
+    def track_last_ms(self):
+        """Device milliseconds of the last smoothing call (needs OPT_TIMING): gather + pieces + start, the rounds, marginals + records, the whole call."""
+        out = (C.c_float * 4)()
+        self.L.ctag_track_last_ms(self.h, out)
+        return dict(zip(("setup", "rounds", "marginals", "total"), (float(v) for v in out)))
 
     # ---- pose covariance (include/ctag_pose.h): opts is a CovOptsC (cov_opts(...)) or None for the defaults
     @staticmethod

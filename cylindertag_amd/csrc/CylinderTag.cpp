@@ -700,6 +700,93 @@ void CylinderTag::estimateMultiViewRigPose(const std::vector<std::vector<MarkerI
     }
 }
 
+void CylinderTag::smoothRigTrack(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,
+                                 int nRigs, std::vector<std::vector<TrackInfo>>& track, const std::vector<double>& times, const ctag_track_opts* opts) {
+    track.clear();
+    const size_t n_frames = posesPerFrame.size();
+    if (n_frames == 0) throw std::string("smoothRigTrack, no frames\n");
+    if (covPerFrame.size() != n_frames) throw std::string("smoothRigTrack, one covariance list per frame\n");
+    if (nRigs < 1 || (unsigned long long)n_frames * (unsigned long long)nRigs > (unsigned long long)CTAG_TRACK_MAX_ITEMS)
+        throw std::string("smoothRigTrack, frames x rigs outside 1 .. 65536\n");
+    if (!times.empty() && times.size() != n_frames) throw std::string("smoothRigTrack, one time per frame\n");
+    const size_t n = n_frames * (size_t)nRigs;
+    std::vector<ctag_rig_pose_rec> rec(n);
+    std::vector<ctag_pose_cov_rec> cov(n);
+    std::memset(rec.data(), 0, sizeof(ctag_rig_pose_rec) * n);
+    std::memset(cov.data(), 0, sizeof(ctag_pose_cov_rec) * n);
+    for (size_t f = 0; f < n_frames; f++) {
+        for (int g = 0; g < nRigs; g++) {
+            rec[f * nRigs + g].status = CTAG_POSE_NOT_SEEN;
+            rec[f * nRigs + g].rig = g;
+            rec[f * nRigs + g].frame = (int32_t)f;
+            cov[f * nRigs + g].status = CTAG_COV_NO_POSE;
+        }
+        if (covPerFrame[f].size() != posesPerFrame[f].size()) throw std::string("smoothRigTrack, one covariance per pose\n");
+        for (size_t i = 0; i < posesPerFrame[f].size(); i++) {
+            const RigPoseInfo& p = posesPerFrame[f][i];
+            if (p.rigID < 0 || p.rigID >= nRigs) throw std::string("smoothRigTrack, a rig outside 0 .. nRigs - 1\n");
+            ctag_rig_pose_rec& r = rec[f * nRigs + p.rigID];
+            if (r.status == CTAG_POSE_OK) throw std::string("smoothRigTrack, a rig twice in one frame\n");
+            r.status = CTAG_POSE_OK;
+#ifdef CTAG_WITH_OPENCV
+            const double *pr = p.rvec.ptr<double>(0), *pt = p.tvec.ptr<double>(0);
+#else
+            const double *pr = p.rvec, *pt = p.tvec;
+#endif
+            for (int k = 0; k < 3; k++) {
+                r.rvec[k] = pr[k];
+                r.tvec[k] = pt[k];
+            }
+            ctag_pose_cov_rec& c = cov[f * nRigs + p.rigID];
+            c.status = covPerFrame[f][i].status;
+            c.param = CTAG_COV_PARAM_TANGENT;
+            for (int k = 0; k < 36; k++) c.cov[k] = covPerFrame[f][i].cov[k];
+        }
+    }
+    // the smoother reads n_rigs of the rig set and nothing else: a set of nRigs one-model rigs over a model made for it
+    std::vector<int32_t> ids(nRigs), rig_of_model(nRigs);
+    std::vector<float> zeros3((size_t)nRigs * 3, 0.f), corners((size_t)nRigs * 24, 0.f);
+    for (int g = 0; g < nRigs; g++) ids[g] = rig_of_model[g] = g;
+    ctag_model_view mv;
+    mv.n_models = nRigs;
+    mv.model_size = 1;
+    mv.marker_id = ids.data();
+    mv.base = zeros3.data();
+    mv.axis = zeros3.data();
+    mv.corners = corners.data();
+    ctag_model* model = nullptr;
+    ctag_rigs* rigs = nullptr;
+    int st = ctag_model_create(&mv, &model);
+    if (st == CTAG_OK) st = ctag_rigs_create(model, rig_of_model.data(), nRigs, &rigs);
+    std::vector<ctag_track_rec> out(n);
+    std::vector<ctag_track_stat> stat((size_t)nRigs);
+    if (st == CTAG_OK)
+        st = ctag_rig_track_smooth(h_, rigs, rec.data(), cov.data(), (int)n_frames, times.empty() ? nullptr : times.data(), opts, out.data(), stat.data());
+    if (rigs) ctag_rigs_free(rigs);
+    if (model) ctag_model_free(model);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    track.assign(n_frames, std::vector<TrackInfo>((size_t)nRigs));
+    for (size_t f = 0; f < n_frames; f++)
+        for (int g = 0; g < nRigs; g++) {
+            const ctag_track_rec& t = out[f * nRigs + g];
+            TrackInfo& ti = track[f][g];
+            ti.rigID = t.rig;
+            ti.status = t.status;
+            ti.measured = (t.flags & CTAG_TRACK_FLAG_MEASURED) != 0;
+            ti.downweighted = (t.flags & CTAG_TRACK_FLAG_DOWNWEIGHTED) != 0;
+            for (int k = 0; k < 3; k++) {
+                ti.rvec[k] = t.rvec[k];
+                ti.tvec[k] = t.tvec[k];
+                ti.w[k] = t.w[k];
+                ti.v[k] = t.v[k];
+            }
+            for (int k = 0; k < 36; k++) ti.cov[k] = t.cov[k];
+            for (int k = 0; k < 6; k++) ti.velSigma[k] = t.vel_sigma[k];
+            ti.mahalanobis2 = t.mahalanobis2;
+            ti.weight = t.weight;
+        }
+}
+
 static void pose_vectors(const PoseInfo& p, double* r, double* t) {
 #ifdef CTAG_WITH_OPENCV
     const double *pr = p.rvec.ptr<double>(0), *pt = p.tvec.ptr<double>(0);

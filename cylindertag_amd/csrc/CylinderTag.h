@@ -65,6 +65,7 @@ struct Mat1i {
 
 struct ctag_handle;
 struct ctag_params;  // include/ctag_types.h: the detector's tunables (the reference's member constants, header/corner_detector.h:90-144)
+struct ctag_track_opts;  // include/ctag_pose.h: the options of smoothRigTrack
 
 // reference: header/corner_detector.h:16-22
 struct MarkerInfo {
@@ -135,6 +136,17 @@ struct RobustPoseInfo {
     std::vector<bool> inlier;  // nPoints entries, in the correspondence builder's point order
     double scalePx = 0, sigmaHat = 0, costLs0 = 0, costLs = 0, cost0 = 0, cost = 0, maxResidualPx = 0;
     double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};  // the refitted pose
+};
+// one frame of a rig's smoothed track (new): the fields of ctag_track_rec (include/ctag_pose.h, track smoothing)
+struct TrackInfo {
+    int rigID = -1;
+    int status = 0;  // CTAG_TRACK_*; the fields below are 0 unless it is CTAG_TRACK_OK or CTAG_TRACK_SINGULAR
+    bool measured = false, downweighted = false;
+    double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};  // the smoothed pose, in the frame of the input poses
+    double w[3] = {0, 0, 0}, v[3] = {0, 0, 0};        // angular (rad / s) and translational (model units / s) velocity
+    double cov[36] = {0};                             // row-major 6x6 of the pose, tangent parametrisation
+    double velSigma[6] = {0};
+    double mahalanobis2 = 0, weight = 0;
 };
 // the annotated frame of drawAxis: rows x cols pixels of 3 bytes, channel c = Scalar component c (imgMark in the reference)
 struct AxisImage {
@@ -251,6 +263,15 @@ class CylinderTag {
     void estimateMultiViewRigPose(const std::vector<std::vector<MarkerInfo>>& markersPerCamera, std::vector<ModelInfo> reconstruct_model,
                                   const std::vector<int>& rigOfModel, const std::vector<CamInfo>& cameras,
                                   const std::vector<ViewPose>& cameraPoses, std::vector<RigPoseInfo>& pose);
+
+    // One smoothed trajectory per rig over consecutive frames (new; include/ctag_pose.h, ctag_rig_track_smooth): posesPerFrame[f] is what
+    // estimateRigPose (or estimateMultiViewRigPose) returned for frame f -- a rig that is not in the list is unmeasured in that frame --
+    // and covPerFrame[f][i] the covariance of posesPerFrame[f][i]: its status (CTAG_COV_OK or not) and its cov, which must be in the
+    // TANGENT parametrisation, are read.  track[f][g] is frame f of rig g, for every f and every g < nRigs.  times: one per frame,
+    // strictly increasing, or empty for f * opts.dt; opts: null for the defaults.  Throws std::string on error.
+    void smoothRigTrack(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,
+                        int nRigs, std::vector<std::vector<TrackInfo>>& track, const std::vector<double>& times = std::vector<double>(),
+                        const ctag_track_opts* opts = nullptr);
 
     // Draw the axes of the posed markers (reference: header/CylinderTag.h:33, CylinderTag.cpp:211-246): pose[i] is drawn on
     // markers[i] -- the reference pairs them by list position, after estimatePose has erased the poses without a model -- with

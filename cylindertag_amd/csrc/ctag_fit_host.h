@@ -22,6 +22,7 @@
 #include "../../include/ctag_pose.h"
 #include "ctag_fit_solve.h"
 #include "ctag_internal.h"
+#include "ctag_lm.h"
 #include "ctag_pose_dev.h"
 #include "ctag_schur6.h"
 
@@ -434,18 +435,12 @@ struct Lm {
     // stops after max_rounds rounds either way.  Returns whether the trial is accepted.
     template <class Opts>
     bool decide(int g, bool trial_usable, double cost_trial, const Opts& o) {
-        rounds[g]++;
-        const bool accept = trial_usable && cost_trial < cost[g];
-        if (accept) {
-            const double drop = cost[g] - cost_trial;
-            cost[g] = cost_trial;
-            lambda[g] = std::max(lambda[g] / 3.0, 1e-9);
-            if (drop < o.rel_tol * cost[g]) active[g] = 0;
-        } else {
-            lambda[g] *= 4.0;
-            if (lambda[g] > o.lambda_max) active[g] = 0;
-        }
-        if (rounds[g] >= o.max_rounds) active[g] = 0;
+        LmState s{lambda[g], cost[g], active[g], rounds[g]};
+        const bool accept = lm_decide(s, trial_usable, cost_trial, o.rel_tol, o.lambda_max, o.max_rounds);
+        lambda[g] = s.lambda;
+        cost[g] = s.cost;
+        active[g] = s.active;
+        rounds[g] = s.rounds;
         return accept;
     }
 };

@@ -7,6 +7,12 @@
 #pragma once
 #include "ctag_math.h"
 
+#ifdef __HIPCC__
+#define CTL_UNROLL _Pragma("unroll")
+#else
+#define CTL_UNROLL
+#endif
+
 namespace ctl {
 
 // Cyclic Jacobi eigen-decomposition of a symmetric N x N matrix.  a (row-major, full storage) is destroyed, v receives
@@ -335,6 +341,54 @@ CTM_HD bool chol6_solve(double* H, const double* g, double* x) {
         for (int k = i + 1; k < N; k++) sacc -= H[k * N + i] * x[k];
         x[i] = sacc / H[i * N + i];
     }
+    return true;
+}
+
+// Inverse of a symmetric 6x6 C (row-major, the lower triangle is read) by Cholesky, C = L L^T: inv = L^-T L^-1, exactly
+// symmetric.  min_pivot is the smallest pivot (the diagonal entry before its square root) met; false as soon as a pivot is not
+// above min_allowed (or is not a number).
+CTM_HD bool chol6_inverse(const double* C, double* inv, double min_allowed, double& min_pivot) {
+    constexpr int N = 6;
+    double L[36], W[36];
+    min_pivot = C[0];
+CTL_UNROLL
+    for (int j = 0; j < N; j++) {
+        double d = C[j * N + j];
+CTL_UNROLL
+        for (int k = 0; k < j; k++) d -= L[j * N + k] * L[j * N + k];
+        if (!(d >= min_pivot)) min_pivot = d;
+        if (!(d > min_allowed)) return false;
+        d = ctm::sqrt64(d);
+        L[j * N + j] = d;
+CTL_UNROLL
+        for (int i = j + 1; i < N; i++) {
+            double sacc = C[i * N + j];
+CTL_UNROLL
+            for (int k = 0; k < j; k++) sacc -= L[i * N + k] * L[j * N + k];
+            L[i * N + j] = sacc / d;
+        }
+    }
+CTL_UNROLL
+    for (int j = 0; j < N; j++) {  // column j of W = L^-1 (lower triangular)
+        W[j * N + j] = 1.0 / L[j * N + j];
+CTL_UNROLL
+        for (int i = j + 1; i < N; i++) {
+            double sacc = 0.0;
+CTL_UNROLL
+            for (int k = j; k < i; k++) sacc -= L[i * N + k] * W[k * N + j];
+            W[i * N + j] = sacc / L[i * N + i];
+        }
+    }
+CTL_UNROLL
+    for (int a = 0; a < N; a++)
+CTL_UNROLL
+        for (int b = a; b < N; b++) {
+            double sacc = 0.0;
+CTL_UNROLL
+            for (int k = b; k < N; k++) sacc += W[k * N + a] * W[k * N + b];
+            inv[a * N + b] = sacc;
+            inv[b * N + a] = sacc;
+        }
     return true;
 }
 

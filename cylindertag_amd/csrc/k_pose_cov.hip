@@ -50,54 +50,6 @@ struct CovLds {
     double norm[kCovMaxPts];  // residual norm of point i, written and read by its owner lane
 };
 
-// Inverse of a symmetric 6x6 C (row-major, the lower triangle is read) by Cholesky, C = L L^T: inv = L^-T L^-1, exactly
-// symmetric.  min_pivot is the smallest pivot (the diagonal entry before its square root) met; false as soon as a pivot is not
-// above min_allowed (or is not a number).
-__device__ __forceinline__ bool chol6_inverse(const double* C, double* inv, double min_allowed, double& min_pivot) {
-    constexpr int N = 6;
-    double L[36], W[36];
-    min_pivot = C[0];
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        double d = C[j * N + j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= L[j * N + k] * L[j * N + k];
-        if (!(d >= min_pivot)) min_pivot = d;
-        if (!(d > min_allowed)) return false;
-        d = ctm::sqrt64(d);
-        L[j * N + j] = d;
-#pragma unroll
-        for (int i = j + 1; i < N; i++) {
-            double sacc = C[i * N + j];
-#pragma unroll
-            for (int k = 0; k < j; k++) sacc -= L[i * N + k] * L[j * N + k];
-            L[i * N + j] = sacc / d;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < N; j++) {  // column j of W = L^-1 (lower triangular)
-        W[j * N + j] = 1.0 / L[j * N + j];
-#pragma unroll
-        for (int i = j + 1; i < N; i++) {
-            double sacc = 0.0;
-#pragma unroll
-            for (int k = j; k < i; k++) sacc -= L[i * N + k] * W[k * N + j];
-            W[i * N + j] = sacc / L[i * N + i];
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < N; a++)
-#pragma unroll
-        for (int b = a; b < N; b++) {
-            double sacc = 0.0;
-#pragma unroll
-            for (int k = b; k < N; k++) sacc += W[k * N + a] * W[k * N + b];
-            inv[a * N + b] = sacc;
-            inv[b * N + a] = sacc;
-        }
-    return true;
-}
-
 // a record whose status is not CTAG_COV_OK: the status and 348 zero bytes, one 8-byte word per lane
 __device__ __forceinline__ void cov_store_status(ctag_pose_cov_rec* P, int status, int lane) {
     if (lane < (int)(sizeof(ctag_pose_cov_rec) / 8)) reinterpret_cast<unsigned long long*>(P)[lane] = lane == 0 ? (unsigned long long)(unsigned)status : 0ull;
@@ -206,7 +158,7 @@ __global__ __launch_bounds__(64) void k_pose_cov(Src src, PoseModelDev model, Co
                     e++;
                 }
         }
-        good = good && chol6_inverse(C, inv, kCovMinPivot, min_pivot);
+        good = good && ctl::chol6_inverse(C, inv, kCovMinPivot, min_pivot);
         if (!good) {
             cov_store_status(O, CTAG_COV_SINGULAR, lane);
             continue;

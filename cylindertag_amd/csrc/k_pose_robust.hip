@@ -27,6 +27,7 @@
 #include "../../include/ctag_pose.h"
 #include "ctag_cov_src.h"
 #include "ctag_internal.h"
+#include "ctag_loss.h"
 #include "ctag_pose_dev.h"
 #include "ctag_schur6.h"
 #include "ctag_wave.h"
@@ -65,24 +66,6 @@ struct RobustLds {
     };
     double med;
 };
-
-// rule 5: rho(s) and rho'(s) for the loss's scale a (a2 = a * a, both positive)
-__device__ __forceinline__ void robust_loss(int loss, double a, double a2, double s, double& rho, double& w) {
-    if (loss == CTAG_LOSS_HUBER) {
-        if (s <= a2) {
-            rho = s;
-            w = 1.0;
-        } else {
-            const double q = ctm::sqrt64(s);
-            rho = 2.0 * a * q - a2;
-            w = a / q;
-        }
-    } else {
-        const double q = 1.0 + s / a2;
-        rho = a2 * ctm::log64(q);
-        w = 1.0 / q;
-    }
-}
 
 // a record whose status is not CTAG_ROBUST_OK: the status and 228 zero bytes, one 8-byte word per lane
 __device__ __forceinline__ void robust_store_status(ctag_robust_pose_rec* P, int status, int lane) {
