@@ -36,6 +36,8 @@ POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag
                 "ctag_estimate_pose_robust", "ctag_estimate_rig_pose_robust", "ctag_estimate_mv_rig_pose_robust",
                 "ctag_track_opts_default", "ctag_rig_track_smooth_device", "ctag_mv_rig_track_smooth_device", "ctag_rig_track_smooth",
                 "ctag_mv_rig_track_smooth", "ctag_track_last_ms",
+                "ctag_hand_eye_opts_default", "ctag_rig_hand_eye_fit_device", "ctag_mv_rig_hand_eye_fit_device", "ctag_rig_hand_eye_fit",
+                "ctag_mv_rig_hand_eye_fit", "ctag_hand_eye_last_ms",
                 "ctag_model_fit_opts_default", "ctag_model_fit_device", "ctag_model_fit", "ctag_model_save", "ctag_model_fit_last_ms",
                 "ctag_rig_fit_opts_default", "ctag_rig_fit_device", "ctag_rig_fit", "ctag_rig_fit_last_ms",
                 "ctag_camera_fit_opts_default", "ctag_camera_fit_device", "ctag_camera_fit", "ctag_camera_fit_last_ms", "ctag_camera_set_get",
@@ -92,6 +94,21 @@ TRACK_OK, TRACK_NOT_TRACKED, TRACK_BAD_INPUT, TRACK_SINGULAR = range(4)
 TRACK_LOSS_NONE = 2
 TRACK_MAX_ITEMS = 65536
 TRACK_FLAG_MEASURED, TRACK_FLAG_DOWNWEIGHTED = 1, 2
+# ctag_link_pose / ctag_hand_eye_rec / ctag_hand_eye_frame_rec: a link pose per frame in, one record per rig and one per (frame, rig) out of a
+# hand-eye calibration (include/ctag_pose.h)
+LINK_POSE_DT = np.dtype([("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
+assert LINK_POSE_DT.itemsize == 48
+HAND_EYE_DT = np.dtype([("status", "<i4"), ("rig", "<i4"), ("n_used", "<i4"), ("n_downweighted", "<i4"), ("rounds", "<i4"), ("dof", "<i4"),
+                        ("P", LINK_POSE_DT), ("Q", LINK_POSE_DT), ("cost0", "<f8"), ("cost", "<f8"), ("lambda", "<f8"), ("sigma2_hat", "<f8"),
+                        ("min_pivot", "<f8"), ("cov", "<f8", (12, 12))])
+assert HAND_EYE_DT.itemsize == 1312
+HAND_EYE_FRAME_DT = np.dtype([("status", "<i4"), ("rig", "<i4"), ("frame", "<i4"), ("flags", "<u4"), ("e", "<f8", (6,)), ("mahalanobis2", "<f8"),
+                              ("weight", "<f8")])
+assert HAND_EYE_FRAME_DT.itemsize == 80
+HE_OK, HE_TOO_FEW, HE_BAD_INPUT, HE_SINGULAR = range(4)
+HAND_EYE_CAMERA_ON_LINK, HAND_EYE_RIG_ON_LINK = 0, 1
+HAND_EYE_MAX_ITEMS = 65536
+HE_FLAG_USED, HE_FLAG_DOWNWEIGHTED = 1, 2
 # ctag_model_fit_stat: one record per model of a model reconstruction (include/ctag_pose.h)
 MODEL_FIT_STAT_DT = np.dtype([("status", "<i4"), ("n_records", "<i4"), ("n_points_fitted", "<i4"), ("n_points_held", "<i4"), ("rounds", "<i4"),
                               ("reserved", "<i4"), ("cost0", "<f8"), ("cost", "<f8"), ("lambda", "<f8"), ("rms_px", "<f8")])
@@ -204,6 +221,25 @@ def track_opts(**fields):
             setattr(o, k, float(v))
         else:
             raise TypeError("ctag_track_opts has no field %r" % k)
+    return o
+
+
+class HandEyeOptsC(C.Structure):  # ctag_hand_eye_opts
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("loss", C.c_int32), ("max_iterations", C.c_int32), ("loss_scale", C.c_double),
+                ("lambda0", C.c_double)]
+
+
+def hand_eye_opts(**fields):
+    """ctag_hand_eye_opts_default, then the given fields."""
+    o = HandEyeOptsC()
+    load_library().ctag_hand_eye_opts_default(C.byref(o))
+    for k, v in fields.items():
+        if k in ("mode", "loss", "max_iterations", "struct_size"):
+            setattr(o, k, int(v))
+        elif k in ("loss_scale", "lambda0"):
+            setattr(o, k, float(v))
+        else:
+            raise TypeError("ctag_hand_eye_opts has no field %r" % k)
     return o
 
 
@@ -444,6 +480,14 @@ def load_library():
         fn.argtypes = [vp, vp, vp, vp, C.c_int, vp, trkp, vp, vp]
     L.ctag_track_last_ms.restype = C.c_int
     L.ctag_track_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    hep = C.POINTER(HandEyeOptsC)
+    L.ctag_hand_eye_opts_default.restype = None
+    L.ctag_hand_eye_opts_default.argtypes = [hep]
+    for fn in (L.ctag_rig_hand_eye_fit_device, L.ctag_mv_rig_hand_eye_fit_device, L.ctag_rig_hand_eye_fit, L.ctag_mv_rig_hand_eye_fit):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, vp, vp, C.c_int, vp, hep, vp, vp]
+    L.ctag_hand_eye_last_ms.restype = C.c_int
+    L.ctag_hand_eye_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     fitp = C.POINTER(ModelFitOptsC)
     L.ctag_model_fit_opts_default.restype = None
     L.ctag_model_fit_opts_default.argtypes = [fitp]
@@ -1181,6 +1225,61 @@ class Detector:
         out = (C.c_float * 4)()
         self.L.ctag_track_last_ms(self.h, out)
         return dict(zip(("setup", "rounds", "marginals", "total"), (float(v) for v in out)))
+
+    # ---- hand-eye calibration (include/ctag_pose.h): opts is a HandEyeOptsC (hand_eye_opts(...)) or None for the defaults
+    @staticmethod
+    def _links(name, links, n_frames):
+        links = np.ascontiguousarray(links, LINK_POSE_DT).reshape(-1)
+        if len(links) != n_frames:
+            raise ValueError("%s: %d link poses for %d frames" % (name, len(links), n_frames))
+        return links
+
+    def _hand_eye(self, fn, name, rec_dt, rigs, poses, cov, n_frames, links, opts, want_frames):
+        n = n_frames * rigs.n_rigs
+        poses = np.ascontiguousarray(poses, rec_dt).reshape(-1)
+        cov = np.ascontiguousarray(cov, POSE_COV_DT).reshape(-1)
+        if len(poses) != n or len(cov) != n:
+            raise ValueError("%s: %d pose and %d covariance records for %d frames x %d rigs" % (name, len(poses), len(cov), n_frames, rigs.n_rigs))
+        links = self._links(name, links, n_frames)
+        out = np.zeros(rigs.n_rigs, HAND_EYE_DT)
+        frames = np.zeros(max(n, 1), HAND_EYE_FRAME_DT) if want_frames else None
+        st = fn(self.h, rigs.r, poses.ctypes.data, cov.ctypes.data, n_frames, links.ctypes.data, self._optp(opts), out.ctypes.data,
+                frames.ctypes.data if want_frames else None)
+        if st != 0:
+            raise CtagError(st, name)
+        return out, (frames[:n].reshape(n_frames, rigs.n_rigs) if want_frames else None)
+
+    def fit_hand_eye(self, rigs, rig_poses, cov, n_frames, links, opts=None, frames=True):
+        """n_frames x rigs.n_rigs host RIG_POSE_DT records with their POSE_COV_DT records and n_frames LINK_POSE_DT link poses ->
+        (HAND_EYE_DT [n_rigs], HAND_EYE_FRAME_DT [n_frames, n_rigs] or None when frames is false).  Waits."""
+        return self._hand_eye(self.L.ctag_rig_hand_eye_fit, "ctag_rig_hand_eye_fit", RIG_POSE_DT, rigs, rig_poses, cov, n_frames, links, opts, frames)
+
+    def fit_mv_hand_eye(self, rigs, mv_poses, cov, n_frames, links, opts=None, frames=True):
+        """The same from MV_POSE_DT records (poses in the reference frame)."""
+        return self._hand_eye(self.L.ctag_mv_rig_hand_eye_fit, "ctag_mv_rig_hand_eye_fit", MV_POSE_DT, rigs, mv_poses, cov, n_frames, links, opts, frames)
+
+    def _hand_eye_device(self, fn, name, rigs, poses_ptr, cov_ptr, n_frames, links, opts, out_ptr, frames_ptr):
+        links = self._links(name, links, n_frames)
+        st = fn(self.h, rigs.r, poses_ptr, cov_ptr, n_frames, links.ctypes.data, self._optp(opts), out_ptr, frames_ptr or None)
+        if st != 0:
+            raise CtagError(st, name)
+
+    def fit_hand_eye_device(self, rigs, rig_poses_ptr, cov_ptr, n_frames, links, out_ptr, frames_ptr=None, opts=None):
+        """Device RIG_POSE_DT / POSE_COV_DT records and host link poses -> n_rigs device HAND_EYE_DT records at out_ptr and, unless frames_ptr
+        is None, n_frames * n_rigs HAND_EYE_FRAME_DT records at frames_ptr; enqueued."""
+        self._hand_eye_device(self.L.ctag_rig_hand_eye_fit_device, "ctag_rig_hand_eye_fit_device", rigs, rig_poses_ptr, cov_ptr, n_frames, links, opts,
+                              out_ptr, frames_ptr)
+
+    def fit_mv_hand_eye_device(self, rigs, mv_poses_ptr, cov_ptr, n_frames, links, out_ptr, frames_ptr=None, opts=None):
+        """The same from device MV_POSE_DT records."""
+        self._hand_eye_device(self.L.ctag_mv_rig_hand_eye_fit_device, "ctag_mv_rig_hand_eye_fit_device", rigs, mv_poses_ptr, cov_ptr, n_frames, links,
+                              opts, out_ptr, frames_ptr)
+
+    def hand_eye_last_ms(self):
+        """Device milliseconds of the last hand-eye call (needs OPT_TIMING): gather + start, the rounds, covariance + records, the whole call."""
+        out = (C.c_float * 4)()
+        self.L.ctag_hand_eye_last_ms(self.h, out)
+        return dict(zip(("setup", "rounds", "finish", "total"), (float(v) for v in out)))
 
     # ---- pose covariance (include/ctag_pose.h): opts is a CovOptsC (cov_opts(...)) or None for the defaults
     @staticmethod

@@ -700,18 +700,20 @@ void CylinderTag::estimateMultiViewRigPose(const std::vector<std::vector<MarkerI
     }
 }
 
-void CylinderTag::smoothRigTrack(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,
-                                 int nRigs, std::vector<std::vector<TrackInfo>>& track, const std::vector<double>& times, const ctag_track_opts* opts) {
-    track.clear();
+// the per-frame lists of estimateRigPose and their covariances as the n_frames x nRigs records of the batch calls: a rig that is not in a
+// frame's list is CTAG_POSE_NOT_SEEN there.  `who` names the caller in what is thrown; times: the caller's, checked where smoothRigTrack
+// has always checked them, or null.
+static void rig_records(const std::string& who, const std::vector<std::vector<RigPoseInfo>>& posesPerFrame,
+                        const std::vector<std::vector<PoseCovInfo>>& covPerFrame, int nRigs, unsigned long long max_items,
+                        const std::vector<double>* times, std::vector<ctag_rig_pose_rec>& rec, std::vector<ctag_pose_cov_rec>& cov) {
     const size_t n_frames = posesPerFrame.size();
-    if (n_frames == 0) throw std::string("smoothRigTrack, no frames\n");
-    if (covPerFrame.size() != n_frames) throw std::string("smoothRigTrack, one covariance list per frame\n");
-    if (nRigs < 1 || (unsigned long long)n_frames * (unsigned long long)nRigs > (unsigned long long)CTAG_TRACK_MAX_ITEMS)
-        throw std::string("smoothRigTrack, frames x rigs outside 1 .. 65536\n");
-    if (!times.empty() && times.size() != n_frames) throw std::string("smoothRigTrack, one time per frame\n");
+    if (n_frames == 0) throw who + ", no frames\n";
+    if (covPerFrame.size() != n_frames) throw who + ", one covariance list per frame\n";
+    if (nRigs < 1 || (unsigned long long)n_frames * (unsigned long long)nRigs > max_items) throw who + ", frames x rigs outside 1 .. 65536\n";
+    if (times && !times->empty() && times->size() != n_frames) throw who + ", one time per frame\n";
     const size_t n = n_frames * (size_t)nRigs;
-    std::vector<ctag_rig_pose_rec> rec(n);
-    std::vector<ctag_pose_cov_rec> cov(n);
+    rec.resize(n);
+    cov.resize(n);
     std::memset(rec.data(), 0, sizeof(ctag_rig_pose_rec) * n);
     std::memset(cov.data(), 0, sizeof(ctag_pose_cov_rec) * n);
     for (size_t f = 0; f < n_frames; f++) {
@@ -721,12 +723,12 @@ void CylinderTag::smoothRigTrack(const std::vector<std::vector<RigPoseInfo>>& po
             rec[f * nRigs + g].frame = (int32_t)f;
             cov[f * nRigs + g].status = CTAG_COV_NO_POSE;
         }
-        if (covPerFrame[f].size() != posesPerFrame[f].size()) throw std::string("smoothRigTrack, one covariance per pose\n");
+        if (covPerFrame[f].size() != posesPerFrame[f].size()) throw who + ", one covariance per pose\n";
         for (size_t i = 0; i < posesPerFrame[f].size(); i++) {
             const RigPoseInfo& p = posesPerFrame[f][i];
-            if (p.rigID < 0 || p.rigID >= nRigs) throw std::string("smoothRigTrack, a rig outside 0 .. nRigs - 1\n");
+            if (p.rigID < 0 || p.rigID >= nRigs) throw who + ", a rig outside 0 .. nRigs - 1\n";
             ctag_rig_pose_rec& r = rec[f * nRigs + p.rigID];
-            if (r.status == CTAG_POSE_OK) throw std::string("smoothRigTrack, a rig twice in one frame\n");
+            if (r.status == CTAG_POSE_OK) throw who + ", a rig twice in one frame\n";
             r.status = CTAG_POSE_OK;
 #ifdef CTAG_WITH_OPENCV
             const double *pr = p.rvec.ptr<double>(0), *pt = p.tvec.ptr<double>(0);
@@ -743,27 +745,48 @@ void CylinderTag::smoothRigTrack(const std::vector<std::vector<RigPoseInfo>>& po
             for (int k = 0; k < 36; k++) c.cov[k] = covPerFrame[f][i].cov[k];
         }
     }
-    // the smoother reads n_rigs of the rig set and nothing else: a set of nRigs one-model rigs over a model made for it
-    std::vector<int32_t> ids(nRigs), rig_of_model(nRigs);
-    std::vector<float> zeros3((size_t)nRigs * 3, 0.f), corners((size_t)nRigs * 24, 0.f);
-    for (int g = 0; g < nRigs; g++) ids[g] = rig_of_model[g] = g;
-    ctag_model_view mv;
-    mv.n_models = nRigs;
-    mv.model_size = 1;
-    mv.marker_id = ids.data();
-    mv.base = zeros3.data();
-    mv.axis = zeros3.data();
-    mv.corners = corners.data();
+}
+
+// the smoother and the hand-eye fit read n_rigs of the rig set and nothing else: a set of nRigs one-model rigs over a model made for it
+struct CountRigs {
     ctag_model* model = nullptr;
     ctag_rigs* rigs = nullptr;
-    int st = ctag_model_create(&mv, &model);
-    if (st == CTAG_OK) st = ctag_rigs_create(model, rig_of_model.data(), nRigs, &rigs);
+    int status = CTAG_OK;
+    explicit CountRigs(int nRigs) {
+        std::vector<int32_t> ids(nRigs), rig_of_model(nRigs);
+        std::vector<float> zeros3((size_t)nRigs * 3, 0.f), corners((size_t)nRigs * 24, 0.f);
+        for (int g = 0; g < nRigs; g++) ids[g] = rig_of_model[g] = g;
+        ctag_model_view mv;
+        mv.n_models = nRigs;
+        mv.model_size = 1;
+        mv.marker_id = ids.data();
+        mv.base = zeros3.data();
+        mv.axis = zeros3.data();
+        mv.corners = corners.data();
+        status = ctag_model_create(&mv, &model);
+        if (status == CTAG_OK) status = ctag_rigs_create(model, rig_of_model.data(), nRigs, &rigs);
+    }
+    ~CountRigs() {
+        if (rigs) ctag_rigs_free(rigs);
+        if (model) ctag_model_free(model);
+    }
+    CountRigs(const CountRigs&) = delete;
+    CountRigs& operator=(const CountRigs&) = delete;
+};
+
+void CylinderTag::smoothRigTrack(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,
+                                 int nRigs, std::vector<std::vector<TrackInfo>>& track, const std::vector<double>& times, const ctag_track_opts* opts) {
+    track.clear();
+    std::vector<ctag_rig_pose_rec> rec;
+    std::vector<ctag_pose_cov_rec> cov;
+    rig_records("smoothRigTrack", posesPerFrame, covPerFrame, nRigs, CTAG_TRACK_MAX_ITEMS, &times, rec, cov);
+    const size_t n_frames = posesPerFrame.size(), n = rec.size();
+    CountRigs set(nRigs);
+    int st = set.status;
     std::vector<ctag_track_rec> out(n);
     std::vector<ctag_track_stat> stat((size_t)nRigs);
     if (st == CTAG_OK)
-        st = ctag_rig_track_smooth(h_, rigs, rec.data(), cov.data(), (int)n_frames, times.empty() ? nullptr : times.data(), opts, out.data(), stat.data());
-    if (rigs) ctag_rigs_free(rigs);
-    if (model) ctag_model_free(model);
+        st = ctag_rig_track_smooth(h_, set.rigs, rec.data(), cov.data(), (int)n_frames, times.empty() ? nullptr : times.data(), opts, out.data(), stat.data());
     if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
     track.assign(n_frames, std::vector<TrackInfo>((size_t)nRigs));
     for (size_t f = 0; f < n_frames; f++)
@@ -785,6 +808,62 @@ void CylinderTag::smoothRigTrack(const std::vector<std::vector<RigPoseInfo>>& po
             ti.mahalanobis2 = t.mahalanobis2;
             ti.weight = t.weight;
         }
+}
+
+void CylinderTag::calibrateHandEye(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,
+                                   const std::vector<LinkPose>& links, int nRigs, std::vector<HandEyeInfo>& result, const ctag_hand_eye_opts* opts) {
+    result.clear();
+    std::vector<ctag_rig_pose_rec> rec;
+    std::vector<ctag_pose_cov_rec> cov;
+    rig_records("calibrateHandEye", posesPerFrame, covPerFrame, nRigs, CTAG_HAND_EYE_MAX_ITEMS, nullptr, rec, cov);
+    const size_t n_frames = posesPerFrame.size(), n = rec.size();
+    if (links.size() != n_frames) throw std::string("calibrateHandEye, one link pose per frame\n");
+    std::vector<ctag_link_pose> lk(n_frames);
+    for (size_t f = 0; f < n_frames; f++)
+        for (int k = 0; k < 3; k++) {
+            lk[f].rvec[k] = links[f].rvec[k];
+            lk[f].tvec[k] = links[f].tvec[k];
+        }
+    CountRigs set(nRigs);
+    int st = set.status;
+    std::vector<ctag_hand_eye_rec> out((size_t)nRigs);
+    std::vector<ctag_hand_eye_frame_rec> fr(n);
+    if (st == CTAG_OK) st = ctag_rig_hand_eye_fit(h_, set.rigs, rec.data(), cov.data(), (int)n_frames, lk.data(), opts, out.data(), fr.data());
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    result.assign((size_t)nRigs, HandEyeInfo());
+    for (int g = 0; g < nRigs; g++) {
+        const ctag_hand_eye_rec& r = out[g];
+        HandEyeInfo& hi = result[g];
+        hi.rigID = r.rig;
+        hi.status = r.status;
+        hi.nUsed = r.n_used;
+        hi.nDownweighted = r.n_downweighted;
+        hi.rounds = r.rounds;
+        hi.dof = r.dof;
+        for (int k = 0; k < 3; k++) {
+            hi.P.rvec[k] = r.P.rvec[k];
+            hi.P.tvec[k] = r.P.tvec[k];
+            hi.Q.rvec[k] = r.Q.rvec[k];
+            hi.Q.tvec[k] = r.Q.tvec[k];
+        }
+        hi.cost0 = r.cost0;
+        hi.cost = r.cost;
+        hi.lambda = r.lambda;
+        hi.sigma2Hat = r.sigma2_hat;
+        hi.minPivot = r.min_pivot;
+        for (int k = 0; k < 144; k++) hi.cov[k] = r.cov[k];
+        hi.frames.assign(n_frames, HandEyeFrameInfo());
+        for (size_t f = 0; f < n_frames; f++) {
+            const ctag_hand_eye_frame_rec& q = fr[f * nRigs + g];
+            HandEyeFrameInfo& fi = hi.frames[f];
+            fi.status = q.status;
+            fi.used = (q.flags & CTAG_HE_FLAG_USED) != 0;
+            fi.downweighted = (q.flags & CTAG_HE_FLAG_DOWNWEIGHTED) != 0;
+            for (int k = 0; k < 6; k++) fi.e[k] = q.e[k];
+            fi.mahalanobis2 = q.mahalanobis2;
+            fi.weight = q.weight;
+        }
+    }
 }
 
 static void pose_vectors(const PoseInfo& p, double* r, double* t) {

@@ -66,6 +66,7 @@ struct Mat1i {
 struct ctag_handle;
 struct ctag_params;  // include/ctag_types.h: the detector's tunables (the reference's member constants, header/corner_detector.h:90-144)
 struct ctag_track_opts;  // include/ctag_pose.h: the options of smoothRigTrack
+struct ctag_hand_eye_opts;  // include/ctag_pose.h: the options of calibrateHandEye
 
 // reference: header/corner_detector.h:16-22
 struct MarkerInfo {
@@ -147,6 +148,27 @@ struct TrackInfo {
     double cov[36] = {0};                             // row-major 6x6 of the pose, tangent parametrisation
     double velSigma[6] = {0};
     double mahalanobis2 = 0, weight = 0;
+};
+// a robot's link pose in one frame, base <- gripper (new): X_out = R(rvec) X_in + tvec; a non-finite entry drops the frame
+struct LinkPose {
+    double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
+};
+// one frame of one rig's hand-eye problem (new): the fields of ctag_hand_eye_frame_rec (include/ctag_pose.h, hand-eye calibration)
+struct HandEyeFrameInfo {
+    int status = 0;
+    bool used = false, downweighted = false;
+    double e[6] = {0};  // the residual at the returned state: rotation, translation
+    double mahalanobis2 = 0, weight = 0;
+};
+// the two fixed transforms of one rig's hand-eye problem (new): the fields of ctag_hand_eye_rec
+struct HandEyeInfo {
+    int rigID = -1;
+    int status = 0;  // CTAG_HE_*
+    int nUsed = 0, nDownweighted = 0, rounds = 0, dof = 0;
+    LinkPose P, Q;   // mode 0: camera <- gripper, base <- rig; mode 1: camera <- base, gripper <- rig
+    double cost0 = 0, cost = 0, lambda = 0, sigma2Hat = 0, minPivot = 0;
+    double cov[144] = {0};  // row-major 12x12: P's rotation and translation, then Q's
+    std::vector<HandEyeFrameInfo> frames;  // one per frame
 };
 // the annotated frame of drawAxis: rows x cols pixels of 3 bytes, channel c = Scalar component c (imgMark in the reference)
 struct AxisImage {
@@ -272,6 +294,13 @@ class CylinderTag {
     void smoothRigTrack(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,
                         int nRigs, std::vector<std::vector<TrackInfo>>& track, const std::vector<double>& times = std::vector<double>(),
                         const ctag_track_opts* opts = nullptr);
+
+    // The two fixed transforms between the camera's rig poses and a robot's link poses (new; include/ctag_pose.h,
+    // ctag_rig_hand_eye_fit): posesPerFrame and covPerFrame as smoothRigTrack takes them, links[f] the link pose (base <- gripper) of
+    // frame f; result[g] is the problem of rig g, for every g < nRigs.  opts: null for the defaults (camera on the link, no loss).
+    // Throws std::string on error.
+    void calibrateHandEye(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,
+                          const std::vector<LinkPose>& links, int nRigs, std::vector<HandEyeInfo>& result, const ctag_hand_eye_opts* opts = nullptr);
 
     // Draw the axes of the posed markers (reference: header/CylinderTag.h:33, CylinderTag.cpp:211-246): pose[i] is drawn on
     // markers[i] -- the reference pairs them by list position, after estimatePose has erased the poses without a model -- with

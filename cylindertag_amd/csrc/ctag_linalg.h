@@ -347,7 +347,9 @@ CTM_HD bool chol6_solve(double* H, const double* g, double* x) {
 // Inverse of a symmetric 6x6 C (row-major, the lower triangle is read) by Cholesky, C = L L^T: inv = L^-T L^-1, exactly
 // symmetric.  min_pivot is the smallest pivot (the diagonal entry before its square root) met; false as soon as a pivot is not
 // above min_allowed (or is not a number).
-CTM_HD bool chol6_inverse(const double* C, double* inv, double min_allowed, double& min_pivot) {
+// chol6_inverse_factor: the same, and with Linv the lower triangle of L^-1 (row-major 6x6, the upper triangle 0) is returned too:
+// inv = Linv^T Linv.
+CTM_HD bool chol6_inverse_factor(const double* C, double* inv, double* Linv, double min_allowed, double& min_pivot) {
     constexpr int N = 6;
     double L[36], W[36];
     min_pivot = C[0];
@@ -389,7 +391,17 @@ CTL_UNROLL
             inv[a * N + b] = sacc;
             inv[b * N + a] = sacc;
         }
+    if (Linv) {
+CTL_UNROLL
+        for (int a = 0; a < N; a++)
+CTL_UNROLL
+            for (int b = 0; b < N; b++) Linv[a * N + b] = b <= a ? W[a * N + b] : 0.0;
+    }
     return true;
+}
+
+CTM_HD bool chol6_inverse(const double* C, double* inv, double min_allowed, double& min_pivot) {
+    return chol6_inverse_factor(C, inv, nullptr, min_allowed, min_pivot);
 }
 
 CTM_HD bool finite64(double x) { return (ctm::f64_to_bits(x) & 0x7ff0000000000000ULL) != 0x7ff0000000000000ULL; }

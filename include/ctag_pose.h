@@ -503,7 +503,7 @@ int ctag_estimate_mv_rig_pose_robust(ctag_handle* h, const ctag_frame_result* re
 #define CTAG_TRACK_MAX_ITEMS 65536 /* n_frames x n_rigs of one call */
 
 #define CTAG_TRACK_FLAG_MEASURED 1u     /* rule 1 */
-#define CTAG_TRACK_FLAG_DOWNWEIGHTED 2u /* the loss's weight at the returned state is below 1 */
+#define CTAG_TRACK_FLAG_DOWNWEIGHTED 2u /* the loss's weight at the returned state is below 1 (CTAG_HE_FLAG_DOWNWEIGHTED is defined otherwise) */
 
 typedef struct ctag_track_opts {
     uint32_t struct_size;    /* filled by ctag_track_opts_default, checked */
@@ -564,6 +564,127 @@ int ctag_mv_rig_track_smooth(ctag_handle* h, const ctag_rigs* rigs, const ctag_m
 /* device time of the last smoothing call's kernels (needs CTAG_OPT_TIMING), milliseconds: gather + pieces + start, the rounds, the
  * marginals and the records, the whole call */
 int ctag_track_last_ms(ctag_handle* h, float* out4);
+
+/* ---- hand-eye calibration: the two fixed transforms between the camera's poses and a robot's link poses (k_hand_eye.hip) -----------------
+ * Every pose above lives in the camera's (or the reference) frame.  A robot, stage or tracked arm reports a link pose per frame; this call
+ * takes the n_frames x n_rigs rig pose records of a batch (record w = f * n_rigs + g, either record kind, as the smoother takes them) with
+ * their covariance records and one link pose per frame, and returns per rig the two fixed transforms P and Q of
+ *      A_f ~ P o C_f o Q,        X_cam = R_P (R_C (R_Q X_rig + t_Q) + t_C) + t_P,
+ * A_f the measured pose (camera or reference frame <- rig) and C_f the link pose as the mode says.  links: a HOST array of n_frames
+ * ctag_link_pose, link_f = base <- gripper.
+ *      CTAG_HAND_EYE_CAMERA_ON_LINK (eye in hand): C_f = link_f^-1, P = camera <- gripper, Q = base <- rig;
+ *      CTAG_HAND_EYE_RIG_ON_LINK (eye to hand):    C_f = link_f,    P = camera <- base,    Q = gripper <- rig.
+ * One kernel path serves both: the mode only decides whether the links are inverted when they are taken in.  Every rig g is one
+ * independent problem; all problems of a call share the link poses.  This is OpenCV's calibrateHandEye / calibrateRobotWorldHandEye
+ * with every frame weighted by its own covariance, and the answer comes with a covariance of its own.  Nothing above is changed by it.
+ *   1. Used frames.  Frame f is used for rig g when it is measured exactly as rule 1 of the smoother says (pose CTAG_POSE_OK, covariance
+ *      CTAG_COV_OK with param CTAG_COV_PARAM_TANGENT, unit-diagonal scaling, every pivot above 1e-12; W_f = cov^-1) and all six entries
+ *      of its link pose are finite.  A link pose with a non-finite entry makes the frame unused for every rig: that is how a caller
+ *      drops a frame.  Bad input is what it is for the smoother (a CTAG_COV_OK covariance with param CTAG_COV_PARAM_RVEC, a rig or
+ *      frame field that is not the record's place): CTAG_HE_BAD_INPUT for that rig only.
+ *   2. Unknowns: (a, b, c, d), 12 tangent coordinates.  R_P <- Exp(a) R_P, t_P <- t_P + b, R_Q <- Exp(c) R_Q, t_Q <- t_Q + d.
+ *   3. Cost = half the sum over the used frames of rho(e^T W_f e), e = [Log(R_pred Rm_f^T); t_pred - tm_f].  rho is the identity for
+ *      CTAG_TRACK_LOSS_NONE and ctag_loss.h's Huber or Cauchy with a = loss_scale otherwise: the function and the use of the smoother's
+ *      rule 4.  The link poses are taken as exact.
+ *   4. Jacobian, exact.  Rotation rows: Jl^-1(phi) for a, Jl^-1(phi) R_P R_C for c, phi = the rotation residual.  Translation rows:
+ *      -[R_P (R_C t_Q + t_C)]x for a, I for b, R_P R_C for d.
+ *   5. Start, on the device, from the used frames in frame order, k0 the first used frame.  S = sum_k alpha_k beta_k^T with
+ *      alpha_k = Log(Rm_k Rm_k0^T), beta_k = Log(R_C,k R_C,k0^T); pairs in which |alpha| or |beta| exceeds 3 rad are left out of S (Log's
+ *      branch next to a half turn is not stable under noise) but stay in the cost.  R_P is the rotation nearest S (svd3, the determinant
+ *      fixed, as rule 2 of the camera-set fit); R_Q the rotation nearest sum_f R_C,f^T R_P^T Rm_f; (t_Q, t_P) solve the 6x6 normal
+ *      equations of [R_P R_C,f | I] [t_Q; t_P] = tm_f - R_P t_C,f by Cholesky.
+ *   6. Minimisation: Levenberg-Marquardt, (A + lambda diag A) delta = -g, the loss by its weight alone.  One lambda per problem from
+ *      lambda0; the round control is the fits' (ctag_lm.h: rel_tol 1e-12, lambda_max 1e6, max_iterations), decided on the device, so
+ *      the call does not wait.  A round whose factorisation meets a pivot that is not positive is a reject.  Problems that have
+ *      stopped skip their rounds.  max_iterations = 1 with lambda0 = 0 is one undamped Gauss-Newton step from the start of rule 5.
+ *   7. Status per problem: CTAG_HE_OK; CTAG_HE_TOO_FEW, fewer than 3 used frames; CTAG_HE_BAD_INPUT (rule 1); CTAG_HE_SINGULAR when
+ *      the start's 6x6 meets a pivot that is not positive, when the cost is not finite, or when the undamped Gauss-Newton matrix at
+ *      the returned state, scaled to unit diagonal, has a Cholesky pivot that is not above 1e-12: link rotations that are all about
+ *      one axis, and pure translations.  On singular P and Q are the last accepted state (0 when the start itself failed) and cov is 0.
+ *   8. Result: ctag_hand_eye_rec, one per rig.  dof = 6 n_used - 12; sigma2_hat = 2 cost / dof (0 when dof <= 0); min_pivot the smallest
+ *      pivot of the scaled matrix; cov the inverse of the undamped Gauss-Newton matrix at the returned state in rule 2's coordinates
+ *      and order, symmetric bit for bit, NOT scaled by sigma2_hat: the input covariances already carry the noise.  A problem that is
+ *      CTAG_HE_TOO_FEW or CTAG_HE_BAD_INPUT has every field 0 except status and rig (and n_used for TOO_FEW).  ctag_hand_eye_frame_rec,
+ *      optional, row f * n_rigs + g: for a used frame of a problem that has a state (CTAG_HE_OK, or singular at the returned state)
+ *      the problem's status, CTAG_HE_FLAG_USED, the residual e, mahalanobis2 = e^T W_f e and weight = rho' at the returned state, and
+ *      CTAG_HE_FLAG_DOWNWEIGHTED when a loss is set and mahalanobis2 exceeds loss_scale^2: there Huber's weight falls below 1 and
+ *      Cauchy's, which is below 1 at every frame, below 1/2.  n_downweighted counts those frames.  Every other frame record is 0 except rig and frame.
+ *   9. Deterministic.  Every sum over frames is taken in chunks of 64 consecutive frame indices, lane = frame mod 64, unused frames
+ *      adding exact zeros, by wave_sum_f64's tree; the chunks are added in ascending order by one owner.  No floating-point atomics.
+ *      A problem's bytes do not depend on its rig slot, on the other rigs, on the grid or on the run.
+ *  10. CTAG_ERR_ARG: a null argument (frames_dev / frames excepted), n_frames < 1, a wrong struct_size, an unknown mode or loss,
+ *      loss_scale that is not positive and finite, lambda0 that is negative or not finite, max_iterations < 1, n_frames x n_rigs above
+ *      CTAG_HAND_EYE_MAX_ITEMS.  Device memory of one call: 452 bytes per (frame, rig) item, 144 per frame, 744 per chunk of 64 frames
+ *      of a rig and 432 per rig; at most 1772 bytes per item (one-frame rigs), 0.12 GB at the bound. */
+#define CTAG_HE_OK 0
+#define CTAG_HE_TOO_FEW 1     /* rule 7 */
+#define CTAG_HE_BAD_INPUT 2   /* rule 1 */
+#define CTAG_HE_SINGULAR 3    /* rule 7 */
+
+#define CTAG_HAND_EYE_CAMERA_ON_LINK 0   /* eye-in-hand: link = base<-gripper; the library uses C_f = link_f^-1 */
+#define CTAG_HAND_EYE_RIG_ON_LINK 1      /* eye-to-hand: link = base<-gripper; C_f = link_f */
+#define CTAG_HAND_EYE_MAX_ITEMS 65536    /* n_frames x n_rigs of one call */
+
+#define CTAG_HE_FLAG_USED 1u          /* rule 1 */
+#define CTAG_HE_FLAG_DOWNWEIGHTED 2u  /* a loss is set and the frame lies beyond its scale at the returned state: rule 8; NOT the smoother's "weight below 1" */
+
+typedef struct ctag_link_pose { double rvec[3], tvec[3]; } ctag_link_pose;   /* 48 bytes: X_out = R(rvec) X_in + tvec */
+
+typedef struct ctag_hand_eye_opts {
+    uint32_t struct_size;    /* filled by ctag_hand_eye_opts_default, checked */
+    int32_t mode;            /* CTAG_HAND_EYE_CAMERA_ON_LINK (default) or CTAG_HAND_EYE_RIG_ON_LINK */
+    int32_t loss;            /* CTAG_TRACK_LOSS_NONE (default), CTAG_LOSS_HUBER or CTAG_LOSS_CAUCHY */
+    int32_t max_iterations;  /* >= 1; default 20 */
+    double loss_scale;       /* a of the loss, in units of the Mahalanobis norm; default 4 */
+    double lambda0;          /* >= 0; default 1e-3 */
+} ctag_hand_eye_opts;        /* 32 bytes */
+
+typedef struct ctag_hand_eye_rec {   /* one per rig */
+    int32_t status;          /* CTAG_HE_* */
+    int32_t rig;
+    int32_t n_used;
+    int32_t n_downweighted;
+    int32_t rounds;          /* accepted + rejected */
+    int32_t dof;             /* 6 n_used - 12 */
+    ctag_link_pose P, Q;     /* the mode's table above */
+    double cost0;            /* at the start of rule 5 */
+    double cost;             /* at the returned state */
+    double lambda;
+    double sigma2_hat;
+    double min_pivot;
+    double cov[144];         /* rule 8; rows/cols a, b, c, d */
+} ctag_hand_eye_rec;         /* 1312 bytes */
+
+typedef struct ctag_hand_eye_frame_rec {
+    int32_t status;          /* the problem's, where the frame is used */
+    int32_t rig;
+    int32_t frame;
+    uint32_t flags;          /* CTAG_HE_FLAG_* */
+    double e[6];             /* rule 3's residual at the returned state: rotation, translation */
+    double mahalanobis2;
+    double weight;
+} ctag_hand_eye_frame_rec;   /* 80 bytes */
+
+void ctag_hand_eye_opts_default(ctag_hand_eye_opts* opts);
+/* Device records in, device records out.  Writes exactly n_rigs result records to out_dev and, unless frames_dev is NULL,
+ * n_frames x n_rigs frame records to frames_dev, and no byte outside them.  Enqueued on the handle's stream; returns without waiting for
+ * its own work or for anything else on the stream, with one exception: the workspace is the handle's, so an earlier hand-eye call of
+ * this handle that is still in flight is waited for first.  links is copied before the call returns.  The rig set only gives n_rigs.
+ * opts == NULL means the defaults. */
+int ctag_rig_hand_eye_fit_device(ctag_handle* h, const ctag_rigs* rigs, const ctag_rig_pose_rec* rig_poses_dev, const ctag_pose_cov_rec* cov_dev,
+                                 int n_frames, const ctag_link_pose* links, const ctag_hand_eye_opts* opts, ctag_hand_eye_rec* out_dev,
+                                 ctag_hand_eye_frame_rec* frames_dev);
+int ctag_mv_rig_hand_eye_fit_device(ctag_handle* h, const ctag_rigs* rigs, const ctag_mv_pose_rec* mv_poses_dev, const ctag_pose_cov_rec* cov_dev,
+                                    int n_frames, const ctag_link_pose* links, const ctag_hand_eye_opts* opts, ctag_hand_eye_rec* out_dev,
+                                    ctag_hand_eye_frame_rec* frames_dev);
+/* The same with HOST arrays in and out (frames may be NULL); they wait for completion. */
+int ctag_rig_hand_eye_fit(ctag_handle* h, const ctag_rigs* rigs, const ctag_rig_pose_rec* rig_poses, const ctag_pose_cov_rec* cov, int n_frames,
+                          const ctag_link_pose* links, const ctag_hand_eye_opts* opts, ctag_hand_eye_rec* out, ctag_hand_eye_frame_rec* frames);
+int ctag_mv_rig_hand_eye_fit(ctag_handle* h, const ctag_rigs* rigs, const ctag_mv_pose_rec* mv_poses, const ctag_pose_cov_rec* cov, int n_frames,
+                             const ctag_link_pose* links, const ctag_hand_eye_opts* opts, ctag_hand_eye_rec* out, ctag_hand_eye_frame_rec* frames);
+/* device time of the last hand-eye call's kernels (needs CTAG_OPT_TIMING), milliseconds: gather + start, the rounds, the covariance and
+ * the records, the whole call */
+int ctag_hand_eye_last_ms(ctag_handle* h, float* out4);
 
 /* ---- model reconstruction: the corner lists themselves, from detections of the objects (k_model_fit.hip) ---------------------------
  * Every pose call above takes a ctag_model; this call makes one.  From the detection records of a few dozen to a few thousand
