@@ -374,6 +374,7 @@ hipError_t launch_line_fits(const ChunkPlan& pl, const Workspace& ws, hipStream_
 int welsch_limits(int32_t* out, int capacity);  // the sizes at which k_line_sort / k_welsch / k_welsch_lat change form (k_quad.hip); returns their count
 hipError_t launch_features(const ChunkPlan& pl, const Workspace& ws, const DetectParams& p, hipStream_t s);
 hipError_t launch_edge_refine(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, const DetectParams& p, hipStream_t s);
+hipError_t launch_edge_refine_sums(const ChunkPlan& pl, const Workspace& ws, hipStream_t s);  // launch_edge_refine's k_edge_refine_sums alone, on what ws.feat1 / nfeat / status / refine_n0 hold
 hipError_t launch_markers(const ChunkPlan& pl, const Workspace& ws, const DetectParams& p, ctag_frame_result* out, const PendingCtx& pend, hipStream_t s);
 // sums and maxima over the frames of the last chunk: components, candidates, quads, features, markers -> out10 (device, 5 x int64 sums then 5 x int64 maxima)
 hipError_t launch_counters(int nframes, const Workspace& ws, const ctag_frame_result* results, long long* out10, hipStream_t s);

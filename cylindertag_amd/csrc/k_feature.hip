@@ -487,7 +487,7 @@ constexpr int kRefineRegionLarge = CTAG_REFINE_REGION_LARGE;
 //         than kRefineSamples samples (edges longer than 1024 px; `only_long`).
 // MODE 1: the searches only (256 threads): per sample n0 = Mn / Mcount goes to P.n0 (NaN: no edge point).  No sample rows in LDS, so
 //         a block is the 21.5 KB pixel box and little else.
-// The ordered sums, line parameters and corners of a batch are kernels of their own: k_edge_refine_sums (one wave per quad: rebuilds every sample's point from
+// The ordered sums, line parameters and corners of a batch are kernels of their own: k_edge_refine_sums (one wave per two quads: rebuilds every sample's point from
 // n0 with the search's own expressions) and k_edge_refine_tail, below.
 // Batches run MODE 1, the sums, the tails (then MODE 0 for the rare long quads).  In one kernel the serial tail -- 48 chains of 128 dependent FP64 adds on one
 // wave, then divisions / atan2 / sin / cos on 8 lanes -- held a 40 KB, four-wave block while three of its waves idled, at four
@@ -544,7 +544,9 @@ __device__ __forceinline__ void refine_sync() { __syncthreads(); }
 __device__ __forceinline__ void sums_sync() { __syncthreads(); }
 #else
 __device__ __forceinline__ void refine_sync() { lds_barrier(); }
-__device__ __forceinline__ void sums_sync() { lds_wait(); }
+// (the second wait is the same one in the form the compiler's wait-count pass reads: without it the pass takes an LDS read from before the ordering point for
+// outstanding, and waits for it -- and for the scalar loads requested since -- at the value's first use)
+__device__ __forceinline__ void sums_sync() { lds_wait(), __builtin_amdgcn_s_waitcnt(0xc07f); }
 #endif
 // REGION: bytes of the quad's pixel neighbourhood staged in LDS.  kRefineRegion holds the box of every quad of a 1080p-class frame; frames above 1920x1200 have quads
 // of twice the size (a diagonal strip's box is ~190 x 190 px, up to 240 x 240) and batches of them run the search kernel with kRefineRegionLarge -- three blocks per CU
@@ -840,111 +842,54 @@ void k_edge_refine(RefinePtrs P, int rows, int cols, int subpix, int nframes, in
         if (q + gx < nq) refine_sync();
     }
 }
-// ---- the sums kernel (round 5): TERMS in LDS.  Its round-4 form (k_edge_refine<2>, docs/history.md) kept rows of x, y, the products and the weights, and every step of
-// a sum was a load of two operands, a multiplication and the (ordered) addition; 64 registers of operand buffers held it to three waves per SIMD and half of its time it
-// waited: 1.03 ms per 4096 frames.  Here the lane that builds a sample also multiplies -- (A B) w, the same two roundings in the same order, for the sample's twelve sums --
-// and a sum's step is one addition: segments of 16 samples (64 lanes = 4 edges x 16), 48 rows of 16 terms (6.9 KB), a chain's row index IS its lane
-// (12 edge + 6 pass + moment), ~100 registers, four waves per SIMD.
-// What bounds it now is LDS BANDWIDTH: a quad's 48 x 128 terms are written once and read once, 98 KB, and 393 K quads per 4096 frames are 38.5 GB against the
-// 78 TB/s the 256 CUs' LDS move at 128 B per clock: 0.49 ms; the kernel runs 0.70-0.73.  Timing builds without its global loads, without its stores, without
-// both: 4.40 / 4.40 / 4.39 against 4.45 ms edge_refine -- memory is not what it waits for; halving its vector instructions (the position parameters' divisions,
-// a table now) did not move it either.  The transposition sample-lane -> sum-lane is the work.
+// ---- the sums kernel: PRODUCTS in LDS, weights as scalars, two quads per wave.  Its round-4 form (k_edge_refine<2>, docs/history.md) kept rows of x, y, the products and
+// the weights, and every step of a sum was a load of two operands, a multiplication and the (ordered) addition: 1.03 ms per 4096 frames.  Round 5 had the lane that
+// builds a sample write its twelve terms (A B) w -- six moments x two weightings -- and a chain lane per term add them: 48 rows of 16 terms per segment, 98 KB per quad
+// written once and read once, and that LDS traffic bounded it (floor 0.49 ms, measured 0.70-0.73).
+// The twelve terms are six products A B of {x, y, xx, xy, yy, 1}, each times two weights, and at 128 samples per edge the weights are functions of the sample index
+// alone: alpha_s = (15 + s) / 158 towards the last corner, 1 - alpha_s towards the next one, for every quad, edge and frame.  So only the six products cross from
+// sample lanes to sum lanes; a chain lane is (edge, moment), 24 per quad, and carries BOTH sums: accN += T * wn_s, accL += T * wl_s -- the product T wn_s rounded, then
+// added, the same two roundings in the same order as (A B) w in the build lane -- with wn_s, wl_s wave-uniform operands out of a table in constant memory (c_sums_w:
+// scalar loads, one per four samples).  A sample without an edge point writes x = y = 0 and "1" = 0: every term is +0.0, as before.  24 chain lanes would leave 40 idle
+// and an LDS read costs its lanes, not its addresses, so a wave works on TWO quads of its block at a time (q and q + per_frame: slots 0 and 1, chain lanes 0-23 and
+// 24-47; the build phase alternates between them).  Per quad: 6 x 8 B x 512 written, 24 x 8 B x 128 read, 49 KB -- half of round 5's, and the floor with it (0.25 ms).
+// Measured per 4096 frames, parent and this form alternating in one call (kernel trace, mean of 6 launches, three runs each): 0.707 / 0.716 / 0.718 ms before,
+// 0.451 / 0.449 / 0.453 ms now; edge_refine as a stage 4.44-4.48 -> 4.19 ms.  No single bound is left: a pair is ~4300 SIMD cycles of vector issue (2 x 8 build segments
+// of ~33 FP64-class instructions, 8 x 64 chain multiplications and additions: 0.34 ms at four waves per SIMD), reading 1.6 GB of n0 once is 0.32 ms at 5 TB/s, LDS 0.25 ms.
+// Registers: the n0 of the NEXT pair is requested into the registers of this pair, a segment at a time, as soon as the segment's samples are built -- every load is a
+// pair's time old when it is used, and there is one set of 2 x 8 doubles instead of two.
 #ifndef CTAG_REFINE_SUMS2_WAVES
 #define CTAG_REFINE_SUMS2_WAVES 4
 #endif
 constexpr int kSumSeg = 16, kSumSegs = kRefineSamples / kSumSeg;
 constexpr int kSumPitch = kSumSeg + 2;  // doubles per row: 36 words -- an odd multiple of four, so the ds_read_b128 of 16 consecutive lanes (rows) cover the 64 banks exactly once
-struct SumsPrefetch {
-    double n0[kSumSegs];  // of sample 16 g + (tid & 15) of edge tid >> 4
-    float cx, cy;
-};
-__device__ __forceinline__ void sums_prefetch(const RefinePtrs& P, int frame, int qidx, SumsPrefetch& R) {
-    const int tid = threadIdx.x;
-    const double* src = P.n0 + ((size_t)frame * (CTAG_MAX_FEATURES * 2) + qidx) * (4 * kRefineSamples) + (tid >> 4) * kRefineSamples + (tid & 15);
-#pragma unroll
-    for (int g = 0; g < kSumSegs; g++) R.n0[g] = src[g * kSumSeg];
-    const FeatureDev* F = P.feat1 + (size_t)frame * CTAG_MAX_FEATURES + (qidx >> 1);
-    const int c = (qidx & 1) * 4 + (tid & 3);
-    R.cx = F->c[2 * c];
-    R.cy = F->c[2 * c + 1];
-}
-// the 48 ordered sums of one quad -> acc_out[edge * 12 + pass * 6 + {Mx, My, Mxx, Mxy, Myy, N}]; false: no such quad, or one with an edge of more than kRefineSamples samples
-// (the caller has checked qidx against the frame's feature count; s_alpha: the samples' position parameters, the same for every quad)
-__device__ __forceinline__ bool refine_sums_quad(const SumsPrefetch& pre, const double* s_alpha, double* acc_out) {
-    __shared__ __attribute__((aligned(16))) double s_t[48][kSumPitch];
-    __shared__ float s_cx[4], s_cy[4];
-    __shared__ double s_nrm[4][2];
-    __shared__ int s_ns[4];
-    const int tid = threadIdx.x;
-    if (tid < 4) {
-        s_cx[tid] = pre.cx;
-        s_cy[tid] = pre.cy;
-    }
-    sums_sync();
-    if (tid < 4) {  // :609-615
-        const int a = tid, b = (tid + 1) & 3;
-        const double nx = s_cy[b] - s_cy[a];
-        const double ny = -s_cx[b] + s_cx[a];
-        const double mag = ctm::sqrt64(nx * nx + ny * ny);
-        const double ns_d = mag / 8 > 128.0 ? mag / 8 : 128.0;
-        s_ns[tid] = (int)ns_d;
-        s_nrm[tid][0] = nx / mag;
-        s_nrm[tid][1] = ny / mag;
-    }
-    sums_sync();
-    if (max(max(s_ns[0], s_ns[1]), max(s_ns[2], s_ns[3])) > kRefineSamples) return false;  // k_edge_refine_long's
-    const int edge = tid >> 4, loc = tid & 15;
-    const float ax = s_cx[edge], ay = s_cy[edge], bx = s_cx[(edge + 1) & 3], by = s_cy[(edge + 1) & 3];
-    const double nx = s_nrm[edge][0], ny = s_nrm[edge][1];
-    double* const mine = &s_t[edge * 12][loc];
-    const double2* const row2 = reinterpret_cast<const double2*>(s_t[tid < 48 ? tid : 0]);
-    double acc = 0.0;
-#pragma unroll
-    for (int g = 0; g < kSumSegs; g++) {
-        // the sample's point with the search's own expressions: x0 = alpha ax + (1 - alpha) bx, best = x0 + n0 nx (:619-621, :656-657)
-        const double alpha = s_alpha[kSumSeg * g + loc];  // (15.0 + s) / (nsamples + 30) (:619): every edge of this quad has kRefineSamples samples, so the quotient is per sample index
-        const double x0 = alpha * ax + (1 - alpha) * bx;
-        const double y0 = alpha * ay + (1 - alpha) * by;
-        const double n0 = pre.n0[g];
-        const bool ok = n0 == n0;  // NaN: no edge point
-        const double x = ok ? x0 + n0 * nx : 0.0, y = ok ? y0 + n0 * ny : 0.0;
-        const double wn = ok ? 1 - alpha : 0.0, wl = ok ? alpha : 0.0;  // weights towards the next / the last corner; a sample without an edge point adds +0.0 to every sum
-        const double xx = x * x, xy = x * y, yy = y * y;
-        if (g) sums_sync();  // the sums of the segment before are done with the rows
-        mine[0 * kSumPitch] = x * wn;   // (x 1) w: x 1 is exact
-        mine[1 * kSumPitch] = y * wn;
-        mine[2 * kSumPitch] = xx * wn;  // (A B) w: the product first, as the reference's left-to-right evaluation rounds it
-        mine[3 * kSumPitch] = xy * wn;
-        mine[4 * kSumPitch] = yy * wn;
-        mine[5 * kSumPitch] = wn;       // (1 1) w
-        mine[6 * kSumPitch] = x * wl;
-        mine[7 * kSumPitch] = y * wl;
-        mine[8 * kSumPitch] = xx * wl;
-        mine[9 * kSumPitch] = xy * wl;
-        mine[10 * kSumPitch] = yy * wl;
-        mine[11 * kSumPitch] = wl;
-        sums_sync();
-        if (tid < 48) {  // sequential (sample-order) accumulation: bit-identical to the reference's running sums
-            double t[kSumSeg];
-#pragma unroll
-            for (int u = 0; u < kSumSeg / 2; u++) {
-                const double2 v = row2[u];
-                t[2 * u] = v.x, t[2 * u + 1] = v.y;
-            }
-#pragma unroll
-            for (int u = 0; u < kSumSeg; u++) acc += t[u];
+constexpr int kSumRows = 24;            // rows of a quad: edge * 6 + {x, y, xx, xy, yy, 1}
+// w[s] = {1 - alpha_s, alpha_s}, alpha_s = (15.0 + s) / (nsamples + 30) at 128 samples (:619): the doubles the search kernel and the build phase form (IEEE division
+// and subtraction, here at compile time).  In constant memory, not `const`: the chains index it with compile-time sample indices, and what the compiler may not fold
+// into 256 literals per pair it loads with scalar loads.
+struct SumsWeights {
+    double w[kRefineSamples][2];
+    constexpr SumsWeights() : w{} {
+        for (int s = 0; s < kRefineSamples; s++) {
+            const double alpha = (15.0 + s) / (kRefineSamples + 30);
+            w[s][0] = 1 - alpha;
+            w[s][1] = alpha;
         }
     }
-    if (tid < 48) acc_out[tid] = acc;
-    sums_sync();
-    return true;
-}
-// The sums go back to global memory -- into the first 49 doubles of the quad's own n0 block, which is dead once they are formed: [0, 48) the sums, [48] 1.0 when the
-// quad has them (0.0: no such quad here, or k_edge_refine_long's) -- and the tails (line parameters, corners) are a kernel of their own, k_edge_refine_tail: five
-// divisions, atan2, sin / cos per line in double are what the sums kernel's registers went to, and a chain as long as a quad's sums that only 8 lanes walk.
+};
+__constant__ SumsWeights c_sums_w = SumsWeights();
+typedef const double __attribute__((address_space(4))) * SumsWeightPtr;  // a pointer into constant memory that stays one: uniform loads through it are scalar loads
+struct SumsPrefetch {
+    double n0[2][kSumSegs];  // [slot][g]: of sample 16 g + (tid & 15) of edge tid >> 4
+    float cx, cy;            // corner tid & 3 of the quad in slot (tid >> 2) & 1
+};
+// The sums go back to global memory -- into the first 49 doubles of the quad's own n0 block, which is dead once they are formed: [0, 48) the sums at
+// edge * 12 + pass * 6 + {Mx, My, Mxx, Mxy, Myy, N}, [48] 1.0 when the quad has them (0.0: k_edge_refine_long's, an edge of more than kRefineSamples samples) -- and
+// the tails (line parameters, corners) are a kernel of their own, k_edge_refine_tail: five divisions, atan2, sin / cos per line in double are what the sums kernel's
+// registers went to, and a chain as long as a quad's sums that only 8 lanes walk.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CTAG_REFINE_SUMS2_WAVES, 8)))
 void k_edge_refine_sums(RefinePtrs P, int nframes, int per_frame) {
-    // per_frame blocks per frame, blocks b and b + 8 -- one XCD -- on the same frame; a block loops over the frame's quads with the next quad's inputs in flight
+    // per_frame blocks per frame, blocks b and b + 8 -- one XCD -- on the same frame; a block loops over the frame's quads two at a time, the next two's inputs in flight
     if (blockDim.x != 64) __builtin_trap();  // sums_sync orders the phases of ONE wave; any other launch size would race silently
     const int b = blockIdx.x;
     const int frame = ((b >> 3) / per_frame) * 8 + (b & 7);
@@ -952,35 +897,147 @@ void k_edge_refine_sums(RefinePtrs P, int nframes, int per_frame) {
     if (frame >= nframes) return;
     if (P.status[frame] != CTAG_OK) return;
     const int nq = 2 * min(P.nfeat[frame], CTAG_MAX_FEATURES);
-    int q = bx;
-    if (q >= nq) return;
-    __shared__ double s_acc[48];
-    __shared__ double s_alpha[kRefineSamples];  // a double division per sample and quad otherwise: more than half of the kernel's vector instructions
+    if (bx >= nq) return;
+    __shared__ __attribute__((aligned(16))) double s_t[2 * kSumRows][kSumPitch];
+    __shared__ float s_cx[8], s_cy[8];  // [slot * 4 + corner]
+    __shared__ double s_nrm[8][2];
+    __shared__ int s_ns[8];
+    __shared__ double s_alpha[kRefineSamples];  // the build lanes' position parameters: a double division per sample and quad otherwise
     const int tid = threadIdx.x;
     for (int k = tid; k < kRefineSamples; k += 64) s_alpha[k] = (15.0 + k) / (kRefineSamples + 30);
-    // The loop is ROTATED so that nothing a quad needs has been requested less than a quad's time ago -- and it took the ISA to see that it was not so: with
+    const int edge = tid >> 4, loc = tid & 15;
+    double* const n0_frame = P.n0 + (size_t)frame * (CTAG_MAX_FEATURES * 2) * (4 * kRefineSamples);
+    const uint32_t lane_off = (uint32_t)((edge * kRefineSamples + loc) * sizeof(double));  // of sample `loc` of edge `edge` in a quad's block, bytes
+    constexpr uint32_t kSegBytes = kSumSeg * sizeof(double);
+    auto n0_at = [](const double* base, uint32_t off) -> double { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + off); };
+    const FeatureDev* const F_frame = P.feat1 + (size_t)frame * CTAG_MAX_FEATURES;
+    SumsPrefetch pre;
+    auto request_corner = [&](int qa, int qb) {  // (qb == qa: no quad in slot 1, its lanes compute slot 0's geometry again and nobody reads it)
+        const int qi = (tid & 4) ? qb : qa;
+        const FeatureDev* F = F_frame + (qi >> 1);
+        const int c = (qi & 1) * 4 + (tid & 3);
+        pre.cx = F->c[2 * c];
+        pre.cy = F->c[2 * c + 1];
+    };
+    // The loop is ROTATED so that nothing a pair needs has been requested less than a pair's time ago -- and it took the ISA to see when it was not so: with
     // "request next, work, store, cur = next" the compiler's wait-count pass, merging the loop's entry (cur's own loads outstanding) with its back edge, put
-    // a wait for all vector memory before the first use of `cur`, right behind the requests for the next quad (so the prefetch hid nothing, here and in round 4's kernel),
-    // and the copy at the end waited for the stores just issued.  Now: cur's first loads are awaited explicitly before the loop (vmem_wait: the pass
-    // understands it), and an iteration is work(cur) -> cur = next (a wait for loads a quad old) -> request the quad after -> store this quad's sums.
-    SumsPrefetch cur, nxt;
-    sums_prefetch(P, frame, q, cur);
+    // a wait for all vector memory before the first use of `cur`, right behind the requests for the next quad.  Now: the first pair's loads are awaited explicitly
+    // before the loop (vmem_wait: the pass understands it), and inside it a register is requested again right after its last use, in the order of its next use.
+    // The requests are UNCONDITIONAL: the pass counts a load behind a branch as not issued, and with "if there is a next pair" around them it waited for all
+    // vector memory at every segment.  A slot without a next quad reads one word of the frame's block instead (every lane the same one: a single cache line), and
+    // a slot without a quad, or with a long one, is built from whatever came and never stored.
+    int q0 = bx, q1 = bx + per_frame;  // slots 0 and 1; q1 >= nq: slot 1 is empty
+    const int step = 2 * per_frame;
+    request_corner(q0, q1 < nq ? q1 : q0);
+#pragma unroll
+    for (int g = 0; g < kSumSegs; g++) {
+        pre.n0[0][g] = n0_at(n0_frame + (size_t)q0 * (4 * kRefineSamples), lane_off + g * kSegBytes);
+        pre.n0[1][g] = 0.0;
+        if (q1 < nq) pre.n0[1][g] = n0_at(n0_frame + (size_t)q1 * (4 * kRefineSamples), lane_off + g * kSegBytes);
+    }
     vmem_wait();
-    int qn = q + per_frame;
-    if (qn < nq) sums_prefetch(P, frame, qn, nxt);
+    sums_sync();  // s_alpha
+    const double2* const row2 = reinterpret_cast<const double2*>(s_t[tid < 2 * kSumRows ? tid : 0]);
     for (;;) {
-        const bool have = refine_sums_quad(cur, s_alpha, s_acc);
-        const double mine = tid < 48 ? s_acc[tid] : (have ? 1.0 : 0.0);
-        double* const out = P.n0 + ((size_t)frame * (CTAG_MAX_FEATURES * 2) + q) * (4 * kRefineSamples);
-        sums_sync();
-        q = qn;
-        qn += per_frame;
-        if (q < nq) {
-            cur = nxt;
-            if (qn < nq) sums_prefetch(P, frame, qn, nxt);
+        const bool have1 = q1 < nq;
+        const int nq0 = q0 + step, nq1 = q1 + step;
+        const bool next0 = nq0 < nq, next1 = nq1 < nq;
+        if (tid < 8) {
+            s_cx[tid] = pre.cx;
+            s_cy[tid] = pre.cy;
         }
-        if (tid < 48 ? have : tid == 48) out[tid] = mine;  // [0, 48): the sums; [48]: 1.0 when the quad has them
-        if (q >= nq) break;
+        sums_sync();
+        request_corner(next0 ? nq0 : q0, next1 ? nq1 : q0);  // (no next pair: this pair's first quad again, a line the cache has)
+        if (tid < 8) {  // :609-615
+            const int a = tid, b = (tid & 4) | ((tid + 1) & 3);
+            const double nx = s_cy[b] - s_cy[a];
+            const double ny = -s_cx[b] + s_cx[a];
+            const double mag = ctm::sqrt64(nx * nx + ny * ny);
+            const double ns_d = mag / 8 > 128.0 ? mag / 8 : 128.0;
+            s_ns[tid] = (int)ns_d;
+            s_nrm[tid][0] = nx / mag;
+            s_nrm[tid][1] = ny / mag;
+        }
+        sums_sync();
+        // a quad with an edge of more than kRefineSamples samples is k_edge_refine_long's: nothing of it is stored but its flag 0.0 (uniform: every lane reads the same words)
+        const bool do0 = __builtin_amdgcn_readfirstlane(max(max(s_ns[0], s_ns[1]), max(s_ns[2], s_ns[3]))) <= kRefineSamples;
+        const bool do1 = have1 && __builtin_amdgcn_readfirstlane(max(max(s_ns[4], s_ns[5]), max(s_ns[6], s_ns[7]))) <= kRefineSamples;
+        float ax[2], ay[2], bx_[2], by[2];
+        double nx[2], ny[2];
+#pragma unroll
+        for (int sl = 0; sl < 2; sl++) {
+            ax[sl] = s_cx[4 * sl + edge], ay[sl] = s_cy[4 * sl + edge], bx_[sl] = s_cx[4 * sl + ((edge + 1) & 3)], by[sl] = s_cy[4 * sl + ((edge + 1) & 3)];
+            nx[sl] = s_nrm[4 * sl + edge][0], ny[sl] = s_nrm[4 * sl + edge][1];
+        }
+        // the next pair's blocks (uniform) and this lane's place in them; no next quad: the frame's first word, for every lane
+        const double* const nbase[2] = {n0_frame + (size_t)(next0 ? nq0 : 0) * (4 * kRefineSamples), n0_frame + (size_t)(next1 ? nq1 : 0) * (4 * kRefineSamples)};
+        const uint32_t noff[2] = {next0 ? lane_off : 0u, next1 ? lane_off : 0u};
+        double accN = 0.0, accL = 0.0;
+        // (15.0 + s) / (nsamples + 30) (:619): every edge of these quads has kRefineSamples samples, so the quotient is per sample index.  A segment's is read with
+        // the rows of the segment before: a wait for LDS is a wait for the scalar loads too, and behind the weights' requests it would wait for them at once
+        double alpha_next = s_alpha[loc];
+#pragma unroll
+        for (int g = 0; g < kSumSegs; g++) {
+            const double alpha = alpha_next;
+            if (g) sums_sync();  // the sums of the segment before are done with the rows
+            // this segment's 32 weights: scalar loads, requested HERE, ahead of the build phase that hides them -- as loop invariants the compiler would load all 256
+            // ahead of the loop and spill them
+            SumsWeightPtr wp = (SumsWeightPtr)&c_sums_w.w[kSumSeg * g][0];
+            asm volatile("" : "+s"(wp));
+            double w[2 * kSumSeg];
+#pragma unroll
+            for (int u = 0; u < 2 * kSumSeg; u++) w[u] = wp[u];
+#pragma unroll
+            for (int sl = 0; sl < 2; sl++) {
+                // the sample's point with the search's own expressions: x0 = alpha ax + (1 - alpha) bx, best = x0 + n0 nx (:619-621, :656-657)
+                const double x0 = alpha * ax[sl] + (1 - alpha) * bx_[sl];
+                const double y0 = alpha * ay[sl] + (1 - alpha) * by[sl];
+                const double n0 = pre.n0[sl][g];
+                const bool ok = n0 == n0;  // NaN: no edge point
+                const double x = ok ? x0 + n0 * nx[sl] : 0.0, y = ok ? y0 + n0 * ny[sl] : 0.0;
+                double* const mine = &s_t[sl * kSumRows + edge * 6][loc];
+                mine[0 * kSumPitch] = x;  // the factors A B of (A B) w: x 1 and 1 1 are exact
+                mine[1 * kSumPitch] = y;
+                mine[2 * kSumPitch] = x * x;
+                mine[3 * kSumPitch] = x * y;
+                mine[4 * kSumPitch] = y * y;
+                mine[5 * kSumPitch] = ok ? 1.0 : 0.0;  // a sample without an edge point adds +0.0 to every sum, which equals the reference skipping it
+                pre.n0[sl][g] = n0_at(nbase[sl], noff[sl] + ((sl ? next1 : next0) ? g * kSegBytes : 0u));
+            }
+            if (g + 1 < kSumSegs) alpha_next = s_alpha[kSumSeg * (g + 1) + loc];
+            sums_sync();
+            if (tid < 2 * kSumRows) {  // sequential (sample-order) accumulation: bit-identical to the reference's running sums
+                double t[kSumSeg];
+#pragma unroll
+                for (int u = 0; u < kSumSeg / 2; u++) {
+                    const double2 v = row2[u];
+                    t[2 * u] = v.x, t[2 * u + 1] = v.y;
+                }
+#pragma unroll
+                for (int u = 0; u < kSumSeg; u++) {  // (A B) w rounded, then added: no fma (the library is built with -ffp-contract=off)
+                    accN += t[u] * w[2 * u];
+                    accL += t[u] * w[2 * u + 1];
+                }
+            }
+        }
+        {
+            const int sl = tid >= kSumRows ? 1 : 0, r = tid - sl * kSumRows;
+            const int e = r / 6, m = r - e * 6;
+            double* const out = n0_frame + (size_t)(sl ? q1 : q0) * (4 * kRefineSamples);
+            if (tid < 2 * kSumRows) {
+                if (sl ? do1 : do0) {
+                    out[e * 12 + m] = accN;      // weighting towards the next corner
+                    out[e * 12 + 6 + m] = accL;  // ... towards the last one
+                }
+            } else if (tid == 48) {
+                n0_frame[(size_t)q0 * (4 * kRefineSamples) + 48] = do0 ? 1.0 : 0.0;
+            } else if (tid == 49 && have1) {
+                n0_frame[(size_t)q1 * (4 * kRefineSamples) + 48] = do1 ? 1.0 : 0.0;
+            }
+        }
+        if (!next0) break;
+        q0 = nq0, q1 = nq1;
+        sums_sync();  // the last segment's sums are done with the rows
     }
 }
 // lines and corners of the quads whose sums k_edge_refine_sums left: 8 quads per wave -- a lane per (edge, pass) line (:667-678 / :743-754), then a lane per corner (:757-776)
@@ -1751,6 +1808,15 @@ hipError_t launch_features(const ChunkPlan& pl, const Workspace& ws, const Detec
     else hipLaunchKernelGGL(k_features<128>, dim3(pl.nframes), dim3(128), 0, s, P, pl.nframes, p.feature_size);
     return hipGetLastError();
 }
+// the sums kernel's one launch: per_frame blocks of one wave for each of the frames rounded up to whole groups of 8 (a group's blocks interleave its frames)
+static void launch_refine_sums(const ChunkPlan& pl, const RefinePtrs& P, hipStream_t s) {
+    const int f8 = ((pl.nframes + 7) / 8) * 8;
+    hipLaunchKernelGGL(k_edge_refine_sums, dim3(f8 * pl.refine_sums_gx), dim3(64), 0, s, P, pl.nframes, pl.refine_sums_gx);
+}
+hipError_t launch_edge_refine_sums(const ChunkPlan& pl, const Workspace& ws, hipStream_t s) {  // that launch alone (the probe of libctag_testkit.so)
+    launch_refine_sums(pl, refine_ptrs(nullptr, 0, 0, ws, DetectParams{}), s);
+    return hipGetLastError();
+}
 hipError_t launch_edge_refine(const ChunkPlan& pl, const uint8_t* frames, ptrdiff_t frame_stride, ptrdiff_t row_stride, const Workspace& ws, const DetectParams& p, hipStream_t s) {
     const int nframes = pl.nframes, refine_gx = pl.refine_gx, f8 = ((nframes + 7) / 8) * 8;
     const RefinePtrs P = refine_ptrs(frames, frame_stride, row_stride, ws, p);
@@ -1764,7 +1830,7 @@ hipError_t launch_edge_refine(const ChunkPlan& pl, const uint8_t* frames, ptrdif
     if (pl.refine == RefineForm::SplitLarge) hipLaunchKernelGGL((k_edge_refine<1, kRefineRegionLarge>), dim3(f8 * refine_gx), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, refine_gx);
     else if (pl.refine == RefineForm::SplitLooping) hipLaunchKernelGGL(k_edge_refine<1>, dim3(f8 * refine_gx), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, refine_gx);
     else hipLaunchKernelGGL(k_edge_refine<1>, dim3(refine_gx, nframes), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes, 0);
-    hipLaunchKernelGGL(k_edge_refine_sums, dim3(f8 * pl.refine_sums_gx), dim3(64), 0, s, P, nframes, pl.refine_sums_gx);
+    launch_refine_sums(pl, P, s);
     hipLaunchKernelGGL(k_edge_refine_tail, dim3(13, nframes), dim3(64), 0, s, P, nframes, 13);  // 13 x 8 quads: the synthetic frames' 96; a block loops when a frame has more
     hipLaunchKernelGGL(k_edge_refine_long, dim3(4, nframes), dim3(kRefineThreads), 0, s, P, ws.g.rows, ws.g.cols, p.subpix_dist, nframes);
     return hipGetLastError();

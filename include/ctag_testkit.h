@@ -193,6 +193,19 @@ int ctag_testkit_welsch_fit(ctag_handle* h, int n_frames, const int32_t* edges_p
  * int32 values, returns their count. */
 int ctag_testkit_welsch_limits(int32_t* out, int capacity);
 
+/* ---- edgeRefine's ordered sums alone (k_edge_refine_sums; cylindertag_amd/csrc/k_feature.hip: launch_edge_refine_sums) -----------------------
+ * The sums kernel of a batch's edge refinement on caller-made inputs, launched with the plan's grid.  Works on the workspace of the handle's
+ * last chunk: run a detect call of at least n_frames frames, more than four, with the corner refinement on first.  Frame f has nfeat[f] features
+ * (0..CTAG_MAX_FEATURES) and the status status[f] (the kernel works on CTAG_OK frames only); corners = host float [sum nfeat][16], a feature's 8
+ * corners (x, y) as K7 leaves them, quad 0 then quad 1; n0 = host double [sum 2 nfeat][4][128], per quad, edge and sample the search kernel's result
+ * (NaN: no edge point), all frames back to back.  The probe writes nfeat, status, feat1 and the quads' n0 blocks, launches the kernel on the
+ * handle's stream, waits, and copies the first 49 doubles of every quad's block back: sums = host double [sum 2 nfeat][49], [0, 48) the sums at
+ * edge * 12 + weighting * 6 + {Mx, My, Mxx, Mxy, Myy, N}, [48] 1.0 where the quad has them.  What the kernel does not write comes back as
+ * the n0 that was there.  CTAG_ERR_ARG where an input does not fit: no such workspace, n_frames above the last chunk's frames or so few that the
+ * plan runs edgeRefine as one kernel, a feature count out of range. */
+int ctag_testkit_refine_sums(ctag_handle* h, int n_frames, const int32_t* nfeat, const int32_t* status, const float* corners, const double* n0,
+                             double* sums);
+
 /* ---- the reduced system of the model reconstruction (cylindertag_amd/csrc/k_model_fit.hip; include/ctag_pose.h, model reconstruction) ---------
  * k_mfit_record, k_mfit_assemble and k_mfit_solve at a caller-given state instead of inside the fit's loop.  results: n_frames HOST detection
  * records; poses: n_poses HOST pose records over them, as ctag_pose_batch_device orders them -- the CTAG_POSE_OK ones are the observation records

@@ -24,7 +24,7 @@ SYNTH_SEED = 0x4354616753594E00  # "CTagSYN\0", SURVEY.md 8(d)
 # every symbol include/ctag_testkit.h declares (tests check the library exports all of them)
 EXPORTS = ["ctag_debug_fetch", "ctag_math_probe", "ctag_testkit_wave_probe", "ctag_testkit_exp32_k0_sweep", "ctag_testkit_unpack_gathered", "ctag_testkit_stall_stream", "ctag_synth_frames_device", "ctag_synth_frame_host",
            "ctag_synth_layout_truth", "ctag_synth3d_frames_device", "ctag_synth3d_frame_host", "ctag_synth3d_model",
-           "ctag_testkit_dense_edge_probe", "ctag_testkit_plan", "ctag_testkit_welsch_fit", "ctag_testkit_welsch_limits",
+           "ctag_testkit_dense_edge_probe", "ctag_testkit_plan", "ctag_testkit_welsch_fit", "ctag_testkit_welsch_limits", "ctag_testkit_refine_sums",
            "ctag_testkit_model_fit_system", "ctag_testkit_model_fit_limits", "ctag_testkit_rig_fit_system", "ctag_testkit_rig_fit_limits",
            "ctag_testkit_camera_fit_system", "ctag_testkit_camera_fit_limits",
            "ctag_testkit_intrinsics_fit_system", "ctag_testkit_intrinsics_fit_poses", "ctag_testkit_intrinsics_fit_limits"]
@@ -107,6 +107,8 @@ def load_library():
                                                 C.c_double, C.c_double, vp, vp]
     L.ctag_testkit_welsch_fit.restype = C.c_int
     L.ctag_testkit_welsch_fit.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.ctag_testkit_refine_sums.restype = C.c_int
+    L.ctag_testkit_refine_sums.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.ctag_testkit_welsch_limits.restype = C.c_int
     L.ctag_testkit_welsch_limits.argtypes = [i32p, C.c_int]
     L.ctag_testkit_model_fit_system.restype = C.c_int
@@ -331,6 +333,20 @@ class Detector(ca.Detector):
         if st != 0:
             raise CtagError(st, "ctag_testkit_welsch_fit")
         return lines
+
+    def refine_sums(self, nfeat, status, corners, n0):
+        """edgeRefine's sums kernel alone (ctag_testkit_refine_sums) on the workspace of the last chunk: nfeat, status per frame; corners float32
+        [sum nfeat, 16]; n0 float64 [sum 2 nfeat, 4, 128] -> float64 [sum 2 nfeat, 49], the first 49 doubles of every quad's block after the kernel."""
+        nfeat = np.ascontiguousarray(nfeat, np.int32)
+        status = np.ascontiguousarray(status, np.int32)
+        nq = 2 * int(nfeat.sum())
+        corners = np.ascontiguousarray(corners, np.float32).reshape(nq // 2, 16)
+        n0 = np.ascontiguousarray(n0, np.float64).reshape(nq, 4, 128)
+        sums = np.zeros((nq, 49), np.float64)
+        st = self.T.ctag_testkit_refine_sums(self.h, len(nfeat), nfeat.ctypes.data, status.ctypes.data, corners.ctypes.data, n0.ctypes.data, sums.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_testkit_refine_sums")
+        return sums
 
     def model_fit_system(self, results, poses, model, camera, model_index, lam, min_obs=2, pass_records=0):
         """The reduced system of the model reconstruction for one model at a given state (ctag_testkit_model_fit_system): host detection

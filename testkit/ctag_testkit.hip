@@ -824,6 +824,56 @@ int ctag_testkit_welsch_fit(ctag_handle* h, int n_frames, const int32_t* edges_p
 
 int ctag_testkit_welsch_limits(int32_t* out, int capacity) { return welsch_limits(out, out ? std::max(capacity, 0) : 0); }
 
+int ctag_testkit_refine_sums(ctag_handle* h, int n_frames, const int32_t* nfeat, const int32_t* status, const float* corners, const double* n0, double* sums) {
+    if (!h || n_frames < 1 || !nfeat || !status) return CTAG_ERR_ARG;
+    HandleView v{};
+    handle_view(h, &v);
+    if (!v.ws || !v.ws->base || !v.ws->refine_n0 || n_frames > v.last_chunk_frames) return CTAG_ERR_ARG;
+    const Workspace& W = *v.ws;
+    size_t total = 0;
+    for (int f = 0; f < n_frames; f++) {
+        if (nfeat[f] < 0 || nfeat[f] > CTAG_MAX_FEATURES) return CTAG_ERR_ARG;
+        total += (size_t)nfeat[f];
+    }
+    if (total > 0 && (!corners || !n0 || !sums)) return CTAG_ERR_ARG;
+    const FrameGeom& g = W.g;
+    const ChunkPlan pl = plan_chunk(PlanIn{g.rows, g.cols, g.tw, n_frames, 1, 1, nullptr, 0, 0, W.kp, 0, 0, false, DevKnobs{}});
+    if (pl.refine == RefineForm::None || pl.refine == RefineForm::One) return CTAG_ERR_ARG;  // the chain would not launch this kernel for such a call
+    constexpr size_t kQuad = 4 * 128;  // doubles of a quad's n0 block
+    TK_TRY(hipSetDevice(v.device));
+    hipStream_t s = static_cast<hipStream_t>(ctag_stream(h));
+    TK_TRY(hipStreamSynchronize(s));
+    TK_TRY(hipMemcpy(W.nfeat, nfeat, (size_t)n_frames * 4, hipMemcpyHostToDevice));
+    TK_TRY(hipMemcpy(W.status, status, (size_t)n_frames * 4, hipMemcpyHostToDevice));
+    size_t f0 = 0;
+    for (int f = 0; f < n_frames; f++) {
+        const size_t nf = (size_t)nfeat[f];
+        if (nf == 0) continue;
+        std::vector<FeatureDev> feats(nf);
+        for (size_t k = 0; k < nf; k++) {
+            FeatureDev F{};
+            std::memcpy(F.c, corners + (f0 + k) * 16, sizeof(F.c));
+            feats[k] = F;
+        }
+        TK_TRY(hipMemcpy(W.feat1 + (size_t)f * CTAG_MAX_FEATURES, feats.data(), nf * sizeof(FeatureDev), hipMemcpyHostToDevice));
+        TK_TRY(hipMemcpy(W.refine_n0 + (size_t)f * (CTAG_MAX_FEATURES * 2) * kQuad, n0 + f0 * 2 * kQuad, nf * 2 * kQuad * 8, hipMemcpyHostToDevice));
+        f0 += nf;
+    }
+    if (launch_edge_refine_sums(pl, W, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return CTAG_ERR_HIP;
+    }
+    TK_TRY(hipStreamSynchronize(s));
+    f0 = 0;
+    for (int f = 0; f < n_frames; f++) {
+        const size_t nq = (size_t)nfeat[f] * 2;
+        if (nq == 0) continue;
+        TK_TRY(hipMemcpy2D(sums + f0 * 49, 49 * 8, W.refine_n0 + (size_t)f * (CTAG_MAX_FEATURES * 2) * kQuad, kQuad * 8, 49 * 8, nq, hipMemcpyDeviceToHost));
+        f0 += nq;
+    }
+    return CTAG_OK;
+}
+
 int ctag_testkit_model_fit_system(ctag_handle* h, const ctag_frame_result* results, int n_frames, const ctag_pose_rec* poses, int n_poses,
                                   const ctag_model* model, const ctag_camera* camera, int model_index, double lambda, int min_obs, int pass_records,
                                   double* S, double* g, double* delta, int32_t* held, int32_t* bad_pivot) {
