@@ -36,6 +36,9 @@ POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag
                 "ctag_estimate_pose_robust", "ctag_estimate_rig_pose_robust", "ctag_estimate_mv_rig_pose_robust",
                 "ctag_track_opts_default", "ctag_rig_track_smooth_device", "ctag_mv_rig_track_smooth_device", "ctag_rig_track_smooth",
                 "ctag_mv_rig_track_smooth", "ctag_track_last_ms",
+                "ctag_track_filter_opts_default", "ctag_track_filter_create", "ctag_track_filter_free", "ctag_track_filter_reset",
+                "ctag_rig_track_filter_device", "ctag_mv_rig_track_filter_device", "ctag_rig_track_filter", "ctag_mv_rig_track_filter",
+                "ctag_track_filter_predict_device", "ctag_track_filter_predict", "ctag_track_filter_last_ms",
                 "ctag_hand_eye_opts_default", "ctag_rig_hand_eye_fit_device", "ctag_mv_rig_hand_eye_fit_device", "ctag_rig_hand_eye_fit",
                 "ctag_mv_rig_hand_eye_fit", "ctag_hand_eye_last_ms",
                 "ctag_model_fit_opts_default", "ctag_model_fit_device", "ctag_model_fit", "ctag_model_save", "ctag_model_fit_last_ms",
@@ -93,7 +96,7 @@ assert TRACK_STAT_DT.itemsize == 40
 TRACK_OK, TRACK_NOT_TRACKED, TRACK_BAD_INPUT, TRACK_SINGULAR = range(4)
 TRACK_LOSS_NONE = 2
 TRACK_MAX_ITEMS = 65536
-TRACK_FLAG_MEASURED, TRACK_FLAG_DOWNWEIGHTED = 1, 2
+TRACK_FLAG_MEASURED, TRACK_FLAG_DOWNWEIGHTED, TRACK_FLAG_GATED, TRACK_FLAG_STARTED = 1, 2, 4, 8
 # ctag_link_pose / ctag_hand_eye_rec / ctag_hand_eye_frame_rec: a link pose per frame in, one record per rig and one per (frame, rig) out of a
 # hand-eye calibration (include/ctag_pose.h)
 LINK_POSE_DT = np.dtype([("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
@@ -221,6 +224,26 @@ def track_opts(**fields):
             setattr(o, k, float(v))
         else:
             raise TypeError("ctag_track_opts has no field %r" % k)
+    return o
+
+
+class TrackFilterOptsC(C.Structure):  # ctag_track_filter_opts
+    _fields_ = [("struct_size", C.c_uint32), ("loss", C.c_int32), ("max_gap", C.c_int32), ("reserved", C.c_int32), ("dt", C.c_double),
+                ("q_rot", C.c_double), ("q_trans", C.c_double), ("vel0_sigma_rot", C.c_double), ("vel0_sigma_trans", C.c_double),
+                ("loss_scale", C.c_double), ("gate", C.c_double)]
+
+
+def track_filter_opts(**fields):
+    """ctag_track_filter_opts_default, then the given fields."""
+    o = TrackFilterOptsC()
+    load_library().ctag_track_filter_opts_default(C.byref(o))
+    for k, v in fields.items():
+        if k in ("loss", "max_gap", "struct_size"):
+            setattr(o, k, int(v))
+        elif k in ("dt", "q_rot", "q_trans", "vel0_sigma_rot", "vel0_sigma_trans", "loss_scale", "gate"):
+            setattr(o, k, float(v))
+        else:
+            raise TypeError("ctag_track_filter_opts has no field %r" % k)
     return o
 
 
@@ -480,6 +503,23 @@ def load_library():
         fn.argtypes = [vp, vp, vp, vp, C.c_int, vp, trkp, vp, vp]
     L.ctag_track_last_ms.restype = C.c_int
     L.ctag_track_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    tfp = C.POINTER(TrackFilterOptsC)
+    L.ctag_track_filter_opts_default.restype = None
+    L.ctag_track_filter_opts_default.argtypes = [tfp]
+    L.ctag_track_filter_create.restype = C.c_int
+    L.ctag_track_filter_create.argtypes = [vp, vp, tfp, C.POINTER(vp)]
+    L.ctag_track_filter_free.restype = None
+    L.ctag_track_filter_free.argtypes = [vp]
+    L.ctag_track_filter_reset.restype = C.c_int
+    L.ctag_track_filter_reset.argtypes = [vp]
+    for fn in (L.ctag_rig_track_filter_device, L.ctag_mv_rig_track_filter_device, L.ctag_rig_track_filter, L.ctag_mv_rig_track_filter):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, vp, C.c_int, vp, vp]
+    for fn in (L.ctag_track_filter_predict_device, L.ctag_track_filter_predict):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.c_double, vp]
+    L.ctag_track_filter_last_ms.restype = C.c_int
+    L.ctag_track_filter_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     hep = C.POINTER(HandEyeOptsC)
     L.ctag_hand_eye_opts_default.restype = None
     L.ctag_hand_eye_opts_default.argtypes = [hep]
@@ -800,6 +840,100 @@ def pinned_empty(shape, dtype=np.uint8):
     return arr
 
 
+class TrackFilter:
+    """ctag_track_filter (include/ctag_pose.h, track filtering): the causal filter of rigs.n_rigs rig pose tracks on a detector's handle;
+    its state lives on the device between calls.  Made by Detector.track_filter; it keeps its detector alive, and the detector's close()
+    closes it first."""
+
+    def __init__(self, det, rigs, opts=None):
+        self.L, self.det, self.n_rigs = det.L, det, rigs.n_rigs
+        f = C.c_void_p()
+        st = self.L.ctag_track_filter_create(det.h, rigs.r, C.byref(opts) if opts is not None else None, C.byref(f))
+        if st != 0:
+            raise CtagError(st, "ctag_track_filter_create")
+        self.f = f
+
+    @staticmethod
+    def _times(name, times, n_frames):
+        if times is None:
+            return None
+        t = np.ascontiguousarray(np.atleast_1d(times), np.float64).reshape(-1)
+        if len(t) != n_frames:
+            raise ValueError("%s: %d times for %d frames" % (name, len(t), n_frames))
+        return t
+
+    def _step(self, fn, name, rec_dt, poses, cov, n_frames, times):
+        n = n_frames * self.n_rigs
+        poses = np.ascontiguousarray(poses, rec_dt).reshape(-1)
+        cov = np.ascontiguousarray(cov, POSE_COV_DT).reshape(-1)
+        if len(poses) != n or len(cov) != n:
+            raise ValueError("%s: %d pose and %d covariance records for %d frames x %d rigs" % (name, len(poses), len(cov), n_frames, self.n_rigs))
+        t = self._times(name, times, n_frames)
+        out = np.zeros(max(n, 1), TRACK_DT)
+        st = fn(self.f, poses.ctypes.data, cov.ctypes.data, n_frames, None if t is None else t.ctypes.data, out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, name)
+        return out[:n].reshape(n_frames, self.n_rigs)
+
+    def step(self, rig_poses, cov, n_frames=1, times=None):
+        """n_frames x n_rigs host RIG_POSE_DT records with their POSE_COV_DT records, in order -> TRACK_DT [n_frames, n_rigs].  Waits."""
+        return self._step(self.L.ctag_rig_track_filter, "ctag_rig_track_filter", RIG_POSE_DT, rig_poses, cov, n_frames, times)
+
+    def step_mv(self, mv_poses, cov, n_frames=1, times=None):
+        """The same from MV_POSE_DT records."""
+        return self._step(self.L.ctag_mv_rig_track_filter, "ctag_mv_rig_track_filter", MV_POSE_DT, mv_poses, cov, n_frames, times)
+
+    def _step_device(self, fn, name, poses_ptr, cov_ptr, n_frames, times, out_ptr):
+        t = self._times(name, times, n_frames)
+        st = fn(self.f, poses_ptr, cov_ptr, n_frames, None if t is None else t.ctypes.data, out_ptr)
+        if st != 0:
+            raise CtagError(st, name)
+
+    def step_device(self, rig_poses_ptr, cov_ptr, out_ptr, n_frames=1, times=None):
+        """Device records in, n_frames * n_rigs device TRACK_DT records at out_ptr; enqueued."""
+        self._step_device(self.L.ctag_rig_track_filter_device, "ctag_rig_track_filter_device", rig_poses_ptr, cov_ptr, n_frames, times, out_ptr)
+
+    def step_mv_device(self, mv_poses_ptr, cov_ptr, out_ptr, n_frames=1, times=None):
+        self._step_device(self.L.ctag_mv_rig_track_filter_device, "ctag_mv_rig_track_filter_device", mv_poses_ptr, cov_ptr, n_frames, times, out_ptr)
+
+    def predict(self, t):
+        """The prediction to time t, TRACK_DT [n_rigs]; the state is untouched.  Waits."""
+        out = np.zeros(self.n_rigs, TRACK_DT)
+        st = self.L.ctag_track_filter_predict(self.f, float(t), out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, "ctag_track_filter_predict")
+        return out
+
+    def predict_device(self, t, out_ptr):
+        st = self.L.ctag_track_filter_predict_device(self.f, float(t), out_ptr)
+        if st != 0:
+            raise CtagError(st, "ctag_track_filter_predict_device")
+
+    def reset(self):
+        st = self.L.ctag_track_filter_reset(self.f)
+        if st != 0:
+            raise CtagError(st, "ctag_track_filter_reset")
+
+    def track_filter_last_ms(self):
+        """Device milliseconds of the last step call's kernel (needs OPT_TIMING)."""
+        out = C.c_float()
+        self.L.ctag_track_filter_last_ms(self.f, C.byref(out))
+        return float(out.value)
+
+    def close(self):
+        if getattr(self, "f", None):
+            self.L.ctag_track_filter_free(self.f)
+            self.f = None
+            if self in getattr(self.det, "_filters", ()):
+                self.det._filters.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Detector:
     """One ctag_handle (one GPU).  Mirrors the reference's usage: construct with the dictionary, call detect()."""
 
@@ -820,6 +954,8 @@ class Detector:
         self.h = h
 
     def close(self):
+        for f in list(getattr(self, "_filters", ())):   # a filter's state hangs on the handle: freed first, as CylinderTag's destructor does
+            f.close()
         if getattr(self, "h", None):
             self.L.ctag_destroy(self.h)
             self.h = None
@@ -1225,6 +1361,15 @@ class Detector:
         out = (C.c_float * 4)()
         self.L.ctag_track_last_ms(self.h, out)
         return dict(zip(("setup", "rounds", "marginals", "total"), (float(v) for v in out)))
+
+    def track_filter(self, rigs, opts=None):
+        """A TrackFilter for rigs.n_rigs rigs on this detector (include/ctag_pose.h, track filtering); opts is a TrackFilterOptsC
+        (track_filter_opts(...)) or None for the defaults.  The detector closes the filters it made that are still open when it is closed."""
+        f = TrackFilter(self, rigs, opts)
+        if not hasattr(self, "_filters"):
+            self._filters = []
+        self._filters.append(f)
+        return f
 
     # ---- hand-eye calibration (include/ctag_pose.h): opts is a HandEyeOptsC (hand_eye_opts(...)) or None for the defaults
     @staticmethod

@@ -25,7 +25,10 @@ CylinderTag::CylinderTag(const Mat1i& set_state, int feature_size, int device_id
     create(device_id, params);
 }
 
-CylinderTag::~CylinderTag() { ctag_destroy(h_); }
+CylinderTag::~CylinderTag() {
+    stopRigTracking();
+    ctag_destroy(h_);
+}
 
 // reference: CylinderTag::load_from_file, CylinderTag.cpp:16-41
 void CylinderTag::load_from_file(const std::string path) {
@@ -774,6 +777,26 @@ struct CountRigs {
     CountRigs& operator=(const CountRigs&) = delete;
 };
 
+// a track record of either the smoother or the filter as the class returns it
+static void track_info(const ctag_track_rec& t, TrackInfo& ti) {
+    ti.rigID = t.rig;
+    ti.status = t.status;
+    ti.measured = (t.flags & CTAG_TRACK_FLAG_MEASURED) != 0;
+    ti.downweighted = (t.flags & CTAG_TRACK_FLAG_DOWNWEIGHTED) != 0;
+    ti.gated = (t.flags & CTAG_TRACK_FLAG_GATED) != 0;
+    ti.started = (t.flags & CTAG_TRACK_FLAG_STARTED) != 0;
+    for (int k = 0; k < 3; k++) {
+        ti.rvec[k] = t.rvec[k];
+        ti.tvec[k] = t.tvec[k];
+        ti.w[k] = t.w[k];
+        ti.v[k] = t.v[k];
+    }
+    for (int k = 0; k < 36; k++) ti.cov[k] = t.cov[k];
+    for (int k = 0; k < 6; k++) ti.velSigma[k] = t.vel_sigma[k];
+    ti.mahalanobis2 = t.mahalanobis2;
+    ti.weight = t.weight;
+}
+
 void CylinderTag::smoothRigTrack(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,
                                  int nRigs, std::vector<std::vector<TrackInfo>>& track, const std::vector<double>& times, const ctag_track_opts* opts) {
     track.clear();
@@ -790,24 +813,54 @@ void CylinderTag::smoothRigTrack(const std::vector<std::vector<RigPoseInfo>>& po
     if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
     track.assign(n_frames, std::vector<TrackInfo>((size_t)nRigs));
     for (size_t f = 0; f < n_frames; f++)
-        for (int g = 0; g < nRigs; g++) {
-            const ctag_track_rec& t = out[f * nRigs + g];
-            TrackInfo& ti = track[f][g];
-            ti.rigID = t.rig;
-            ti.status = t.status;
-            ti.measured = (t.flags & CTAG_TRACK_FLAG_MEASURED) != 0;
-            ti.downweighted = (t.flags & CTAG_TRACK_FLAG_DOWNWEIGHTED) != 0;
-            for (int k = 0; k < 3; k++) {
-                ti.rvec[k] = t.rvec[k];
-                ti.tvec[k] = t.tvec[k];
-                ti.w[k] = t.w[k];
-                ti.v[k] = t.v[k];
-            }
-            for (int k = 0; k < 36; k++) ti.cov[k] = t.cov[k];
-            for (int k = 0; k < 6; k++) ti.velSigma[k] = t.vel_sigma[k];
-            ti.mahalanobis2 = t.mahalanobis2;
-            ti.weight = t.weight;
-        }
+        for (int g = 0; g < nRigs; g++) track_info(out[f * nRigs + g], track[f][g]);
+}
+
+void CylinderTag::stopRigTracking() {
+    if (filter_) ctag_track_filter_free(filter_);
+    filter_ = nullptr;
+    filter_rigs_ = 0;
+}
+
+void CylinderTag::startRigTracking(int nRigs, const ctag_track_filter_opts* opts) {
+    stopRigTracking();
+    if (nRigs < 1 || nRigs > CTAG_TRACK_MAX_ITEMS) throw std::string("startRigTracking, rigs outside 1 .. 65536\n");
+    CountRigs set(nRigs);
+    int st = set.status;
+    if (st == CTAG_OK) st = ctag_track_filter_create(h_, set.rigs, opts, &filter_);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    filter_rigs_ = nRigs;
+}
+
+void CylinderTag::track_rigs(const std::vector<RigPoseInfo>& poses, const std::vector<PoseCovInfo>& covs, const double* time, std::vector<TrackInfo>& track) {
+    track.clear();
+    if (!filter_) throw std::string("trackRigs, startRigTracking first\n");
+    std::vector<ctag_rig_pose_rec> rec;
+    std::vector<ctag_pose_cov_rec> cov;
+    rig_records("trackRigs", {poses}, {covs}, filter_rigs_, CTAG_TRACK_MAX_ITEMS, nullptr, rec, cov);
+    std::vector<ctag_track_rec> out(rec.size());
+    const int st = ctag_rig_track_filter(filter_, rec.data(), cov.data(), 1, time, out.data());
+    if (st != CTAG_OK) throw std::string("trackRigs, ") + ctag_strerror(st) + "\n";
+    track.resize(out.size());
+    for (size_t g = 0; g < out.size(); g++) track_info(out[g], track[g]);
+}
+
+void CylinderTag::trackRigs(const std::vector<RigPoseInfo>& poses, const std::vector<PoseCovInfo>& covs, double time, std::vector<TrackInfo>& track) {
+    track_rigs(poses, covs, &time, track);
+}
+
+void CylinderTag::trackRigs(const std::vector<RigPoseInfo>& poses, const std::vector<PoseCovInfo>& covs, std::vector<TrackInfo>& track) {
+    track_rigs(poses, covs, nullptr, track);
+}
+
+void CylinderTag::predictRigs(double time, std::vector<TrackInfo>& track) {
+    track.clear();
+    if (!filter_) throw std::string("predictRigs, startRigTracking first\n");
+    std::vector<ctag_track_rec> out((size_t)filter_rigs_);
+    const int st = ctag_track_filter_predict(filter_, time, out.data());
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    track.resize(out.size());
+    for (size_t g = 0; g < out.size(); g++) track_info(out[g], track[g]);
 }
 
 void CylinderTag::calibrateHandEye(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,

@@ -66,6 +66,8 @@ struct Mat1i {
 struct ctag_handle;
 struct ctag_params;  // include/ctag_types.h: the detector's tunables (the reference's member constants, header/corner_detector.h:90-144)
 struct ctag_track_opts;  // include/ctag_pose.h: the options of smoothRigTrack
+struct ctag_track_filter;       // ... the live filter behind startRigTracking / trackRigs / predictRigs
+struct ctag_track_filter_opts;  // ... and its options
 struct ctag_hand_eye_opts;  // include/ctag_pose.h: the options of calibrateHandEye
 
 // reference: header/corner_detector.h:16-22
@@ -143,6 +145,7 @@ struct TrackInfo {
     int rigID = -1;
     int status = 0;  // CTAG_TRACK_*; the fields below are 0 unless it is CTAG_TRACK_OK or CTAG_TRACK_SINGULAR
     bool measured = false, downweighted = false;
+    bool gated = false, started = false;              // the track filter's flags (trackRigs); false from smoothRigTrack
     double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};  // the smoothed pose, in the frame of the input poses
     double w[3] = {0, 0, 0}, v[3] = {0, 0, 0};        // angular (rad / s) and translational (model units / s) velocity
     double cov[36] = {0};                             // row-major 6x6 of the pose, tangent parametrisation
@@ -295,6 +298,17 @@ class CylinderTag {
                         int nRigs, std::vector<std::vector<TrackInfo>>& track, const std::vector<double>& times = std::vector<double>(),
                         const ctag_track_opts* opts = nullptr);
 
+    // The live counterpart (new; include/ctag_pose.h, track filtering): startRigTracking makes a filter for nRigs rigs (every track EMPTY;
+    // opts: null for the defaults) in place of any earlier one; trackRigs gives it one frame -- poses and covs as one frame's lists of
+    // smoothRigTrack -- at `time` (above the last one given), or without a time at (frames given so far) * opts.dt, and returns
+    // track[g] for every g < nRigs; predictRigs returns the prediction to `time` and leaves the filter as it was; stopRigTracking drops
+    // the filter (the destructor does too).  They throw std::string on error.
+    void startRigTracking(int nRigs, const ctag_track_filter_opts* opts = nullptr);
+    void trackRigs(const std::vector<RigPoseInfo>& poses, const std::vector<PoseCovInfo>& covs, double time, std::vector<TrackInfo>& track);
+    void trackRigs(const std::vector<RigPoseInfo>& poses, const std::vector<PoseCovInfo>& covs, std::vector<TrackInfo>& track);
+    void predictRigs(double time, std::vector<TrackInfo>& track);
+    void stopRigTracking();
+
     // The two fixed transforms between the camera's rig poses and a robot's link poses (new; include/ctag_pose.h,
     // ctag_rig_hand_eye_fit): posesPerFrame and covPerFrame as smoothRigTrack takes them, links[f] the link pose (base <- gripper) of
     // frame f; result[g] is the problem of rig g, for every g < nRigs.  opts: null for the defaults (camera on the link, no loss).
@@ -326,6 +340,9 @@ class CylinderTag {
     int state_rows_ = 0, state_cols_ = 0;
     int featureSize_ = 0;
     ctag_handle* h_ = nullptr;
+    ctag_track_filter* filter_ = nullptr;  // startRigTracking
+    int filter_rigs_ = 0;
+    void track_rigs(const std::vector<RigPoseInfo>& poses, const std::vector<PoseCovInfo>& covs, const double* time, std::vector<TrackInfo>& track);
     AxisImage axis_image_;
 };
 

@@ -1,6 +1,6 @@
 // ctag_loss.h -- Ceres 2.0's stock Huber and Cauchy losses on a squared norm s, stated once for the kernels that minimise under a
-// loss: the robust refit (k_pose_robust.hip, s = a point's squared reprojection residual) and the track smoother (k_track.hip, s = a
-// frame's squared Mahalanobis norm).  Device only.
+// loss: the robust refit (k_pose_robust.hip, s = a point's squared reprojection residual), the track smoother (k_track.hip, s = a
+// frame's squared Mahalanobis norm) and the track filter (k_track_filter.hip, s = the innovation's).  Device only.
 #pragma once
 #include "../../include/ctag_pose.h"
 #include "ctag_math.h"

@@ -1,6 +1,6 @@
 // ctag_so3.h -- SO(3) on 3x3 row-major doubles and the "measured" rule that turns a rig pose record and its covariance record into a
-// sample (R, t, W = cov^-1), stated once for the kernels that consume covariance records: the track smoother (k_track.hip) and the
-// hand-eye fit (k_hand_eye.hip).  Device only.
+// sample (R, t, W = cov^-1), stated once for the kernels that consume covariance records: the track smoother (k_track.hip), the track
+// filter (k_track_filter.hip) and the hand-eye fit (k_hand_eye.hip).  Device only.
 #pragma once
 #include "../../include/ctag_pose.h"
 #include "ctag_linalg.h"
@@ -70,6 +70,31 @@ __device__ __forceinline__ void so3_jlinv(const double* p, double* J) {
     J[5] = 0.5 * p[0] + c * (p[1] * p[2]);
     J[6] = 0.5 * p[1] + c * (p[2] * p[0]);
     J[7] = -0.5 * p[0] + c * (p[2] * p[1]);
+    J[8] = 1.0 + c * (p[2] * p[2] - t2);
+}
+// the left Jacobian of SO(3): Exp(p + d) = Exp(Jl d + O(d^2)) Exp(p), Jl = I + b [p]x + c [p]x^2, b = (1 - cos th) / th^2,
+// c = (th - sin th) / th^3, their series below th^2 = 1e-2 (the closed forms cancel there)
+__device__ __forceinline__ void so3_jl(const double* p, double* J) {
+    const double t2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+    double b, c;
+    if (t2 < 1e-2) {
+        b = 0.5 + t2 * (-1.0 / 24.0 + t2 * (1.0 / 720.0 + t2 * (-1.0 / 40320.0 + t2 * (1.0 / 3628800.0))));
+        c = 1.0 / 6.0 + t2 * (-1.0 / 120.0 + t2 * (1.0 / 5040.0 + t2 * (-1.0 / 362880.0 + t2 * (1.0 / 39916800.0))));
+    } else {
+        const double th = ctm::sqrt64(t2);
+        double sn, cs;
+        ctm::sincos64(th, &sn, &cs);
+        b = (1.0 - cs) / t2;
+        c = (th - sn) / (t2 * th);
+    }
+    J[0] = 1.0 + c * (p[0] * p[0] - t2);
+    J[1] = -b * p[2] + c * (p[0] * p[1]);
+    J[2] = b * p[1] + c * (p[0] * p[2]);
+    J[3] = b * p[2] + c * (p[1] * p[0]);
+    J[4] = 1.0 + c * (p[1] * p[1] - t2);
+    J[5] = -b * p[0] + c * (p[1] * p[2]);
+    J[6] = -b * p[1] + c * (p[2] * p[0]);
+    J[7] = b * p[0] + c * (p[2] * p[1]);
     J[8] = 1.0 + c * (p[2] * p[2] - t2);
 }
 

@@ -565,6 +565,92 @@ int ctag_mv_rig_track_smooth(ctag_handle* h, const ctag_rigs* rigs, const ctag_m
  * marginals and the records, the whole call */
 int ctag_track_last_ms(ctag_handle* h, float* out4);
 
+/* ---- track filtering: the smoother's causal counterpart, one frame at a time (k_track_filter.hip) -----------------------------------------
+ * The smoother needs every frame of a batch; a live caller has the frames up to now.  A ctag_track_filter holds per rig the state of an
+ * extended Kalman filter on (R, t, w, v) under the smoother's model (white noise on acceleration) in device memory between calls.  A
+ * step call takes the n_frames x n_rigs pose and covariance records of the call (record w = f * n_rigs + g, rig and frame fields equal
+ * to their place in THIS call's arrays) in order, from the state the previous call left, and writes n_frames x n_rigs ctag_track_rec;
+ * n_frames = 1 is the live use.  times: a HOST array of n_frames finite, strictly increasing doubles, the first above the last time the
+ * filter was given; it is copied before the call returns.  NULL means t = (frames given since creation or reset + f) * opts.dt.
+ *   1. Measured and bad input are the smoother's rule 1 (the same functions).  cov_f below is the covariance record's matrix read from
+ *      its upper triangle.  If any record of rig g in a call is bad input, every record of rig g of that call is CTAG_TRACK_BAD_INPUT,
+ *      all other fields 0 except rig and frame, and the state of rig g is left exactly as it was.  Other rigs are unaffected.
+ *   2. A track is EMPTY (at creation and after a reset) or TRACKING.  EMPTY and an unmeasured frame: CTAG_TRACK_NOT_TRACKED, every other
+ *      field 0 except rig and frame.  EMPTY and a measured frame starts the track: R = Rm, t = tm, w = v = 0,
+ *      P = blockdiag(cov_f, vel0_sigma_rot^2 I, vel0_sigma_trans^2 I) in the order theta, t, w, v; flags MEASURED | STARTED,
+ *      mahalanobis2 0, weight 1: the smoother's first frame, a measurement plus the velocity prior.
+ *   3. Predict over D = t - t_prev: E = Exp(D w), R- = E R, t- = t + D v, w and v kept.  F has the blocks theta,theta = E,
+ *      theta,w = D Jl(D w) (Jl the left Jacobian of SO(3)), t,t = I, t,v = D I, w,w = v,v = I.  P- = F P F^T + Q; per axis
+ *      Q = q [[D^3 / 3, D^2 / 2], [D^2 / 2, D]] between (theta, w) with q_rot and between (t, v) with q_trans: the inverse of the motion
+ *      term of the smoother's rule 4.
+ *   4. Update at a measured frame: phi = Log(R- Rm^T), e = [phi; t- - tm], H = [Jl^-1(phi) 0 0 0; 0 I 0 0].  S = H P- H^T + cov_f is
+ *      scaled to unit diagonal and factored with pivots above 1e-12; d^2 = e^T S^-1 e.  Gate: gate > 0 and d^2 > gate^2 gives flags
+ *      MEASURED | GATED, weight 0, and the state treats the frame as unmeasured (rule 5).  Otherwise omega = rho'(d^2) of the loss with
+ *      a = loss_scale (ctag_loss.h; 1 without a loss), C = cov_f / omega, K = P- H^T (H P- H^T + C)^-1 (the same factorisation; S itself
+ *      when omega = 1), delta = -K e, R = Exp(delta_theta) R-, the other nine unknowns additive,
+ *      P = (I - K H) P- (I - K H)^T + K C K^T (Joseph form; every entry (a <= b) is computed once and mirrored: P is symmetric bit for
+ *      bit).  DOWNWEIGHTED when omega < 1; mahalanobis2 = d^2, weight = omega.  A factorisation that fails, or a d^2 that is not finite,
+ *      makes the frame CTAG_TRACK_SINGULAR (flags MEASURED, every other field 0 except rig and frame) and the track EMPTY.
+ *   5. An unmeasured or gated frame while TRACKING: the prediction is the result and the new state, status OK, mahalanobis2 0, weight 1
+ *      (unmeasured) or 0 (gated).  On the max_gap-th consecutive such frame the track goes to EMPTY and that frame is
+ *      CTAG_TRACK_NOT_TRACKED (a gated one keeps its flags): measured frames at most max_gap indices apart stay one track, as in the
+ *      smoother's rule 2.
+ *   6. Record: rvec = Log(R), cov the pose block of P, vel_sigma the square roots of the diagonal of its velocity block.
+ *   7. The predict calls give rule 3's prediction to time t (finite, above the last time given) for every rig, n_rigs records with
+ *      frame 0, flags 0, weight 1, and leave the state and the filter's clock untouched.  An EMPTY track gives CTAG_TRACK_NOT_TRACKED.
+ *   8. Deterministic and split-invariant.  Bad input apart, the bytes of a frame's record (the frame field excepted, which counts within
+ *      the call) depend only on that rig's records and times up to that frame: not on how the frames were divided among calls, on g, on
+ *      n_rigs, on the other rigs or on the run.  Every entry has one owner lane and one order of summation; no floating-point atomics.
+ *   9. CTAG_ERR_ARG: a null argument (times and opts excepted), n_frames < 1, a wrong struct_size, an unknown loss, max_gap < 1, dt /
+ *      q_rot / q_trans / vel0_sigma_rot / vel0_sigma_trans / loss_scale that are not positive and finite, a gate that is negative or
+ *      not finite, times that are not finite and strictly increasing, a time that does not exceed the last one the filter was given
+ *      (checked on the host: no device wait), n_frames x n_rigs above CTAG_TRACK_MAX_ITEMS.  A refused call changes nothing.
+ *  10. Device memory: 1320 bytes per rig, owned by the filter; no per-item workspace.  One kernel launch per call, one wavefront a rig. */
+#define CTAG_TRACK_FLAG_GATED 4u      /* rule 4: the measurement was refused by the gate */
+#define CTAG_TRACK_FLAG_STARTED 8u    /* rule 2: the track starts at this frame */
+
+typedef struct ctag_track_filter ctag_track_filter;
+
+typedef struct ctag_track_filter_opts {
+    uint32_t struct_size;    /* filled by ctag_track_filter_opts_default, checked */
+    int32_t loss;            /* CTAG_TRACK_LOSS_NONE (default), CTAG_LOSS_HUBER or CTAG_LOSS_CAUCHY */
+    int32_t max_gap;         /* >= 1; default 5 */
+    int32_t reserved;        /* 0 */
+    double dt;               /* seconds between frames when times == NULL; default 1 / 30 */
+    double q_rot;            /* as ctag_track_opts, the same defaults */
+    double q_trans;
+    double vel0_sigma_rot;
+    double vel0_sigma_trans;
+    double loss_scale;
+    double gate;             /* Mahalanobis norm above which a measurement is refused; 0 = off, the default: on hand-held motion at the default
+                              * q every gate of 3 .. 8 refuses correctly decoded frames (tools/track_filter_study.py) */
+} ctag_track_filter_opts;    /* 72 bytes */
+
+void ctag_track_filter_opts_default(ctag_track_filter_opts* opts);
+/* The rig set only gives n_rigs.  opts == NULL means the defaults.  Several filters may live on one handle; each is freed before the
+ * handle is destroyed.  Every track starts EMPTY. */
+int ctag_track_filter_create(ctag_handle* h, const ctag_rigs* rigs, const ctag_track_filter_opts* opts, ctag_track_filter** filter);
+void ctag_track_filter_free(ctag_track_filter* filter);
+/* every track EMPTY again, the frame count 0 and no last time; enqueued */
+int ctag_track_filter_reset(ctag_track_filter* filter);
+/* Device records in, device records out, enqueued on the handle's stream behind whatever wrote the records; returns without waiting.
+ * (The times of a call of more than one frame are staged in two buffers of the filter's in turn: such a call waits only if the one before
+ * the previous one is still in flight.  A one-frame call never waits.) */
+int ctag_rig_track_filter_device(ctag_track_filter* filter, const ctag_rig_pose_rec* rig_poses_dev, const ctag_pose_cov_rec* cov_dev, int n_frames,
+                                 const double* times, ctag_track_rec* out_dev);
+int ctag_mv_rig_track_filter_device(ctag_track_filter* filter, const ctag_mv_pose_rec* mv_poses_dev, const ctag_pose_cov_rec* cov_dev, int n_frames,
+                                    const double* times, ctag_track_rec* out_dev);
+/* The same with HOST arrays in and out; they wait for completion. */
+int ctag_rig_track_filter(ctag_track_filter* filter, const ctag_rig_pose_rec* rig_poses, const ctag_pose_cov_rec* cov, int n_frames, const double* times,
+                          ctag_track_rec* out);
+int ctag_mv_rig_track_filter(ctag_track_filter* filter, const ctag_mv_pose_rec* mv_poses, const ctag_pose_cov_rec* cov, int n_frames, const double* times,
+                             ctag_track_rec* out);
+/* rule 7: n_rigs records to out_dev (enqueued) / to out (waits) */
+int ctag_track_filter_predict_device(ctag_track_filter* filter, double t, ctag_track_rec* out_dev);
+int ctag_track_filter_predict(ctag_track_filter* filter, double t, ctag_track_rec* out);
+/* device time of the filter's last step call's kernel (needs CTAG_OPT_TIMING), milliseconds */
+int ctag_track_filter_last_ms(ctag_track_filter* filter, float* out1);
+
 /* ---- hand-eye calibration: the two fixed transforms between the camera's poses and a robot's link poses (k_hand_eye.hip) -----------------
  * Every pose above lives in the camera's (or the reference) frame.  A robot, stage or tracked arm reports a link pose per frame; this call
  * takes the n_frames x n_rigs rig pose records of a batch (record w = f * n_rigs + g, either record kind, as the smoother takes them) with
