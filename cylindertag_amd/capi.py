@@ -38,7 +38,10 @@ POSE_EXPORTS = ["ctag_model_load", "ctag_model_create", "ctag_model_free", "ctag
                 "ctag_mv_rig_track_smooth", "ctag_track_last_ms",
                 "ctag_track_filter_opts_default", "ctag_track_filter_create", "ctag_track_filter_free", "ctag_track_filter_reset",
                 "ctag_rig_track_filter_device", "ctag_mv_rig_track_filter_device", "ctag_rig_track_filter", "ctag_mv_rig_track_filter",
-                "ctag_track_filter_predict_device", "ctag_track_filter_predict", "ctag_track_filter_last_ms",
+                "ctag_track_filter_predict_device", "ctag_track_filter_predict", "ctag_track_filter_last_ms", "ctag_track_filter_set_cov_scale",
+                "ctag_track_noise_opts_default", "ctag_rig_track_noise_fit_device", "ctag_mv_rig_track_noise_fit_device", "ctag_rig_track_noise_fit",
+                "ctag_mv_rig_track_noise_fit", "ctag_rig_track_noise_score_device", "ctag_mv_rig_track_noise_score_device",
+                "ctag_rig_track_noise_score", "ctag_mv_rig_track_noise_score", "ctag_track_noise_last_ms",
                 "ctag_hand_eye_opts_default", "ctag_rig_hand_eye_fit_device", "ctag_mv_rig_hand_eye_fit_device", "ctag_rig_hand_eye_fit",
                 "ctag_mv_rig_hand_eye_fit", "ctag_hand_eye_last_ms",
                 "ctag_model_fit_opts_default", "ctag_model_fit_device", "ctag_model_fit", "ctag_model_save", "ctag_model_fit_last_ms",
@@ -97,6 +100,20 @@ TRACK_OK, TRACK_NOT_TRACKED, TRACK_BAD_INPUT, TRACK_SINGULAR = range(4)
 TRACK_LOSS_NONE = 2
 TRACK_MAX_ITEMS = 65536
 TRACK_FLAG_MEASURED, TRACK_FLAG_DOWNWEIGHTED, TRACK_FLAG_GATED, TRACK_FLAG_STARTED = 1, 2, 4, 8
+# ctag_track_noise_rec / _round / _score: the track noise fit's result, trace row and score entry (include/ctag_pose.h)
+TRACK_NOISE_DT = np.dtype([("status", "<i4"), ("rig", "<i4"), ("n_terms", "<i4"), ("n_free", "<i4"), ("rounds", "<i4"), ("flags", "<u4"),
+                           ("q_rot", "<f8"), ("q_trans", "<f8"), ("cov_scale", "<f8"), ("log2_sigma", "<f8", (3,)), ("score", "<f8"),
+                           ("score_start", "<f8"), ("mean_m2", "<f8")])
+assert TRACK_NOISE_DT.itemsize == 96
+TRACK_NOISE_ROUND_DT = np.dtype([("u", "<f8", (3,)), ("value", "<f8", (3,)), ("L", "<f8"), ("winner", "<i4"), ("reserved", "<i4")])
+assert TRACK_NOISE_ROUND_DT.itemsize == 64
+TRACK_NOISE_SCORE_DT = np.dtype([("L", "<f8"), ("sum_m2", "<f8"), ("n_terms", "<i4"), ("n_singular", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+assert TRACK_NOISE_SCORE_DT.itemsize == 32
+NOISE_OK, NOISE_BAD_INPUT, NOISE_TOO_FEW, NOISE_SINGULAR = range(4)
+NOISE_PER_RIG, NOISE_POOLED = 0, 1
+NOISE_FREE_Q_ROT, NOISE_FREE_Q_TRANS, NOISE_FREE_COV_SCALE = 1, 2, 4
+NOISE_FLAG_EDGE = 1
+NOISE_MAX_SCORE_CAND = 64
 # ctag_link_pose / ctag_hand_eye_rec / ctag_hand_eye_frame_rec: a link pose per frame in, one record per rig and one per (frame, rig) out of a
 # hand-eye calibration (include/ctag_pose.h)
 LINK_POSE_DT = np.dtype([("rvec", "<f8", (3,)), ("tvec", "<f8", (3,))])
@@ -245,6 +262,37 @@ def track_filter_opts(**fields):
         else:
             raise TypeError("ctag_track_filter_opts has no field %r" % k)
     return o
+
+
+class TrackNoiseOptsC(C.Structure):  # ctag_track_noise_opts
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("free_mask", C.c_int32), ("rounds", C.c_int32), ("max_gap", C.c_int32),
+                ("min_terms", C.c_int32), ("dt", C.c_double), ("q_rot", C.c_double), ("q_trans", C.c_double), ("cov_scale", C.c_double),
+                ("vel0_sigma_rot", C.c_double), ("vel0_sigma_trans", C.c_double), ("span", C.c_double)]
+
+
+def track_noise_opts(**fields):
+    """ctag_track_noise_opts_default, then the given fields."""
+    o = TrackNoiseOptsC()
+    load_library().ctag_track_noise_opts_default(C.byref(o))
+    for k, v in fields.items():
+        if k in ("mode", "free_mask", "rounds", "max_gap", "min_terms", "struct_size"):
+            setattr(o, k, int(v))
+        elif k in ("dt", "q_rot", "q_trans", "cov_scale", "vel0_sigma_rot", "vel0_sigma_trans", "span"):
+            setattr(o, k, float(v))
+        else:
+            raise TypeError("ctag_track_noise_opts has no field %r" % k)
+    return o
+
+
+def apply_track_noise(rec, **over):
+    """A fitted TRACK_NOISE_DT record -> (track_filter_opts with its q_rot and q_trans and the fields of `over`, cov_scale): the options to
+    create a filter with and the scale to give its set_cov_scale."""
+    rec = np.asarray(rec, TRACK_NOISE_DT).reshape(-1)
+    if len(rec) != 1:
+        raise ValueError("apply_track_noise: one record, got %d" % len(rec))
+    fields = dict(q_rot=float(rec["q_rot"][0]), q_trans=float(rec["q_trans"][0]))
+    fields.update(over)
+    return track_filter_opts(**fields), float(rec["cov_scale"][0])
 
 
 class HandEyeOptsC(C.Structure):  # ctag_hand_eye_opts
@@ -520,6 +568,19 @@ def load_library():
         fn.argtypes = [vp, C.c_double, vp]
     L.ctag_track_filter_last_ms.restype = C.c_int
     L.ctag_track_filter_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ctag_track_filter_set_cov_scale.restype = C.c_int
+    L.ctag_track_filter_set_cov_scale.argtypes = [vp, C.c_double]
+    tnp = C.POINTER(TrackNoiseOptsC)
+    L.ctag_track_noise_opts_default.restype = None
+    L.ctag_track_noise_opts_default.argtypes = [tnp]
+    for fn in (L.ctag_rig_track_noise_fit_device, L.ctag_mv_rig_track_noise_fit_device, L.ctag_rig_track_noise_fit, L.ctag_mv_rig_track_noise_fit):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, vp, vp, C.c_int, vp, tnp, vp, vp]
+    for fn in (L.ctag_rig_track_noise_score_device, L.ctag_mv_rig_track_noise_score_device, L.ctag_rig_track_noise_score, L.ctag_mv_rig_track_noise_score):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, vp, vp, C.c_int, vp, tnp, vp, C.c_int, vp]
+    L.ctag_track_noise_last_ms.restype = C.c_int
+    L.ctag_track_noise_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     hep = C.POINTER(HandEyeOptsC)
     L.ctag_hand_eye_opts_default.restype = None
     L.ctag_hand_eye_opts_default.argtypes = [hep]
@@ -913,6 +974,12 @@ class TrackFilter:
         st = self.L.ctag_track_filter_reset(self.f)
         if st != 0:
             raise CtagError(st, "ctag_track_filter_reset")
+
+    def set_cov_scale(self, s):
+        """From the next call on every covariance is read as s * cov (ctag_track_filter_set_cov_scale); s positive and finite."""
+        st = self.L.ctag_track_filter_set_cov_scale(self.f, float(s))
+        if st != 0:
+            raise CtagError(st, "ctag_track_filter_set_cov_scale")
 
     def track_filter_last_ms(self):
         """Device milliseconds of the last step call's kernel (needs OPT_TIMING)."""
@@ -1370,6 +1437,109 @@ class Detector:
             self._filters = []
         self._filters.append(f)
         return f
+
+    # ---- track noise fit (include/ctag_pose.h): opts is a TrackNoiseOptsC (track_noise_opts(...)) or None for the defaults
+    @staticmethod
+    def _noise_inputs(name, rec_dt, rigs, poses, cov, n_frames, times):
+        n = n_frames * rigs.n_rigs
+        poses = np.ascontiguousarray(poses, rec_dt).reshape(-1)
+        cov = np.ascontiguousarray(cov, POSE_COV_DT).reshape(-1)
+        if len(poses) != n or len(cov) != n:
+            raise ValueError("%s: %d pose and %d covariance records for %d frames x %d rigs" % (name, len(poses), len(cov), n_frames, rigs.n_rigs))
+        return poses, cov, Detector._noise_times(name, times, n_frames)
+
+    @staticmethod
+    def _noise_times(name, times, n_frames):
+        t = None if times is None else np.ascontiguousarray(times, np.float64).reshape(-1)
+        if t is not None and len(t) != n_frames:
+            raise ValueError("%s: %d times for %d frames" % (name, len(t), n_frames))
+        return t
+
+    @staticmethod
+    def _noise_searches(rigs, opts):
+        o = opts if opts is not None else track_noise_opts()
+        return (1 if o.mode == NOISE_POOLED else rigs.n_rigs), max(int(o.rounds), 1)
+
+    def _fit_noise(self, fn, name, rec_dt, rigs, poses, cov, n_frames, times, opts, trace):
+        poses, cov, t = self._noise_inputs(name, rec_dt, rigs, poses, cov, n_frames, times)
+        ns, rounds = self._noise_searches(rigs, opts)
+        out = np.zeros(ns, TRACK_NOISE_DT)
+        tr = np.zeros(ns * min(rounds, 16), TRACK_NOISE_ROUND_DT) if trace else None
+        st = fn(self.h, rigs.r, poses.ctypes.data, cov.ctypes.data, n_frames, None if t is None else t.ctypes.data, self._optp(opts),
+                out.ctypes.data, None if tr is None else tr.ctypes.data)
+        if st != 0:
+            raise CtagError(st, name)
+        return (out, tr.reshape(ns, -1)) if trace else out
+
+    def fit_track_noise(self, rigs, rig_poses, cov, n_frames, times=None, opts=None, trace=False):
+        """The filter's q_rot, q_trans and covariance scale from n_frames x rigs.n_rigs host RIG_POSE_DT records with their POSE_COV_DT
+        records -> TRACK_NOISE_DT [n_rigs] (per rig) or [1] (pooled); with trace=True also TRACK_NOISE_ROUND_DT [searches, rounds].  Waits."""
+        return self._fit_noise(self.L.ctag_rig_track_noise_fit, "ctag_rig_track_noise_fit", RIG_POSE_DT, rigs, rig_poses, cov, n_frames, times, opts, trace)
+
+    def fit_mv_track_noise(self, rigs, mv_poses, cov, n_frames, times=None, opts=None, trace=False):
+        """The same from MV_POSE_DT records."""
+        return self._fit_noise(self.L.ctag_mv_rig_track_noise_fit, "ctag_mv_rig_track_noise_fit", MV_POSE_DT, rigs, mv_poses, cov, n_frames, times, opts, trace)
+
+    def _fit_noise_device(self, fn, name, rigs, poses_ptr, cov_ptr, n_frames, times, opts, out_ptr, trace_ptr):
+        t = self._noise_times(name, times, n_frames)
+        st = fn(self.h, rigs.r, poses_ptr, cov_ptr, n_frames, None if t is None else t.ctypes.data, self._optp(opts), out_ptr, trace_ptr)
+        if st != 0:
+            raise CtagError(st, name)
+
+    def fit_track_noise_device(self, rigs, rig_poses_ptr, cov_ptr, n_frames, out_ptr, trace_ptr=None, times=None, opts=None):
+        """Device RIG_POSE_DT / POSE_COV_DT records -> device TRACK_NOISE_DT records at out_ptr and, when trace_ptr is given, the trace; enqueued."""
+        self._fit_noise_device(self.L.ctag_rig_track_noise_fit_device, "ctag_rig_track_noise_fit_device", rigs, rig_poses_ptr, cov_ptr, n_frames, times, opts,
+                               out_ptr, trace_ptr)
+
+    def fit_mv_track_noise_device(self, rigs, mv_poses_ptr, cov_ptr, n_frames, out_ptr, trace_ptr=None, times=None, opts=None):
+        """The same from device MV_POSE_DT records."""
+        self._fit_noise_device(self.L.ctag_mv_rig_track_noise_fit_device, "ctag_mv_rig_track_noise_fit_device", rigs, mv_poses_ptr, cov_ptr, n_frames, times,
+                               opts, out_ptr, trace_ptr)
+
+    @staticmethod
+    def _noise_cands(name, cands):
+        c = np.ascontiguousarray(cands, np.float64).reshape(-1, 3)
+        return c
+
+    def _score_noise(self, fn, name, rec_dt, rigs, poses, cov, n_frames, cands, times, opts):
+        poses, cov, t = self._noise_inputs(name, rec_dt, rigs, poses, cov, n_frames, times)
+        c = self._noise_cands(name, cands)
+        out = np.zeros(max(len(c), 1) * rigs.n_rigs, TRACK_NOISE_SCORE_DT)
+        st = fn(self.h, rigs.r, poses.ctypes.data, cov.ctypes.data, n_frames, None if t is None else t.ctypes.data, self._optp(opts),
+                c.ctypes.data, len(c), out.ctypes.data)
+        if st != 0:
+            raise CtagError(st, name)
+        return out[:len(c) * rigs.n_rigs].reshape(len(c), rigs.n_rigs)
+
+    def score_track_noise(self, rigs, rig_poses, cov, n_frames, cands, times=None, opts=None):
+        """The score alone at cands [n_cand, 3] = (q_rot, q_trans, cov_scale) -> TRACK_NOISE_SCORE_DT [n_cand, n_rigs].  Waits."""
+        return self._score_noise(self.L.ctag_rig_track_noise_score, "ctag_rig_track_noise_score", RIG_POSE_DT, rigs, rig_poses, cov, n_frames, cands, times, opts)
+
+    def score_mv_track_noise(self, rigs, mv_poses, cov, n_frames, cands, times=None, opts=None):
+        """The same from MV_POSE_DT records."""
+        return self._score_noise(self.L.ctag_mv_rig_track_noise_score, "ctag_mv_rig_track_noise_score", MV_POSE_DT, rigs, mv_poses, cov, n_frames, cands, times, opts)
+
+    def _score_noise_device(self, fn, name, rigs, poses_ptr, cov_ptr, n_frames, cands, times, opts, out_ptr):
+        t = self._noise_times(name, times, n_frames)
+        c = self._noise_cands(name, cands)
+        st = fn(self.h, rigs.r, poses_ptr, cov_ptr, n_frames, None if t is None else t.ctypes.data, self._optp(opts), c.ctypes.data, len(c), out_ptr)
+        if st != 0:
+            raise CtagError(st, name)
+
+    def score_track_noise_device(self, rigs, rig_poses_ptr, cov_ptr, n_frames, cands, out_ptr, times=None, opts=None):
+        """Device records in, n_cand * n_rigs device TRACK_NOISE_SCORE_DT entries at out_ptr; enqueued."""
+        self._score_noise_device(self.L.ctag_rig_track_noise_score_device, "ctag_rig_track_noise_score_device", rigs, rig_poses_ptr, cov_ptr, n_frames, cands,
+                                 times, opts, out_ptr)
+
+    def score_mv_track_noise_device(self, rigs, mv_poses_ptr, cov_ptr, n_frames, cands, out_ptr, times=None, opts=None):
+        self._score_noise_device(self.L.ctag_mv_rig_track_noise_score_device, "ctag_mv_rig_track_noise_score_device", rigs, mv_poses_ptr, cov_ptr, n_frames,
+                                 cands, times, opts, out_ptr)
+
+    def track_noise_last_ms(self):
+        """Device milliseconds of the last noise call's kernels (needs OPT_TIMING)."""
+        out = C.c_float()
+        self.L.ctag_track_noise_last_ms(self.h, C.byref(out))
+        return float(out.value)
 
     # ---- hand-eye calibration (include/ctag_pose.h): opts is a HandEyeOptsC (hand_eye_opts(...)) or None for the defaults
     @staticmethod

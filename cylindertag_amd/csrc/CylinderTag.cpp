@@ -832,6 +832,54 @@ void CylinderTag::startRigTracking(int nRigs, const ctag_track_filter_opts* opts
     filter_rigs_ = nRigs;
 }
 
+void CylinderTag::startRigTracking(int nRigs, const TrackNoiseInfo& noise, const ctag_track_filter_opts* opts) {
+    ctag_track_filter_opts o;
+    ctag_track_filter_opts_default(&o);
+    if (opts) o = *opts;
+    o.q_rot = noise.qRot;
+    o.q_trans = noise.qTrans;
+    startRigTracking(nRigs, &o);
+    const int st = ctag_track_filter_set_cov_scale(filter_, noise.covScale);
+    if (st != CTAG_OK) {
+        stopRigTracking();
+        throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    }
+}
+
+void CylinderTag::calibrateTrackNoise(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,
+                                      int nRigs, std::vector<TrackNoiseInfo>& result, const std::vector<double>& times, const ctag_track_noise_opts* opts) {
+    result.clear();
+    std::vector<ctag_rig_pose_rec> rec;
+    std::vector<ctag_pose_cov_rec> cov;
+    rig_records("calibrateTrackNoise", posesPerFrame, covPerFrame, nRigs, CTAG_TRACK_MAX_ITEMS, &times, rec, cov);
+    const size_t n_frames = posesPerFrame.size();
+    CountRigs set(nRigs);
+    int st = set.status;
+    const size_t n_search = opts && opts->mode == CTAG_NOISE_POOLED ? 1 : (size_t)nRigs;
+    std::vector<ctag_track_noise_rec> out(n_search);
+    if (st == CTAG_OK)
+        st = ctag_rig_track_noise_fit(h_, set.rigs, rec.data(), cov.data(), (int)n_frames, times.empty() ? nullptr : times.data(), opts, out.data(), nullptr);
+    if (st != CTAG_OK) throw __FUNCTION__ + std::string(", ") + ctag_strerror(st) + "\n";
+    result.resize(n_search);
+    for (size_t q = 0; q < n_search; q++) {
+        const ctag_track_noise_rec& r = out[q];
+        TrackNoiseInfo& ni = result[q];
+        ni.rigID = r.rig;
+        ni.status = r.status;
+        ni.nTerms = r.n_terms;
+        ni.nFree = r.n_free;
+        ni.rounds = r.rounds;
+        ni.flags = r.flags;
+        ni.qRot = r.q_rot;
+        ni.qTrans = r.q_trans;
+        ni.covScale = r.cov_scale;
+        for (int k = 0; k < 3; k++) ni.log2Sigma[k] = r.log2_sigma[k];
+        ni.score = r.score;
+        ni.scoreStart = r.score_start;
+        ni.meanM2 = r.mean_m2;
+    }
+}
+
 void CylinderTag::track_rigs(const std::vector<RigPoseInfo>& poses, const std::vector<PoseCovInfo>& covs, const double* time, std::vector<TrackInfo>& track) {
     track.clear();
     if (!filter_) throw std::string("trackRigs, startRigTracking first\n");

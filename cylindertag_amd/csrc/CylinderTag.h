@@ -68,6 +68,7 @@ struct ctag_params;  // include/ctag_types.h: the detector's tunables (the refer
 struct ctag_track_opts;  // include/ctag_pose.h: the options of smoothRigTrack
 struct ctag_track_filter;       // ... the live filter behind startRigTracking / trackRigs / predictRigs
 struct ctag_track_filter_opts;  // ... and its options
+struct ctag_track_noise_opts;   // ... the options of calibrateTrackNoise
 struct ctag_hand_eye_opts;  // include/ctag_pose.h: the options of calibrateHandEye
 
 // reference: header/corner_detector.h:16-22
@@ -151,6 +152,16 @@ struct TrackInfo {
     double cov[36] = {0};                             // row-major 6x6 of the pose, tangent parametrisation
     double velSigma[6] = {0};
     double mahalanobis2 = 0, weight = 0;
+};
+// the filter's noise levels fitted from a recorded track (new): the fields of ctag_track_noise_rec (include/ctag_pose.h, track noise fit)
+struct TrackNoiseInfo {
+    int rigID = -1;    // -1 for the pooled search
+    int status = 0;    // CTAG_NOISE_*
+    int nTerms = 0, nFree = 0, rounds = 0;
+    unsigned flags = 0;  // CTAG_NOISE_FLAG_EDGE << axis
+    double qRot = 0, qTrans = 0, covScale = 1;
+    double log2Sigma[3] = {0, 0, 0};
+    double score = 0, scoreStart = 0, meanM2 = 0;
 };
 // a robot's link pose in one frame, base <- gripper (new): X_out = R(rvec) X_in + tvec; a non-finite entry drops the frame
 struct LinkPose {
@@ -304,10 +315,20 @@ class CylinderTag {
     // track[g] for every g < nRigs; predictRigs returns the prediction to `time` and leaves the filter as it was; stopRigTracking drops
     // the filter (the destructor does too).  They throw std::string on error.
     void startRigTracking(int nRigs, const ctag_track_filter_opts* opts = nullptr);
+    // ... with the noise levels calibrateTrackNoise fitted: opts (null for the defaults) with q_rot and q_trans replaced by the fitted ones,
+    // and the filter reads every covariance as noise.covScale times it (ctag_track_filter_set_cov_scale)
+    void startRigTracking(int nRigs, const TrackNoiseInfo& noise, const ctag_track_filter_opts* opts = nullptr);
     void trackRigs(const std::vector<RigPoseInfo>& poses, const std::vector<PoseCovInfo>& covs, double time, std::vector<TrackInfo>& track);
     void trackRigs(const std::vector<RigPoseInfo>& poses, const std::vector<PoseCovInfo>& covs, std::vector<TrackInfo>& track);
     void predictRigs(double time, std::vector<TrackInfo>& track);
     void stopRigTracking();
+
+    // The filter's q_rot, q_trans and covariance scale from a recorded track (new; include/ctag_pose.h, ctag_rig_track_noise_fit):
+    // posesPerFrame, covPerFrame and times as smoothRigTrack takes them.  result holds one entry per rig (CTAG_NOISE_PER_RIG) or one with
+    // rigID -1 (CTAG_NOISE_POOLED); opts: null for the defaults.  Throws std::string on error.
+    void calibrateTrackNoise(const std::vector<std::vector<RigPoseInfo>>& posesPerFrame, const std::vector<std::vector<PoseCovInfo>>& covPerFrame,
+                             int nRigs, std::vector<TrackNoiseInfo>& result, const std::vector<double>& times = std::vector<double>(),
+                             const ctag_track_noise_opts* opts = nullptr);
 
     // The two fixed transforms between the camera's rig poses and a robot's link poses (new; include/ctag_pose.h,
     // ctag_rig_hand_eye_fit): posesPerFrame and covPerFrame as smoothRigTrack takes them, links[f] the link pose (base <- gripper) of

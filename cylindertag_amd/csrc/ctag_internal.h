@@ -386,7 +386,7 @@ void build_pick_table(uint8_t* table, uint16_t* table16);  // kPickN*20*10 bytes
 
 // accessor of the opaque handle for the state of its back ends, each created on first use: the pose back end (k_pose.hip), the overlay (k_draw.hip),
 // the rig poses (k_rig_pose.hip), the multi-GPU gather layer (ctag_gather.hip), the multi-view rig poses (k_mv_pose.hip), the pose covariance (k_pose_cov.hip), the model reconstruction (k_model_fit.hip) the rig assembly (k_rig_fit.hip), the camera set fit (k_cam_fit.hip) and the intrinsics fit (k_intr_fit.hip), whose states are each a fit::Timed of ctag_fit_host.h, and the robust refit (k_pose_robust.hip).  ctag_destroy frees them in this order.
-enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kCovState, kFitState, kRigFitState, kCamFitState, kIntrFitState, kRobustState, kTrackState, kHandEyeState, kNumSiblingStates };
+enum SiblingState { kPoseState, kDrawState, kRigState, kGatherState, kMvState, kCovState, kFitState, kRigFitState, kCamFitState, kIntrFitState, kRobustState, kTrackState, kHandEyeState, kTrackNoiseState, kNumSiblingStates };
 void** handle_state_slot(struct ::ctag_handle* h, SiblingState which, void (*free_fn)(void*));
 // the model's device copies on `device` (k_pose.hip); the camera's distortion model is one the pose back end handles
 int model_to_device(struct ::ctag_model* m, int device);

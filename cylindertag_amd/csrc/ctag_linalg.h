@@ -349,7 +349,9 @@ CTM_HD bool chol6_solve(double* H, const double* g, double* x) {
 // above min_allowed (or is not a number).
 // chol6_inverse_factor: the same, and with Linv the lower triangle of L^-1 (row-major 6x6, the upper triangle 0) is returned too:
 // inv = Linv^T Linv.
-CTM_HD bool chol6_inverse_factor(const double* C, double* inv, double* Linv, double min_allowed, double& min_pivot) {
+// chol6_inverse_factor_diag: the same, and with Ldiag the six diagonal entries of L (the square roots of the pivots) are returned too:
+// log det C = 2 sum_j log Ldiag[j].  Linv and Ldiag may each be null; neither changes any other result.
+CTM_HD bool chol6_inverse_factor_diag(const double* C, double* inv, double* Linv, double min_allowed, double& min_pivot, double* Ldiag) {
     constexpr int N = 6;
     double L[36], W[36];
     min_pivot = C[0];
@@ -397,7 +399,15 @@ CTL_UNROLL
 CTL_UNROLL
             for (int b = 0; b < N; b++) Linv[a * N + b] = b <= a ? W[a * N + b] : 0.0;
     }
+    if (Ldiag) {
+CTL_UNROLL
+        for (int j = 0; j < N; j++) Ldiag[j] = L[j * N + j];
+    }
     return true;
+}
+
+CTM_HD bool chol6_inverse_factor(const double* C, double* inv, double* Linv, double min_allowed, double& min_pivot) {
+    return chol6_inverse_factor_diag(C, inv, Linv, min_allowed, min_pivot, nullptr);
 }
 
 CTM_HD bool chol6_inverse(const double* C, double* inv, double min_allowed, double& min_pivot) {

@@ -623,7 +623,8 @@ typedef struct ctag_track_filter_opts {
     double vel0_sigma_trans;
     double loss_scale;
     double gate;             /* Mahalanobis norm above which a measurement is refused; 0 = off, the default: on hand-held motion at the default
-                              * q every gate of 3 .. 8 refuses correctly decoded frames (tools/track_filter_study.py) */
+                              * q every gate of 3 .. 8 refuses correctly decoded frames (tools/track_filter_study.py).
+                              * The track noise fit below gives the q and the covariance scale of a recorded track, with which a gate is meant to be used. */
 } ctag_track_filter_opts;    /* 72 bytes */
 
 void ctag_track_filter_opts_default(ctag_track_filter_opts* opts);
@@ -650,6 +651,152 @@ int ctag_track_filter_predict_device(ctag_track_filter* filter, double t, ctag_t
 int ctag_track_filter_predict(ctag_track_filter* filter, double t, ctag_track_rec* out);
 /* device time of the filter's last step call's kernel (needs CTAG_OPT_TIMING), milliseconds */
 int ctag_track_filter_last_ms(ctag_track_filter* filter, float* out1);
+/* From the next call on the filter reads every cov_f (rules 2 and 4) as s * cov_f; rule 1 still judges cov_f itself.  s must be positive and
+ * finite, else CTAG_ERR_ARG and nothing changes.  The default is 1, and x * 1.0 is exact: a filter that never calls this produces the
+ * bytes it always produced.  The scale is what the track noise fit below returns as cov_scale. */
+int ctag_track_filter_set_cov_scale(ctag_track_filter* filter, double s);
+
+/* ---- track noise fit: the filter's two process-noise densities and the covariance scale from a recorded track (k_track_noise.hip) ---------
+ * The smoother and the filter take q_rot and q_trans from the caller and trust the covariance records' scale.  This call fits the three
+ * numbers from a recorded batch by maximum likelihood on the filter's own innovations.  The batch has the filter's layout (record
+ * w = f * n_rigs + g, rig and frame fields equal to their place; times a HOST array of n_frames finite, strictly increasing doubles, copied
+ * before the call returns, or NULL for t = f * opts.dt).  A candidate is theta = (q_rot, q_trans, s).
+ *   1. Measured and bad input are the filter's rule 1 (the same functions, on cov_f itself).  A rig with a bad record is
+ *      CTAG_NOISE_BAD_INPUT: its score entries are 0 apart from the status.
+ *   2. The score L_g(theta) of rig g: run the filter's rules 2-5 from an EMPTY track over all frames in order, with no loss and no gate,
+ *      the call's max_gap, vel0_sigma_rot and vel0_sigma_trans, q_rot and q_trans from theta, and every cov_f replaced by s * cov_f (at
+ *      the start of a track, rule 2, as well as in rule 4).  At every rule-4 update add l_f = log det S_f + d^2_f, S_f = H P- H^T + s cov_f
+ *      and d^2 rule 4's; log det S_f comes from rule 4's factorisation: sum_a log S_aa + 2 sum_j log L_jj, L the Cholesky factor of the
+ *      unit-diagonal matrix (ctag_math.h's log64).  The sum runs in frame order and has one owner.  Beside L: n_terms, the number of
+ *      updates; sum_m2, the sum of d^2; n_singular, the frames where rule 4 gives CTAG_TRACK_SINGULAR (such a frame empties the track as
+ *      in the filter and adds nothing to the sums).
+ *   3. The fit minimises L over the parameters named in free_mask; the others stay at their start values opts.q_rot, opts.q_trans,
+ *      opts.cov_scale.  CTAG_NOISE_PER_RIG: n_rigs independent searches on L_g and n_rigs result records.  CTAG_NOISE_POOLED: one search on
+ *      the sum of L_g (and of n_terms, sum_m2, n_singular) over the rigs that are not bad input, in rig order, and one record with rig -1;
+ *      CTAG_NOISE_BAD_INPUT when every rig is.
+ *   4. The search is a grid search in u = log2(value / start) per free axis, decided on the device, centre u = 0 at first.  Round
+ *      r = 0 .. rounds - 1 evaluates 5 points per free axis, u = u_centre + k h_r for k = -2 .. 2 with h_r = span / 2^(r+1): 1, 5, 25 or
+ *      125 candidates.  Candidate c has k_j = (c / 5^j) % 5 - 2 on the j-th free axis (axes in the order q_rot, q_trans, cov_scale; the
+ *      first free axis is the lowest digit), value = start * exp64(u * ln 2).
+ *   5. A candidate with n_singular > 0 is disqualified.  The round's winner is the smallest L, ties to the lowest index; it is the next
+ *      centre.  The previous centre is among the candidates (all k_j = 0), so L never rises from round to round.
+ *   6. Status.  CTAG_NOISE_BAD_INPUT (rule 1, rule 3): the start values, rounds 0, every other number 0.  CTAG_NOISE_TOO_FEW: n_terms at the start values (round 0's centre) is below min_terms; the values returned are the start
+ *      values, score = score_start, n_terms and mean_m2 those of the start values, rounds 1.  CTAG_NOISE_SINGULAR: every candidate of
+ *      some round was disqualified; the values returned are that round's centre, rounds counts that round, score, n_terms and mean_m2 are 0.
+ *   7. Result, a ctag_track_noise_rec, when the status is CTAG_NOISE_OK: the last round's winner's values, score = L and n_terms there,
+ *      mean_m2 = sum_m2 / n_terms (about 6 when the filter is consistent), score_start = L at the start values, rounds = opts.rounds.
+ *      flags: CTAG_NOISE_FLAG_EDGE << axis when the last round's winner lies at k = -2 or 2 on that axis.  log2_sigma[axis]: from the last
+ *      round's grid, c = ((L+ - 2 L0) + L-) / h^2 along the axis through the winner, sigma = sqrt(2 / c) in octaves; 0 where the axis is
+ *      fixed, the winner is at an edge, a neighbour was disqualified or c <= 0.
+ *   8. Trace (optional, NULL allowed): rounds records per search, ctag_track_noise_round, row search * rounds + r: the winner's u and
+ *      value, its L and its index; a round that was not evaluated, or had no winner, has winner -1 and every other field 0.
+ *   9. Deterministic: the bytes of a per-rig record depend only on that rig's records, the times and the options (not on g apart from
+ *      the rig field, on n_rigs or on the other rigs); the pooled search of a one-rig batch gives the per-rig bytes apart from rig.
+ *  10. CTAG_ERR_ARG: the filter's rule-9 cases (null argument, times and opts and trace excepted; n_frames < 1; struct_size; max_gap < 1;
+ *      dt, q_rot, q_trans, cov_scale, vel0_sigma_rot, vel0_sigma_trans not positive and finite; times not finite and strictly increasing;
+ *      n_frames x n_rigs above CTAG_TRACK_MAX_ITEMS), an unknown mode, a free_mask outside 0 .. 7, rounds outside 1 .. 16, min_terms < 1,
+ *      a span that is not positive and finite, n_cand outside 1 .. CTAG_NOISE_MAX_SCORE_CAND or a candidate value that is not positive
+ *      and finite in a score call.  A free_mask of 0 is legal: one candidate, and the record carries the scores of the start values.
+ *  11. One wavefront per (candidate, rig) item: k_track_noise walks the frames as the filter does and keeps four sums; one small launch
+ *      per round (k_track_noise_select) makes the pooled sums and the argmin and writes the next candidates.  Nothing waits on the host.
+ * Using the result.  The filter: q_rot and q_trans into ctag_track_filter_opts, cov_scale through ctag_track_filter_set_cov_scale; then a
+ * gate is usable.  The smoother has no scale of its own and needs none: its poses depend only on q / s, so a caller
+ * passes q_rot / s and q_trans / s in ctag_track_opts and multiplies the returned cov by s and vel_sigma by sqrt(s). */
+#define CTAG_NOISE_OK 0
+#define CTAG_NOISE_BAD_INPUT 1
+#define CTAG_NOISE_TOO_FEW 2
+#define CTAG_NOISE_SINGULAR 3
+
+#define CTAG_NOISE_PER_RIG 0
+#define CTAG_NOISE_POOLED 1
+
+#define CTAG_NOISE_FREE_Q_ROT 1
+#define CTAG_NOISE_FREE_Q_TRANS 2
+#define CTAG_NOISE_FREE_COV_SCALE 4
+
+#define CTAG_NOISE_FLAG_EDGE 1u          /* << axis: 0 q_rot, 1 q_trans, 2 cov_scale */
+#define CTAG_NOISE_MAX_SCORE_CAND 64     /* candidates of one score call */
+
+typedef struct ctag_track_noise_opts {
+    uint32_t struct_size;    /* filled by ctag_track_noise_opts_default, checked */
+    int32_t mode;            /* CTAG_NOISE_PER_RIG (default) or CTAG_NOISE_POOLED */
+    int32_t free_mask;       /* CTAG_NOISE_FREE_*, 0 .. 7; default 7 */
+    int32_t rounds;          /* 1 .. 16; default 10 */
+    int32_t max_gap;         /* >= 1; default 5 */
+    int32_t min_terms;       /* >= 1; default 8 */
+    double dt;               /* seconds between frames when times == NULL; default 1 / 30 */
+    double q_rot;            /* the start values; defaults 0.1, 3000 and 1 */
+    double q_trans;
+    double cov_scale;
+    double vel0_sigma_rot;   /* as ctag_track_filter_opts, the same defaults */
+    double vel0_sigma_trans;
+    double span;             /* octaves; round 0 reaches from -span / 2 to span / 2 around the start; default 16 */
+} ctag_track_noise_opts;     /* 80 bytes */
+
+typedef struct ctag_track_noise_rec {
+    int32_t status;          /* CTAG_NOISE_* */
+    int32_t rig;             /* -1 for the pooled search */
+    int32_t n_terms;
+    int32_t n_free;
+    int32_t rounds;          /* rounds evaluated */
+    uint32_t flags;          /* CTAG_NOISE_FLAG_EDGE << axis */
+    double q_rot;
+    double q_trans;
+    double cov_scale;
+    double log2_sigma[3];    /* rule 7 */
+    double score;
+    double score_start;
+    double mean_m2;
+} ctag_track_noise_rec;      /* 96 bytes */
+
+typedef struct ctag_track_noise_round {   /* rule 8 */
+    double u[3];
+    double value[3];
+    double L;
+    int32_t winner;
+    int32_t reserved;        /* 0 */
+} ctag_track_noise_round;    /* 64 bytes */
+
+typedef struct ctag_track_noise_score {   /* rule 2: entry cand * n_rigs + g of a score call */
+    double L;
+    double sum_m2;
+    int32_t n_terms;
+    int32_t n_singular;
+    int32_t status;          /* CTAG_NOISE_OK or CTAG_NOISE_BAD_INPUT */
+    int32_t reserved;        /* 0 */
+} ctag_track_noise_score;    /* 32 bytes */
+
+void ctag_track_noise_opts_default(ctag_track_noise_opts* opts);
+/* Device records in; n_rigs (per rig) or 1 (pooled) device result records to out_dev and, when trace_dev is not NULL, rounds trace records per
+ * search, and no byte outside them.  Every round is enqueued on the handle's stream; the call returns without waiting for its own work
+ * or for anything else on the stream, with one exception: the workspace is the handle's and grow-only, so an earlier noise call of this
+ * handle that is still in flight is waited for first.  The rig set only gives n_rigs.  opts == NULL means the defaults. */
+int ctag_rig_track_noise_fit_device(ctag_handle* h, const ctag_rigs* rigs, const ctag_rig_pose_rec* rig_poses_dev, const ctag_pose_cov_rec* cov_dev,
+                                    int n_frames, const double* times, const ctag_track_noise_opts* opts, ctag_track_noise_rec* out_dev,
+                                    ctag_track_noise_round* trace_dev);
+int ctag_mv_rig_track_noise_fit_device(ctag_handle* h, const ctag_rigs* rigs, const ctag_mv_pose_rec* mv_poses_dev, const ctag_pose_cov_rec* cov_dev,
+                                       int n_frames, const double* times, const ctag_track_noise_opts* opts, ctag_track_noise_rec* out_dev,
+                                       ctag_track_noise_round* trace_dev);
+/* The same with HOST arrays in and out; they wait for completion. */
+int ctag_rig_track_noise_fit(ctag_handle* h, const ctag_rigs* rigs, const ctag_rig_pose_rec* rig_poses, const ctag_pose_cov_rec* cov, int n_frames,
+                             const double* times, const ctag_track_noise_opts* opts, ctag_track_noise_rec* out, ctag_track_noise_round* trace);
+int ctag_mv_rig_track_noise_fit(ctag_handle* h, const ctag_rigs* rigs, const ctag_mv_pose_rec* mv_poses, const ctag_pose_cov_rec* cov, int n_frames,
+                                const double* times, const ctag_track_noise_opts* opts, ctag_track_noise_rec* out, ctag_track_noise_round* trace);
+/* Rule 2 alone, at n_cand caller-given candidates: cand is a HOST array of n_cand x 3 doubles (q_rot, q_trans, s), copied before the call
+ * returns; n_cand x n_rigs entries to out_dev (entry cand * n_rigs + g).  Of opts only max_gap, dt and the vel0 sigmas are used (the others
+ * are still checked).  The tool for plotting a likelihood surface; enqueued like the fit. */
+int ctag_rig_track_noise_score_device(ctag_handle* h, const ctag_rigs* rigs, const ctag_rig_pose_rec* rig_poses_dev, const ctag_pose_cov_rec* cov_dev,
+                                      int n_frames, const double* times, const ctag_track_noise_opts* opts, const double* cand, int n_cand,
+                                      ctag_track_noise_score* out_dev);
+int ctag_mv_rig_track_noise_score_device(ctag_handle* h, const ctag_rigs* rigs, const ctag_mv_pose_rec* mv_poses_dev, const ctag_pose_cov_rec* cov_dev,
+                                         int n_frames, const double* times, const ctag_track_noise_opts* opts, const double* cand, int n_cand,
+                                         ctag_track_noise_score* out_dev);
+int ctag_rig_track_noise_score(ctag_handle* h, const ctag_rigs* rigs, const ctag_rig_pose_rec* rig_poses, const ctag_pose_cov_rec* cov, int n_frames,
+                               const double* times, const ctag_track_noise_opts* opts, const double* cand, int n_cand, ctag_track_noise_score* out);
+int ctag_mv_rig_track_noise_score(ctag_handle* h, const ctag_rigs* rigs, const ctag_mv_pose_rec* mv_poses, const ctag_pose_cov_rec* cov, int n_frames,
+                                  const double* times, const ctag_track_noise_opts* opts, const double* cand, int n_cand, ctag_track_noise_score* out);
+/* device time of the last noise call's kernels, fit or score (needs CTAG_OPT_TIMING), milliseconds */
+int ctag_track_noise_last_ms(ctag_handle* h, float* out1);
 
 /* ---- hand-eye calibration: the two fixed transforms between the camera's poses and a robot's link poses (k_hand_eye.hip) -----------------
  * Every pose above lives in the camera's (or the reference) frame.  A robot, stage or tracked arm reports a link pose per frame; this call
